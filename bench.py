@@ -9,6 +9,11 @@ reference's eval.py loop -- by the per-batch PSNR and ONE packed all-gather of
 sd3unet_gq_0.25 (codebook 2^16, dim 16, 1 group), bs = 16 per GPU, fp32.
 `--config gq_0.50|gq_1.00|gq2_0.25|vq_16|lfq_16 [--size 512]` runs configs[3] / configs[4].
 
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step).  `--full` adds what the
+headline does not need, after the timed region: per-stage split, quantiser-only calls, the dominant kernel's roofline, the
+reference's own GPU call sequence and the CPU baseline with in-run parity.  `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy, so that two builds can be compared output for output on identical (seeded) inputs.
+
 Launch: `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the process either is one rank of an
 external launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`: RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* in the environment) or -- when RANK is not set -- starts the N ranks itself as fresh child
@@ -63,7 +68,13 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--config", default="gq_0.25", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the per-stage split, quantiser-only calls, the roofline of the "
+                         "dominant kernel, the reference's GPU call sequence and the CPU baseline with in-run parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (zhat, reconstruction, the quantiser's info, the gathered "
+                         "indices and PSNR) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and in-run parity")
     ap.add_argument("--no-reference-gpu", action="store_true",
                     help="skip the same-run leg that times the REFERENCE's own GPU call sequence (ATen / MIOpen convolutions, "
                          "gq_cuda op -> argmax -> index_select) on this device")
@@ -217,7 +228,7 @@ def pmc_traffic(kernel, config="gq_0.25"):
 
 # End-to-end parity gates (GPU encoder -> GPU quantiser -> GPU decoder against the reference's CPU path on the same input).
 # ONE definition: tests/test_gpu_modules.py, tests/test_gpu_e2e_goldens.py gate on these numbers,
-# bench.py prints them beside what it measured, BASELINE.md / DESIGN.md quote them.
+# bench.py --full prints them beside what it measured, BASELINE.md / DESIGN.md quote them.
 GATES = {
     "z_enc_max_abs": 5e-5,               # |z_gpu - z_cpu| at 256^2 (measured 3-5e-6)
     "z_enc_max_abs_512": 2e-4,           # ... at 512^2
@@ -577,6 +588,35 @@ def reference_gpu_path(vae, x, cfg, product_indices, product_images_per_s, steps
     }
 
 
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 * 10 ** 6        # files, headers included
+NPY_HEADER_BYTES = 4096                # room left per file for the .npy header (numpy writes 128 bytes or a few more)
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: tensor} as outdir/<name>.npy: floating point as float32 (float64 stays float64), integers and booleans as
+    float64 (exact below 2^53).  While the arrays fit in `limit` bytes together they are written whole; otherwise the limit is
+    shared out, smallest array first, and an array larger than its share is written as a fixed sample of its flattened elements
+    (positions drawn by numpy's default_rng(0), sorted), identical from run to run for the same shapes.  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    conv = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy() if t.is_floating_point() and t.dtype != torch.float64 else t.detach().cpu().numpy()
+        conv[name] = a.astype(np.float64 if a.dtype.kind in "iub" else a.dtype, copy=False)
+    left, written = limit - NPY_HEADER_BYTES * len(conv), {}
+    for i, (name, a) in enumerate(sorted(conv.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(conv) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
+
+
 # ----------------------------------------------------------------------------- main
 def main():
     args = parse_args()
@@ -613,6 +653,7 @@ def main():
     tokens = (args.size // 8) ** 2 * (cfg["K"] if cfg["family"] in ("gq", "gq2", "vq") else 1)
     layout = StepRecord(args.batch, tokens, n_metrics=1)
     gather_ev = []
+    last = {}        # --dump-outputs: what the latest step handed its caller
 
     @torch.no_grad()
     def step():
@@ -624,6 +665,8 @@ def main():
         out = gather_step(record, world)
         e1.record()
         gather_ev.append((e0, e1))
+        if args.dump_outputs:
+            last.update(zhat=zhat, info=info, rec=rec, gathered=out)
         return out
 
     def sync():
@@ -655,8 +698,9 @@ def main():
         step()
     sync()
     gather_ev.clear()
-    _lib.profile_reserve(4 * args.steps + 64)   # event pairs created here, none inside the timed region
-    _lib.profile_enable(True)
+    if args.full:       # the roofline's per-launch kernel time: hipEvents on the quantiser's dispatches
+        _lib.profile_reserve(4 * args.steps + 64)   # event pairs created here, none inside the timed region
+        _lib.profile_enable(True)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]   # per-step spread (async, ~free)
     t0 = time.perf_counter()
     marks[0].record()
@@ -670,8 +714,17 @@ def main():
     step_ms = {"p10": pick(per_step, 0.10), "p50": pick(per_step, 0.50), "p90": pick(per_step, 0.90),
                "note": "device time between per-step events, rank 0"}
     gather_ms = sorted(a.elapsed_time(b) for a, b in gather_ev)
-    launches, kernel_ms = _lib.profile_collect()
-    _lib.profile_enable(False)
+    if args.full:
+        launches, kernel_ms = _lib.profile_collect()
+        _lib.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        idx_all, psnr_all = layout.unpack(last["gathered"])
+        arrays = {"zhat": last["zhat"], "reconstruction": last["rec"], "gathered_indices": idx_all,
+                  "gathered_psnr": psnr_all[..., 0]}
+        arrays.update({"info_" + "".join(c if c.isalnum() else "_" for c in k): v
+                       for k, v in last["info"].items() if torch.is_tensor(v)})
+        shapes = dump_outputs(args.dump_outputs, arrays)
+        print(f"bench.py: wrote {len(shapes)} arrays of the last timed step to {args.dump_outputs}: {shapes}", file=sys.stderr)
 
     # Per-stage split, measured AFTER the timed region on this rank's stream, no collective.
     def stage_split(reps=5):
@@ -692,7 +745,7 @@ def main():
         return {"encoder": round(med(0), 3), "quantiser": round(med(1), 3), "decoder": round(med(2), 3),
                 "psnr+pack": round(med(3), 3), "note": "median of 5 untimed extra steps, torch events"}
 
-    stages = stage_split()
+    stages = stage_split() if args.full else None
 
     # The quantiser alone, back to back (no conv kernels in between): what a tokenizer-only caller pays per call.
     def quantiser_call_us(reps=20):
@@ -708,7 +761,7 @@ def main():
         torch.cuda.synchronize()
         return a.elapsed_time(b) / reps * 1e3
 
-    call_us = quantiser_call_us()
+    call_us = quantiser_call_us() if args.full else None
 
     # The same call on SURVEY.md 8(d)'s quantiser-only inputs (mu = 0.9 randn, logvar = -1.5 + 0.3 randn: ~1.1 bit per dimension, near
     # the trained operating point -- the z of this bench's seeded-random encoder has sigma ~ 1, logvar ~ 0, where the score is nearly
@@ -732,7 +785,7 @@ def main():
         torch.cuda.synchronize()
         return a.elapsed_time(b) / reps * 1e3
 
-    call_us_8d = quantiser_call_us_8d()
+    call_us_8d = quantiser_call_us_8d() if args.full else None
 
     # The fp32 MFMA filter on the same rows, for comparison (same indices; untimed extra quantiser calls).
     def fp32_filter_us(reps=5):
@@ -753,7 +806,7 @@ def main():
         return ms / max(n_l, 1) * 1e3
 
     mfma_family = cfg["family"] in ("gq", "gq2", "vq")
-    fp32_us = fp32_filter_us() if (mfma_family and _lib.get_filter() == "auto") else None
+    fp32_us = fp32_filter_us() if (args.full and mfma_family and _lib.get_filter() == "auto") else None
 
     # per-rank medians and the MAX of the elapsed times over ranks
     cpu_coll = args.dist_backend != "nccl"
@@ -773,7 +826,8 @@ def main():
         rows = args.batch * tokens
         per_row = (2.0 if cfg["family"] == "vq" else 4.0) * dim * N_CODES   # 4*dim*N flops per row (VQ: 2*dim*N)
         flops = per_row * rows
-        if mfma_family:
+        roofline = None
+        if args.full and mfma_family:
             avg_ms = kernel_ms / max(launches, 1)
             achieved = flops / (avg_ms * 1e-3) / 1e12 if launches else 0.0
             plan = _lib.debug_plan(rows, N_CODES, dim)
@@ -888,7 +942,7 @@ def main():
                              "timing": "hipEvents attached to the dispatch (hipExtLaunchKernelGGL) on the launch stream, over the "
                                        "timed region; event pairs pre-created",
                              "algorithmic_flops_per_launch": flops})
-        else:
+        elif args.full:
             # LFQ: sign + 16-bit pack, elementwise: HBM-bound, 4*16 B in + 4*16 B q out + 8 B index per row
             nbytes = rows * (16 * 4 * 2 + 8)
             roofline = {"kernel": "lfq_pack_kernel (sign + big-endian pack; closed form of the arg-min over {+-1}^16)",
@@ -929,12 +983,13 @@ def main():
             "gather_ms": {"p50": pick(gather_ms, 0.5), "p90": pick(gather_ms, 0.9),
                           "bytes_per_rank": layout.words * 4, "per_rank_p50": rank_gather_ms},
             "rank_step_ms_p50": rank_step_ms,
-            "roofline": roofline,
-            "stages_ms": stages,
             "step_ms": step_ms,
-            "quantiser_rows_per_s": round(rows / (stages["quantiser"] * 1e-3)),
+            "full": args.full,
         }
-        if world == 1 and not args.no_reference_gpu:
+        if args.full:
+            line.update({"roofline": roofline, "stages_ms": stages,
+                         "quantiser_rows_per_s": round(rows / (stages["quantiser"] * 1e-3))})
+        if args.full and world == 1 and not args.no_reference_gpu:
             with torch.no_grad():
                 _, info_p = vae.encode(x, return_reg_log=True)
             line["reference_gpu_path"] = reference_gpu_path(vae, x, cfg, info_p["indices"], line["value"],
@@ -945,7 +1000,7 @@ def main():
             # against steady state.
             line["vs_baseline_note"] = ("null: BASELINE.md has no published number for this metric; the reference's own GPU call sequence, "
                                         "measured in this run with the same warm-up treatment, is in reference_gpu_path")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], line["parity"] = cpu_baseline_and_parity(vae, x, cfg, args.channels_last)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -121,3 +121,37 @@ def test_bench_reads_the_committed_pmc_passes_per_shape():
         assert all(os.path.exists(os.path.join(b.ROOT, f)) for f in prov["files_sha256_16"]) and prov["launches_averaged"] >= 5
     assert b.pmc_traffic("gq_filter_bf16_kernel", "gq_0.25_512") == (None, None)
     assert b.pmc_traffic("gq_filter_bf16_kernel", None) == (None, None)
+
+
+def test_plain_run_is_the_default_and_dump_outputs_is_off():
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit_and_samples_reproducibly(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, whole while they fit; past the limit a fixed seeded sample of the largest,
+    the same in every run, and the files (headers included) stay within the limit."""
+    import numpy as np
+    import torch
+
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    arrays = {"rec": torch.randn(4, 3, 64, 64, generator=g), "idx": torch.randint(0, 65536, (4, 1, 8, 8), generator=g),
+              "half": torch.randn(5, generator=g).half(), "kl": torch.tensor(0.25, dtype=torch.float64)}
+    shapes = b.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert shapes == {"kl": [], "half": [5], "idx": [4, 1, 8, 8], "rec": [4, 3, 64, 64]}
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in arrays}
+    assert got["rec"].dtype == np.float32 and np.array_equal(got["rec"], arrays["rec"].numpy())
+    assert got["idx"].dtype == np.float64 and np.array_equal(got["idx"], arrays["idx"].numpy())
+    assert got["half"].dtype == np.float32 and got["kl"].dtype == np.float64 and float(got["kl"]) == 0.25
+    limit = 40000 + 4 * b.NPY_HEADER_BYTES          # rec (196 608 bytes) does not fit
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+    s1, s2 = np.load(tmp_path / "s1" / "rec.npy"), np.load(tmp_path / "s2" / "rec.npy")
+    assert s1.ndim == 1 and 0 < s1.size < arrays["rec"].numel() and np.array_equal(s1, s2)
+    assert np.isin(s1, arrays["rec"].numpy().reshape(-1)).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "idx.npy"), got["idx"])      # the small ones stay whole

@@ -102,7 +102,7 @@ def test_vq_and_lfq_512_end_to_end_vs_reference_golden():
 
 @pytest.mark.e2e
 def test_bench_line_contract_small_run():
-    """`python bench.py` as the driver runs it (fresh process, N = 1) prints ONE JSON line with the contract's fields: metric /
+    """`python bench.py --full` (fresh process, N = 1) prints ONE JSON line with the contract's fields: metric /
     value / unit / n_gpus / steps / warmup / ms_per_step / scaling / dtype / config.workload, the `roofline` object of the
     dominant kernel (bound, achieved, peak, frac, traffic), `cpu_baseline` (two legs that agree bit for bit) and the in-run
     `parity` figures (indices 100 % equal on the CPU encoder's z; end to end within the stated tolerance)."""
@@ -110,8 +110,8 @@ def test_bench_line_contract_small_run():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1"], capture_output=True,
-                         text=True, timeout=900, cwd=root)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -151,6 +151,48 @@ def test_bench_line_contract_small_run():
     wt = rf["whole_call_traffic"]
     assert wt and wt["bytes"] > rf["traffic"] and set(wt["per_kernel"]) >= {"gq_prep_kernel", "gq_rerank_kernel"} and len(wt["per_kernel"]) == 3
     assert par["reference_top2_gap_at_differing_rows"] == [] or max(par["reference_top2_gap_at_differing_rows"]) < bench.GATES["near_tie_gap"]
+
+
+@pytest.mark.e2e
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full prints the headline only (none of the figures --full adds), and `--dump-outputs DIR` writes
+    what the last timed step computed: the step's indices and reconstruction equal what the same seeded model computes here on the
+    same seeded input (the channels_last stack is bit-reproducible at the bench shapes; the reconstruction is held to the smoke
+    tolerance)."""
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs",
+                          str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in line, k
+    for k in ("roofline", "stages_ms", "quantiser_rows_per_s", "reference_gpu_path", "cpu_baseline", "parity"):
+        assert k not in line, k
+    assert line["full"] is False and line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32"
+    assert line["unit"] == "images/s" and abs(line["value"] * line["ms_per_step"] / 1e3 - 16) < 0.01
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"zhat", "reconstruction", "gathered_indices", "gathered_psnr", "info_indices"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum((tmp_path / f).stat().st_size for f in os.listdir(tmp_path)) <= bench.DUMP_LIMIT_BYTES
+    vae = bench.build_model(DEV, bench.CONFIGS["gq_0.25"]).to(memory_format=torch.channels_last)
+    g = torch.Generator().manual_seed(1000)
+    x = (torch.rand(16, 3, 256, 256, generator=g) * 2 - 1).to(DEV).contiguous(memory_format=torch.channels_last)
+    with torch.no_grad():
+        zhat, info = vae.encode(x, return_reg_log=True)
+        rec = vae.decode(zhat).float().cpu().numpy()
+    ind = info["indices"].cpu().numpy()
+    assert files["reconstruction"].shape == rec.shape and files["info_indices"].shape == ind.shape
+    assert np.array_equal(files["info_indices"], ind.astype(np.float64))
+    assert np.array_equal(files["gathered_indices"].reshape(-1), ind.reshape(-1).astype(np.float64))
+    assert float(np.abs(files["reconstruction"] - rec).max()) <= 2e-4 * max(1.0, float(np.abs(rec).max()))
+    assert files["gathered_psnr"].shape == (1, 16) and np.isfinite(files["gathered_psnr"]).all()
 
 
 # ------------------------------------------------------------------------------------------ run-to-run reproducibility

@@ -5,7 +5,7 @@ set -u
 R=${1:-r01}
 OUT=gpurun_out/lines_$R
 mkdir -p "$OUT"
-run() { name=$1; shift; python bench.py "$@" 2>/dev/null | grep '^{' | tail -1 > "$OUT/line_$name.json"; python - "$OUT/line_$name.json" <<'PY'
+run() { name=$1; shift; python bench.py --full "$@" 2>/dev/null | grep '^{' | tail -1 > "$OUT/line_$name.json"; python - "$OUT/line_$name.json" <<'PY'
 import json, sys
 l = json.loads(open(sys.argv[1]).read()); r = l["roofline"]
 print(sys.argv[1].split("/")[-1], l["value"], l["unit"], "vs_baseline", l.get("vs_baseline"), "frac", r.get("frac"), "filter us", r.get("avg_launch_us"),

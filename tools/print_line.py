@@ -1,4 +1,4 @@
-"""Print the headline fields of a bench.py JSON line (a file holding the line, or stdin)."""
+"""Print the headline fields of a `bench.py --full` JSON line (a file holding the line, or stdin)."""
 import json
 import sys
 
