@@ -30,6 +30,7 @@
  *   fsq_quantize_f32 / fsq_dequant_f32  pit/quantization/fsq.py:29-89.
  *   gn_silu_f32      pit/modules/unet.py:49-57 (Normalize + nonlinearity pairs).
  *   gq_index_histogram eval.py:127,137-141,152-154 (stubbed-out histogram).
+ *   gq_ssim_f32      pit/evaluations/ssim.py:5-63 (get_ssim / get_ssim_and_msssim via pytorch_msssim), eval.py:170-178.
  */
 #ifndef GQHIP_H_
 #define GQHIP_H_
@@ -51,7 +52,8 @@ extern "C" {
                                *    32 keep the filter's fp16 codebook image there;
                                * 8: module-level eval forwards of GaussianQuantRegularizer2 (gq_quantize_z_gauss_f32: the Gaussian branch's
                                *    statistics and lambda state on the device) and VQQuantizer (vq_quantize_z_f32: layouts, straight-through
-                               *    value and codebook loss inside the launches) */
+                               *    value and codebook loss inside the launches); additive since, the version unchanged: per-image SSIM /
+                               *    MS-SSIM (gq_ssim_f32) and the three-metric step record (gq_step_record_ssim_f32) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -477,6 +479,27 @@ int gq_indices_from_u16(const uint16_t *in, int64_t *idx, int64_t count,
 int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image);
 int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
                        int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
+
+/* Per-image SSIM and MS-SSIM -- pit/evaluations/ssim.py:5-63 (get_ssim / get_ssim_and_msssim: pytorch_msssim's ssim / ms_ssim
+ * with data_range 255, size_average False, the 11-tap sigma-1.5 Gaussian window, K = (0.01, 0.03), MS-SSIM weights
+ * (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) over five scales joined by avg_pool2d(2, 2, padding = side % 2)).
+ * x, x_rec: B images [B, C, H, W], fp32, NCHW (layout 0) or NHWC / channels_last (layout 1), both the same layout; zero_mean != 0:
+ * images in [-1, 1] scaled by (x + 1) 127.5, else by x 255, in fp32 like the reference; the window and the maps in fp64 from there
+ * (csrc/gq_ssim.h).  A side under 11 is left unfiltered, as pytorch_msssim does.  ssim_out_or_null / msssim_out_or_null: B fp32
+ * values each; a NULL msssim_out skips levels 1-4; when H < 256 or W < 256 MS-SSIM is NaN (ssim.py:31-34).  One launch per level,
+ * sums in a fixed order: bit-reproducible.  workspace: gq_ssim_workspace_bytes(B, C, H, W) bytes, ZERO when first used; every
+ * call leaves it zero again (one stream at a time).  Asynchronous on `stream`, no allocation: graph-capturable. */
+int64_t gq_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_t H, int64_t W, int layout, int zero_mean,
+                float *ssim_out_or_null, float *msssim_out_or_null, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
+/* The three-metric step record -- eval.py:152-154,165-178 (indices, PSNR, SSIM, MS-SSIM with zero_mean = True) in the wire
+ * format of pit_hip/eval_dist.py:StepRecord with n_metrics = 3:
+ *     rec [3 B + (n_idx + 1) / 2] int32 = [ B x (psnr, ssim, ms_ssim) as fp32 bits, image-major | indices as uint16 pairs ].
+ * The PSNR words and the index words come from the kernel of gq_step_record_f32 (bit-identical to it), SSIM / MS-SSIM from that
+ * of gq_ssim_f32.  workspace: gq_step_record_ssim_workspace_bytes(B, C, H, W) bytes, ZERO when first used, left zero. */
+int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
+                            int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
 
 /* ---- profiling recorder ------------------------------------------------------
  * When enabled, every launch of the MFMA filter kernel is bracketed with

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Image-sharded evaluation of the hot path (the part of the reference's eval.py this repo covers):
-encode -> quantize -> decode per rank, ONE packed all_gather per step, rank 0 prints PSNR mean/std,
-codebook usage and entropy of the gathered indices.
+encode -> quantize -> decode per rank, ONE packed all_gather per step, rank 0 prints PSNR mean/std (with
+--metrics psnr,ssim,ms_ssim also SSIM and MS-SSIM, in eval.py's format), codebook usage and entropy of the gathered indices.
 
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/eval_sharded.py \
-      --base configs/sd3unet_gq_0.25.yaml [--ckpt model.ckpt] [--dataset DIR|list.txt] --img_size 256 --bs 16
+      --base configs/sd3unet_gq_0.25.yaml [--ckpt model.ckpt] [--dataset DIR|list.txt] --img_size 256 --bs 16 \
+      [--metrics psnr,ssim,ms_ssim]
 Without --dataset a seeded synthetic image bank is used (no data offline)."""
 import argparse
 import os
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--img_size", type=int, default=256)
     ap.add_argument("--bs", type=int, default=1)
     ap.add_argument("--num", type=int, default=64, help="synthetic images when no --dataset is given")
+    ap.add_argument("--metrics", default="psnr", help="psnr, or psnr,ssim,ms_ssim (eval.py:165-178)")
     a = ap.parse_args()
     env = init_from_env(a.dist_backend)
     rank, world = env["rank"], env["world"]
@@ -52,10 +54,15 @@ def main():
         images_for = lambda ids: bank[ids]  # noqa: E731
     with torch.no_grad():  # tokens per image from a probe (depends on the config's downsampling and K)
         tokens = model.encode(images_for([0]).to(device), return_reg_log=True)[1]["indices"][0].numel()
-    out = evaluate_sharded(model, images_for, n, a.bs, rank, world, device, tokens)
+    metrics = tuple(m.strip() for m in a.metrics.split(",") if m.strip())
+    out = evaluate_sharded(model, images_for, n, a.bs, rank, world, device, tokens, metrics=metrics)
     if rank == 0 and out is not None:
         psnr = out["psnr"].float()
         print(f"PSNR: {psnr.mean():.4f} (±{psnr.std(unbiased=False):.4f})  over {psnr.numel()} images")
+        for key, label in (("ssim", "SSIM"), ("ms_ssim", "MS-SSIM")):   # eval.py:224-225: NaN when a side is under 256
+            if key in out:
+                v = out[key].float()
+                print(f"{label}: {v.mean():.4f} (±{v.std(unbiased=False):.4f})")
         n_codes = getattr(model.regularization, "n_samples", 65536)
         _, usage, ent = codebook_usage(out["indices"].to(device), n_codes)   # eval.py:137-141
         print(f"codebook usage: {usage:.4f}  entropy: {ent:.3f} bits")

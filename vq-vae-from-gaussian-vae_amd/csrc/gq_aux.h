@@ -245,7 +245,8 @@ __global__ __launch_bounds__(256) void from_u16_kernel(const uint16_t *__restric
 // of eval.py:152-154 publish per batch.  Blocks [0, B * chunks): one contiguous chunk of one image, the squared differences in
 // the reference's fp32 op order ((x + 1) 127.5 - (x_rec + 1) 127.5, squared), summed in fp64; the LAST block of an image (a ticket
 // per image, reset for the next call) adds the chunk sums in chunk order -- a fixed order: the value is bit-reproducible -- and
-// writes 20 log10(255 / sqrt(mse)).  The blocks after those pack the indices.
+// writes 20 log10(255 / sqrt(mse)).  The blocks after those pack the indices.  The three-metric record (gq_step_record_ssim_f32)
+// runs the same kernel with stride 3: [ B x (psnr, ssim, ms_ssim) | indices ], its PSNR words those of stride 1 bit for bit.
 struct StepRecordParams {
   const float *x, *x_rec;     // [B, per_image] in the SAME dense layout
   const int64_t *idx;         // [n_idx]
@@ -254,6 +255,7 @@ struct StepRecordParams {
   int *ticket;                // [B], all zero between calls (workspace)
   long per_image, n_idx;
   int B, chunks, psnr_blocks;
+  int stride;                 // int32 words per image in the metric block: PSNR of image b at rec[b * stride], indices at rec[B * stride]
 };
 constexpr int kPsnrChunk = 256 * 4 * 8;      // floats per block: eight 16-byte loads per thread
 
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams
     if (2 * w < p.n_idx) {
       const unsigned lo = (unsigned)p.idx[2 * w] & 0xffffu;
       const unsigned hi = 2 * w + 1 < p.n_idx ? (unsigned)p.idx[2 * w + 1] & 0xffffu : 0u;
-      p.rec[p.B + w] = (int)(lo | (hi << 16));
+      p.rec[(long)p.B * p.stride + w] = (int)(lo | (hi << 16));
     }
     return;
   }
@@ -304,7 +306,7 @@ __global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams
   for (int k = 0; k < p.chunks; ++k) sum += __hip_atomic_load(&p.partial[(long)b * p.chunks + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const float mse = (float)(sum / (double)p.per_image);
   const float psnr = (float)(20.0 * log10(255.0 / sqrt((double)mse)));      // identical images: +inf, like the reference
-  p.rec[b] = __float_as_int(psnr);
+  p.rec[(long)b * p.stride] = __float_as_int(psnr);
   p.ticket[b] = 0;                             // ready for the next call on this workspace
 }
 

@@ -23,6 +23,7 @@
 #include "gq_rerank.h"
 #include "gq_scores.h"
 #include "gq_scores_f16.h"
+#include "gq_ssim.h"
 
 using namespace gqhip;
 
@@ -939,15 +940,11 @@ int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image) {
   return B * chunks * 8 + ((B * 4 + 7) / 8) * 8;
 }
 
-int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
-                       int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
-  if (B < 0 || per_image < 1 || n_idx < 0 || B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0 && n_idx == 0) return GQHIP_OK;
-  if (!rec || (B > 0 && (!x || !x_rec)) || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
-  if (B > 0 && (!workspace_zeroed || workspace_bytes < gq_step_record_workspace_bytes(B, per_image))) return GQHIP_ERR_WORKSPACE;
+static int step_record_launch(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                              int64_t n_idx, void *workspace_zeroed, int stride, hipStream_t st) {
   StepRecordParams p{};
   p.x = x; p.x_rec = x_rec; p.idx = idx; p.rec = rec;
-  p.per_image = (long)per_image; p.n_idx = (long)n_idx; p.B = (int)B;
+  p.per_image = (long)per_image; p.n_idx = (long)n_idx; p.B = (int)B; p.stride = stride;
   p.chunks = (int)((per_image + kPsnrChunk - 1) / kPsnrChunk);
   if ((int64_t)p.chunks * B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
   p.psnr_blocks = p.chunks * (int)B;
@@ -955,8 +952,142 @@ int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, i
   p.ticket = reinterpret_cast<int *>(static_cast<char *>(workspace_zeroed) + B * p.chunks * 8);
   const int64_t words = (n_idx + 1) / 2;
   const int64_t blocks = p.psnr_blocks + (words + 255) / 256;
-  hipLaunchKernelGGL(step_record_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(step_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
   return check_launch();
+}
+
+int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                       int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
+  if (B < 0 || per_image < 1 || n_idx < 0 || B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0 && n_idx == 0) return GQHIP_OK;
+  if (!rec || (B > 0 && (!x || !x_rec)) || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
+  if (B > 0 && (!workspace_zeroed || workspace_bytes < gq_step_record_workspace_bytes(B, per_image))) return GQHIP_ERR_WORKSPACE;
+  return step_record_launch(x, x_rec, idx, rec, B, per_image, n_idx, workspace_zeroed, 1, static_cast<hipStream_t>(stream));
+}
+
+// ---- SSIM / MS-SSIM (csrc/gq_ssim.h) ---------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t kSsimMsMin = 256;          // pit/evaluations/ssim.py:31-34: MS-SSIM only when both sides are >= 256
+
+struct SsimPlan {
+  gqssim::Level lv[gqssim::kLevels];
+  int levels;                                // 5 when MS-SSIM is defined for the size, else 1
+  int64_t part_doubles, p1_doubles, p2_doubles, ticket_bytes, bytes;
+};
+
+bool ssim_plan(int64_t B, int64_t C, int64_t H, int64_t W, SsimPlan &pl) {
+  if (B < 1 || C < 1 || H < 1 || W < 1 || B > 0x3fffffff || H > 0x3fffffff || W > 0x3fffffff) return false;
+  pl = SsimPlan{};
+  pl.levels = (H >= kSsimMsMin && W >= kSsimMsMin) ? gqssim::kLevels : 1;
+  int64_t h = H, w = W, part = 0;
+  for (int l = 0; l < pl.levels; ++l) {
+    gqssim::Level &L = pl.lv[l];
+    L.H = (int)h; L.W = (int)w;
+    L.Ho = (int)(h >= gqssim::kWin ? h - gqssim::kWin + 1 : h);
+    L.Wo = (int)(w >= gqssim::kWin ? w - gqssim::kWin + 1 : w);
+    L.tiles_y = (L.Ho + gqssim::kTH - 1) / gqssim::kTH;
+    L.tiles_x = (L.Wo + gqssim::kTW - 1) / gqssim::kTW;
+    L.part = (long)part;
+    const int64_t blocks = B * C * L.tiles_x * L.tiles_y;
+    if (blocks > 0x3fffffff) return false;
+    part += blocks;                            // tile records of two doubles
+    h = (h + 1) / 2;                           // avg_pool2d(2, 2, padding = side % 2): floor(s / 2) + s % 2
+    w = (w + 1) / 2;
+  }
+  pl.part_doubles = 2 * part;
+  pl.p1_doubles = pl.levels > 1 ? 2 * B * C * (int64_t)pl.lv[1].H * pl.lv[1].W : 0;
+  pl.p2_doubles = pl.levels > 2 ? 2 * B * C * (int64_t)pl.lv[2].H * pl.lv[2].W : 0;
+  pl.ticket_bytes = ((B * 4 + 255) / 256) * 256;
+  pl.bytes = pl.ticket_bytes + 8 * (pl.part_doubles + pl.p1_doubles + pl.p2_doubles);
+  return true;
+}
+
+// pytorch_msssim's window: exp(-(k - 5)^2 / (2 sigma^2)) in fp32, divided by its (fp32, left-to-right) sum.
+void ssim_window(float *g) {
+  float sum = 0.0f;
+  for (int k = 0; k < gqssim::kWin; ++k) {
+    const float d = (float)(k - gqssim::kWin / 2);
+    g[k] = expf(-(d * d) / 4.5f);
+    sum += g[k];
+  }
+  for (int k = 0; k < gqssim::kWin; ++k) g[k] /= sum;
+}
+
+int ssim_launch(const float *x, const float *y, int64_t B, int64_t C, int layout, int zero_mean, float *ssim_out, float *ms_out,
+                long out_stride, const SsimPlan &pl, void *ws, hipStream_t st) {
+  gqssim::Params p{};
+  p.x = x; p.y = y;
+  p.ssim_out = ssim_out; p.ms_out = ms_out; p.out_stride = out_stride;
+  ssim_window(p.win);
+  for (int l = 0; l < pl.levels; ++l) p.lv[l] = pl.lv[l];
+  p.B = (int)B; p.C = (int)C; p.layout = layout; p.zero_mean = zero_mean ? 1 : 0;
+  const int levels = ms_out ? pl.levels : 1;
+  p.final_level = levels - 1;
+  p.nan_ms = ms_out && pl.levels == 1;
+  char *base = static_cast<char *>(ws);
+  p.ticket = reinterpret_cast<int *>(base);
+  p.partial = reinterpret_cast<double *>(base + pl.ticket_bytes);
+  double *p1 = p.partial + pl.part_doubles, *p2 = p1 + pl.p1_doubles;
+  const int64_t n1 = pl.p1_doubles / 2, n2 = pl.p2_doubles / 2;
+  for (int l = 0; l < levels; ++l) {
+    const gqssim::Level &L = pl.lv[l];
+    p.level = l;
+    // level 1 / 3 read P1, level 2 / 4 read P2; each level pools into the other buffer
+    p.px = l == 0 ? nullptr : (l & 1) ? p1 : p2;
+    p.py = l == 0 ? nullptr : (l & 1) ? p1 + n1 : p2 + n2;
+    p.qx = l + 1 < levels ? ((l & 1) ? p2 : p1) : nullptr;
+    p.qy = l + 1 < levels ? ((l & 1) ? p2 + n2 : p1 + n1) : nullptr;
+    p.ssim_blocks = (int)(B * C * L.tiles_x * L.tiles_y);
+    int64_t blocks = p.ssim_blocks;
+    if (p.qx) blocks += (B * C * (int64_t)pl.lv[l + 1].H * pl.lv[l + 1].W + 255) / 256;
+    if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
+    const bool fh = L.H >= gqssim::kWin, fw = L.W >= gqssim::kWin;
+    const dim3 grid((unsigned)blocks);
+    if (fh && fw) hipLaunchKernelGGL((gqssim::ssim_level_kernel<true, true>), grid, dim3(256), 0, st, p);
+    else if (fh) hipLaunchKernelGGL((gqssim::ssim_level_kernel<true, false>), grid, dim3(256), 0, st, p);
+    else if (fw) hipLaunchKernelGGL((gqssim::ssim_level_kernel<false, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((gqssim::ssim_level_kernel<false, false>), grid, dim3(256), 0, st, p);
+    const int rc = check_launch();
+    if (rc != GQHIP_OK) return rc;
+  }
+  return GQHIP_OK;
+}
+}  // namespace
+
+int64_t gq_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+  SsimPlan pl;
+  return ssim_plan(B, C, H, W, pl) ? pl.bytes : -1;
+}
+
+int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_t H, int64_t W, int layout, int zero_mean,
+                float *ssim_out_or_null, float *msssim_out_or_null, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
+  SsimPlan pl;
+  if (!ssim_plan(B, C, H, W, pl) || (layout != 0 && layout != 1) || !x || !x_rec) return GQHIP_ERR_INVALID_ARG;
+  if (!ssim_out_or_null && !msssim_out_or_null) return GQHIP_OK;
+  if (!workspace_zeroed || workspace_bytes < pl.bytes) return GQHIP_ERR_WORKSPACE;
+  return ssim_launch(x, x_rec, B, C, layout, zero_mean, ssim_out_or_null, msssim_out_or_null, 1, pl, workspace_zeroed,
+                     static_cast<hipStream_t>(stream));
+}
+
+int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+  SsimPlan pl;
+  if (!ssim_plan(B, C, H, W, pl)) return -1;
+  const int64_t head = ((gq_step_record_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
+  return head + pl.bytes;
+}
+
+int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
+                            int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
+  SsimPlan pl;
+  if (!ssim_plan(B, C, H, W, pl) || (layout != 0 && layout != 1) || n_idx < 0) return GQHIP_ERR_INVALID_ARG;
+  if (!x || !x_rec || !rec || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
+  if (!workspace_zeroed || workspace_bytes < gq_step_record_ssim_workspace_bytes(B, C, H, W)) return GQHIP_ERR_WORKSPACE;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t head = ((gq_step_record_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
+  int rc = step_record_launch(x, x_rec, idx, rec, B, C * H * W, n_idx, workspace_zeroed, 3, st);    // PSNR words + indices
+  if (rc != GQHIP_OK) return rc;
+  return ssim_launch(x, x_rec, B, C, layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3, pl,
+                     static_cast<char *>(workspace_zeroed) + head, st);
 }
 
 int gqhip_profile_enable(int on) {

@@ -107,6 +107,10 @@ _SIGNATURES = {
     "gq_indices_from_u16": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
     "gq_step_record_workspace_bytes": (_i64, [_i64, _i64]),
     "gq_step_record_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "gq_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gq_ssim_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp]),
+    "gq_step_record_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gq_step_record_ssim_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
     "gqhip_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_reserve": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_collect": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -1127,6 +1131,49 @@ def step_record(x, x_rec, idx, rec, ws_cache: dict):
     with torch.cuda.device(x.device):
         _check(lib().gq_step_record_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, per, idx.numel(),
                                         ws.data_ptr(), ws.numel(), _stream()), "gq_step_record_f32")
+    return rec
+
+
+def ssim_ok(x, x_rec) -> bool:
+    """gq_ssim_f32 applies: fp32 HIP images [B, C, H, W] of one dense layout (NCHW or channels_last), B >= 1."""
+    if not (x.is_cuda and x_rec.is_cuda and x.device == x_rec.device and x.dtype == torch.float32
+            and x_rec.dtype == torch.float32 and x.dim() == 4 and x.shape == x_rec.shape and x.shape[0] > 0 and x[0].numel() > 0):
+        return False
+    la, lb = image_layout(x), image_layout(x_rec)
+    return la is not None and la == lb
+
+
+def _ssim_ws(ws_cache: dict, key, need: int, device):
+    ws = ws_cache.get(key)
+    if ws is None:
+        ws = ws_cache[key] = torch.zeros(max(need, 8), dtype=torch.uint8, device=device)   # zeroed once, left zero by every call
+    return ws
+
+
+def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
+    """Per-image (SSIM, MS-SSIM or None) as fp32 [B] tensors on x's device (gqhip.h: gq_ssim_f32; pit/evaluations/ssim.py:5-63).
+    MS-SSIM is NaN when a side is under 256.  ``ws_cache``: the caller's dict that keeps the self-resetting workspace."""
+    B, C, H, W = x.shape
+    layout = image_layout(x)
+    ssim = torch.empty(B, dtype=torch.float32, device=x.device)
+    ms = torch.empty(B, dtype=torch.float32, device=x.device) if msssim else None
+    ws = _ssim_ws(ws_cache, ("ssim", x.device, B, C, H, W), lib().gq_ssim_workspace_bytes(B, C, H, W), x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().gq_ssim_f32(x.data_ptr(), x_rec.data_ptr(), B, C, H, W, layout, 1 if zero_mean else 0, ssim.data_ptr(),
+                                 ms.data_ptr() if ms is not None else None, ws.data_ptr(), ws.numel(), _stream()), "gq_ssim_f32")
+    return ssim, ms
+
+
+def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
+    """rec[:] = [ B x (PSNR, SSIM, MS-SSIM) of (x, x_rec; zero_mean) as fp32 bits | idx as uint16 pairs ] (gqhip.h:
+    gq_step_record_ssim_f32; eval.py:152-154,165-178): the PSNR and index words are those of step_record bit for bit."""
+    B, C, H, W = x.shape
+    idx = idx.contiguous()
+    ws = _ssim_ws(ws_cache, ("rec3", x.device, B, C, H, W), lib().gq_step_record_ssim_workspace_bytes(B, C, H, W), x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().gq_step_record_ssim_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
+                                             image_layout(x), idx.numel(), ws.data_ptr(), ws.numel(), _stream()),
+               "gq_step_record_ssim_f32")
     return rec
 
 

@@ -13,6 +13,8 @@ metric -> all_gather, :207-257 rank-0 re-interleave).  What changes:
 * records stay on the device; nothing is copied to the host until the end.
 * no data-path collective besides that gather: images are independent, the
   4 MiB codebook and the weights are replicated (regenerated from the seed).
+* SSIM and MS-SSIM (eval.py:170-178, pit/evaluations/ssim.py) ride in the same
+  record (``metrics=("psnr", "ssim", "ms_ssim")``): still one gather per step.
 
 Sharding semantics are exactly ``DistributedSampler(shuffle=False)`` (pads the
 index list by wrapping so every rank gets ceil(N/W) items) followed by a
@@ -26,6 +28,7 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.distributed as dist
+import torch.nn.functional as F
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -99,8 +102,8 @@ class StepRecord:
         if flat.numel() != self.bs * self.tokens or metrics.numel() != self.metric_words:
             raise ValueError(f"StepRecord.pack: got {flat.numel()} indices / {metrics.numel()} metrics, layout is "
                              f"{self.bs} x {self.tokens} / {self.metric_words}")
-        if self.check_range and flat.numel() and (int(flat.max()) >= 65536 or int(flat.min()) < 0):
-            raise ValueError("StepRecord.pack: the uint16 wire format needs 0 <= index < 65536")
+        if self.check_range:
+            _check_index_range(flat)
         if flat.numel() % 2:
             flat = torch.cat([flat, flat.new_zeros(1)])
         u16 = flat.to(torch.int32)  # values < 65536
@@ -123,6 +126,30 @@ class StepRecord:
                 return _lib.step_record(x, x_rec, indices, rec, self.__dict__.setdefault("_ws", {}))
         return self.pack(indices, psnr_zero_mean(x, x_rec)[:, None])
 
+    def pack_with_metrics(self, indices: torch.Tensor, x: torch.Tensor, x_rec: torch.Tensor) -> torch.Tensor:
+        """pack(indices, metrics of (x, x_rec) with zero_mean) for the one-metric layout (PSNR: pack_with_psnr) or the
+        three-metric one (PSNR, SSIM, MS-SSIM per image: eval.py:165-178).  Three metrics on a HIP device: ONE library call
+        (gq_step_record_ssim_f32, whose PSNR and index words are those of pack_with_psnr bit for bit); elsewhere, or for a
+        layout the kernels do not take, the torch expressions."""
+        if self.n_metrics == 1:
+            return self.pack_with_psnr(indices, x, x_rec)
+        if self.n_metrics != 3:
+            raise ValueError(f"StepRecord.pack_with_metrics: n_metrics is 1 (psnr) or 3 (psnr, ssim, ms_ssim), not {self.n_metrics}")
+        if indices.is_cuda:
+            from . import _lib
+
+            if indices.numel() != self.bs * self.tokens or x.shape[0] != self.bs:
+                raise ValueError(f"StepRecord.pack_with_metrics: got {indices.numel()} indices / {x.shape[0]} images, layout "
+                                 f"is {self.bs} x {self.tokens}")
+            x, x_rec = _dense_pair(x, x_rec)
+            if _lib.step_record_ok(x, x_rec, indices) and _lib.ssim_ok(x, x_rec):
+                if self.check_range:
+                    _check_index_range(indices.reshape(-1))
+                rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
+                return _lib.step_record_ssim(x, x_rec, indices, rec, self.__dict__.setdefault("_ws", {}))
+        ssim, ms = get_ssim_and_msssim(x, x_rec, zero_mean=True)
+        return self.pack(indices, torch.stack([psnr_zero_mean(x, x_rec), ssim.to(torch.float32), ms.to(torch.float32)], 1))
+
     def unpack(self, rec: torch.Tensor):
         """rec: int32 [..., words] -> (indices int64 [..., bs, tokens], metrics fp32 [..., bs, n_metrics])."""
         lead = rec.shape[:-1]
@@ -131,6 +158,11 @@ class StepRecord:
         lo, hi = words & 0xFFFF, (words >> 16) & 0xFFFF
         flat = torch.stack([lo, hi], dim=-1).reshape(*lead, -1)[..., : self.bs * self.tokens]
         return flat.reshape(*lead, self.bs, self.tokens), metrics
+
+
+def _check_index_range(flat: torch.Tensor) -> None:
+    if flat.numel() and (int(flat.max()) >= 65536 or int(flat.min()) < 0):
+        raise ValueError("StepRecord.pack: the uint16 wire format needs 0 <= index < 65536")
 
 
 def gather_step(rec: torch.Tensor, world: int, always_collective: bool = False) -> torch.Tensor:
@@ -164,6 +196,124 @@ def psnr_zero_mean(x: torch.Tensor, x_rec: torch.Tensor) -> torch.Tensor:
     return get_psnr(x, x_rec, zero_mean=True)
 
 
+# ----------------------------------------------------------------------------- SSIM / MS-SSIM
+# pit/evaluations/ssim.py:5-63 calls pytorch_msssim (1.0) with data_range 255 and size_average False.  On a HIP device the images
+# go to gq_ssim_f32 (csrc/gq_ssim.h: fp64 moments and maps, one launch per scale); elsewhere -- and for layouts the kernel does
+# not take -- _ssim_torch / _ms_ssim_torch restate pytorch_msssim's op sequence (grouped conv2d with the fp32 window, avg_pool2d)
+# in the inputs' dtype.
+_MS_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+_SSIM_WS: Dict[tuple, dict] = {}      # per (device, stream): the library's self-resetting workspaces
+
+
+def ssim_window(size: int = 11, sigma: float = 1.5) -> torch.Tensor:
+    """pytorch_msssim's 1-D Gaussian window: exp(-(k - size // 2)^2 / (2 sigma^2)) in fp32, divided by its sum."""
+    coords = torch.arange(size, dtype=torch.float32) - size // 2
+    g = torch.exp(-(coords ** 2) / (2 * sigma ** 2))
+    return g / g.sum()
+
+
+def _gaussian_filter(x: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
+    """Separable 'valid' filter per channel: along H, then W; a side shorter than the window is skipped."""
+    c = x.shape[1]
+    out = x
+    for i, s in enumerate(x.shape[2:]):
+        if s >= win.numel():
+            w = win.reshape(1, 1, 1, -1).repeat(c, 1, 1, 1).transpose(2 + i, -1)
+            out = F.conv2d(out, w, stride=1, padding=0, groups=c)
+    return out
+
+
+def _ssim_torch(X: torch.Tensor, Y: torch.Tensor, win: torch.Tensor, data_range: float = 255.0):
+    """One scale: (ssim, cs) per (image, channel), in X's dtype."""
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    win = win.to(X.device, dtype=X.dtype)
+    mu1, mu2 = _gaussian_filter(X, win), _gaussian_filter(Y, win)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1.pow(2), mu2.pow(2), mu1 * mu2
+    sigma1_sq = _gaussian_filter(X * X, win) - mu1_sq
+    sigma2_sq = _gaussian_filter(Y * Y, win) - mu2_sq
+    sigma12 = _gaussian_filter(X * Y, win) - mu1_mu2
+    cs_map = (2 * sigma12 + c2) / (sigma1_sq + sigma2_sq + c2)
+    ssim_map = ((2 * mu1_mu2 + c1) / (mu1_sq + mu2_sq + c1)) * cs_map
+    return torch.flatten(ssim_map, 2).mean(-1), torch.flatten(cs_map, 2).mean(-1)
+
+
+def _ms_ssim_torch(X: torch.Tensor, Y: torch.Tensor, win: torch.Tensor, data_range: float = 255.0) -> torch.Tensor:
+    """Five scales joined by avg_pool2d(2, padding = side % 2); per image."""
+    weights = torch.tensor(_MS_WEIGHTS, dtype=torch.float32).to(X)     # the reference's fp32 weights, whatever X's dtype
+    mcs = []
+    for i in range(len(_MS_WEIGHTS)):
+        ssim_pc, cs = _ssim_torch(X, Y, win, data_range)
+        if i < len(_MS_WEIGHTS) - 1:
+            mcs.append(torch.relu(cs))
+            padding = [s % 2 for s in X.shape[2:]]
+            X = F.avg_pool2d(X, kernel_size=2, padding=padding)
+            Y = F.avg_pool2d(Y, kernel_size=2, padding=padding)
+    vals = torch.stack(mcs + [torch.relu(ssim_pc)], dim=0)
+    return torch.prod(vals ** weights.view(-1, 1, 1), dim=0).mean(1)
+
+
+def _scale(x: torch.Tensor, zero_mean: bool) -> torch.Tensor:
+    return (x + 1) * 127.5 if zero_mean else x * 255
+
+
+def _frames(x: torch.Tensor, is_video: bool) -> torch.Tensor:
+    """[B, C, T, H, W] -> [B * T, C, H, W] (image-major); images pass through."""
+    if not is_video:
+        return x
+    b, c, t, h, w = x.shape
+    return x.permute(0, 2, 1, 3, 4).reshape(b * t, c, h, w)
+
+
+def _dense_pair(a: torch.Tensor, b: torch.Tensor):
+    """HIP fp32 image batches in ONE dense layout, so the kernels take them: b follows a's layout (a channels_last decoder output
+    against NCHW inputs costs one copy, not a fall-back); other tensors pass through."""
+    from . import _lib
+
+    if not (a.is_cuda and b.is_cuda and a.dim() == 4 and a.shape == b.shape and a.dtype == b.dtype == torch.float32):
+        return a, b
+    la = _lib.image_layout(a)
+    if la is None:
+        a, la = a.contiguous(), 0
+    if _lib.image_layout(b) != la:
+        b = b.contiguous(memory_format=torch.channels_last if la == 1 else torch.contiguous_format)
+    return a, b
+
+
+def _image_quality(x_input: torch.Tensor, x_recon: torch.Tensor, zero_mean: bool, is_video: bool, msssim: bool):
+    """(ssim, ms_ssim or None) per item; video items average their frames."""
+    a, b = _dense_pair(_frames(x_input, is_video), _frames(x_recon, is_video))
+    from . import _lib
+
+    if _lib.ssim_ok(a, b):
+        key = (a.device, torch.cuda.current_stream(a.device).cuda_stream)
+        ssim, ms = _lib.image_quality(a, b, zero_mean, msssim, _SSIM_WS.setdefault(key, {}))
+    else:
+        X, Y = _scale(a, zero_mean), _scale(b, zero_mean)
+        win = ssim_window()
+        ssim = _ssim_torch(X, Y, win)[0].mean(1)
+        ms = _ms_ssim_torch(X, Y, win) if msssim else None
+    if is_video:
+        n = x_input.shape[0]
+        ssim = ssim.reshape(n, -1).mean(1)
+        ms = ms.reshape(n, -1).mean(1) if ms is not None else None
+    return ssim, ms
+
+
+def get_ssim(x_input: torch.Tensor, x_recon: torch.Tensor, zero_mean: bool = False, is_video: bool = False) -> torch.Tensor:
+    """pit/evaluations/ssim.py:5-27: SSIM per item on the [0, 255] scale (``zero_mean``: inputs in [-1, 1], else [0, 1]);
+    ``is_video``: [B, C, T, H, W], the frames' mean."""
+    return _image_quality(x_input, x_recon, zero_mean, is_video, msssim=False)[0]
+
+
+def get_ssim_and_msssim(x_input: torch.Tensor, x_recon: torch.Tensor, zero_mean: bool = False, is_video: bool = False):
+    """pit/evaluations/ssim.py:30-63: (SSIM, MS-SSIM) per item; MS-SSIM is NaN when H or W is under 256."""
+    h, w = x_input.shape[2 + is_video], x_input.shape[3 + is_video]
+    if h < 256 or w < 256:
+        ssim = get_ssim(x_input, x_recon, zero_mean, is_video)
+        return ssim, torch.ones_like(ssim) * torch.nan
+    return _image_quality(x_input, x_recon, zero_mean, is_video, msssim=True)
+
+
 def cal_ent(hist: torch.Tensor):
     """eval.py:137-141 (dead code there): codebook usage (fraction of entries hit at least once)
     and entropy in bits of the usage histogram, with the reference's ``+ 1e-5`` inside the log.  Returns
@@ -186,22 +336,39 @@ def codebook_usage(indices: torch.Tensor, n_codes: int):
 
 @torch.no_grad()
 def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world: int, device,
-                     tokens_per_image: int) -> Optional[Dict[str, torch.Tensor]]:
+                     tokens_per_image: int, metrics: Sequence[str] = ("psnr",)) -> Optional[Dict[str, torch.Tensor]]:
     """The reference eval loop for this path: each rank encodes/decodes its shard, one gather per
-    step, rank 0 returns indices + PSNR in dataset order.  ``images_for(ids) -> [len(ids),3,H,W]``."""
+    step, rank 0 returns indices + PSNR in dataset order.  ``images_for(ids) -> [len(ids),3,H,W]``.
+    ``metrics``: ("psnr",) or ("psnr", "ssim", "ms_ssim") (eval.py:165-178; any order): the three-metric record, still ONE
+    gather per step, and "ssim" / "ms_ssim" in the result too."""
+    names = set(metrics)
+    if names == {"psnr"}:
+        n_metrics = 1
+    elif names == {"psnr", "ssim", "ms_ssim"}:
+        n_metrics = 3
+    else:
+        raise ValueError(f"evaluate_sharded: metrics are ('psnr',) or ('psnr', 'ssim', 'ms_ssim'), got {tuple(metrics)}")
     batches = shard_batches(n_images, world, rank, bs)
-    layout = StepRecord(bs, tokens_per_image, n_metrics=1, check_range=True)
+    layout = StepRecord(bs, tokens_per_image, n_metrics=n_metrics, check_range=True)
     gathered = []
     for ids in batches:
         x = images_for(ids).to(device, non_blocking=True)
         zhat, info = model.encode(x, return_reg_log=True)
         rec_img = model.decode(zhat)
-        rec = layout.pack_with_psnr(info["indices"], x, rec_img)
+        if n_metrics == 1:
+            rec = layout.pack_with_psnr(info["indices"], x, rec_img)
+        else:
+            rec = layout.pack_with_metrics(info["indices"], x, rec_img)
         gathered.append(gather_step(rec, world))
     if rank != 0 or not gathered:
         return None
     allrec = torch.stack(gathered, dim=1)  # [W, steps, words]
-    idx, met = layout.unpack(allrec)       # [W, steps, bs, tokens], [W, steps, bs, 1]
+    idx, met = layout.unpack(allrec)       # [W, steps, bs, tokens], [W, steps, bs, n_metrics]
     per_rank_idx = [idx[r].reshape(-1, tokens_per_image) for r in range(world)]
-    per_rank_psnr = [met[r].reshape(-1) for r in range(world)]
-    return {"indices": reinterleave(per_rank_idx), "psnr": reinterleave(per_rank_psnr)}
+    if n_metrics == 1:
+        per_rank_psnr = [met[r].reshape(-1) for r in range(world)]
+        return {"indices": reinterleave(per_rank_idx), "psnr": reinterleave(per_rank_psnr)}
+    out = {"indices": reinterleave(per_rank_idx)}
+    for k, name in enumerate(("psnr", "ssim", "ms_ssim")):
+        out[name] = reinterleave([met[r][..., k].reshape(-1) for r in range(world)])
+    return out
