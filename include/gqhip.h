@@ -501,6 +501,17 @@ int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int
 int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
                             int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
 
+/* Fused multi-head self-attention forward -- pit/modules/vit.py:142-151 (nn.MultiheadAttention(x, x, x, need_weights=False):
+ * softmax(q k^T / sqrt(d)) v per (batch, head), no mask, no dropout; csrc/gq_attn.h).
+ * qkv: [B, L, 3E] fp32, contiguous, 16-byte aligned: the in-projection output F.linear(x, in_proj_weight, in_proj_bias), read in
+ * place -- q, k, v are its three E-wide column blocks, head h is columns h d .. h d + d - 1 of each.  out: [B, L, E] fp32 with the
+ * heads concatenated (the operand of out_proj).  Head dim d = E / H: 64 is built (any other -> GQHIP_ERR_INVALID_ARG); any L >= 1;
+ * B H <= 65535.  Precision: exact fp32 products on the fp32 matrix cores, fp32 online softmax; S and P never reach memory.
+ * Fixed-order sums: bit-reproducible.  workspace: gq_mha_workspace_bytes(B, L, E, H) bytes (0 today: NULL is fine).
+ * Asynchronous on `stream`, no allocation: graph-capturable. */
+int64_t gq_mha_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H);
+int gq_mha_fwd_f32(const float *qkv, float *out, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace, void *stream);
+
 /* ---- profiling recorder ------------------------------------------------------
  * When enabled, every launch of the MFMA filter kernel is bracketed with
  * hipEvents on its own stream.  gqhip_profile_collect synchronises those

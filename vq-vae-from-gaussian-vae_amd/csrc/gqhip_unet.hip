@@ -13,6 +13,7 @@
 #include "gq_wino_gemm.h"
 #include "gq_conv3.h"
 #include "gq_conv_f32.h"
+#include "gq_attn.h"
 
 using namespace gqhip;
 
@@ -631,6 +632,21 @@ int gqhip_checksum_tensors(const void *table_dev, int64_t count, uint64_t *sums_
   if (hipMemsetAsync(sums_dev, 0, sizeof(uint64_t) * count, st) != hipSuccess) return check_launch();
   hipLaunchKernelGGL(checksum_tensors_kernel, dim3((unsigned)count, kChecksumSlices), dim3(256), 0, st,
                      static_cast<const ChecksumEntry *>(table_dev), reinterpret_cast<unsigned long long *>(sums_dev));
+  return check_launch();
+}
+
+int64_t gq_mha_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H) {
+  (void)B; (void)L; (void)E; (void)H;
+  return 0;   // the fp32 route keeps everything on chip: no scratch
+}
+
+int gq_mha_fwd_f32(const float *qkv, float *out, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace, void *stream) {
+  (void)workspace;
+  if (B < 0 || L < 0 || H < 1 || E != H * kAttnD || B * H > 65535 || L > (int64_t)0x7fffffff / 3 / E) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0 || L == 0) return GQHIP_OK;
+  if (!qkv || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return GQHIP_ERR_INVALID_ARG;
+  const dim3 grid((unsigned)((L + kAttnQRows - 1) / kAttnQRows), (unsigned)(B * H));
+  hipLaunchKernelGGL(mha_fwd_f32_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, (int)L, (int)E, (int)H);
   return check_launch();
 }
 

@@ -111,6 +111,8 @@ _SIGNATURES = {
     "gq_ssim_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp]),
     "gq_step_record_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gq_step_record_ssim_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
+    "gq_mha_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gq_mha_fwd_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "gqhip_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_reserve": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_collect": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -1175,6 +1177,29 @@ def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
                                              image_layout(x), idx.numel(), ws.data_ptr(), ws.numel(), _stream()),
                "gq_step_record_ssim_f32")
     return rec
+
+
+MHA_HEAD_DIMS = (64,)    # head dims gq_mha_fwd_f32 is built for
+_mha_ws: dict = {}
+
+
+def mha_fwd(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(d)) v per (batch, head) from the in-projection output ``qkv`` [B, L, 3E] fp32 on a HIP device,
+    read in place; returns [B, L, E] with the heads concatenated (gqhip.h: gq_mha_fwd_f32; pit/modules/vit.py:142-151)."""
+    qkv = _dev(qkv, torch.float32, "qkv")
+    if qkv.dim() != 3 or qkv.shape[2] % 3 != 0 or heads < 1 or (qkv.shape[2] // 3) % heads != 0:
+        raise GqHipError(f"mha_fwd: qkv must be [B, L, 3E] with E divisible by heads={heads}, got {tuple(qkv.shape)}")
+    B, L, E3 = qkv.shape
+    E = E3 // 3
+    if E // heads not in MHA_HEAD_DIMS:
+        raise GqHipError(f"mha_fwd: head dim {E // heads} is not built (built: {MHA_HEAD_DIMS})")
+    if qkv.data_ptr() % 16 != 0:
+        qkv = qkv.clone()
+    out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
+    ws = _ssim_ws(_mha_ws, (qkv.device, B, L, E, heads), lib().gq_mha_workspace_bytes(B, L, E, heads), qkv.device)
+    with torch.cuda.device(qkv.device):
+        _check(lib().gq_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, E, heads, ws.data_ptr(), _stream()), "gq_mha_fwd_f32")
+    return out
 
 
 def profile_enable(on: bool) -> None:
