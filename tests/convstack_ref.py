@@ -122,8 +122,9 @@ def silu_lip() -> float:
 
 
 def gn_own_error(norm: torch.nn.GroupNorm, x64: torch.Tensor, act: bool) -> torch.Tensor:
-    """What an fp32 evaluation of [swish](GroupNorm(x)) can lose by itself: the statistics (fp32 partial sums: relative 8u of mean
-    and of var), the folded scale / shift, the sigmoid (v_exp + one Newton step: a few ulp)."""
+    """What an fp32 evaluation of [swish](GroupNorm(x)) can lose by itself: the statistics (relative 8u of |mean| + std and of
+    var + eps -- the gate tests/test_gpu_groupnorm_offsets.py holds every statistics producer to, at any mean / std), the folded
+    scale / shift, the sigmoid (v_exp + one Newton step: a few ulp)."""
     xhat, rstd, mean = gn_parts(norm, x64)
     gam = norm.weight.detach().abs()[None, :, None, None]
     bet = norm.bias.detach().abs()[None, :, None, None]

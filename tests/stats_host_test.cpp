@@ -1,6 +1,7 @@
 // Host-side check of csrc/gq_stats.h (CPU suite, no GPU): the integer split of an fp32 addend (stat_add_f32) is
 // bit-identical to the fp64 split (stat_add), sums are order-independent, the value read back is the exact sum of the
-// addends down to 2^-56, and out-of-range addends poison the record.  Built and run by tests/test_host.py.
+// addends down to 2^-56, out-of-range addends poison the record, and the shifted per-thread partials (StatPartial) give
+// the mean and variance of an fp64 two-pass for mean / std up to 1e4, whatever the thread partition.  Built and run by tests/test_host.py.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -71,6 +72,77 @@ int main() {
   stat_add_f32(p, 1.0f, INFINITY);
   stat_load(p, s, ss);
   if (!(s != s) || !(ss != ss)) { std::printf("FAIL: poison not reported\n"); return 1; }
-  std::printf("ok: %zu addends, %zu in the order test\n", vals.size(), fin.size());
+  // 4. shifted partials (StatPartial): groups x = c + sigma N(0, 1) in fp32, c / sigma up to 1e4, plus an outlier that is the
+  //    first value of its thread.  The record read back by the consumers' formula var = SS / n - mean^2 must match an fp64
+  //    two-pass over the same fp32 values to 2^-40 of var + 2^-50 mean^2 (the fp64 floor of that formula; 2^-40 leaves 2^16
+  //    below the 8 x 2^-24 the GPU tests allow), and the same data cut into threads two different ways gives the same sums
+  //    up to the fp64 arithmetic inside a thread and the per-addend truncation at 2^-56.
+  std::normal_distribution<double> gauss(0.0, 1.0);
+  const double ratios[] = {0.0, 1.0, 10.0, 100.0, 1000.0, 1e4};
+  const double sigmas[] = {0x1p-10, 1.0, 0x1p10};
+  const int n = 4096;
+  int cases = 0;
+  for (int outlier = 0; outlier < 2; ++outlier)
+    for (double r : ratios)
+      for (double sg : sigmas) {
+        std::vector<float> x(n);
+        for (int i = 0; i < n; ++i) x[i] = (float)(r * sg + sg * gauss(rng));
+        if (outlier) x[0] = (float)(r * sg + 1000.0 * sg);
+        long double m = 0.0L;
+        for (float v : x) m += v;
+        m /= n;
+        long double v2 = 0.0L;
+        for (float v : x) v2 += ((long double)v - m) * ((long double)v - m);
+        const double mean64 = (double)m, var64 = (double)(v2 / n);
+        int64_t rec[2][kStatWords] = {{0}, {0}};
+        const int per[2] = {64, 16};                     // two thread partitions of the same data
+        for (int k = 0; k < 2; ++k)
+          for (int t0 = 0; t0 < n; t0 += per[k]) {
+            StatPartial p;
+            for (int i = t0; i < t0 + per[k]; ++i) stat_partial_add(p, x[i]);
+            stat_partial_flush(rec[k], p);
+          }
+        for (int k = 0; k < 2; ++k) {
+          double s2, ss2;
+          stat_load(rec[k], s2, ss2);
+          const double mean = s2 / n;
+          double var = ss2 / n - mean * mean;
+          var = var > 0.0 ? var : 0.0;
+          const double dm = std::fabs(mean - mean64), dv = std::fabs(var - var64);
+          if (dm > 0x1p-40 * (std::fabs(mean64) + std::sqrt(var64)) || dv > 0x1p-40 * var64 + 0x1p-50 * mean64 * mean64) {
+            std::printf("FAIL: shifted partials, c/sigma %g sigma %g outlier %d partition %d: mean %.17g vs %.17g, var %.17g vs %.17g\n",
+                        r, sg, outlier, per[k], mean, mean64, var, var64);
+            return 1;
+          }
+        }
+        // the two partitions: the same sums up to the fp64 arithmetic inside a thread ((64 + 2) 2^-53 < 2^-46 of the sum of
+        // squares, charged 2^-44) and the truncation of the addends (n / 16 addends of < 2^-56 each per statistic)
+        double sa, ssa, sb, ssb;
+        stat_load(rec[0], sa, ssa);
+        stat_load(rec[1], sb, ssb);
+        if (std::fabs(sa - sb) > (n / 16) * 0x1p-56 + 0x1p-44 * std::sqrt(n * ssa) ||      // sum |v| <= sqrt(n sum v^2)
+            std::fabs(ssa - ssb) > (n / 16) * 0x1p-56 + 0x1p-44 * std::fabs(ssa)) {
+          std::printf("FAIL: partitions disagree: %.17g %.17g / %.17g %.17g\n", sa, sb, ssa, ssb);
+          return 1;
+        }
+        ++cases;
+      }
+  // order independence of the shifted record: the same threads flushed in reverse order give identical limbs
+  {
+    std::vector<float> x(2048);
+    for (auto &v : x) v = (float)(300.0 + gauss(rng));
+    int64_t a[kStatWords] = {0}, b[kStatWords] = {0};
+    for (int t = 0; t < 32; ++t) { StatPartial p; for (int i = 0; i < 64; ++i) stat_partial_add(p, x[64 * t + i]); stat_partial_flush(a, p); }
+    for (int t = 32; t-- > 0;) { StatPartial p; for (int i = 0; i < 64; ++i) stat_partial_add(p, x[64 * t + i]); stat_partial_flush(b, p); }
+    if (std::memcmp(a, b, sizeof(a)) != 0) { std::printf("FAIL: shifted partials order dependence\n"); return 1; }
+    StatPartial p;                                    // a non-finite value poisons, also as the shift
+    stat_partial_add(p, INFINITY);
+    stat_partial_add(p, 1.0f);
+    int64_t q[kStatWords] = {0};
+    stat_partial_flush(q, p);
+    stat_load(q, s, ss);
+    if (!(s != s)) { std::printf("FAIL: shifted partials: poison not reported\n"); return 1; }
+  }
+  std::printf("ok: %zu addends, %zu in the order test, %d shifted-partial groups\n", vals.size(), fin.size(), cases);
   return 0;
 }

@@ -46,8 +46,8 @@ def _stv(stats):
 
 
 def _stats_follow_output(y, what):
-    """The GroupNorm statistics a kernel leaves with its output are sums over THAT output (fp32 partial sums per thread, exact
-    integer accumulation across threads): relative 2e-6 of the sum of magnitudes."""
+    """The GroupNorm statistics a kernel leaves with its output are sums over THAT output (shifted fp64 partial sums per thread,
+    exact integer accumulation across threads): relative 2e-6 of the sum of magnitudes."""
     st = getattr(y, "_gn_stats", None)
     assert st is not None, what
     y64 = R.d64(y)

@@ -109,7 +109,7 @@ __device__ __forceinline__ void conv3_tap(const unsigned char *A, int dy, const 
 template <int COUT>
 __device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3Tile &t, const f32x16 (&acc)[4][2], int64_t *red,
                                                int tid, int wm, int wn, int c, int h) {
-  float s[2] = {0.f, 0.f}, ss[2] = {0.f, 0.f};
+  StatPartial st[2];
   const int W = p.W;
   constexpr int cout = COUT;
   const long pix0 = ((t.b * p.H + t.y0 + 4 * wm) * W + t.x0 + 4 * h) * cout + t.nb * 128;
@@ -129,15 +129,14 @@ __device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3
       for (int r = 0; r < 16; ++r) {
         const float v = acc[rr][j][r] * p.mscale + pb + rv[rr][r];
         p.y[pix0 + ((long)rr * W + (r & 3) + 8 * (r >> 2)) * cout + n] = v;
-        s[j] += v;
-        ss[j] += v * v;
+        if (p.stats) stat_partial_add(st[j], v);
       }
   }
   if (p.stats) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int g = ((2 * wn + j) * 32 + c) / p.cpg;      // group within this block's 128 channels
-      stat_add_f32(red + kStatWords * g, s[j], ss[j]);
+      stat_partial_flush(red + kStatWords * g, st[j]);
     }
     __syncthreads();
     const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
@@ -682,7 +681,7 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
   }
   // ---- epilogue: register r of lane (c, h) = low-resolution position (y0 + 4 wm + rr, x0 + (r & 3) + 8 (r >> 2) + 4 h), i.e.
   // output pixel (2 y + pa, 2 x + pb); channel (2 wn + j) * 32 + c: every store instruction still writes 128-byte runs ----
-  float s[2] = {0.f, 0.f}, ss[2] = {0.f, 0.f};
+  StatPartial sp[2];
   constexpr int cout = COUT;
   const long W2 = 2L * W;
   const long pix0 = ((t.b * 2L * H + 2 * (t.y0 + 4 * wm) + pa) * W2 + 2 * (t.x0 + 4 * h) + pb) * cout + t.nb * 128;
@@ -696,15 +695,14 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
       for (int r = 0; r < 16; ++r) {
         const float v = acc[rr][j][r] * p.mscale + pbias;
         p.y[pix0 + ((long)rr * 2 * W2 + 2 * ((r & 3) + 8 * (r >> 2))) * cout + n] = v;
-        s[j] += v;
-        ss[j] += v * v;
+        if (p.stats) stat_partial_add(sp[j], v);
       }
   }
   if (p.stats) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int g = ((2 * wn + j) * 32 + c) / p.cpg;      // group within this block's 128 channels
-      stat_add_f32(red + kStatWords * g, s[j], ss[j]);
+      stat_partial_flush(red + kStatWords * g, sp[j]);
     }
     __syncthreads();
     const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image

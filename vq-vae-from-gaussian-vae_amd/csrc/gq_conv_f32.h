@@ -263,7 +263,7 @@ __global__ __launch_bounds__(256) void conv3x3_cin_small_kernel(const ConvInPara
   f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
   if (p.bias) bias4 = *reinterpret_cast<const f32x4 *>(p.bias + 4 * g);
   __syncthreads();
-  float s = 0.0f, ss = 0.0f;
+  StatPartial st;
   for (int pass = 0; pass < (TH * TW) / 16; ++pass) {
     const int q = pass * 8 + pr;                    // pixel pair: pixels 2 q, 2 q + 1 of the tile (row-major)
     const int py = (2 * q) / TW, px = (2 * q) % TW;
@@ -291,12 +291,11 @@ __global__ __launch_bounds__(256) void conv3x3_cin_small_kernel(const ConvInPara
     for (int e = 0; e < 2; ++e) {
       const f32x4 o = {acc[e][0] + bias4.x, acc[e][1] + bias4.y, acc[e][2] + bias4.z, acc[e][3] + bias4.w};
       *reinterpret_cast<f32x4 *>(dst + e * COUT) = o;
-      s += (o.x + o.y) + (o.z + o.w);
-      ss += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
+      if (p.stats) stat_partial_add_vec(st, o);
     }
   }
   if (p.stats) {
-    stat_add_f32(&s_stat[g][0], s, ss);
+    stat_partial_flush(&s_stat[g][0], st);
     __syncthreads();
     const int64_t v = (&s_stat[0][0])[tid];         // 32 groups x 8 words = 256 words: one per thread
     stat_flush_word(p.stats + (long)b * 32 * kStatWords + tid, v);

@@ -4,7 +4,7 @@
 // their output, accumulated across threads and blocks by atomics.  A floating-point atomic sum depends on the order
 // in which the adds land, so the statistics -- and with them the encoder's z and, at a near-tie, a token -- could
 // differ between two runs of the same input (the reference's CPU path is deterministic: pit/quantization/
-// gaussian.py:136-150 sees one z per image).  Here every addend (one thread's fp32 partial sum) is converted EXACTLY
+// gaussian.py:136-150 sees one z per image).  Here every addend (one thread's partial sums: StatPartial below) is converted EXACTLY
 // to a 120-bit fixed-point number held in three signed 64-bit limbs of 40 payload bits each, and the limbs are summed
 // with integer atomics: integer addition is associative, so the total is the exact sum of the addends whatever the
 // order, and the statistics are bit-reproducible by construction.
@@ -67,7 +67,8 @@ __device__ __forceinline__ void stat_add(int64_t *rec, double s, double ss) {
 // The same for a thread's fp32 partial sums (the common case), by integer arithmetic on the fp32 bits: the 24-bit
 // significand m of v = m 2^(e - 150) lands at bit (e - 94) of the fixed-point number, i.e. in limb k = (e - 94) / 40 and,
 // when it straddles, limb k + 1 -- two shifts and at most two atomics instead of ~80 fp64 instructions.  Bit-identical
-// to stat_split((double)v) (tests/test_gpu_convstack_kernels.py compares the kernels that use either form).
+// to stat_split((double)v) (tests/stats_host_test.cpp).  The conv-stack producers no longer add raw fp32 partials (see
+// StatPartial: their variance error grew like (mean / std)^2); the split itself is what the host test pins.
 __device__ __forceinline__ void stat_add_one_f32(int64_t *limbs, int64_t *poison, float v) {
   const unsigned bits = __float_as_uint(v);
   const int e = (int)((bits >> 23) & 0xffu);
@@ -99,6 +100,43 @@ __device__ __forceinline__ void stat_add_f32(int64_t *rec, float s, float ss) {
   stat_add_one_f32(rec, rec + 6, s);
   stat_add_one_f32(rec + 3, rec + 6, ss);
 #endif
+}
+
+// A thread's partial moments of its values v of one group, SHIFTED by the thread's first value v0: d = v - v0 is exact in
+// fp64 (two fp32 values), sum d and sum d^2 accumulate in fp64, and the flush rebuilds sum v = s + n v0 and
+// sum v^2 = ss + v0 (2 s + n v0) in fp64 before the exact limb split.  Why: consumers form var = SS / n - mean^2, so an
+// absolute error e of SS costs e / (n var) of var.  fp32 partials of raw v and v^2 make e ~ 2^-24 n_t SS, i.e. a relative
+// error of var ~ 2^-24 n_t (mean / std)^2 -- 0.3 % at mean / std = 1000 (tests/test_gpu_groupnorm_offsets.py).  Shifted
+// fp64 partials leave ~2^-53 n_t (spread of the thread's d / std)^2 plus 2^-53 (mean / std)^2 for the fp64 rebuild:
+// below 2^-30 of var up to mean / std = 1e4 (tests/stats_host_test.cpp).  fp64 rather than fp32 for d: a thread whose first
+// value is an outlier has d ~ the outlier for all its values, and an fp32 sum of those would cost ~n_t 2^-24 outlier^2 of SS.
+// Every addend is still a function of the thread's own values alone, so the record stays order-independent.
+struct StatPartial {
+  double v0 = 0.0, s = 0.0, ss = 0.0;
+  int n = 0;
+};
+__device__ __forceinline__ void stat_partial_add(StatPartial &p, float v) {
+  if (p.n == 0) p.v0 = (double)v;      // non-finite v0: d = NaN, the record is poisoned as before
+  const double d = (double)v - p.v0;
+  p.s += d;
+  p.ss = __builtin_fma(d, d, p.ss);
+  ++p.n;
+}
+template <typename VEC>
+__device__ __forceinline__ void stat_partial_add_vec(StatPartial &p, VEC v) {
+#pragma unroll
+  for (int e = 0; e < (int)(sizeof(VEC) / sizeof(float)); ++e) stat_partial_add(p, v[e]);
+}
+// (sum v, sum v^2) of the partial, as stat_add takes them
+__device__ __forceinline__ void stat_partial_moments(const StatPartial &p, double &s, double &ss) {
+  const double n = (double)p.n;
+  s = __builtin_fma(n, p.v0, p.s);
+  ss = __builtin_fma(p.v0, __builtin_fma(n, p.v0, 2.0 * p.s), p.ss);
+}
+__device__ __forceinline__ void stat_partial_flush(int64_t *rec, const StatPartial &p) {
+  double s, ss;
+  stat_partial_moments(p, s, ss);
+  stat_add(rec, s, ss);
 }
 
 // word `w` of a block's LDS records -> the same word of the global records (one thread per word)

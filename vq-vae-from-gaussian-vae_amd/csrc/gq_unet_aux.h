@@ -41,14 +41,10 @@ __global__ __launch_bounds__(256) void gn_stats_nhwc_kernel(const float *__restr
   f32x4 pb = {0.f, 0.f, 0.f, 0.f};
   if (pre_bias) pb = *reinterpret_cast<const f32x4 *>(pre_bias + 4 * q);
   const float *base = x + (b * HW) * C + 4 * q;
-  float s = 0.f, ss = 0.f;
-  for (long p = lo + pl; p < hi; p += lanes) {
-    f32x4 v = *reinterpret_cast<const f32x4 *>(base + p * C) + pb;
-    s += (v.x + v.y) + (v.z + v.w);
-    ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-  }
+  StatPartial st;
+  for (long p = lo + pl; p < hi; p += lanes) stat_partial_add_vec(st, *reinterpret_cast<const f32x4 *>(base + p * C) + pb);
   const int g = (4 * q) / cpg;
-  stat_add_f32(red + kStatWords * g, s, ss);
+  stat_partial_flush(red + kStatWords * g, st);
   __syncthreads();
   for (int w = threadIdx.x; w < kStatWords * groups; w += 256) stat_flush_word(stats + kStatWords * (b * groups) + w, red[w]);
 }
@@ -124,15 +120,14 @@ __global__ __launch_bounds__(256) void add_bias_stats_nhwc_kernel(const float *_
   f32x4 pb = {0.f, 0.f, 0.f, 0.f};
   if (bias) pb = *reinterpret_cast<const f32x4 *>(bias + 4 * q);
   const long off = (bi * HW) * C + 4 * q;
-  float s = 0.f, ss = 0.f;
+  StatPartial st;
   for (long p = lo + pl; p < hi; p += lanes) {
     const f32x4 v = *reinterpret_cast<const f32x4 *>(a + off + p * C) + *reinterpret_cast<const f32x4 *>(b + off + p * C) + pb;
     *reinterpret_cast<f32x4 *>(y + off + p * C) = v;
-    s += (v.x + v.y) + (v.z + v.w);
-    ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    stat_partial_add_vec(st, v);
   }
   const int g = (4 * q) / cpg;
-  stat_add_f32(red + kStatWords * g, s, ss);
+  stat_partial_flush(red + kStatWords * g, st);
   __syncthreads();
   for (int w = threadIdx.x; w < kStatWords * groups; w += 256) stat_flush_word(stats + kStatWords * (bi * groups) + w, red[w]);
 }
@@ -539,7 +534,7 @@ __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__r
   vec pb = (vec)(0.f);
   if (bias) pb = reinterpret_cast<const vec *>(bias)[q];
   const long plane = tiles * CV;
-  float s = 0.f, ss = 0.f;
+  StatPartial st;
   for (long ti = lo + tl; ti < hi; ti += lanes) {
     const int tw = (int)(ti % (W / T)), th = (int)(ti / (W / T));
     const vec *mi = reinterpret_cast<const vec *>(M) + (b * tpi + ti) * CV + q;
@@ -587,18 +582,12 @@ __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__r
         vec v = o[j] * mscale + pb;
         if (res) v = v + r[i][j];
         reinterpret_cast<vec *>(y)[off] = v;
-        if constexpr (VW == 4) {
-          s += (v.x + v.y) + (v.z + v.w);
-          ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        } else {
-          s += v.x + v.y;
-          ss += v.x * v.x + v.y * v.y;
-        }
+        stat_partial_add_vec(st, v);
       }
     }
   }
   const int g = (VW * q) / cpg;
-  stat_add_f32(red + kStatWords * g, s, ss);
+  stat_partial_flush(red + kStatWords * g, st);
   __syncthreads();
   for (int w = threadIdx.x; w < kStatWords * groups; w += 256) stat_flush_word(stats + kStatWords * (b * groups) + w, red[w]);
 }
@@ -646,8 +635,8 @@ __global__ __launch_bounds__(256) void add_bias_kernel(const float *__restrict__
 }
 
 // ---- fused GroupNorm (+SiLU), NCHW fp32 --------------------------------------------
-// stats: each block reduces a contiguous slice of one (b, g) chunk; fp32 per-thread partials,
-// fp64 across threads/blocks (two atomics per block).
+// stats: each block reduces a contiguous slice of one (b, g) chunk; shifted fp64 per-thread partials (gq_stats.h:
+// StatPartial), fp64 across the block's threads in a fixed order, the exact limb sum across blocks.
 // pre_bias (nullable, [C]): a per-channel bias still pending on x (the producing conv ran without
 // its bias); it is added on the fly so the separate bias pass disappears.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__ x, const float *__restrict__ pre_bias,
@@ -659,14 +648,14 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float *__restrict__
   const long lo = sl * per, hi = lo + per < chunk ? lo + per : chunk;
   const float *base = x + bg * chunk;
   const int c0 = (int)(bg % groups) * cpg;
-  float s = 0.f, q = 0.f;
+  StatPartial st;
   for (long i = lo + threadIdx.x * 4; i + 3 < hi; i += 256 * 4) {
     f32x4 v = *reinterpret_cast<const f32x4 *>(base + i);
     if (pre_bias) v = v + pre_bias[c0 + (int)(i / HW)];
-    s += (v.x + v.y) + (v.z + v.w);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    stat_partial_add_vec(st, v);
   }
-  double ds = (double)s, dq = (double)q;
+  double ds, dq;
+  stat_partial_moments(st, ds, dq);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     ds += __shfl_xor(ds, o);
