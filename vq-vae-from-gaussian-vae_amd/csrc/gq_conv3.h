@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "gq_common.h"
+#include "gq_epilogue.h"
 #include "gq_stats.h"
 #include "gq_wino_gemm.h"
 
@@ -102,46 +103,37 @@ __device__ __forceinline__ void conv3_tap(const unsigned char *A, int dy, const 
   }
 }
 
-// Epilogue: register r of lane (c, h) = pixel x0 + (r & 3) + 8 (r >> 2) + 4 h of row y0 + 4 wm + rr, channel
-// (2 wn + j) * 32 + c: a store of one register is two 128-byte runs.
-// COUT is a template parameter: with a run-time channel stride none of the 128 loads / 128 stores of a lane has a constant
-// offset and hipcc materialises their addresses (~300 bytes of scratch per lane).
+// Epilogue: * mscale + bias (+ residual), store, GroupNorm statistics of the result -- through LDS (gq_epilogue.h): lane l of
+// wave (wm, wn) handles channels wn * 64 + 4 (l & 15) .. + 3 of pixels x0 + (l >> 4) + 4 i (i < 8) of rows y0 + 4 wm + rr, so
+// its values fall into one group (cpg is a multiple of 4) and one StatPartial holds them.  `sA` is free: the main loop ended
+// with a barrier.  COUT is a template parameter: the stride between a lane's pixels (4 COUT) is then a constant.  The lane
+// index is read afresh (mbcnt) rather than kept from the prologue: no VGPR then lives across the main loop for it.
 template <int COUT>
-__device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3Tile &t, const f32x16 (&acc)[4][2], int64_t *red,
-                                               int tid, int wm, int wn, int c, int h) {
-  StatPartial st[2];
-  const int W = p.W;
+__device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3Tile &t, const f32x16 (&acc)[4][2], unsigned char *sA,
+                                               int64_t *red, int wave, int wm, int wn) {
   constexpr int cout = COUT;
-  const long pix0 = ((t.b * p.H + t.y0 + 4 * wm) * W + t.x0 + 4 * h) * cout + t.nb * 128;
+  const int lane = __lane_id(), tid = wave * 64 + lane;
+  const int n = wn * 64 + 4 * (lane & 15);   // the lane's channel quad within the block's 128
+  float *stage = reinterpret_cast<float *>(sA + wave * kEpiWaveBytes);
+  f32x4 pb = {0.f, 0.f, 0.f, 0.f};
+  if (p.bias) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = (2 * wn + j) * 32 + c;
-    const float pb = p.bias ? p.bias[t.nb * 128 + n] : 0.f;
-    float rv[4][16];   // the 64 residual values of this column tile in flight at once
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        rv[rr][r] = p.res ? p.res[pix0 + ((long)rr * W + (r & 3) + 8 * (r >> 2)) * cout + n] : 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = acc[rr][j][r] * p.mscale + pb + rv[rr][r];
-        p.y[pix0 + ((long)rr * W + (r & 3) + 8 * (r >> 2)) * cout + n] = v;
-        if (p.stats) stat_partial_add(st[j], v);
-      }
+    for (int e = 0; e < 4; ++e) pb[e] = p.bias[t.nb * 128 + n + e];
   }
-  if (p.stats) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int g = ((2 * wn + j) * 32 + c) / p.cpg;      // group within this block's 128 channels
-      stat_partial_flush(red + kStatWords * g, st[j]);
-    }
-    __syncthreads();
-    const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
-    if (tid < kStatWords * gpb) stat_flush_word(p.stats + kStatWords * (t.b * groups + t.nb * gpb) + tid, red[tid]);
+  const long o = ((t.b * p.H + t.y0 + 4 * wm) * p.W + t.x0 + (lane >> 4)) * cout + t.nb * 128 + n;
+  const long slice = (long)p.W * cout;
+  StatPartial st;
+  if (!p.stats) {
+    if (p.res) epi_store<3, false>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
+    else epi_store<2, false>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
+    return;
   }
+  if (p.res) epi_store<3, true>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
+  else epi_store<2, true>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
+  stat_partial_flush(red + kStatWords * (n / p.cpg), st);
+  __syncthreads();
+  const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
+  if (tid < kStatWords * gpb) stat_flush_word(p.stats + kStatWords * (t.b * groups + t.nb * gpb) + tid, red[tid]);
 }
 
 #define GQ_C3_ZERO_ACC(acc)                                                                                         \
@@ -296,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
 #if defined(GQHIP_ABL) && (GQHIP_ABL & 512)         // diagnostic build: no epilogue
   if (acc[0][0][0] == 12345.678f)
 #endif
-  conv3_epilogue<COUT>(p, t, acc, red, tid, wm, wn, c, h);
+  conv3_epilogue<COUT>(p, t, acc, sA, red, wave, wm, wn);
 #ifdef GQHIP_CLOCK_STAMPS
   if (tid == 0 && blockIdx.x < 8192) {
     unsigned long long *o = g_c3_stamps + 4 * blockIdx.x;
@@ -434,7 +426,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
   }
-  conv3_epilogue<COUT>(p, t, acc, red, tid, wm, wn, c, h);
+  conv3_epilogue<COUT>(p, t, acc, sA, red, wave, wm, wn);
 }
 
 // ---- 3x3 convolution with stride 2 on an input padded by one zero row / column at the bottom / right (Downsample,
@@ -562,7 +554,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_f16x3_kernel(const Conv3S2Pa
   for (int chunk = 0; chunk < nch; ++chunk) run_unit(I2{}, I0{}, I1{}, chunk);
   for (int chunk = 0; chunk < nch; ++chunk) run_unit(I2{}, I1{}, I0{}, chunk);
   for (int chunk = 0; chunk < nch; ++chunk) run_unit(I1{}, I1{}, I1{}, chunk);
-  conv3_epilogue<COUT>(p, t, acc, red, tid, wm, wn, c, h);
+  conv3_epilogue<COUT>(p, t, acc, sA, red, wave, wm, wn);
 }
 
 // ---- "nearest x2 upsample, then 3x3 convolution" (Upsample, unet.py:60-73) as its sub-pixel form, computed directly: output
@@ -679,35 +671,28 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
     if (more) commit((chunk + 1) & 1);
     __syncthreads();
   }
-  // ---- epilogue: register r of lane (c, h) = low-resolution position (y0 + 4 wm + rr, x0 + (r & 3) + 8 (r >> 2) + 4 h), i.e.
-  // output pixel (2 y + pa, 2 x + pb); channel (2 wn + j) * 32 + c: every store instruction still writes 128-byte runs ----
-  StatPartial sp[2];
+  // ---- epilogue (gq_epilogue.h): lane l of wave (wm, wn) -> channels wn * 64 + 4 (l & 15) .. + 3 of the low-resolution positions
+  // (y0 + 4 wm + rr, x0 + (l >> 4) + 4 i), i.e. of output pixels (2 y + pa, 2 x + pb): a pixel's 256 bytes are still one run ----
   constexpr int cout = COUT;
+  const int n = wn * 64 + 4 * (lane & 15);
+  f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+  if (p.bias) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bias4[e] = p.bias[t.nb * 128 + n + e];
+  }
+  float *stage = reinterpret_cast<float *>(sA + wave * kEpiWaveBytes);
   const long W2 = 2L * W;
-  const long pix0 = ((t.b * 2L * H + 2 * (t.y0 + 4 * wm) + pa) * W2 + 2 * (t.x0 + 4 * h) + pb) * cout + t.nb * 128;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int n = (2 * wn + j) * 32 + c;
-    const float pbias = p.bias ? p.bias[t.nb * 128 + n] : 0.f;
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = acc[rr][j][r] * p.mscale + pbias;
-        p.y[pix0 + ((long)rr * 2 * W2 + 2 * ((r & 3) + 8 * (r >> 2))) * cout + n] = v;
-        if (p.stats) stat_partial_add(sp[j], v);
-      }
+  const long o = ((t.b * 2L * H + 2 * (t.y0 + 4 * wm) + pa) * W2 + 2 * (t.x0 + (lane >> 4)) + pb) * cout + t.nb * 128 + n;
+  StatPartial sp;
+  if (!p.stats) {
+    epi_store<1, false>(acc, stage, lane, p.y, nullptr, o, 2 * W2 * cout, 8 * cout, p.mscale, bias4, sp);
+    return;
   }
-  if (p.stats) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int g = ((2 * wn + j) * 32 + c) / p.cpg;      // group within this block's 128 channels
-      stat_partial_flush(red + kStatWords * g, sp[j]);
-    }
-    __syncthreads();
-    const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
-    if (tid < kStatWords * gpb) stat_flush_word(p.stats + kStatWords * (t.b * groups + t.nb * gpb) + tid, red[tid]);
-  }
+  epi_store<1, true>(acc, stage, lane, p.y, nullptr, o, 2 * W2 * cout, 8 * cout, p.mscale, bias4, sp);
+  stat_partial_flush(red + kStatWords * (n / p.cpg), sp);
+  __syncthreads();
+  const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
+  if (tid < kStatWords * gpb) stat_flush_word(p.stats + kStatWords * (t.b * groups + t.nb * gpb) + tid, red[tid]);
 }
 
 // ---- 3x3 convolution (stride 1, zero padding 1) into a handful of channels (conv_out: 128 -> 3, unet.py:585-587) with the
