@@ -23,6 +23,8 @@
  *                    and the group permutes into the kernels.
  *   gq_dequant_f32   pit/quantization/gaussian.py:162-178, :347-362.
  *   gq_quantize_z_gauss_f32  pit/quantization/gaussian.py:211-271,273-345 (GaussianQuantRegularizer2.forward, eval).
+ *   gq_gauss_train_f32 / gq_gauss_backward_f32  pit/quantization/gaussian.py:77-119 (GaussianQuantRegularizer.forward in
+ *                    train()) and the autograd backward of it and of GaussianQuantRegularizer2.forward.
  *   vq_argmin_f32    pit/quantization/vq.py:58-73.
  *   vq_quantize_z_f32 pit/quantization/vq.py:39-96 (VQQuantizer.forward, eval).
  *   lfq_pack_f32     pit/quantization/lfq.py:147-158.
@@ -53,7 +55,8 @@ extern "C" {
                                * 8: module-level eval forwards of GaussianQuantRegularizer2 (gq_quantize_z_gauss_f32: the Gaussian branch's
                                *    statistics and lambda state on the device) and VQQuantizer (vq_quantize_z_f32: layouts, straight-through
                                *    value and codebook loss inside the launches); additive since, the version unchanged: per-image SSIM /
-                               *    MS-SSIM (gq_ssim_f32) and the three-metric step record (gq_step_record_ssim_f32) */
+                               *    MS-SSIM (gq_ssim_f32), the three-metric step record (gq_step_record_ssim_f32), the train-mode step of the Gaussian
+                               *    regularizers (gq_gauss_train_f32, gq_gauss_backward_f32) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -219,6 +222,45 @@ int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb,
                             double lv_max, double beta, int use_ste, double log2n, double tolerance, double lam_factor,
                             double lam_lo, double lam_hi, int lam_max_decreases, void *workspace, int64_t workspace_bytes,
                             void *cb_cache_or_null, int64_t cb_cache_bytes, void *stream);
+
+/* ---- the train-mode step of the Gaussian regularizers: GaussianQuantRegularizer.forward in train()
+ * (pit/quantization/gaussian.py:77-119) as ONE call -- an elementwise launch + the one-block statistics launch of
+ * gq_quantize_z_gauss_f32 -- with no codebook and no workspace (csrc/gq_gauss_train.h).  Layouts and groupings as above:
+ *   zhat (layout of zhat above) = mu + noise * sd, sd = float(exp(double(0.5f * logvar))), logvar clamped to [lv_min, lv_max] (NaN
+ *       propagates), every fp32 op rounded separately; sd_out_or_null receives sd in the same layout;
+ *   kl2row (caller-owned, rows = B L K floats, row = (b L + l) K + k): per row the fp64 sum, in ascending g, of
+ *       1.4426 * 0.5 * (mu^2 + var - 1 - logvar) (the element in the reference's fp32 op order), rounded once -- the values
+ *       gq_quantize_z_gauss_f32 reduces;
+ *   scalars_out / lam_state / log2n / tolerance / lam_factor / lam_lo / lam_hi / lam_max_decreases: as gq_quantize_z_gauss_f32
+ *       (same 64 bytes, same fixed-order reduction, same fp64 state machine; GQ1's train branch passes lam_max_decreases = 1);
+ *   loss_divisor (> 0): kl_loss = sum(ge kl2 + eq kl2 + le kl2) / loss_divisor * lam -- B for GQ1 (gaussian.py:96-98:
+ *       sum over [1, 2], sum / B), rows for a mean (gaussian.py:241; then scalars_out and lam_state are bit-identical to
+ *       gq_quantize_z_gauss_f32's on the same z and state).
+ * Accesses are 16 bytes wide along the contiguous axis (L for BCHW, c for BLC) when the shape and the pointers allow (L % 4 == 0;
+ * K % 4 == 0 or dim % 4 == 0; 16-byte aligned tensors), 4 bytes otherwise.  rows == 0: GQHIP_OK, nothing is launched. */
+int gq_gauss_train_f32(const float *z, const float *noise, float *zhat, float *sd_out_or_null, float *kl2row, void *scalars_out,
+                       double *lam_state, int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping, double lv_min,
+                       double lv_max, double log2n, double tolerance, double lam_factor, double lam_lo, double lam_hi,
+                       int lam_max_decreases, double loss_divisor, void *stream);
+
+/* ---- the backward of both train-mode forwards (gq_gauss_train_f32; gq_quantize_z_gauss_f32 under autograd) in ONE elementwise
+ * launch that writes the whole grad_z (layout of z: the mu half and the logvar half).
+ *   z, noise: the forward's; g_zhat_or_null / g_sd_or_null (layout of zhat): gradients arriving at zhat (for GQ2 with the straight-
+ *   through mix: at zhat plus at zhat_noquant, summed by the caller) and at sd; g_kl_or_null: ONE float on the device, the gradient
+ *   arriving at kl_loss; NULL = zero.  lam_before (device double[3], 8-byte aligned): { lam, lam_min, lam_max } as they were BEFORE
+ *   the forward's update (a device copy taken ahead of the forward call); thresholds, clamp, layout, grouping and loss_divisor as
+ *   the forward's.  Per row the kernel recomputes kl2 with the forward's function and order, so its class is the forward's:
+ *       w(row) = (float)lam_max if kl2 > float(log2n + tol), (float)lam_min if kl2 < float(log2n - tol), 1 otherwise
+ *       coef   = g_kl * (float)lam * w(row) / loss_divisor
+ *       grad_mu     = g_zhat + coef * 1.4426 * mu
+ *       grad_logvar = inside ? g_zhat * noise * 0.5 * sd + g_sd * 0.5 * sd + coef * 1.4426 * 0.5 * (var - 1) : 0
+ *   inside = (lv_min <= logvar <= lv_max) on the unclamped value (torch.clamp's gradient mask); sd / var = fp64 exp rounded once,
+ *   1.4426 * 0.5 = float(0.7213) as in the forward.  Error against an fp64 evaluation: a few 2^-24 of the sum of |terms|
+ *   (tests/test_gpu_train_step.py).  Reads nothing from the host, no atomics: graph-capturable like the forward. */
+int gq_gauss_backward_f32(const float *z, const float *noise, const float *g_zhat_or_null, const float *g_sd_or_null,
+                          const float *g_kl_or_null, const double *lam_before, float *grad_z, int64_t B, int64_t L, int64_t c,
+                          int64_t dim, int layout, int grouping, double lv_min, double lv_max, double log2n, double tolerance,
+                          double loss_divisor, void *stream);
 
 /* zhat from indices (same layouts as above). */
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B,

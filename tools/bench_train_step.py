@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Time one training step (forward + backward) through the Gaussian regularizers alone, on the device.
+
+    python tools/bench_train_step.py [--root TREE] [--iters 200] [--warmup 20] [--label NAME]
+
+Modules: GaussianQuantRegularizer("bchw", 65536, group=16) in train() and GaussianQuantRegularizer2(16, 65536) under autograd, on
+z = [16, 32, 32, 32] and [16, 32, 64, 64] (gq_0.25 at 256^2 and 512^2), NCHW and channels_last.  A step is
+    zhat, info = m(z);  ((zhat * w).sum() + 0.37 * info["kl_loss"]).backward()
+`--iters` timed steps after `--warmup`, in 10 batches, each between two device events (the time between the events includes whatever
+the host makes the device wait for, which is the point: the op-by-op path stops the host three times per step).  Prints one JSON line
+per (module, shape, layout): median / min / max over the batches of the per-step time in microseconds.
+
+`--root TREE` imports pit_hip from another checkout (its libgqhip.so must be built): the A/B against a parent commit runs this same
+script against both trees, alternating, in one session (profiles/README.md).  GQHIP_TRAIN_FUSED=0 in the environment selects the
+torch path of the current tree instead."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'")
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.join(a.root, "vq-vae-from-gaussian-vae_amd"))
+    import torch
+
+    from pit_hip.quantization.gaussian import GaussianQuantRegularizer, GaussianQuantRegularizer2
+
+    assert torch.cuda.is_available(), "needs a HIP device"
+    dev = torch.device("cuda:0")
+    batches = 10
+    per = max(1, a.iters // batches)
+    for kind in ("gq1", "gq2"):
+        if a.only and a.only not in kind:
+            continue
+        for hw in (32, 64):
+            for channels_last in (False, True):
+                g = torch.Generator().manual_seed(hw)
+                z = torch.cat([0.95 * torch.randn(16, 16, hw, hw, generator=g), -0.9 + 0.5 * torch.randn(16, 16, hw, hw, generator=g)], 1)
+                z, w = z.to(dev), torch.randn(16, 16, hw, hw, generator=g).to(dev)
+                if channels_last:
+                    z, w = z.contiguous(memory_format=torch.channels_last), w.contiguous(memory_format=torch.channels_last)
+                z.requires_grad_(True)
+                m = (GaussianQuantRegularizer("bchw", 65536, group=16) if kind == "gq1" else GaussianQuantRegularizer2(16, 65536))
+                m = m.to(dev).train()
+
+                def step():
+                    z.grad = None
+                    zhat, info = m(z)
+                    ((zhat * w).sum() + 0.37 * info["kl_loss"]).backward()
+
+                for _ in range(a.warmup):
+                    step()
+                torch.cuda.synchronize()
+                times = []
+                for _ in range(batches):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(per):
+                        step()
+                    e1.record()
+                    e1.synchronize()
+                    times.append(e0.elapsed_time(e1) * 1e3 / per)
+                print(json.dumps({"label": a.label, "module": kind, "z": [16, 32, hw, hw], "channels_last": channels_last,
+                                  "steps": per * batches, "us_median": round(statistics.median(times), 2),
+                                  "us_min": round(min(times), 2), "us_max": round(max(times), 2),
+                                  "fused": os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -74,8 +74,9 @@ struct GaussStatsParams {
   double lam_factor, lam_lo, lam_hi;
   float thr_hi, thr_lo, log2n;      // float(n + tol), float(n - tol), float(n): torch compares the fp32 tensor with the scalar cast to fp32
   int lam_max_decreases;    // 1: gaussian.py:109-112 (GQ1); 0: GQ2, whose decrease is a no-op expression (gaussian.py:251)
+  double loss_divisor;      // kl_loss = sum(weighted kl2) / loss_divisor * lam: rows for GQ2's mean (gaussian.py:241), B for GQ1 (gaussian.py:96-98)
 };
-static_assert(sizeof(GaussStatsParams) == 72, "fits the header's pad");
+static_assert(sizeof(GaussStatsParams) == 80, "fits the header's pad");
 
 // Workspace header (first 8 KiB of the caller's workspace).  Everything in it is (re)written by the kernels of ONE
 // call: gq_prep_kernel resets the counters and writes the max|cb| partials, the re-rank reduces them per wave.
@@ -98,7 +99,7 @@ struct WsHeader {
   float absmax_part[kAbsmaxParts];    // one partial per code block of gq_prep_kernel
   unsigned long long stamps[48];      // diagnostic builds only (GQHIP_CLOCK_STAMPS)
   GaussStatsParams gs;                // gs.rows > 0: the re-rank launch carries one extra block that runs gauss_stats_block (written by the first launch)
-  int pad2[110];
+  int pad2[108];
   float r2_part[kAbsmaxParts];        // max squared code norm per code block (fp16 filter's norm bound, gq_rerank.h)
   int pad3[256];
   unsigned long long cbsum[kAbsmaxParts];   // content hash of the codebook slice each code block of gq_prep_kernel read in THIS call

@@ -92,7 +92,7 @@ __device__ __forceinline__ void gauss_stats_block(const GaussStatsParams &p) {
   const float qnan = __builtin_nanf("");
   const float mean = (float)(a / (double)p.rows);
   const float kmin = any_nan ? qnan : fmn, kmax = any_nan ? qnan : fmx;                 // torch.min / max propagate NaN
-  const float wmean = (float)(b / (double)p.rows);
+  const float wmean = (float)(b / p.loss_divisor);                                      // GQ2: the mean (divisor = rows); GQ1: sum / B
   const float kl_loss = wmean * (float)lam;                                             // torch.mean(kl_loss) * self.lam
   double l = lam, lmin = lam_min, lmax = lam_max;
   const double f = p.lam_factor;

@@ -18,6 +18,7 @@
 #include "gq_common.h"
 #include "gq_filter.h"
 #include "gq_filter_bf16.h"
+#include "gq_gauss_train.h"
 #include "gq_grid.h"
 #include "gq_prep.h"
 #include "gq_rerank.h"
@@ -792,6 +793,7 @@ int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb,
   gp.rows = (long)rows; gp.lam_state = lam_state; gp.scalars = scalars_out;
   gp.thr_hi = (float)(log2n + tolerance); gp.thr_lo = (float)(log2n - tolerance); gp.log2n = (float)log2n;
   gp.lam_factor = lam_factor; gp.lam_lo = lam_lo; gp.lam_hi = lam_hi; gp.lam_max_decreases = lam_max_decreases;
+  gp.loss_divisor = (double)rows;                    // the mean of gaussian.py:241
   bool stats_done = false;
   in.gs = gp; in.stats_done = &stats_done;
   int rc = run_argmax<kModeGQ>(in, nullptr, nullptr, nullptr, cb, idx, zhat, dim, rows, n, beta, workspace, workspace_bytes,
@@ -799,6 +801,97 @@ int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb,
   if (rc != GQHIP_OK || stats_done) return rc;       // dims 8 / 16 / 32: the statistics block ran as one extra block of the re-rank launch
   gp.kl2row = reinterpret_cast<const float *>(static_cast<char *>(workspace) + ws_layout(rows, n, dim).kl2);
   hipLaunchKernelGGL(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st, gp);
+  return check_launch();
+}
+
+// ---- the train-mode step of the Gaussian regularizers (gq_gauss_train.h) ----
+namespace {
+// which slab form serves this shape with 16-byte accesses (gq_gauss_train.h): 0 = one element per thread step (every shape),
+// 1 = four rows wide, 2 = four g wide; `ptr_bits` = the OR of every pointer the kernel vectorises
+int train_variant(int layout, int grouping, int64_t dim, int64_t K, int64_t L, uintptr_t ptr_bits, long rows, long *items) {
+  const bool al = (ptr_bits & 15u) == 0;
+  if (layout == GQHIP_LAYOUT_BCHW) {
+    if (al && L % 4 == 0) { *items = rows / 4; return 1; }
+  } else {
+    if (al && (grouping == GQHIP_GROUP_CONTIGUOUS || K == 1) && dim % 4 == 0) { *items = rows; return 2; }
+    if (al && grouping == GQHIP_GROUP_STRIDED && K % 4 == 0) { *items = rows / 4; return 1; }
+  }
+  *items = rows;
+  return 0;
+}
+unsigned train_grid(long items) {
+  const long blocks = (items + 255) / 256;
+  return (unsigned)(blocks < kTrainMaxBlocks ? blocks : kTrainMaxBlocks);
+}
+bool train_shape_ok(int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping) {
+  if (B < 0 || L < 1 || c < 1 || dim < 1 || dim > kMaxDim || c % dim != 0) return false;
+  return (layout == GQHIP_LAYOUT_BCHW || layout == GQHIP_LAYOUT_BLC) &&
+         (grouping == GQHIP_GROUP_STRIDED || grouping == GQHIP_GROUP_CONTIGUOUS);
+}
+}  // namespace
+
+int gq_gauss_train_f32(const float *z, const float *noise, float *zhat, float *sd_out_or_null, float *kl2row, void *scalars_out,
+                       double *lam_state, int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping, double lv_min,
+                       double lv_max, double log2n, double tolerance, double lam_factor, double lam_lo, double lam_hi,
+                       int lam_max_decreases, double loss_divisor, void *stream) {
+  if (!z || !noise || !zhat || !kl2row || !scalars_out || !lam_state || !train_shape_ok(B, L, c, dim, layout, grouping))
+    return GQHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(scalars_out) & 7u) || (reinterpret_cast<uintptr_t>(lam_state) & 7u)) return GQHIP_ERR_INVALID_ARG;
+  const int64_t K = c / dim, rows = B * L * K;
+  if (rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
+  if (rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  GaussTrainParams p{};
+  p.z = z; p.noise = noise; p.zhat = zhat; p.sd_out = sd_out_or_null; p.kl2row = kl2row;
+  p.lv_min = (float)lv_min; p.lv_max = (float)lv_max;
+  p.dim = (int)dim; p.K = (int)K; p.L = (int)L; p.c = (int)c;
+  p.layout = layout == GQHIP_LAYOUT_BCHW ? 1 : 2; p.grouping = grouping;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(zhat) |
+                         reinterpret_cast<uintptr_t>(sd_out_or_null);
+  const int variant = train_variant(layout, grouping, dim, K, L, bits, (long)rows, &p.items);
+  const dim3 grid(train_grid(p.items));
+  switch (variant) {
+    case 1: hipLaunchKernelGGL((gauss_train_fwd_kernel<4, false>), grid, dim3(256), 0, st, p); break;
+    case 2: hipLaunchKernelGGL((gauss_train_fwd_kernel<4, true>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((gauss_train_fwd_kernel<1, false>), grid, dim3(256), 0, st, p);
+  }
+  int rc = check_launch();
+  if (rc != GQHIP_OK) return rc;
+  GaussStatsParams gp{};
+  gp.kl2row = kl2row; gp.rows = (long)rows; gp.lam_state = lam_state; gp.scalars = scalars_out;
+  gp.thr_hi = (float)(log2n + tolerance); gp.thr_lo = (float)(log2n - tolerance); gp.log2n = (float)log2n;
+  gp.lam_factor = lam_factor; gp.lam_lo = lam_lo; gp.lam_hi = lam_hi; gp.lam_max_decreases = lam_max_decreases;
+  gp.loss_divisor = loss_divisor;
+  hipLaunchKernelGGL(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st, gp);      // the second launch: same stream, in order
+  return check_launch();
+}
+
+int gq_gauss_backward_f32(const float *z, const float *noise, const float *g_zhat_or_null, const float *g_sd_or_null,
+                          const float *g_kl_or_null, const double *lam_before, float *grad_z, int64_t B, int64_t L, int64_t c,
+                          int64_t dim, int layout, int grouping, double lv_min, double lv_max, double log2n, double tolerance,
+                          double loss_divisor, void *stream) {
+  if (!z || !noise || !lam_before || !grad_z || !train_shape_ok(B, L, c, dim, layout, grouping)) return GQHIP_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(lam_before) & 7u) || (reinterpret_cast<uintptr_t>(g_kl_or_null) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  const int64_t K = c / dim, rows = B * L * K;
+  if (rows == 0) return GQHIP_OK;
+  if (rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
+  GaussTrainParams p{};
+  p.z = z; p.noise = noise; p.g_zhat = g_zhat_or_null; p.g_sd = g_sd_or_null; p.g_kl = g_kl_or_null;
+  p.lam_before = lam_before; p.grad_z = grad_z; p.divisor = loss_divisor;
+  p.thr_hi = (float)(log2n + tolerance); p.thr_lo = (float)(log2n - tolerance);
+  p.lv_min = (float)lv_min; p.lv_max = (float)lv_max;
+  p.dim = (int)dim; p.K = (int)K; p.L = (int)L; p.c = (int)c;
+  p.layout = layout == GQHIP_LAYOUT_BCHW ? 1 : 2; p.grouping = grouping;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(g_zhat_or_null) |
+                         reinterpret_cast<uintptr_t>(g_sd_or_null) | reinterpret_cast<uintptr_t>(grad_z);
+  const int variant = train_variant(layout, grouping, dim, K, L, bits, (long)rows, &p.items);
+  const dim3 grid(train_grid(p.items));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (variant) {
+    case 1: hipLaunchKernelGGL((gauss_train_bwd_kernel<4, false>), grid, dim3(256), 0, st, p); break;
+    case 2: hipLaunchKernelGGL((gauss_train_bwd_kernel<4, true>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((gauss_train_bwd_kernel<1, false>), grid, dim3(256), 0, st, p);
+  }
   return check_launch();
 }
 

@@ -51,6 +51,12 @@ _SIGNATURES = {
                                                ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_double, ctypes.c_int, _vp, _i64, _vp, _i64, _vp]),
+    "gq_gauss_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp]),
+    "gq_gauss_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                             _vp]),
     "vq_quantize_z_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
                                          ctypes.c_int, _vp, _i64, _vp, _i64, _vp]),
     "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
@@ -361,6 +367,84 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
                                              float(lam_range[0]), float(lam_range[1]), 1 if lam_max_decreases else 0,
                                              wptr, wbytes, cptr, cbytes, _stream()), "gq_quantize_z_gauss_f32")
     return idx, zhat, (pure if use_ste else zhat), noquant, std, scalars
+
+
+def _z_geometry(z, dim: int, layout: str):
+    """(B, L, c, K, rows, shape of zhat) of an encoder output z holding [mu | logvar] in a module layout (gqhip.h)."""
+    if layout == "bchw":
+        B, c2, L = z.shape[0], z.shape[1], int(z[0, 0].numel())
+        c = c2 // 2
+        shape = (B, c) + tuple(z.shape[2:])
+    else:
+        B, L, c2 = z.shape
+        c = c2 // 2
+        shape = (B, L, c)
+    K = c // dim
+    return B, L, c, K, B * L * K, shape
+
+
+def _lam_ok(t, name: str) -> None:
+    if not (t.is_cuda and t.dtype == torch.float64 and t.numel() == 3 and t.is_contiguous()):
+        raise GqHipError(f"{name} must be a contiguous float64 [3] tensor on the HIP device")
+
+
+def gq_gauss_train(z, dim: int, layout: str, grouping: int, noise, lam_state, log2n: int, tolerance: float, lam_factor: float,
+                   lam_range, lam_max_decreases: bool, loss_divisor: float, lv_range=(-30.0, 20.0), want_std: bool = False):
+    """GaussianQuantRegularizer's train-mode forward in one call (gqhip.h: gq_gauss_train_f32): no codebook, no workspace.
+    ``lam_state``: float64 [3] device tensor {lam, lam_min, lam_max}, advanced in place.  Returns (zhat, std or None, kl2row,
+    scalars) with ``scalars`` as gq_quantize_z_gauss returns it."""
+    z, noise = _dev(z, torch.float32, "z"), _dev(noise, torch.float32, "noise")
+    _lam_ok(lam_state, "lam_state")
+    B, L, c, K, rows, shape = _z_geometry(z, dim, layout)
+    if tuple(noise.shape) != shape:
+        raise GqHipError(f"noise must have the shape of zhat {shape}, got {tuple(noise.shape)}")
+    dev = z.device
+    zhat = torch.empty(shape, dtype=torch.float32, device=dev)
+    std = torch.empty_like(zhat) if want_std else None
+    kl2row = torch.empty(rows, dtype=torch.float32, device=dev)
+    scalars = torch.empty(64, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _check(lib().gq_gauss_train_f32(z.data_ptr(), noise.data_ptr(), zhat.data_ptr(), _ptr(std), kl2row.data_ptr(),
+                                        scalars.data_ptr(), lam_state.data_ptr(), B, L, c, dim, GQHIP_LAYOUT[layout], grouping,
+                                        float(lv_range[0]), float(lv_range[1]), float(log2n), float(tolerance), float(lam_factor),
+                                        float(lam_range[0]), float(lam_range[1]), 1 if lam_max_decreases else 0,
+                                        float(loss_divisor), _stream()), "gq_gauss_train_f32")
+    return zhat, std, kl2row, scalars
+
+
+def gq_gauss_backward(z, dim: int, layout: str, grouping: int, noise, lam_before, log2n: int, tolerance: float,
+                      loss_divisor: float, g_zhat=None, g_zhat_noquant=None, g_std=None, g_kl=None, lv_range=(-30.0, 20.0)):
+    """grad_z of either train-mode forward in one call (gqhip.h: gq_gauss_backward_f32).  ``lam_before``: the float64 [3] state as
+    it was before the forward.  Gradients may be None (zero); those of zhat and zhat_noquant are summed when both arrive, and a
+    gradient that is not contiguous in the layout of zhat is made so.  ``g_kl``: one float32 on the device."""
+    z, noise = _dev(z, torch.float32, "z"), _dev(noise, torch.float32, "noise")
+    _lam_ok(lam_before, "lam_before")
+    B, L, c, K, rows, shape = _z_geometry(z, dim, layout)
+
+    def grad(t, name):
+        if t is None:
+            return None
+        t = _dev(t, torch.float32, name)
+        if tuple(t.shape) != shape:
+            raise GqHipError(f"{name} must have the shape of zhat {shape}, got {tuple(t.shape)}")
+        return t
+
+    g_zhat, g_zhat_noquant, g_std = grad(g_zhat, "g_zhat"), grad(g_zhat_noquant, "g_zhat_noquant"), grad(g_std, "g_std")
+    if g_zhat is not None and g_zhat_noquant is not None:
+        g_zhat = g_zhat + g_zhat_noquant
+    elif g_zhat is None:
+        g_zhat = g_zhat_noquant
+    if g_kl is not None:
+        g_kl = _dev(g_kl, torch.float32, "g_kl")
+        if g_kl.numel() != 1:
+            raise GqHipError("g_kl must hold one float")
+    grad_z = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _check(lib().gq_gauss_backward_f32(z.data_ptr(), noise.data_ptr(), _ptr(g_zhat), _ptr(g_std), _ptr(g_kl),
+                                           lam_before.data_ptr(), grad_z.data_ptr(), B, L, c, dim, GQHIP_LAYOUT[layout], grouping,
+                                           float(lv_range[0]), float(lv_range[1]), float(log2n), float(tolerance),
+                                           float(loss_divisor), _stream()), "gq_gauss_backward_f32")
+    return grad_z
 
 
 def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: Optional[Workspace] = None):

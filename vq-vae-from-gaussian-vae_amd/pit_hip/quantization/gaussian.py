@@ -14,6 +14,16 @@ machine, quant_vq, the straight-through mix) is ONE call as well
 (``gq_quantize_z_gauss_f32``) whenever autograd is not recording; the lambda
 state then advances on the device and is read back only when somebody looks.
 
+Training (``GaussianQuantRegularizer`` in ``train()``, ``GaussianQuantRegularizer2``
+whenever autograd records) on a HIP tensor is one forward library call
+(``gq_gauss_train_f32`` / ``gq_quantize_z_gauss_f32``) and one backward library call
+(``gq_gauss_backward_f32``) behind a single ``torch.autograd.Function``; neither
+reads the host: lambdas, thresholds and the loss stay on the device.  The noise is
+drawn once per forward with ``torch.randn`` in the shape and memory layout of
+``zhat`` (as the eval paths do), so a test can re-draw it from the seed.
+``GQHIP_TRAIN_FUSED=0`` in the environment (read per call) selects the op-by-op
+torch path instead, for A/B runs and as an escape hatch.
+
 backend:
   "hip"   fused path (default here).
   "cuda"  what every shipped GQ YAML says (configs/sd3unet_gq_0.25.yaml:33): in
@@ -61,6 +71,42 @@ def prior_samples(n_samples: int, n_variable: int, seed_rec: int) -> torch.Tenso
 
 def _kl_bits(mu: torch.Tensor, var: torch.Tensor, logvar: torch.Tensor) -> torch.Tensor:
     return 1.4426 * 0.5 * (torch.pow(mu, 2) + var - 1.0 - logvar)
+
+
+def _train_fused() -> bool:
+    """False when GQHIP_TRAIN_FUSED=0 asks for the op-by-op torch path of the train-mode step (read per call)."""
+    return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
+
+
+class _GaussTrainFn(torch.autograd.Function):
+    """One forward library call and one backward library call for the train-mode step of both regularizers.
+
+    ``run(zv, noise, lam_state) -> (zhat, zhat_noquant or None, std or None, scalars, extra tensors)`` is the class's forward call
+    (it advances ``lam_state`` on the device); ``bw`` holds what gq_gauss_backward_f32 needs besides the tensors.  Differentiable
+    outputs: zhat (unless bw["zhat_diff"] is False: then it holds codewords), zhat_noquant, std, kl_loss; ``scalars`` (64 bytes:
+    the statistics and the lambdas after the update) and ``extra`` are not.  Saved: z, the noise and a device copy of the lambdas
+    taken BEFORE the call -- the backward recomputes each row's KL bits and with them its weight, nothing per row is kept."""
+
+    @staticmethod
+    def forward(ctx, zv, noise, lam_state, run, bw):
+        lam_before = lam_state.clone()                      # a device copy, not a read
+        zhat, noquant, std, scalars, extra = run(zv, noise, lam_state)
+        kl_loss = scalars[:16].view(torch.float32)[0].clone()
+        ctx.bw = bw
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(zv, noise, lam_before)
+        ctx.mark_non_differentiable(scalars, *extra, *(() if bw["zhat_diff"] else (zhat,)))
+        return (zhat, noquant, std, kl_loss, scalars) + tuple(extra)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_zhat, g_noquant, g_std, g_kl, *_):
+        zv, noise, lam_before = ctx.saved_tensors
+        bw = ctx.bw
+        grad_z = _lib.gq_gauss_backward(zv, bw["dim"], bw["layout"], bw["grouping"], noise, lam_before, bw["log2n"],
+                                        bw["tolerance"], bw["divisor"], g_zhat=g_zhat if bw["zhat_diff"] else None,
+                                        g_zhat_noquant=g_noquant, g_std=g_std, g_kl=g_kl, lv_range=bw["lv_range"])
+        return grad_z, None, None, None, None
 
 
 class _GaussianQuantBase(nn.Module):
@@ -186,9 +232,46 @@ class GaussianQuantRegularizer(_GaussianQuantBase):
                                                          self._ws, noise=noise)
         return zhat, {"indices": indices, "zhat_noquant": zhat_noquant}
 
+    def _forward_train_fused(self, z):
+        """Train branch (gaussian.py:77-119) as ONE forward library call (gq_gauss_train_f32: sample, per-row KL bits, statistics,
+        re-weighted loss, lambda update on the device) and, under autograd, ONE backward call.  The noise is one torch.randn draw in
+        the shape and memory layout of zhat.  info keeps the reference's keys: kl_loss (0-d fp32, carries grad), bits-mean / -min /
+        -max (0-d fp32, detached: INTEGRATION.md), lam (0-d fp32, the value after the update).  Nothing is read back: m.lam,
+        m.lam_min, m.lam_max pull the device state when somebody looks."""
+        z = z.float()
+        restore = lambda t: t
+        if self.format == "bchw":
+            b, c2, h, w = z.shape
+            if not z.is_contiguous() and z.is_contiguous(memory_format=torch.channels_last):
+                zv, layout = z.permute(0, 2, 3, 1).reshape(b, h * w, c2), "blc"      # a view of the same memory
+                shape_n = (b, h * w, c2 // 2)
+                restore = lambda t: t.view(b, h, w, -1).permute(0, 3, 1, 2)          # logical [B, C, h, w], NHWC memory
+            else:
+                zv, layout, shape_n = z.contiguous(), "bchw", (b, c2 // 2, h, w)
+        else:
+            b, l, c2 = z.shape
+            zv, layout, shape_n = z.contiguous(), "blc", (b, l, c2 // 2)
+        noise = torch.randn(shape_n, dtype=torch.float32, device=z.device)
+
+        def run(zv_, noise_, lam_state):
+            zhat, _, _, sc = _lib.gq_gauss_train(zv_, self.group, layout, _lib.GQHIP_GROUP_STRIDED, noise_, lam_state,
+                                                 self.log_n_samples, self.tolerance, self.lam_factor, self.lam_range,
+                                                 lam_max_decreases=True, loss_divisor=b, lv_range=self.logvar_range)
+            return zhat, None, None, sc, ()
+
+        bw = {"dim": self.group, "layout": layout, "grouping": _lib.GQHIP_GROUP_STRIDED, "log2n": self.log_n_samples,
+              "tolerance": self.tolerance, "divisor": b, "lv_range": tuple(self.logvar_range), "zhat_diff": True}
+        zhat, _, _, kl_loss, sc = _GaussTrainFn.apply(zv, noise, self._lam_state_on(z.device), run, bw)
+        f32, f64 = sc[:16].view(torch.float32), sc[32:56].view(torch.float64)
+        info = {"kl_loss": kl_loss, "bits-mean": f32[1], "bits-min": f32[2], "bits-max": f32[3],
+                "lam": f64[0].to(torch.float32)}
+        return restore(zhat), info
+
     def forward(self, z):
         if not self.training and not self._compat():
             return self._forward_fused(z)
+        if self.training and z.is_cuda and z.numel() > 0 and _train_fused():
+            return self._forward_train_fused(z)
         z = z.float()
         if self.format == "bchw":
             b, c2, h, w = z.shape
@@ -307,25 +390,42 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         zv = zl.reshape(1, -1, zl.shape[-1])
         return zv, "blc", lambda t: torch.movedim(t.reshape(*lead, -1), -1, d)
 
-    def _forward_fused(self, z):
+    def _forward_fused(self, z, autograd=False):
         """Eval forward (gaussian.py:333-345) as ONE library call: quant_gaussian's sample, statistics, re-weighted loss and lambda
         update, quant_vq's arg-max and gather, and the straight-through mix all happen in gq_quantize_z_gauss_f32's launches.  The
         lambda state advances on the device: info["lam"], ["lam-min"], ["lam-max"] are 0-d float64 device tensors (float(...) gives
-        the reference's Python floats) and nothing is read back unless an attribute is inspected."""
+        the reference's Python floats) and nothing is read back unless an attribute is inspected.
+        ``autograd``: the same call behind _GaussTrainFn, whose backward is ONE gq_gauss_backward_f32 call: zhat (with use_ste:
+        (g - g) + v, whose gradient goes to the Gaussian sample), info["zhat_noquant"], info["std"] and info["kl_loss"] are its
+        differentiable outputs, info["mu"] stays the differentiable view of z; without use_ste in eval zhat holds codewords and
+        nothing flows through it.  The noise is one torch.randn draw in the shape and memory layout of zhat."""
         z = z.float()
         assert z.shape[self.dim_idx] % (self.dim * 2) == 0
         zv, layout, restore = self._fused_view(z)
         c = zv.shape[1 if layout == "bchw" else 2] // 2
         shape_n = (zv.shape[0], c, zv.shape[2]) if layout == "bchw" else (zv.shape[0], zv.shape[1], c)
         noise = torch.randn(shape_n, dtype=torch.float32, device=z.device)     # one draw of the size of mu (gaussian.py:222)
-        ind, zhat, zq, noq, std, sc = _lib.gq_quantize_z_gauss(
-            zv, self.prior_samples, self.dim, layout, _lib.GQHIP_GROUP_CONTIGUOUS, noise, self._lam_state_on(z.device),
-            self.log_n_samples, self.tolerance, self.lam_factor, self.lam_range, lam_max_decreases=False, use_ste=self.use_ste,
-            lv_range=self.logvar_range, beta=self.beta, ws=self._ws)
+
+        def run(zv_, noise_, lam_state):
+            ind, zhat, zq, noq, std, sc = _lib.gq_quantize_z_gauss(
+                zv_, self.prior_samples, self.dim, layout, _lib.GQHIP_GROUP_CONTIGUOUS, noise_, lam_state,
+                self.log_n_samples, self.tolerance, self.lam_factor, self.lam_range, lam_max_decreases=False, use_ste=self.use_ste,
+                lv_range=self.logvar_range, beta=self.beta, ws=self._ws)
+            return zhat, noq, std, sc, ((ind, zq) if self.use_ste else (ind,))      # without use_ste zq IS zhat
+
+        if autograd:
+            bw = {"dim": self.dim, "layout": layout, "grouping": _lib.GQHIP_GROUP_CONTIGUOUS, "log2n": self.log_n_samples,
+                  "tolerance": self.tolerance, "divisor": zv.numel() // (2 * self.dim), "lv_range": tuple(self.logvar_range),
+                  "zhat_diff": bool(self.use_ste)}
+            zhat, noq, std, kl_loss, sc, ind, *rest = _GaussTrainFn.apply(zv, noise, self._lam_state_on(z.device), run, bw)
+        else:
+            zhat, noq, std, sc, (ind, *rest) = run(zv, noise, self._lam_state_on(z.device))
+            kl_loss = sc[:16].view(torch.float32)[0]
+        zq = rest[0] if rest else zhat
         f32, f64 = sc[:16].view(torch.float32), sc[32:56].view(torch.float64)
         zhat_o = restore(zhat)                    # with use_ste the kernels stored (zhat_g - zhat_g) + zhat_v here
         d = self.dim_idx % z.dim()
-        info = {"kl_loss": f32[0], "bits-mean": f32[1], "bits-min": f32[2], "bits-max": f32[3],
+        info = {"kl_loss": kl_loss, "bits-mean": f32[1], "bits-min": f32[2], "bits-max": f32[3],
                 "lam-min": f64[1], "lam-max": f64[2], "lam": f64[0],
                 "mu": z.narrow(d, 0, z.shape[d] // 2), "std": restore(std), "zhat_noquant": restore(noq),
                 "indices": restore(ind), "zhat_quant": restore(zq)}
@@ -334,8 +434,11 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         return zhat_o, info
 
     def forward(self, z):
-        if z.is_cuda and not self._compat() and not (torch.is_grad_enabled() and z.requires_grad):
-            return self._forward_fused(z)
+        if z.is_cuda and not self._compat():
+            if not (torch.is_grad_enabled() and z.requires_grad):
+                return self._forward_fused(z)
+            if _train_fused() and z.numel() > 0:
+                return self._forward_fused(z, autograd=True)
         zhat_g, info_g = self.quant_gaussian(z)
         with torch.no_grad():
             zhat_v, info_v = self.quant_vq(z)
