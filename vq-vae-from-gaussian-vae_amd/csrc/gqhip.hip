@@ -3,7 +3,6 @@
 // gfx950 only; built by `make -C vq-vae-from-gaussian-vae_amd/csrc`.
 #include "gqhip.h"
 
-#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -43,6 +42,57 @@ int check_launch() {
 
 namespace {
 
+// ---- diagnostic environment knobs ------------------------------------------
+const char *env_str(const char *name) { return getenv(name); }
+int env_int(const char *name, int dflt) {
+  const char *e = env_str(name);
+  return e ? atoi(e) : dflt;
+}
+double env_f64(const char *name, double dflt) {
+  const char *e = env_str(name);
+  return e ? atof(e) : dflt;
+}
+// GQHIP_FILTER=fp32|bf16|mixed, by their first letters in either case -> the kinds of gqhip_set_filter(); anything else: auto
+int filter_kind_from(const char *e) {
+  if (e && (e[0] == 'f' || e[0] == 'F') && (e[1] == 'p' || e[1] == 'P') && e[2] == '3') return GQHIP_FILTER_FP32;
+  if (e && (e[0] == 'b' || e[0] == 'B')) return GQHIP_FILTER_BF16;
+  if (e && (e[0] == 'm' || e[0] == 'M')) return GQHIP_FILTER_MIXED;   // fp16 + fp8
+  return GQHIP_FILTER_AUTO;
+}
+
+// Every GQHIP_* variable this translation unit reads: diagnostics and A/B timing, never needed in production.  Read once per
+// process, when the library is loaded (g_filter_kind's initialiser is the first user).
+struct Env {
+  int filter = filter_kind_from(env_str("GQHIP_FILTER"));   // initial filter selection (gqhip_set_filter() changes it at run time)
+  int rt = env_int("GQHIP_RT", 0);                           // 1 | 2: row tiles per wave of the filter (default: 2 from 8192 rows)
+  int target_blocks = env_int("GQHIP_TARGET_BLOCKS", 0);     // > 0: filter blocks the code splits aim at (default: 256 / 512, make_plan)
+  int nsplit = env_int("GQHIP_NSPLIT", 0);                   // > 0: code splits of the filter, before make_plan's caps
+  int bf16_waves = env_int("GQHIP_BF16_WAVES", 0);           // 4: two 4-wave blocks per CU instead of one 8-wave block
+  int bf16_ct = env_int("GQHIP_BF16_CT", 0);                 // 8: 8-tile LDS chunks at dim 16 too
+  double ef_coeff = env_f64("GQHIP_EF_COEFF", 0.0);          // > 0: replaces the re-rank's error-bound coefficient in the launch
+  int grid = env_int("GQHIP_GRID", 4);                       // dims of the pruned search: 0 none, 4, 8, 48 = both (dim 8 is slower than the dense path today)
+  int grid_cap = env_int("GQHIP_GRID_CAP", 0);               // > 0: leaves a row may visit before it is handed to the scan (default 256)
+  int grid_inwave = env_int("GQHIP_GRID_INWAVE", 0);         // > 0: listed leaves a row's lanes go through themselves (default kGridLeafCap)
+  int grid_abl = env_int("GQHIP_GRID_ABL", 0);               // ablations of the search kernel (diagnostic builds, make abl, only)
+  int grid_blocks = env_int("GQHIP_GRID_BLOCKS", 0);         // > 0: most blocks of the search launch (default 512)
+  int finish_blocks = env_int("GQHIP_FINISH_BLOCKS", 0);     // > 0: blocks of the finish launch (default 256)
+  int img_cache = env_int("GQHIP_IMG_CACHE", 1);             // 0: no codebook image in the cache, rebuilt in the workspace on every call
+  char scores = env_str("GQHIP_SCORES") ? env_str("GQHIP_SCORES")[0] : 0;   // compat op: d(irect) per-pair kernel, f(32) MFMA kernel at dims 16 / 32 too
+  int scores_nsplit = env_int("GQHIP_SCORES_NSPLIT", 0);     // > 0: code splits per row block of the compat op (tools/scores_sweep.sh)
+  int scores_rot = env_int("GQHIP_SCORES_ROT", 3);           // bit 0 / 1 of its write rotation (gq_scores.h)
+};
+const Env &env() {
+  static const Env e;
+  return e;
+}
+
+// Filter selection: 0 = auto (the fp16 main-product filter at every MFMA dim, GQ and VQ), 1 = always the fp32 MFMA filter,
+// 2 = split-bf16 wherever it applies, 3 = fp16 + fp8 (round 2's default: dim 16 / Gaussian score, split-bf16 elsewhere).
+// Initial value from GQHIP_FILTER, changed at run time by gqhip_set_filter().  Every filter feeds the same exact re-rank, so the
+// choice never changes an index.
+std::atomic<int> g_filter_kind{env().filter};
+int filter_kind() { return g_filter_kind.load(std::memory_order_relaxed); }
+
 // ---- launch plan: identical on the sizing and the launching side -----------
 struct Plan {
   bool mfma;            // filter kernel applies (dim in {4,8,16,32}, n >= 32)
@@ -58,6 +108,14 @@ struct Plan {
   int waves;            // waves per block: 8 (one block per CU) for the split-bf16 filter, else 4
   bool mixed;           // dim 16, Gaussian score: fp16 main product + fp8 corrections instead of three bf16 products
   bool f16;             // fp16 main product only + the data-dependent bound of the re-rank (round 3: the default filter)
+
+  // The fp16 + fp8 filter scores Gaussians only: under that selection a VQ call runs the split-bf16 kernels.  The sizing side does
+  // not know the mode and sizes for the Gaussian score (mode defaulted), which needs no less.
+  bool mixed_in(int mode) const { return mixed && mode == kModeGQ; }
+  // The fp16 filters leave one record per lane half: two record sets per code split for the re-rank (<= kMaxSplit in all).
+  int rec_halves(int mode = kModeGQ) const { return (mixed_in(mode) || f16) ? 2 : 1; }
+  int rec_sets(int mode = kModeGQ) const { return nsplit * rec_halves(mode); }   // record sets per row the re-rank is told of
+  int stored_rec_sets() const { return mfma ? rec_sets() : 0; }                   // ... and how many the workspace holds
 };
 
 // gq_filter_bf16.h / DESIGN.md section 3: 2 x 1057 (the two fp8 correction types: (2^-3 + 2^-8) relative on a term of at most
@@ -73,26 +131,22 @@ constexpr float kMixedN1Limit = 16.0f;   // ... and max|cb| >= 1 (gq_rerank.h)
 constexpr float kF16EfCoeff = 16700.0f;
 constexpr float kF16N1Limit = 255.0f;    // n^2 must stay a finite fp16
 
-// Filter selection: 0 = auto (the fp16 main-product filter at every MFMA dim, GQ and VQ), 1 = always the fp32 MFMA filter,
-// 2 = split-bf16 wherever it applies, 3 = fp16 + fp8 (round 2's default: dim 16 / Gaussian score, split-bf16 elsewhere).
-// Initial value from GQHIP_FILTER=fp32|bf16, changed at run time by gqhip_set_filter().  Both filters feed the
-// same exact re-rank, so the choice never changes an index.
-std::atomic<int> g_filter_kind{[] {
-  const char *e = getenv("GQHIP_FILTER");
-  if (e && (e[0] == 'f' || e[0] == 'F') && (e[1] == 'p' || e[1] == 'P') && e[2] == '3') return 1;   // fp32
-  if (e && (e[0] == 'b' || e[0] == 'B')) return 2;                                                   // bf16
-  if (e && (e[0] == 'm' || e[0] == 'M')) return 3;                                                   // mixed = fp16 + fp8
-  return 0;
-}()};
-bool want_bf16_filter() { return g_filter_kind.load(std::memory_order_relaxed) != 1; }
-bool want_mixed_filter() { return g_filter_kind.load(std::memory_order_relaxed) == 3; }
-bool want_f16_filter() { return g_filter_kind.load(std::memory_order_relaxed) == 0; }
+// The re-rank's bound on the filter's error: its coefficient, and the range of max|cb| (n1) inside which it holds.
+// The one place that knows them: the launch and gqhip_debug_plan (what the tests read) both ask here.
+struct RerankBound {
+  float ef_coeff, n1_limit, n1_min;
+};
+RerankBound rerank_bound(const Plan &pl, int mode, int64_t dim) {
+  if (pl.f16) return {kF16EfCoeff, kF16N1Limit, 0.0f};
+  if (pl.mixed_in(mode)) return {kMixedEfCoeff, kMixedN1Limit, 1.0f};
+  return {pl.bf16 ? (float)(dim == 4 ? 332 : 220 + 24 * dim) : (float)(2 * dim + 4), 0.0f, 0.0f};
+}
 
-// Grid search (gq_grid.h) instead of filter + re-rank: dims 4 / 8, filter selection AUTO, 2^14 <= n <= 2^20 codes, and the caller
-// passed a codebook cache of gqhip_cb_cache_bytes().  GQHIP_GRID=0 disables it, =4 / =8 restricts it to one dim (A/B timing).
+// Grid search (gq_grid.h) instead of filter + re-rank: dims 4 / 8 as GQHIP_GRID allows, filter selection AUTO, 2^14 <= n <= 2^20
+// codes, and the caller passed a codebook cache of gqhip_cb_cache_bytes().
 bool grid_dim_enabled(int64_t dim) {
-  static const int env = getenv("GQHIP_GRID") ? atoi(getenv("GQHIP_GRID")) : 4;     // default: dim 4 only (dim 8 is slower than the
-  return env == 48 ? (dim == 4 || dim == 8) : (env != 0 && dim == env);              // dense path today: =8 / =48 for experiments)
+  const int g = env().grid;
+  return g == 48 ? (dim == 4 || dim == 8) : (g != 0 && dim == g);
 }
 int64_t grid_cache_bytes(int64_t n, int64_t dim) {
   if (!grid_dim_enabled(dim) || n < 16384 || n > (1 << 20)) return 0;
@@ -100,40 +154,32 @@ int64_t grid_cache_bytes(int64_t n, int64_t dim) {
 }
 bool grid_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes) {
   const int64_t need = grid_cache_bytes(n, dim);
-  return need > 0 && cache && cache_bytes >= need && g_filter_kind.load(std::memory_order_relaxed) == 0;
+  return need > 0 && cache && cache_bytes >= need && filter_kind() == GQHIP_FILTER_AUTO;
 }
-// Dims 8 / 16 / 32 (the fp16 main-product filter): the codebook's fp16 operand image is kept in the cache, every 1/256 slice of it
-// validated against -- and, when stale, rebuilt and restamped by -- the code block of the first launch that owns it (gq_prep.h).
-// GQHIP_IMG_CACHE=0 disables it (A/B timing): the image is then rebuilt in the workspace on every call, as before round 5.
-int64_t image_cache_bytes(int64_t n, int64_t dim);   // (needs make_plan)
 
 Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
+  const Env &e = env();
   Plan pl{};
   pl.mfma = (dim == 4 || dim == 8 || dim == 16 || dim == 32) && n >= 1 && rows >= 1;
   pl.tiles_total = (int)((n + kTileCodes - 1) / kTileCodes);
-  static const int env_rt = getenv("GQHIP_RT") ? atoi(getenv("GQHIP_RT")) : 0;
-  static const int env_blocks = getenv("GQHIP_TARGET_BLOCKS") ? atoi(getenv("GQHIP_TARGET_BLOCKS")) : 0;
   pl.rt = rows >= 8192 ? 2 : 1;
-  if (env_rt == 1 || env_rt == 2) pl.rt = env_rt;
-  pl.bf16 = pl.mfma && want_bf16_filter();
-  static const int env_waves = getenv("GQHIP_BF16_WAVES") ? atoi(getenv("GQHIP_BF16_WAVES")) : 0;
-  pl.waves = pl.bf16 ? (env_waves == 4 ? 4 : 8) : 4;
+  if (e.rt == 1 || e.rt == 2) pl.rt = e.rt;
+  pl.bf16 = pl.mfma && filter_kind() != GQHIP_FILTER_FP32;
+  pl.waves = pl.bf16 ? (e.bf16_waves == 4 ? 4 : 8) : 4;
   pl.rows_per_block = 32 * pl.waves * pl.rt;
   pl.row_blocks = (int)((rows + pl.rows_per_block - 1) / pl.rows_per_block);
   // 4-wave blocks: ~2 blocks per CU on 256 CUs; 8-wave blocks: one per CU.  Splits in multiples of 8 so that
   // blockIdx % 8 (XCD) == split % 8.
-  const int target = env_blocks > 0 ? env_blocks : (pl.waves == 8 ? 256 : 512);
+  const int target = e.target_blocks > 0 ? e.target_blocks : (pl.waves == 8 ? 256 : 512);
   int s = (target + pl.row_blocks - 1) / (pl.row_blocks > 0 ? pl.row_blocks : 1);
   s = ((s + 7) / 8) * 8;
-  static const int env_nsplit = getenv("GQHIP_NSPLIT") ? atoi(getenv("GQHIP_NSPLIT")) : 0;
-  if (env_nsplit > 0) s = env_nsplit;
+  if (e.nsplit > 0) s = e.nsplit;
   if (s > kMaxSplit) s = kMaxSplit;
   if (s > pl.tiles_total) s = pl.tiles_total;
   if (s < 1) s = 1;
   pl.tiles_per_split = (pl.tiles_total + s - 1) / s;
   // tiles per LDS chunk: 16 at dim 16 with one block per CU (2 x 64 KiB of LDS, half the chunk barriers: +1-2 %)
-  static const int env_ct = getenv("GQHIP_BF16_CT") ? atoi(getenv("GQHIP_BF16_CT")) : 0;
-  pl.ct = dim == 32 ? 4 : ((dim == 16 && pl.waves == 8 && env_ct != 8) ? 16 : 8);
+  pl.ct = dim == 32 ? 4 : ((dim == 16 && pl.waves == 8 && e.bf16_ct != 8) ? 16 : 8);
 
   // Candidate granularity: GT tiles per half-group.  Behind the bf16 / fp16 filters 4 (64-code candidates): the tracker's top-4
   // insert (12 VALU) runs once per GT tiles, and VALU issue is what those loops are short of (measured at config 2 with the
@@ -141,18 +187,17 @@ Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
   // 16 GT codes cheap to go through.
   // dim 4 keeps the packed split-bf16 filter: 65 536 codes are dense in 4-d -- 3.5 candidate groups per row inside the fp16
   // margin and a quarter of the rows undecided (measured, profiles/r03) -- and its kernel is not MFMA-bound in the first place
-  pl.f16 = pl.bf16 && want_f16_filter() && pl.waves == 8 && dim != 4;
+  pl.f16 = pl.bf16 && filter_kind() == GQHIP_FILTER_AUTO && pl.waves == 8 && dim != 4;
   pl.gt = pl.bf16 ? 4 : (dim <= 8 ? 4 : 2);
   // (Measured in round 4 and not kept: groups of 8 tiles at dim 8, where the tracker's 12 VALU per group weigh twice what they do at
   // dim 16 -- filter 78.9 -> 75.1 us, but the re-rank's 128-code candidates give it back: whole call 128.4 -> 130.2 us.)
   pl.tiles_per_split = (pl.tiles_per_split + pl.gt - 1) / pl.gt * pl.gt;   // a tile group never straddles two splits
   pl.nsplit = (pl.tiles_total + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  pl.mixed = pl.bf16 && want_mixed_filter() && dim == 16 && pl.waves == 8 && pl.ct == 16 && pl.gt == 4;
+  pl.mixed = pl.bf16 && filter_kind() == GQHIP_FILTER_MIXED && dim == 16 && pl.waves == 8 && pl.ct == 16 && pl.gt == 4;
   if (pl.f16) pl.ct = dim == 32 ? 8 : 16;   // one 16-byte vector per MFMA, lane and tile: 16-tile chunks are 16 / 32 KiB
-  if ((pl.mixed || pl.f16) && pl.nsplit > kMaxSplit / 2) {
-    // the fp16 + fp8 filter leaves one record per lane half: 2 nsplit record sets for the re-rank (<= kMaxSplit)
-    const int s3 = kMaxSplit / 2;
-    pl.tiles_per_split = ((pl.tiles_total + s3 - 1) / s3 + pl.gt - 1) / pl.gt * pl.gt;
+  const int split_cap = kMaxSplit / pl.rec_halves();   // the re-rank takes at most kMaxSplit record sets
+  if (pl.nsplit > split_cap) {
+    pl.tiles_per_split = ((pl.tiles_total + split_cap - 1) / split_cap + pl.gt - 1) / pl.gt * pl.gt;
     pl.nsplit = (pl.tiles_total + pl.tiles_per_split - 1) / pl.tiles_per_split;
   }
   // The records carry half-group ids RELATIVE to their split in 16 bits (gq_common.h:Rec): 2 * tiles_per_split / GT <= 65536, i.e.
@@ -160,9 +205,8 @@ Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
   // the split cap allows (n > 2^26 GT / 2: 134 M codes at GT 4) leave the MFMA path for the exhaustive kernel.
   const int64_t max_tps = 32768LL * pl.gt;
   if (pl.mfma && pl.tiles_per_split > max_tps) {
-    const int cap = (pl.mixed || pl.f16) ? kMaxSplit / 2 : kMaxSplit;
     const int64_t need = (pl.tiles_total + max_tps - 1) / max_tps;
-    if (need > cap) {
+    if (need > split_cap) {
       pl.mfma = pl.bf16 = pl.f16 = pl.mixed = false;
     } else {
       pl.tiles_per_split = (int)(((pl.tiles_total + need - 1) / need + pl.gt - 1) / pl.gt * pl.gt);
@@ -174,11 +218,12 @@ Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
 
 inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
-int64_t image_cache_bytes(int64_t n, int64_t dim) {
-  static const bool off = getenv("GQHIP_IMG_CACHE") && atoi(getenv("GQHIP_IMG_CACHE")) == 0;
-  if (off || (dim != 8 && dim != 16 && dim != 32) || n < 1 || g_filter_kind.load(std::memory_order_relaxed) != 0) return 0;
-  const Plan pl = make_plan(65536, n, dim);       // (what the image depends on -- tiles, chunk padding, vectors -- does not depend on rows)
-  if (!pl.f16) return 0;
+// Dims 8 / 16 / 32 (the fp16 main-product filter): the codebook's fp16 operand image is kept in the cache, every 1/256 slice of it
+// validated against -- and, when stale, rebuilt and restamped by -- the code block of the first launch that owns it (gq_prep.h).
+// GQHIP_IMG_CACHE=0 disables it (A/B timing): the image is then rebuilt in the workspace on every call, as before round 5.
+// (What the image depends on -- tiles, chunk padding, vectors -- does not depend on rows: any plan of (n, dim) serves.)
+int64_t image_cache_bytes(const Plan &pl, int64_t dim) {
+  if (env().img_cache == 0 || (dim != 8 && dim != 16 && dim != 32) || filter_kind() != GQHIP_FILTER_AUTO || !pl.f16) return 0;
   return (int64_t)sizeof(GridHdr) + align256((int64_t)(pl.tiles_total + pl.ct) * (dim / 8) * 64 * 16);
 }
 
@@ -186,12 +231,11 @@ struct WsLayout {
   int64_t hdr, rec, fb, dbg, mu, sd, lsd, rowsum, coef, cbimg, rowimg, rowscale, rowaux, kl2, total;
 };
 
-WsLayout ws_layout(int64_t rows, int64_t n, int64_t dim) {
-  const Plan pl = make_plan(rows, n, dim);
+WsLayout ws_layout(const Plan &pl, int64_t rows, int64_t dim) {
   WsLayout w{};
   int64_t off = 0;
   w.hdr = off; off += (int64_t)sizeof(WsHeader);
-  w.rec = off; off += align256((int64_t)sizeof(Rec) * rows * (pl.mfma ? pl.nsplit * ((pl.mixed || pl.f16) ? 2 : 1) : 0));
+  w.rec = off; off += align256((int64_t)sizeof(Rec) * rows * pl.stored_rec_sets());
   w.fb = off;  off += align256(4 * rows);
   w.dbg = off; off += 128 * 1024;     // diagnostic builds only (GQHIP_CLOCK_STAMPS: per-block timeline records of the filter | of the re-rank)
   w.mu = off;  off += align256(4 * rows * dim);
@@ -217,159 +261,136 @@ int g_debug_stats = 0;
 std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_events;   // attached to a dispatch, not yet collected
 std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;     // created ahead of time (gqhip_profile_reserve)
 
-// When profiling is on, the filter is launched through hipExtLaunchKernelGGL with a start and a
-// stop event attached to the dispatch itself, so the elapsed time is the kernel's own duration on
-// its stream (what rocprofv3 --kernel-trace reports), not a marker-to-marker bracket.  The event pairs
-// come from a pool filled by gqhip_profile_reserve(): nothing is created on the launch path, and a
-// launch that finds the pool empty simply is not recorded.
-struct ProfScope {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  explicit ProfScope(bool enable = true) {
+}  // namespace
+
+// When profiling is on, the filter is launched with a start and a stop event attached to the dispatch itself (gqhip_internal.h:
+// launch), so the elapsed time is the kernel's own duration on its stream (what rocprofv3 --kernel-trace reports), not a
+// marker-to-marker bracket.  The event pairs come from a pool filled by gqhip_profile_reserve(): nothing is created on the launch
+// path, and a launch that finds the pool empty simply is not recorded.
+gqhip::ProfScope::ProfScope(bool enable) {
+  std::lock_guard<std::mutex> lk(g_prof_mu);
+  if (g_prof_on && enable && !g_prof_pool.empty()) {
+    a = g_prof_pool.back().first;
+    b = g_prof_pool.back().second;
+    g_prof_pool.pop_back();
+    on = true;
+  }
+}
+gqhip::ProfScope::~ProfScope() {
+  if (on) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (g_prof_on && enable && !g_prof_pool.empty()) {
-      a = g_prof_pool.back().first;
-      b = g_prof_pool.back().second;
-      g_prof_pool.pop_back();
-      on = true;
-    }
+    g_prof_events.emplace_back(a, b);
   }
-  ~ProfScope() {
-    if (on) {
-      std::lock_guard<std::mutex> lk(g_prof_mu);
-      g_prof_events.emplace_back(a, b);
-    }
-  }
-};
+}
+
+namespace {
+
+// ---- which kernel serves a plan: one function per family, nullptr = no instantiation for that shape (GQHIP_ERR_INVALID_ARG) ------
+using FilterKernel = void (*)(FilterParams);
+using FilterBfKernel = void (*)(FilterBfParams);
+using PrepKernel = void (*)(PrepParams);
+using RerankKernel = void (*)(RerankParams);
 
 template <int MODE>
-int launch_filter(const Plan &pl, const FilterParams &fp, int dim, hipStream_t st, bool profile = true) {
-  const dim3 grid((unsigned)(pl.row_blocks * pl.nsplit)), block(256);
-  ProfScope prof(profile);
-#define GQ_LAUNCH(D, R, C, G)                                                                           \
-  do {                                                                                                \
-    if (prof.on)                                                                                      \
-      hipExtLaunchKernelGGL((gq_filter_kernel<D, R, C, MODE, G>), grid, block, 0, st, prof.a, prof.b, 0, fp); \
-    else                                                                                              \
-      hipLaunchKernelGGL((gq_filter_kernel<D, R, C, MODE, G>), grid, block, 0, st, fp);                  \
-  } while (0)
-  if (pl.rt == 2) {
-    switch (dim) {
-      case 4: GQ_LAUNCH(4, 2, 8, 4); break;
-      case 8: GQ_LAUNCH(8, 2, 8, 4); break;
-      case 16: GQ_LAUNCH(16, 2, 8, 2); break;
-      case 32: GQ_LAUNCH(32, 2, 4, 2); break;
-      default: return GQHIP_ERR_INVALID_ARG;
-    }
-  } else {
-    switch (dim) {
-      case 4: GQ_LAUNCH(4, 1, 8, 4); break;
-      case 8: GQ_LAUNCH(8, 1, 8, 4); break;
-      case 16: GQ_LAUNCH(16, 1, 8, 2); break;
-      case 32: GQ_LAUNCH(32, 1, 4, 2); break;
-      default: return GQHIP_ERR_INVALID_ARG;
+FilterKernel filter_kernel(const Plan &pl, int64_t dim) {
+  switch (dim * 10 + pl.rt) {
+    case 41: return gq_filter_kernel<4, 1, 8, MODE, 4>;
+    case 42: return gq_filter_kernel<4, 2, 8, MODE, 4>;
+    case 81: return gq_filter_kernel<8, 1, 8, MODE, 4>;
+    case 82: return gq_filter_kernel<8, 2, 8, MODE, 4>;
+    case 161: return gq_filter_kernel<16, 1, 8, MODE, 2>;
+    case 162: return gq_filter_kernel<16, 2, 8, MODE, 2>;
+    case 321: return gq_filter_kernel<32, 1, 4, MODE, 2>;
+    case 322: return gq_filter_kernel<32, 2, 4, MODE, 2>;
+    default: return nullptr;
+  }
+}
+
+// the split-bf16 kernel <NV, RT, CT> of either block size
+template <int NV, int RT, int CT>
+FilterBfKernel bf16_kernel(int waves) {
+  return waves == 8 ? gq_filter_bf16_kernel<NV, RT, CT, 4, 8> : gq_filter_bf16_kernel<NV, RT, CT, 4, 4>;
+}
+// fp16 main product (FK 2) | fp16 + fp8 (FK 1, dim 16) | split-bf16: template arguments <NV = dim / 8, RT, CT, GT, WAVES, FK>
+FilterBfKernel filter_bf16_kernel(const Plan &pl, int64_t dim, bool mixed) {
+  const int key = (int)dim * 10 + pl.rt;
+  if (pl.f16) {
+    switch (key) {
+      case 81: return gq_filter_bf16_kernel<1, 1, 16, 4, 8, 2>;
+      case 82: return gq_filter_bf16_kernel<1, 2, 16, 4, 8, 2>;
+      case 161: return gq_filter_bf16_kernel<2, 1, 16, 4, 8, 2>;
+      case 162: return gq_filter_bf16_kernel<2, 2, 16, 4, 8, 2>;
+      case 321: return gq_filter_bf16_kernel<4, 1, 8, 4, 8, 2>;
+      case 322: return gq_filter_bf16_kernel<4, 2, 8, 4, 8, 2>;
+      default: return nullptr;
     }
   }
-#undef GQ_LAUNCH
-  return check_launch();
+  switch (key) {
+    case 41: return bf16_kernel<0, 1, 8>(pl.waves);
+    case 42: return bf16_kernel<0, 2, 8>(pl.waves);
+    case 81: return bf16_kernel<1, 1, 8>(pl.waves);
+    case 82: return bf16_kernel<1, 2, 8>(pl.waves);
+    // dim 16: the 16-tile chunks of the plan (pl.ct == 16: one 8-wave block per CU) have a split-bf16 kernel at two row tiles only;
+    // one row tile runs 8-tile chunks over the same image (its padding covers either)
+    case 161: return mixed ? gq_filter_bf16_kernel<2, 1, 16, 4, 8, 1> : bf16_kernel<2, 1, 8>(pl.waves);
+    case 162:
+      if (mixed) return gq_filter_bf16_kernel<2, 2, 16, 4, 8, 1>;
+      return pl.ct == 16 ? gq_filter_bf16_kernel<2, 2, 16, 4, 8> : bf16_kernel<2, 2, 8>(pl.waves);
+    case 321: return bf16_kernel<4, 1, 4>(pl.waves);
+    case 322: return bf16_kernel<4, 2, 4>(pl.waves);
+    default: return nullptr;
+  }
+}
+
+// images: 0 none or split-bf16 (the same kernel writes them when the parameters name them), 1 fp16 + fp8, 2 fp16 main product
+template <int MODE, bool FROM_Z>
+PrepKernel prep_kernel_z(int64_t dim, bool mixed, bool f16) {
+  if constexpr (MODE == kModeGQ) {
+    if (mixed && dim == 16) return gq_prep_kernel<MODE, 16, FROM_Z, 1>;
+  }
+  switch ((int)dim * 10 + (f16 ? 2 : 0)) {
+    case 40: return gq_prep_kernel<MODE, 4, FROM_Z>;
+    case 80: return gq_prep_kernel<MODE, 8, FROM_Z>;
+    case 160: return gq_prep_kernel<MODE, 16, FROM_Z>;
+    case 320: return gq_prep_kernel<MODE, 32, FROM_Z>;
+    case 82: return gq_prep_kernel<MODE, 8, FROM_Z, 2>;
+    case 162: return gq_prep_kernel<MODE, 16, FROM_Z, 2>;
+    case 322: return gq_prep_kernel<MODE, 32, FROM_Z, 2>;
+    default: return nullptr;
+  }
+}
+template <int MODE>
+PrepKernel prep_kernel(bool from_z, int64_t dim, bool mixed, bool f16) {
+  return from_z ? prep_kernel_z<MODE, true>(dim, mixed, f16) : prep_kernel_z<MODE, false>(dim, mixed, f16);
 }
 
 // re-rank: 16 lanes per row, 16 rows per block; NSI = record passes per lane (1 covers up to 16 record sets: every BASELINE shape)
+template <int MODE, int DIM, int GT>
+RerankKernel rerank_kernel_nsi(int rec_sets) {
+  return rec_sets <= 16 ? gq_rerank_kernel<MODE, DIM, GT, 1> : gq_rerank_kernel<MODE, DIM, GT, 4>;
+}
 template <int MODE>
-int launch_rerank(const RerankParams &rp, int64_t rows, int dim, hipStream_t st, bool stats_block = false) {
-  const dim3 grid((unsigned)((rows + 15) / 16 + (stats_block ? 1 : 0)));
-#define GQ_RR(D, G)                                                                                  \
-  do {                                                                                               \
-    if (rp.nsplit <= 16) hipLaunchKernelGGL((gq_rerank_kernel<MODE, D, G, 1>), grid, dim3(256), 0, st, rp); \
-    else hipLaunchKernelGGL((gq_rerank_kernel<MODE, D, G, 4>), grid, dim3(256), 0, st, rp);           \
-  } while (0)
-  switch (dim * 100 + rp.gt) {
-    case 404: GQ_RR(4, 4); break;
-    case 804: GQ_RR(8, 4); break;
-    case 1602: GQ_RR(16, 2); break;
-    case 1604: GQ_RR(16, 4); break;
-    case 3202: GQ_RR(32, 2); break;
-    case 3204: GQ_RR(32, 4); break;
-    default: return GQHIP_ERR_INVALID_ARG;
+RerankKernel rerank_kernel(int64_t dim, int gt, int rec_sets) {
+  switch (dim * 100 + gt) {
+    case 404: return rerank_kernel_nsi<MODE, 4, 4>(rec_sets);
+    case 804: return rerank_kernel_nsi<MODE, 8, 4>(rec_sets);
+    case 1602: return rerank_kernel_nsi<MODE, 16, 2>(rec_sets);
+    case 1604: return rerank_kernel_nsi<MODE, 16, 4>(rec_sets);
+    case 3202: return rerank_kernel_nsi<MODE, 32, 2>(rec_sets);
+    case 3204: return rerank_kernel_nsi<MODE, 32, 4>(rec_sets);
+    default: return nullptr;
   }
-#undef GQ_RR
-  return check_launch();
 }
 
+struct GridKernels {
+  void (*build)(GridBuildParams);
+  void (*search)(GridParams);
+  void (*finish)(GridParams);
+};
 template <int MODE>
-int launch_filter_bf16(const Plan &pl, const FilterBfParams &fp, int dim, bool mixed, hipStream_t st) {
-  const dim3 grid((unsigned)(pl.row_blocks * pl.nsplit));
-  const dim3 fblock((unsigned)(64 * pl.waves));
-  ProfScope prof;
-  if (pl.f16) {
-#define GQ_LAUNCH_F16G(NV, R, C, G)                                                                                  \
-  do {                                                                                                             \
-    if (prof.on)                                                                                                   \
-      hipExtLaunchKernelGGL((gq_filter_bf16_kernel<NV, R, C, G, 8, 2>), grid, fblock, 0, st, prof.a, prof.b, 0, fp); \
-    else                                                                                                           \
-      hipLaunchKernelGGL((gq_filter_bf16_kernel<NV, R, C, G, 8, 2>), grid, fblock, 0, st, fp);                      \
-  } while (0)
-#define GQ_LAUNCH_F16(NV, R, C) GQ_LAUNCH_F16G(NV, R, C, 4)
-    switch (dim * 10 + pl.rt) {
-      case 81: GQ_LAUNCH_F16(1, 1, 16); break;
-      case 82: GQ_LAUNCH_F16(1, 2, 16); break;
-      case 161: GQ_LAUNCH_F16(2, 1, 16); break;
-      case 162: GQ_LAUNCH_F16(2, 2, 16); break;
-      case 321: GQ_LAUNCH_F16(4, 1, 8); break;
-      case 322: GQ_LAUNCH_F16(4, 2, 8); break;
-      default: return GQHIP_ERR_INVALID_ARG;
-    }
-#undef GQ_LAUNCH_F16
-#undef GQ_LAUNCH_F16G
-    return check_launch();
-  }
-#define GQ_LAUNCH_BF1(NV, R, C, G, W)                                                                       \
-  do {                                                                                                    \
-    if (prof.on)                                                                                          \
-      hipExtLaunchKernelGGL((gq_filter_bf16_kernel<NV, R, C, G, W>), grid, fblock, 0, st, prof.a, prof.b, 0, fp); \
-    else                                                                                                  \
-      hipLaunchKernelGGL((gq_filter_bf16_kernel<NV, R, C, G, W>), grid, fblock, 0, st, fp);                  \
-  } while (0)
-#define GQ_LAUNCH_BF(NV, R, C)                                                                            \
-  do {                                                                                                    \
-    if (pl.waves == 8) GQ_LAUNCH_BF1(NV, R, C, 4, 8);                                                     \
-    else GQ_LAUNCH_BF1(NV, R, C, 4, 4);                                                                   \
-  } while (0)
-  if (pl.rt == 2) {
-    switch (dim) {
-      case 4: GQ_LAUNCH_BF(0, 2, 8); break;
-      case 8: GQ_LAUNCH_BF(1, 2, 8); break;
-      case 16:
-        if (mixed) {
-          if (prof.on)
-            hipExtLaunchKernelGGL((gq_filter_bf16_kernel<2, 2, 16, 4, 8, 1>), grid, fblock, 0, st, prof.a, prof.b, 0, fp);
-          else
-            hipLaunchKernelGGL((gq_filter_bf16_kernel<2, 2, 16, 4, 8, 1>), grid, fblock, 0, st, fp);
-        }
-        else if (pl.ct == 16) GQ_LAUNCH_BF1(2, 2, 16, 4, 8);
-        else GQ_LAUNCH_BF(2, 2, 8);
-        break;
-      default: GQ_LAUNCH_BF(4, 2, 4); break;
-    }
-  } else {
-    switch (dim) {
-      case 4: GQ_LAUNCH_BF(0, 1, 8); break;
-      case 8: GQ_LAUNCH_BF(1, 1, 8); break;
-      case 16:
-        if (mixed) {
-          if (prof.on)
-            hipExtLaunchKernelGGL((gq_filter_bf16_kernel<2, 1, 16, 4, 8, 1>), grid, fblock, 0, st, prof.a, prof.b, 0, fp);
-          else
-            hipLaunchKernelGGL((gq_filter_bf16_kernel<2, 1, 16, 4, 8, 1>), grid, fblock, 0, st, fp);
-        }
-        else GQ_LAUNCH_BF(2, 1, 8);
-        break;
-      default: GQ_LAUNCH_BF(4, 1, 4); break;
-    }
-  }
-#undef GQ_LAUNCH_BF
-#undef GQ_LAUNCH_BF1
-  return check_launch();
+GridKernels grid_kernels(int64_t dim) {   // (grid_applies() has let dims 4 / 8 through)
+  if (dim == 4) return {gq_grid_build_kernel<4>, gq_grid_kernel<MODE, 4>, gq_grid_finish_kernel<MODE, 4>};
+  return {gq_grid_build_kernel<8>, gq_grid_kernel<MODE, 8>, gq_grid_finish_kernel<MODE, 8>};
 }
 
 // What the first launch reads: either z in the module layout (FROM_Z) or ready-made rows.
@@ -379,45 +400,202 @@ struct PrepInput {
   float lv_min = 0.f, lv_max = 0.f;
   float *mu_out = nullptr, *sd_out = nullptr;   // FROM_Z: optional copies of the row operands for the caller
   float *sd_layout = nullptr;                   // FROM_Z: optional sd in the layout of zhat
-  bool want_kl2 = false;                        // FROM_Z: leave the per-row KL bits in the workspace (ws_layout().kl2)
+  bool want_kl2 = false;                        // FROM_Z: leave the per-row KL bits in the workspace (WsLayout::kl2)
   int ste_kind = 0;                             // straight-through mix where zhat is stored (gq_common.h:WsHeader)
   const float *ste = nullptr;
   float *pure = nullptr;
-  GaussStatsParams gs{};                        // want_kl2: the statistics block's parameters (kl2row is filled in by run_argmax)
+  GaussStatsParams gs{};                        // want_kl2: the statistics block's parameters (kl2row is filled in by prep_params)
   bool *stats_done = nullptr;                   // out: the statistics block ran inside the re-rank launch (no launch of its own needed)
+  WsLayout *layout = nullptr;                   // out: where this call put things in the workspace, for the kernels the caller appends
 };
 
-template <int MODE, bool FROM_Z>
-int launch_prep(const PrepParams &pp, int dim, bool mixed, bool f16, hipStream_t st) {
-  const dim3 grid((unsigned)(pp.row_blocks + kPrepCodeBlocks));
-  if constexpr (MODE == kModeGQ) {
-    if (mixed && dim == 16) {
-      hipLaunchKernelGGL((gq_prep_kernel<MODE, 16, FROM_Z, 1>), grid, dim3(256), 0, st, pp);
-      return check_launch();
-    }
-  }
-  if (f16) {
-    switch (dim) {
-      case 8: hipLaunchKernelGGL((gq_prep_kernel<MODE, 8, FROM_Z, 2>), grid, dim3(256), 0, st, pp); break;
-      case 16: hipLaunchKernelGGL((gq_prep_kernel<MODE, 16, FROM_Z, 2>), grid, dim3(256), 0, st, pp); break;
-      case 32: hipLaunchKernelGGL((gq_prep_kernel<MODE, 32, FROM_Z, 2>), grid, dim3(256), 0, st, pp); break;
-      default: return GQHIP_ERR_INVALID_ARG;
-    }
-    return check_launch();
-  }
-  switch (dim) {
-    case 4: hipLaunchKernelGGL((gq_prep_kernel<MODE, 4, FROM_Z>), grid, dim3(256), 0, st, pp); break;
-    case 8: hipLaunchKernelGGL((gq_prep_kernel<MODE, 8, FROM_Z>), grid, dim3(256), 0, st, pp); break;
-    case 16: hipLaunchKernelGGL((gq_prep_kernel<MODE, 16, FROM_Z>), grid, dim3(256), 0, st, pp); break;
-    case 32: hipLaunchKernelGGL((gq_prep_kernel<MODE, 32, FROM_Z>), grid, dim3(256), 0, st, pp); break;
-    default: return GQHIP_ERR_INVALID_ARG;
-  }
-  return check_launch();
+// One arg-max call after its checks: what the three paths below share.
+struct Call {
+  const PrepInput &in;
+  const float *lsd;                             // the caller's log sd rows, or NULL
+  const float *cb;
+  int64_t *idx;
+  float *zhat;
+  int64_t dim, rows, n;
+  double beta;
+  void *cb_cache;
+  int64_t cb_cache_bytes;
+  const OutMap &omap;
+  hipStream_t st;
+  Plan pl;
+  WsLayout w;
+  char *ws;
+  WsHeader *hdr;
+  float *ws_lsd;
+  const float *r_mu, *r_sd, *r_lsd;             // the rows every later kernel reads
+  bool from_z() const { return in.z != nullptr; }
+  template <class T>
+  T *at(int64_t off) const { return reinterpret_cast<T *>(ws + off); }
+};
+
+template <int MODE>
+RerankParams rerank_params(const Call &c) {
+  const Plan &pl = c.pl;
+  RerankParams rp{};
+  rp.mu = c.r_mu; rp.sd = MODE == kModeGQ ? c.r_sd : nullptr; rp.lsd = c.r_lsd; rp.cb = c.cb;
+  rp.rowsum = c.at<const double>(c.w.rowsum);
+  rp.coef = c.at<const float>(c.w.coef);
+  rp.rec = c.at<const Rec>(c.w.rec);
+  rp.idx = c.idx; rp.zhat = c.zhat; rp.hdr = c.hdr;
+  rp.fb_list = c.at<int>(c.w.fb);
+  rp.rows = (int)c.rows; rp.n = (int)c.n; rp.dim = (int)c.dim;
+  const RerankBound b = rerank_bound(pl, MODE, c.dim);
+  rp.ef_coeff = env().ef_coeff > 0.0 ? (float)env().ef_coeff : b.ef_coeff;
+  rp.n1_limit = b.n1_limit; rp.n1_min = b.n1_min;
+  if (pl.f16) rp.rowaux = c.at<const float>(c.w.rowaux);
+  rp.beta = (float)c.beta; rp.nsplit = pl.rec_sets(MODE); rp.gt = pl.gt; rp.all_rows = pl.mfma ? 0 : 1; rp.stats = g_debug_stats;
+  rp.omap = c.omap;
+  rp.dbg = c.ws + c.w.dbg + 64 * 1024;
+  rp.rec_halves = pl.rec_halves(MODE);
+  rp.tiles_per_split = pl.tiles_per_split; rp.tiles_total = pl.tiles_total;
+  return rp;
 }
 
-// prep -> filter -> re-rank (MFMA dims) | prep -> exhaustive (other dims), shared by GQ and VQ.
-// Three launches per call (round 4: the rows the candidates cannot decide are finished inside the re-rank, gq_rerank.h);
-// nothing derived from the codebook or the rows survives the call.
+// The first launch of the MFMA dims: rows (+ zhat_noquant), bound sums, max|cb| partials, header -- and, on the dense path, the
+// operand images of the plan's filter.  The grid search reads no image; the cache it validates is its spatial index
+// (`cache_stale`: the builder that follows rebuilds it), where the dense path may keep the codebook's fp16 image in the cache.
+template <int MODE>
+PrepParams prep_params(const Call &c, bool grid, bool stats_in_rerank) {
+  const PrepInput &in = c.in;
+  const Plan &pl = c.pl;
+  const bool scaled = !grid && (pl.mixed_in(MODE) || pl.f16);
+  PrepParams pp{};
+  pp.z = in.z; pp.noise = in.noise; pp.zhat_noquant = in.zhat_noquant; pp.lv_min = in.lv_min; pp.lv_max = in.lv_max;
+  pp.sd_layout = in.sd_layout; pp.kl2row = in.want_kl2 ? c.at<float>(c.w.kl2) : nullptr;
+  pp.ste_kind = in.ste_kind; pp.ste = in.ste; pp.pure = in.pure;
+  if (stats_in_rerank) {
+    pp.gs = in.gs;
+    pp.gs.kl2row = pp.kl2row;
+  }
+  pp.mu = const_cast<float *>(c.r_mu); pp.sd = const_cast<float *>(c.r_sd);
+  pp.lsd = const_cast<float *>(c.from_z() ? c.ws_lsd : c.lsd);
+  pp.lsd_out = (!c.from_z() && MODE == kModeGQ && !c.lsd) ? c.ws_lsd : nullptr;
+  pp.rowsum = c.at<double>(c.w.rowsum);
+  pp.coef = c.at<float>(c.w.coef);
+  pp.cb = c.cb;
+  pp.hdr = c.hdr; pp.rows = c.rows; pp.n = (int)c.n; pp.tiles_total = pl.tiles_total;
+  pp.row_blocks = (int)((c.rows * c.dim + 255) / 256);
+  pp.beta = (float)c.beta; pp.omap = c.omap;
+  pp.rowimg = (!grid && pl.bf16) ? c.at<u32x4>(c.w.rowimg) : nullptr;
+  pp.cbimg = (!grid && pl.bf16) ? c.at<u32x4>(c.w.cbimg) : nullptr;
+  pp.rowscale = scaled ? c.at<float>(c.w.rowscale) : nullptr;
+  pp.rowaux = (!grid && pl.f16) ? c.at<float>(c.w.rowaux) : nullptr;
+  GridHdr *ch = reinterpret_cast<GridHdr *>(c.cb_cache);
+  const int64_t img = grid ? 0 : image_cache_bytes(pl, c.dim);
+  if (grid) {
+    pp.cache_sums = ch->blk_sum; pp.cache_stale = &ch->stale;
+  } else if (ch && img > 0 && c.cb_cache_bytes >= img) {
+    pp.cbimg = reinterpret_cast<u32x4 *>(static_cast<char *>(c.cb_cache) + sizeof(GridHdr));
+    pp.cache_sums = ch->blk_sum;     // (of the header only the slice hashes are used: a slice is current iff its hash matches)
+  }
+  return pp;
+}
+
+// dims outside {4, 8, 16, 32}: prep -> exact score of every code (gq_exhaustive_kernel)
+template <int MODE>
+int run_exhaustive(const Call &c) {
+  const PrepInput &in = c.in;
+  if (hipMemsetAsync(c.hdr, 0, sizeof(WsHeader), c.st) != hipSuccess) return check_launch();
+  if (c.from_z()) {
+    PrepPlainParams pq{};
+    pq.z = in.z; pq.noise = in.noise; pq.zhat_noquant = in.zhat_noquant;
+    pq.sd_layout = in.sd_layout; pq.kl2row = in.want_kl2 ? c.at<float>(c.w.kl2) : nullptr;
+    pq.vq = MODE == kModeVQ ? 1 : 0;
+    pq.hdr = c.hdr; pq.ste_kind = in.ste_kind; pq.ste = in.ste; pq.pure = in.pure;
+    pq.mu = const_cast<float *>(c.r_mu); pq.sd = const_cast<float *>(c.r_sd); pq.lsd = c.ws_lsd;
+    pq.rows = c.rows; pq.dim = (int)c.dim; pq.lv_min = in.lv_min; pq.lv_max = in.lv_max; pq.omap = c.omap;
+    const int rc = launch(prep_plain_kernel, dim3((unsigned)((c.rows * c.dim + 255) / 256)), dim3(256), 0, c.st, pq);
+    if (rc != GQHIP_OK) return rc;
+  }
+  const int ex_blocks = (int)(c.rows < 4096 ? c.rows : 4096);
+  return launch(gq_exhaustive_kernel<MODE>, dim3((unsigned)ex_blocks), dim3(256), 0, c.st, rerank_params<MODE>(c));
+}
+
+// dims 4 / 8 with a codebook cache: prep (rows, bound sums, max|cb|, codebook hash) -> index builder (exits unless the hash says the
+// cache is stale) -> pruned exact search (gq_grid.h) -> the rows it left undecided.  Four launches, no filter, no re-rank.
+template <int MODE>
+int run_grid(const Call &c) {
+  const Env &e = env();
+  const GridKernels k = grid_kernels<MODE>(c.dim);
+  const PrepParams pp = prep_params<MODE>(c, true, false);
+  const dim3 pgrid((unsigned)(pp.row_blocks + kPrepCodeBlocks));
+  int rc = launch(prep_kernel<MODE>(c.from_z(), c.dim, false, false), pgrid, dim3(256), 0, c.st, pp);
+  if (rc != GQHIP_OK) return rc;
+  GridBuildParams bp{};
+  bp.cb = c.cb; bp.cache = static_cast<char *>(c.cb_cache); bp.hdr = c.hdr; bp.n = (int)c.n;
+  rc = launch(k.build, dim3(1), dim3(kGridBuildThreads), 0, c.st, bp);
+  if (rc != GQHIP_OK) return rc;
+  GridParams gp{};
+  gp.mu = c.r_mu; gp.sd = c.r_sd; gp.lsd = c.r_lsd; gp.rowsum = pp.rowsum; gp.coef = pp.coef; gp.cb = c.cb;
+  gp.cache = static_cast<const char *>(c.cb_cache);
+  gp.idx = c.idx; gp.zhat = c.zhat; gp.hdr = c.hdr; gp.rows = (int)c.rows; gp.n = (int)c.n; gp.beta = (float)c.beta;
+  gp.leaf_cap = e.grid_cap > 0 ? e.grid_cap : 256;     // leaves a row may visit before it is handed to the scan (a flat score)
+  gp.inwave_cap = e.grid_inwave > 0 ? e.grid_inwave : kGridLeafCap;
+  gp.stats = g_debug_stats; gp.omap = c.omap;
+  gp.abl = e.grid_abl;
+  // the list of undecided rows lives in the (otherwise unused) candidate-record region: 16 B x rows x record sets >= 12 B x rows
+  gp.und_row = c.at<int>(c.w.rec);
+  gp.und_thr = c.at<float>(c.w.rec) + c.rows;
+  gp.und_margin = c.at<float>(c.w.rec) + 2 * c.rows;
+  const int64_t nsets = (c.rows + 31) / 32;                        // (a block's eight waves fetch four rows at a time from a counter)
+  const int64_t max_blocks = e.grid_blocks > 0 ? e.grid_blocks : 512;
+  const dim3 ggrid((unsigned)(nsets < max_blocks ? nsets : max_blocks));   // two 512-thread blocks per CU: one wave of blocks
+  rc = launch(ProfScope(), k.search, ggrid, dim3(kGridThreads), 0, c.st, gp);
+  if (rc != GQHIP_OK) return rc;
+  // launch 4: the rows the search left undecided, a block per row (exits at once when there are none)
+  const dim3 fgrid((unsigned)(e.finish_blocks > 0 ? e.finish_blocks : 256));
+  return launch(k.finish, fgrid, dim3(kGridThreads), 0, c.st, gp);
+}
+
+// prep -> filter -> re-rank.  Three launches per call (round 4: the rows the candidates cannot decide are finished inside the
+// re-rank, gq_rerank.h); `stats_in_rerank`: one more block of the re-rank launch runs GQ2's statistics (gq_gauss.h).
+template <int MODE>
+int run_dense(const Call &c, bool stats_in_rerank) {
+  const Plan &pl = c.pl;
+  const bool mixed = pl.mixed_in(MODE);
+  // ---- launch 1 ----
+  const PrepParams pp = prep_params<MODE>(c, false, stats_in_rerank);
+  const dim3 pgrid((unsigned)(pp.row_blocks + kPrepCodeBlocks));
+  int rc = launch(prep_kernel<MODE>(c.from_z(), c.dim, mixed, pl.f16), pgrid, dim3(256), 0, c.st, pp);
+  if (rc != GQHIP_OK) return rc;
+
+  // ---- launch 2: the filter ----
+  const dim3 fgrid((unsigned)(pl.row_blocks * pl.nsplit));
+  if (pl.bf16) {
+    FilterBfParams fp{};
+    fp.cbimg = pp.cbimg; fp.rowimg = pp.rowimg;
+    fp.rec = c.at<Rec>(c.w.rec);
+    fp.rows = (int)c.rows; fp.n = (int)c.n;
+    fp.nsplit = pl.nsplit; fp.tiles_total = pl.tiles_total; fp.tiles_per_split = pl.tiles_per_split;
+    fp.hdr = c.hdr;
+    fp.dbg = c.ws + c.w.dbg;    // diagnostic builds only
+    fp.rowscale = pp.rowscale;
+    rc = launch(ProfScope(), filter_bf16_kernel(pl, c.dim, mixed), fgrid, dim3((unsigned)(64 * pl.waves)), 0, c.st, fp);
+  } else {
+    FilterParams fp{};
+    fp.mu = c.r_mu; fp.sd = c.r_sd; fp.cb = c.cb;
+    fp.rec = c.at<Rec>(c.w.rec);
+    fp.rows = (int)c.rows; fp.n = (int)c.n; fp.beta = (float)c.beta;
+    fp.nsplit = pl.nsplit; fp.tiles_total = pl.tiles_total; fp.tiles_per_split = pl.tiles_per_split;
+    fp.hdr = c.hdr;
+    fp.dbg = c.ws + c.w.dbg;      // diagnostic builds only
+    rc = launch(ProfScope(), filter_kernel<MODE>(pl, c.dim), fgrid, dim3(256), 0, c.st, fp);
+  }
+  if (rc != GQHIP_OK) return rc;
+
+  // ---- launch 3: exact re-rank of the candidates; rows they cannot decide are finished by their own block ----
+  const RerankParams rp = rerank_params<MODE>(c);
+  const dim3 rgrid((unsigned)((c.rows + 15) / 16 + (stats_in_rerank ? 1 : 0)));
+  return launch(rerank_kernel<MODE>(c.dim, rp.gt, rp.nsplit), rgrid, dim3(256), 0, c.st, rp);
+}
+
+// The fused arg-max, shared by GQ and VQ: checks, plan and workspace layout (once per call), the rows every kernel reads, then one
+// of the three paths above.  Nothing derived from the codebook or the rows survives the call outside the caller's codebook cache.
 template <int MODE>
 int run_argmax(const PrepInput &in, const float *mu, const float *sd, const float *lsd, const float *cb, int64_t *idx,
                float *zhat, int64_t dim, int64_t rows, int64_t n, double beta, void *workspace,
@@ -427,172 +605,52 @@ int run_argmax(const PrepInput &in, const float *mu, const float *sd, const floa
   if (rows == 0) return GQHIP_OK;   // empty batch: nothing to do (pointers may be NULL)
   const bool from_z = in.z != nullptr;
   if (!cb || !idx || (!from_z && (!mu || (MODE == kModeGQ && !sd)))) return GQHIP_ERR_INVALID_ARG;
-  const WsLayout w = ws_layout(rows, n, dim);
-  if (!workspace || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
-  char *ws = static_cast<char *>(workspace);
-  WsHeader *hdr = reinterpret_cast<WsHeader *>(ws + w.hdr);
   const Plan pl = make_plan(rows, n, dim);
-  float *ws_mu = reinterpret_cast<float *>(ws + w.mu), *ws_sd = reinterpret_cast<float *>(ws + w.sd);
-  float *ws_lsd = reinterpret_cast<float *>(ws + w.lsd);
-  // the rows every later kernel reads
-  const float *r_mu = from_z ? (in.mu_out ? in.mu_out : ws_mu) : mu;
-  const float *r_sd = from_z ? (in.sd_out ? in.sd_out : ws_sd) : sd;
-  const float *r_lsd = from_z ? ws_lsd : (MODE == kModeGQ ? (lsd ? lsd : (pl.mfma ? ws_lsd : nullptr)) : nullptr);
-
-  RerankParams rp{};
-  rp.mu = r_mu; rp.sd = MODE == kModeGQ ? r_sd : nullptr; rp.lsd = r_lsd; rp.cb = cb;
-  rp.rowsum = reinterpret_cast<const double *>(ws + w.rowsum);
-  rp.coef = reinterpret_cast<const float *>(ws + w.coef);
-  rp.rec = reinterpret_cast<const Rec *>(ws + w.rec);
-  rp.idx = idx; rp.zhat = zhat; rp.hdr = hdr;
-  rp.fb_list = reinterpret_cast<int *>(ws + w.fb);
-  rp.rows = (int)rows; rp.n = (int)n; rp.dim = (int)dim;
-  const bool mixed = pl.mixed && MODE == kModeGQ;
-  const bool f16 = pl.f16;
-  rp.ef_coeff = pl.bf16 ? (float)(dim == 4 ? 332 : 220 + 24 * dim) : (float)(2 * dim + 4);
-  if (mixed) { rp.ef_coeff = kMixedEfCoeff; rp.n1_limit = kMixedN1Limit; rp.n1_min = 1.0f; }
-  if (f16) {
-    rp.ef_coeff = kF16EfCoeff; rp.n1_limit = kF16N1Limit; rp.n1_min = 0.0f;
-    rp.rowaux = reinterpret_cast<const float *>(ws + w.rowaux);
-  }
-  static const double env_ef = getenv("GQHIP_EF_COEFF") ? atof(getenv("GQHIP_EF_COEFF")) : 0.0;   // diagnostics
-  if (env_ef > 0.0) rp.ef_coeff = (float)env_ef;
-  rp.beta = (float)beta; rp.nsplit = (mixed || f16) ? 2 * pl.nsplit : pl.nsplit; rp.gt = pl.gt; rp.all_rows = pl.mfma ? 0 : 1; rp.stats = g_debug_stats;
-  rp.omap = omap;
-  rp.dbg = ws + w.dbg + 64 * 1024;
-  rp.rec_halves = (mixed || f16) ? 2 : 1;
-  rp.tiles_per_split = pl.tiles_per_split; rp.tiles_total = pl.tiles_total;
-
-  if (!pl.mfma) {
-    // dims outside {4, 8, 16, 32}: exact score of every code (gq_exhaustive_kernel)
-    if (hipMemsetAsync(hdr, 0, sizeof(WsHeader), st) != hipSuccess) return check_launch();
-    if (from_z) {
-      PrepPlainParams pq{};
-      pq.z = in.z; pq.noise = in.noise; pq.zhat_noquant = in.zhat_noquant;
-      pq.sd_layout = in.sd_layout; pq.kl2row = in.want_kl2 ? reinterpret_cast<float *>(ws + w.kl2) : nullptr;
-      pq.vq = MODE == kModeVQ ? 1 : 0;
-      pq.hdr = hdr; pq.ste_kind = in.ste_kind; pq.ste = in.ste; pq.pure = in.pure;
-      pq.mu = const_cast<float *>(r_mu); pq.sd = const_cast<float *>(r_sd); pq.lsd = ws_lsd;
-      pq.rows = rows; pq.dim = (int)dim; pq.lv_min = in.lv_min; pq.lv_max = in.lv_max; pq.omap = omap;
-      hipLaunchKernelGGL(prep_plain_kernel, dim3((unsigned)((rows * dim + 255) / 256)), dim3(256), 0, st, pq);
-      const int rc = check_launch();
-      if (rc != GQHIP_OK) return rc;
-    }
-    const int ex_blocks = (int)(rows < 4096 ? rows : 4096);
-    hipLaunchKernelGGL((gq_exhaustive_kernel<MODE>), dim3((unsigned)ex_blocks), dim3(256), 0, st, rp);
-    return check_launch();
-  }
-
-  // ---- launch 1: rows (+ zhat_noquant), operand images, bound sums, max|cb| partials, header -------------------
-  PrepParams pp{};
-  pp.z = in.z; pp.noise = in.noise; pp.zhat_noquant = in.zhat_noquant; pp.lv_min = in.lv_min; pp.lv_max = in.lv_max;
-  pp.sd_layout = in.sd_layout; pp.kl2row = in.want_kl2 ? reinterpret_cast<float *>(ws + w.kl2) : nullptr;
-  pp.ste_kind = in.ste_kind; pp.ste = in.ste; pp.pure = in.pure;
-  const bool stats_in_rerank = MODE == kModeGQ && in.want_kl2 && !grid_applies(n, dim, cb_cache, cb_cache_bytes);
-  if (stats_in_rerank) {
-    pp.gs = in.gs;
-    pp.gs.kl2row = pp.kl2row;
-  }
-  if (in.stats_done) *in.stats_done = stats_in_rerank;
-  pp.mu = const_cast<float *>(r_mu); pp.sd = const_cast<float *>(r_sd);
-  pp.lsd = const_cast<float *>(from_z ? ws_lsd : lsd);
-  pp.lsd_out = (!from_z && MODE == kModeGQ && !lsd) ? ws_lsd : nullptr;
-  pp.rowsum = reinterpret_cast<double *>(ws + w.rowsum);
-  pp.coef = reinterpret_cast<float *>(ws + w.coef);
-  pp.rowimg = pl.bf16 ? reinterpret_cast<u32x4 *>(ws + w.rowimg) : nullptr;
-  pp.cb = cb;
-  pp.cbimg = pl.bf16 ? reinterpret_cast<u32x4 *>(ws + w.cbimg) : nullptr;
-  pp.hdr = hdr; pp.rows = rows; pp.n = (int)n; pp.tiles_total = pl.tiles_total;
-  pp.row_blocks = (int)((rows * dim + 255) / 256);
-  pp.beta = (float)beta; pp.omap = omap;
-  pp.rowscale = (mixed || f16) ? reinterpret_cast<float *>(ws + w.rowscale) : nullptr;
-  pp.rowaux = f16 ? reinterpret_cast<float *>(ws + w.rowaux) : nullptr;
+  const WsLayout w = ws_layout(pl, rows, dim);
+  if (!workspace || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
+  if (in.layout) *in.layout = w;
+  Call c{in, lsd, cb, idx, zhat, dim, rows, n, beta, cb_cache, cb_cache_bytes, omap, st, pl, w, static_cast<char *>(workspace)};
+  c.hdr = c.at<WsHeader>(w.hdr);
+  c.ws_lsd = c.at<float>(w.lsd);
+  c.r_mu = from_z ? (in.mu_out ? in.mu_out : c.at<float>(w.mu)) : mu;
+  c.r_sd = from_z ? (in.sd_out ? in.sd_out : c.at<float>(w.sd)) : sd;
+  c.r_lsd = from_z ? c.ws_lsd : (MODE == kModeGQ ? (lsd ? lsd : (pl.mfma ? c.ws_lsd : nullptr)) : nullptr);
+  if (!pl.mfma) return run_exhaustive<MODE>(c);
   const bool grid = grid_applies(n, dim, cb_cache, cb_cache_bytes);
-  if (grid) {
-    // ---- dims 4 / 8: prep (rows, bound sums, max|cb|, codebook hash) -> index builder (exits unless the hash says the cache is
-    //      stale) -> pruned exact search (gq_grid.h).  Three launches, no filter, no re-rank.
-    GridHdr *gh = reinterpret_cast<GridHdr *>(cb_cache);
-    pp.rowimg = nullptr; pp.cbimg = nullptr; pp.rowscale = nullptr; pp.rowaux = nullptr;
-    pp.cache_sums = gh->blk_sum; pp.cache_stale = &gh->stale;
-    int rc = from_z ? launch_prep<MODE, true>(pp, (int)dim, false, false, st) : launch_prep<MODE, false>(pp, (int)dim, false, false, st);
-    if (rc != GQHIP_OK) return rc;
-    GridBuildParams bp{};
-    bp.cb = cb; bp.cache = static_cast<char *>(cb_cache); bp.hdr = hdr; bp.n = (int)n;
-    if (dim == 4) hipLaunchKernelGGL((gq_grid_build_kernel<4>), dim3(1), dim3(kGridBuildThreads), 0, st, bp);
-    else hipLaunchKernelGGL((gq_grid_build_kernel<8>), dim3(1), dim3(kGridBuildThreads), 0, st, bp);
-    rc = check_launch();
-    if (rc != GQHIP_OK) return rc;
-    GridParams gp{};
-    gp.mu = r_mu; gp.sd = r_sd; gp.lsd = r_lsd; gp.rowsum = pp.rowsum; gp.coef = pp.coef; gp.cb = cb;
-    gp.cache = static_cast<const char *>(cb_cache);
-    gp.idx = idx; gp.zhat = zhat; gp.hdr = hdr; gp.rows = (int)rows; gp.n = (int)n; gp.beta = (float)beta;
-    static const int env_cap = getenv("GQHIP_GRID_CAP") ? atoi(getenv("GQHIP_GRID_CAP")) : 0;
-    gp.leaf_cap = env_cap > 0 ? env_cap : 256;     // leaves a row may visit before it is handed to the scan (a flat score)
-    static const int env_inwave = getenv("GQHIP_GRID_INWAVE") ? atoi(getenv("GQHIP_GRID_INWAVE")) : 0;   // diagnostics / tuning
-    gp.inwave_cap = env_inwave > 0 ? env_inwave : kGridLeafCap;
-    gp.stats = g_debug_stats; gp.omap = omap;
-    static const int env_abl = getenv("GQHIP_GRID_ABL") ? atoi(getenv("GQHIP_GRID_ABL")) : 0;   // diagnostic builds (make abl) only
-    gp.abl = env_abl;
-    // the list of undecided rows lives in the (otherwise unused) candidate-record region: 16 B x rows x record sets >= 12 B x rows
-    gp.und_row = reinterpret_cast<int *>(ws + w.rec);
-    gp.und_thr = reinterpret_cast<float *>(ws + w.rec) + rows;
-    gp.und_margin = reinterpret_cast<float *>(ws + w.rec) + 2 * rows;
-    const int64_t nsets = (rows + 31) / 32;                        // (a block's eight waves fetch four rows at a time from a counter)
-    static const int env_blocks = getenv("GQHIP_GRID_BLOCKS") ? atoi(getenv("GQHIP_GRID_BLOCKS")) : 0;   // diagnostics
-    const int64_t max_blocks = env_blocks > 0 ? env_blocks : 512;
-    const dim3 ggrid((unsigned)(nsets < max_blocks ? nsets : max_blocks));   // two 512-thread blocks per CU: one wave of blocks
-    ProfScope prof;
-#define GQ_GRID(D)                                                                                                   \
-  do {                                                                                                               \
-    if (prof.on) hipExtLaunchKernelGGL((gq_grid_kernel<MODE, D>), ggrid, dim3(kGridThreads), 0, st, prof.a, prof.b, 0, gp);    \
-    else hipLaunchKernelGGL((gq_grid_kernel<MODE, D>), ggrid, dim3(kGridThreads), 0, st, gp);                                  \
-  } while (0)
-    if (dim == 4) GQ_GRID(4); else GQ_GRID(8);
-#undef GQ_GRID
-    rc = check_launch();
-    if (rc != GQHIP_OK) return rc;
-    // launch 4: the rows the search left undecided, a block per row (exits at once when there are none)
-    static const int env_fblocks = getenv("GQHIP_FINISH_BLOCKS") ? atoi(getenv("GQHIP_FINISH_BLOCKS")) : 0;   // diagnostics
-    const dim3 fgrid((unsigned)(env_fblocks > 0 ? env_fblocks : 256));
-    if (dim == 4) hipLaunchKernelGGL((gq_grid_finish_kernel<MODE, 4>), fgrid, dim3(kGridThreads), 0, st, gp);
-    else hipLaunchKernelGGL((gq_grid_finish_kernel<MODE, 8>), fgrid, dim3(kGridThreads), 0, st, gp);
-    return check_launch();
-  }
-  if (f16 && cb_cache && image_cache_bytes(n, dim) > 0 && cb_cache_bytes >= image_cache_bytes(n, dim)) {
-    GridHdr *ih = reinterpret_cast<GridHdr *>(cb_cache);          // (only its slice hashes are used: a slice is current iff its hash matches)
-    pp.cbimg = reinterpret_cast<u32x4 *>(static_cast<char *>(cb_cache) + sizeof(GridHdr));
-    pp.cache_sums = ih->blk_sum;
-    pp.cache_stale = nullptr;
-  }
-  int rc = from_z ? launch_prep<MODE, true>(pp, (int)dim, mixed, f16, st) : launch_prep<MODE, false>(pp, (int)dim, mixed, f16, st);
-  if (rc != GQHIP_OK) return rc;
+  const bool stats_in_rerank = MODE == kModeGQ && in.want_kl2 && !grid;
+  if (in.stats_done) *in.stats_done = stats_in_rerank;
+  return grid ? run_grid<MODE>(c) : run_dense<MODE>(c, stats_in_rerank);
+}
 
-  // ---- launch 2: the filter ---------------------------------------------------------------------------------
-  if (pl.bf16) {
-    FilterBfParams fp{};
-    fp.cbimg = pp.cbimg; fp.rowimg = pp.rowimg;
-    fp.rec = reinterpret_cast<Rec *>(ws + w.rec);
-    fp.rows = (int)rows; fp.n = (int)n;
-    fp.nsplit = pl.nsplit; fp.tiles_total = pl.tiles_total; fp.tiles_per_split = pl.tiles_per_split;
-    fp.hdr = hdr;
-    fp.dbg = ws + w.dbg;    // diagnostic builds only
-    fp.rowscale = (mixed || f16) ? reinterpret_cast<const float *>(ws + w.rowscale) : nullptr;
-    rc = launch_filter_bf16<MODE>(pl, fp, (int)dim, mixed, st);
-    if (rc != GQHIP_OK) return rc;
-  } else {
-    FilterParams fp{};
-    fp.mu = r_mu; fp.sd = r_sd; fp.cb = cb;
-    fp.rec = reinterpret_cast<Rec *>(ws + w.rec);
-    fp.rows = (int)rows; fp.n = (int)n; fp.beta = (float)beta;
-    fp.nsplit = pl.nsplit; fp.tiles_total = pl.tiles_total; fp.tiles_per_split = pl.tiles_per_split;
-    fp.hdr = hdr;
-    fp.dbg = ws + w.dbg;      // diagnostic builds only
-    rc = launch_filter<MODE>(pl, fp, (int)dim, st);
-    if (rc != GQHIP_OK) return rc;
-  }
+// ---- the module-level entry points: (B, L, c, dim, layout, grouping) -> groups per position, rows, and where a row's outputs go ----
+struct ZGeom {
+  int64_t K = 0, rows = 0;
+  OutMap om{};
+};
+// `strict` off (gq_dequant_f32 only): that entry point has never bounded dim by kMaxDim -- its kernel takes any -- nor rejected
+// layout / grouping values outside the enums (read as BLC / as the kernel reads them), and callers may rely on either.
+bool z_geometry(int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping, ZGeom *g, bool strict = true) {
+  if (B < 0 || L < 1 || c < 1 || dim < 1 || c % dim != 0) return false;
+  if (strict && (dim > kMaxDim || (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) ||
+                 (grouping != GQHIP_GROUP_STRIDED && grouping != GQHIP_GROUP_CONTIGUOUS)))
+    return false;
+  g->K = c / dim;
+  g->rows = B * L * g->K;
+  g->om.mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  g->om.K = (int)g->K; g->om.L = (int)L; g->om.c = (int)c; g->om.grouping = grouping;
+  return true;
+}
+bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
-  // ---- launch 3: exact re-rank of the candidates; rows they cannot decide are finished by their own block --------------
-  return launch_rerank<MODE>(rp, rows, (int)dim, st, stats_in_rerank);
+// the statistics block's parameters (gq_gauss.h); `kl2row` may be filled in later
+GaussStatsParams gauss_stats_params(const float *kl2row, int64_t rows, double *lam_state, void *scalars, double log2n, double tolerance,
+                                    double lam_factor, double lam_lo, double lam_hi, int lam_max_decreases, double loss_divisor) {
+  GaussStatsParams gp{};
+  gp.kl2row = kl2row; gp.rows = (long)rows; gp.lam_state = lam_state; gp.scalars = scalars;
+  gp.thr_hi = (float)(log2n + tolerance); gp.thr_lo = (float)(log2n - tolerance); gp.log2n = (float)log2n;
+  gp.lam_factor = lam_factor; gp.lam_lo = lam_lo; gp.lam_hi = lam_hi; gp.lam_max_decreases = lam_max_decreases;
+  gp.loss_divisor = loss_divisor;
+  return gp;
 }
 
 }  // namespace
@@ -626,16 +684,15 @@ int gqhip_get_filter(void) { return g_filter_kind.load(std::memory_order_relaxed
 int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8) {
   if (!out8 || rows < 1 || n < 1 || dim < 1 || dim > kMaxDim) return GQHIP_ERR_INVALID_ARG;
   const Plan pl = make_plan(rows, n, dim);
-  const WsLayout w = ws_layout(rows, n, dim);
-  out8[0] = w.rec; out8[1] = pl.mfma ? pl.nsplit * ((pl.mixed || pl.f16) ? 2 : 1) : 0;   // record sets per row (fp16 + fp8: one per lane half)
+  out8[0] = ws_layout(pl, rows, dim).rec; out8[1] = pl.stored_rec_sets();
   out8[2] = pl.gt; out8[3] = pl.tiles_per_split;
   out8[4] = pl.f16 ? 3 : (pl.mixed ? 2 : (pl.bf16 ? 1 : 0));   // 0 fp32 MFMA filter, 1 split-bf16, 2 fp16 + fp8 (Gaussian score), 3 fp16 main product
-  out8[5] = pl.f16 ? (int)kF16EfCoeff : (pl.mixed ? (int)kMixedEfCoeff : (pl.bf16 ? (dim == 4 ? 332 : 220 + 24 * dim) : 2 * dim + 4));
+  out8[5] = (int64_t)rerank_bound(pl, kModeGQ, dim).ef_coeff;
   out8[6] = pl.rt; out8[7] = pl.waves;
   return GQHIP_OK;
 }
 
-int gqhip_grid_search_applies(int64_t n, int64_t dim) { return grid_cache_bytes(n, dim) > 0 && g_filter_kind.load(std::memory_order_relaxed) == 0; }
+int gqhip_grid_search_applies(int64_t n, int64_t dim) { return grid_cache_bytes(n, dim) > 0 && filter_kind() == GQHIP_FILTER_AUTO; }
 
 int gqhip_cb_cache_degenerate(const void *cb_cache, int64_t n, int64_t dim) {
   if (!cb_cache || grid_cache_bytes(n, dim) <= 0) return -1;
@@ -648,12 +705,28 @@ int gqhip_cb_cache_degenerate(const void *cb_cache, int64_t n, int64_t dim) {
 int64_t gqhip_cb_cache_bytes(int64_t n, int64_t dim) {
   if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
   const int64_t g = grid_cache_bytes(n, dim);
-  return g > 0 ? g : image_cache_bytes(n, dim);
+  return g > 0 ? g : image_cache_bytes(make_plan(65536, n, dim), dim);
 }
 
 int64_t gqhip_workspace_bytes(int64_t rows, int64_t n, int64_t dim) {
   if (rows < 0 || n < 1 || dim < 1 || dim > kMaxDim) return -1;
-  return ws_layout(rows < 1 ? 1 : rows, n, dim).total;
+  if (rows < 1) rows = 1;
+  return ws_layout(make_plan(rows, n, dim), rows, dim).total;
+}
+
+// the per-pair kernel of the compat op at the MFMA dims (gq_aux.h), 16 rows per block; nullptr: any other dim
+static auto scores_pair_kernel(int64_t dim, bool beta1) -> decltype(&gq_scores_kernel<4, 16, true>) {
+  switch (dim * 2 + (beta1 ? 1 : 0)) {
+    case 8: return gq_scores_kernel<4, 16, false>;
+    case 9: return gq_scores_kernel<4, 16, true>;
+    case 16: return gq_scores_kernel<8, 16, false>;
+    case 17: return gq_scores_kernel<8, 16, true>;
+    case 32: return gq_scores_kernel<16, 16, false>;
+    case 33: return gq_scores_kernel<16, 16, true>;
+    case 64: return gq_scores_kernel<32, 16, false>;
+    case 65: return gq_scores_kernel<32, 16, true>;
+    default: return nullptr;
+  }
 }
 
 int gq_scores_f32(const float *mu, const float *sd, const float *cb, float *out, int64_t dim,
@@ -662,72 +735,44 @@ int gq_scores_f32(const float *mu, const float *sd, const float *cb, float *out,
   if (rows == 0) return GQHIP_OK;
   if (!mu || !sd || !cb || !out) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
+  const Env &e = env();
   // Default: the score matrix on the matrix cores, HBM-write bound -- dims 16 / 32 as three fp16 products of two-term splits
   // (gq_scores_f16.h), dims 4 / 8 on the fp32 matrix cores (gq_scores.h; GQHIP_SCORES=f32: at every dim).  GQHIP_SCORES=direct:
   // the per-pair restatement of the CUDA kernel's formula (VALU bound, ~3x slower).  Non-finite beta, dims outside
   // {4, 8, 16, 32}: per-pair kernels.
-  static const bool env_direct = getenv("GQHIP_SCORES") && getenv("GQHIP_SCORES")[0] == 'd';
-  if (!env_direct && (dim == 4 || dim == 8 || dim == 16 || dim == 32) && beta == beta && n >= 32) {
+  if (e.scores != 'd' && (dim == 4 || dim == 8 || dim == 16 || dim == 32) && beta == beta && n >= 32) {
     ScoresParams sp{};
     sp.mu = mu; sp.sd = sd; sp.cb = cb; sp.out = out; sp.rows = (int)rows; sp.n = (int)n; sp.beta = beta;
     sp.tiles_total = (int)((n + kTileCodes - 1) / kTileCodes);
-    // diagnostics (tools/scores_sweep.sh): code splits per row block; bit 0 / 1 of the rotation (gq_scores.h), default both
-    static const int env_nsplit = getenv("GQHIP_SCORES_NSPLIT") ? atoi(getenv("GQHIP_SCORES_NSPLIT")) : 0;
-    static const int env_rot = getenv("GQHIP_SCORES_ROT") ? atoi(getenv("GQHIP_SCORES_ROT")) : 3;
-    sp.rot = env_rot;
+    sp.rot = e.scores_rot;
     constexpr int RT = 2;
     const int row_blocks = (int)((rows + 128 * RT - 1) / (128 * RT));
     int s = (512 + row_blocks - 1) / row_blocks;      // ~2 blocks per CU; splits in multiples of 8 (XCD = blockIdx % 8)
     s = ((s + 7) / 8) * 8;
-    if (env_nsplit > 0) s = env_nsplit;
+    if (e.scores_nsplit > 0) s = e.scores_nsplit;
     if (s > sp.tiles_total) s = sp.tiles_total;
     if (s < 1) s = 1;
     sp.tiles_per_split = (sp.tiles_total + s - 1) / s;
     sp.nsplit = (sp.tiles_total + sp.tiles_per_split - 1) / sp.tiles_per_split;
     const dim3 grid((unsigned)(row_blocks * sp.nsplit));
-    // dims 16 / 32: three fp16 products of two-term splits (gq_scores_f16.h) unless GQHIP_SCORES=f32
-    static const bool env_f32 = getenv("GQHIP_SCORES") && getenv("GQHIP_SCORES")[0] == 'f';
-    if (!env_f32 && dim == 16) {
-      hipLaunchKernelGGL((gq_scores_f16x3_kernel<16, RT, 8>), grid, dim3(256), 0, st, sp);
-      return check_launch();
-    }
-    if (!env_f32 && dim == 32) {
-      hipLaunchKernelGGL((gq_scores_f16x3_kernel<32, RT, 4>), grid, dim3(256), 0, st, sp);
-      return check_launch();
-    }
+    const bool f16x3 = e.scores != 'f';
+    if (f16x3 && dim == 16) return launch(gq_scores_f16x3_kernel<16, RT, 8>, grid, dim3(256), 0, st, sp);
+    if (f16x3 && dim == 32) return launch(gq_scores_f16x3_kernel<32, RT, 4>, grid, dim3(256), 0, st, sp);
     switch (dim) {
-      case 4: hipLaunchKernelGGL((gq_scores_mfma_kernel<4, RT, 8>), grid, dim3(256), 0, st, sp); break;
-      case 8: hipLaunchKernelGGL((gq_scores_mfma_kernel<8, RT, 8>), grid, dim3(256), 0, st, sp); break;
-      case 16: hipLaunchKernelGGL((gq_scores_mfma_kernel<16, RT, 8>), grid, dim3(256), 0, st, sp); break;
-      default: hipLaunchKernelGGL((gq_scores_mfma_kernel<32, RT, 4>), grid, dim3(256), 0, st, sp); break;
+      case 4: return launch(gq_scores_mfma_kernel<4, RT, 8>, grid, dim3(256), 0, st, sp);
+      case 8: return launch(gq_scores_mfma_kernel<8, RT, 8>, grid, dim3(256), 0, st, sp);
+      case 16: return launch(gq_scores_mfma_kernel<16, RT, 8>, grid, dim3(256), 0, st, sp);
+      default: return launch(gq_scores_mfma_kernel<32, RT, 4>, grid, dim3(256), 0, st, sp);
     }
-    return check_launch();
   }
   const int cpt = 1;   // codes per thread of gq_scores_kernel (CPT there)
   const unsigned gx = (unsigned)((n + 256 * cpt - 1) / (256 * cpt));
-  constexpr int ROWS = 16;
-  const unsigned gy = (unsigned)((rows + ROWS - 1) / ROWS);
+  const unsigned gy = (unsigned)((rows + 16 - 1) / 16);
   if (gy > 65535u * 32u) return GQHIP_ERR_INVALID_ARG;
-#define GQ_SC(D)                                                                                          \
-  do {                                                                                                    \
-    if (beta == 1.0)                                                                                      \
-      hipLaunchKernelGGL((gq_scores_kernel<D, ROWS, true>), dim3(gx, gy), dim3(256), 0, st, mu, sd, cb, out, \
-                         (int)rows, (int)n, beta);                                                        \
-    else                                                                                                  \
-      hipLaunchKernelGGL((gq_scores_kernel<D, ROWS, false>), dim3(gx, gy), dim3(256), 0, st, mu, sd, cb, out, \
-                         (int)rows, (int)n, beta);                                                        \
-  } while (0)
-  switch (dim) {
-    case 4: GQ_SC(4); break;
-    case 8: GQ_SC(8); break;
-    case 16: GQ_SC(16); break;
-    case 32: GQ_SC(32); break;
-    default:
-      hipLaunchKernelGGL(gq_scores_generic_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0, st, mu, sd, cb,
-                         out, (int)dim, (int)rows, (int)n, beta);
-  }
-#undef GQ_SC
-  return check_launch();
+  if (const auto pair = scores_pair_kernel(dim, beta == 1.0))
+    return launch(pair, dim3(gx, gy), dim3(256), 0, st, mu, sd, cb, out, (int)rows, (int)n, beta);
+  return launch(gq_scores_generic_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)rows), dim3(256), 0, st, mu, sd, cb, out,
+                (int)dim, (int)rows, (int)n, beta);
 }
 
 int gq_argmax_f32(const float *mu, const float *sd, const float *logsd_or_null, const float *cb,
@@ -744,24 +789,17 @@ int gq_quantize_z_f32(const float *z, const float *noise_or_null, const float *c
                       float *sd_out_or_null, int64_t B, int64_t L, int64_t c, int64_t dim, int64_t n, int layout,
                       int grouping, double lv_min, double lv_max, double beta, void *workspace,
                       int64_t workspace_bytes, void *cb_cache_or_null, int64_t cb_cache_bytes, void *stream) {
-  if (!z || !cb || !idx || B < 0 || L < 1 || c < 1 || dim < 1 || dim > kMaxDim || c % dim != 0)
-    return GQHIP_ERR_INVALID_ARG;
-  if ((layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) ||
-      (grouping != GQHIP_GROUP_STRIDED && grouping != GQHIP_GROUP_CONTIGUOUS))
-    return GQHIP_ERR_INVALID_ARG;
+  ZGeom g;
+  if (!z || !cb || !idx || !z_geometry(B, L, c, dim, layout, grouping, &g)) return GQHIP_ERR_INVALID_ARG;
   if (zhat_noquant_or_null && !noise_or_null) return GQHIP_ERR_INVALID_ARG;
-  const int64_t K = c / dim, rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;
-  if (rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;
+  if (g.rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
   PrepInput in;
   in.z = z; in.noise = noise_or_null; in.zhat_noquant = zhat_noquant_or_null;
   in.lv_min = (float)lv_min; in.lv_max = (float)lv_max;
   in.mu_out = mu_out_or_null; in.sd_out = sd_out_or_null;
-  OutMap om{};
-  om.mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  om.K = (int)K; om.L = (int)L; om.c = (int)c; om.grouping = grouping;
-  return run_argmax<kModeGQ>(in, nullptr, nullptr, nullptr, cb, idx, zhat_or_null, dim, rows, n, beta, workspace,
-                             workspace_bytes, cb_cache_or_null, cb_cache_bytes, om, static_cast<hipStream_t>(stream));
+  return run_argmax<kModeGQ>(in, nullptr, nullptr, nullptr, cb, idx, zhat_or_null, dim, g.rows, n, beta, workspace,
+                             workspace_bytes, cb_cache_or_null, cb_cache_bytes, g.om, static_cast<hipStream_t>(stream));
 }
 
 int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb, int64_t *idx, float *zhat,
@@ -770,38 +808,29 @@ int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb,
                             double lv_max, double beta, int use_ste, double log2n, double tolerance, double lam_factor,
                             double lam_lo, double lam_hi, int lam_max_decreases, void *workspace, int64_t workspace_bytes,
                             void *cb_cache_or_null, int64_t cb_cache_bytes, void *stream) {
-  if (!z || !noise || !cb || !idx || !zhat || !zhat_noquant || !scalars_out || !lam_state || B < 0 || L < 1 || c < 1 ||
-      dim < 1 || dim > kMaxDim || c % dim != 0)
+  ZGeom g;
+  if (!z || !noise || !cb || !idx || !zhat || !zhat_noquant || !scalars_out || !lam_state ||
+      !z_geometry(B, L, c, dim, layout, grouping, &g))
     return GQHIP_ERR_INVALID_ARG;
-  if ((layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) ||
-      (grouping != GQHIP_GROUP_STRIDED && grouping != GQHIP_GROUP_CONTIGUOUS))
-    return GQHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(scalars_out) & 7u) || (reinterpret_cast<uintptr_t>(lam_state) & 7u)) return GQHIP_ERR_INVALID_ARG;
-  const int64_t K = c / dim, rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
-  if (rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned8(scalars_out) || !aligned8(lam_state)) return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
+  if (g.rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   PrepInput in;
   in.z = z; in.noise = noise; in.zhat_noquant = zhat_noquant;
   in.lv_min = (float)lv_min; in.lv_max = (float)lv_max;
   in.sd_layout = sd_out_or_null; in.want_kl2 = true;
-  OutMap om{};
-  om.mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  om.K = (int)K; om.L = (int)L; om.c = (int)c; om.grouping = grouping;
   if (use_ste) { in.ste_kind = 1; in.ste = zhat_noquant; in.pure = zhat_quant_or_null; }
-  GaussStatsParams gp{};
-  gp.rows = (long)rows; gp.lam_state = lam_state; gp.scalars = scalars_out;
-  gp.thr_hi = (float)(log2n + tolerance); gp.thr_lo = (float)(log2n - tolerance); gp.log2n = (float)log2n;
-  gp.lam_factor = lam_factor; gp.lam_lo = lam_lo; gp.lam_hi = lam_hi; gp.lam_max_decreases = lam_max_decreases;
-  gp.loss_divisor = (double)rows;                    // the mean of gaussian.py:241
+  in.gs = gauss_stats_params(nullptr, g.rows, lam_state, scalars_out, log2n, tolerance, lam_factor, lam_lo, lam_hi, lam_max_decreases,
+                             (double)g.rows);        // the mean of gaussian.py:241
   bool stats_done = false;
-  in.gs = gp; in.stats_done = &stats_done;
-  int rc = run_argmax<kModeGQ>(in, nullptr, nullptr, nullptr, cb, idx, zhat, dim, rows, n, beta, workspace, workspace_bytes,
-                               cb_cache_or_null, cb_cache_bytes, om, st);
+  WsLayout w{};
+  in.stats_done = &stats_done; in.layout = &w;
+  const int rc = run_argmax<kModeGQ>(in, nullptr, nullptr, nullptr, cb, idx, zhat, dim, g.rows, n, beta, workspace, workspace_bytes,
+                                     cb_cache_or_null, cb_cache_bytes, g.om, st);
   if (rc != GQHIP_OK || stats_done) return rc;       // dims 8 / 16 / 32: the statistics block ran as one extra block of the re-rank launch
-  gp.kl2row = reinterpret_cast<const float *>(static_cast<char *>(workspace) + ws_layout(rows, n, dim).kl2);
-  hipLaunchKernelGGL(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st, gp);
-  return check_launch();
+  in.gs.kl2row = reinterpret_cast<const float *>(static_cast<char *>(workspace) + w.kl2);
+  return launch(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st, in.gs);
 }
 
 // ---- the train-mode step of the Gaussian regularizers (gq_gauss_train.h) ----
@@ -823,121 +852,91 @@ unsigned train_grid(long items) {
   const long blocks = (items + 255) / 256;
   return (unsigned)(blocks < kTrainMaxBlocks ? blocks : kTrainMaxBlocks);
 }
-bool train_shape_ok(int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping) {
-  if (B < 0 || L < 1 || c < 1 || dim < 1 || dim > kMaxDim || c % dim != 0) return false;
-  return (layout == GQHIP_LAYOUT_BCHW || layout == GQHIP_LAYOUT_BLC) &&
-         (grouping == GQHIP_GROUP_STRIDED || grouping == GQHIP_GROUP_CONTIGUOUS);
-}
+uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
 }  // namespace
 
 int gq_gauss_train_f32(const float *z, const float *noise, float *zhat, float *sd_out_or_null, float *kl2row, void *scalars_out,
                        double *lam_state, int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int grouping, double lv_min,
                        double lv_max, double log2n, double tolerance, double lam_factor, double lam_lo, double lam_hi,
                        int lam_max_decreases, double loss_divisor, void *stream) {
-  if (!z || !noise || !zhat || !kl2row || !scalars_out || !lam_state || !train_shape_ok(B, L, c, dim, layout, grouping))
+  ZGeom g;
+  if (!z || !noise || !zhat || !kl2row || !scalars_out || !lam_state || !z_geometry(B, L, c, dim, layout, grouping, &g))
     return GQHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(scalars_out) & 7u) || (reinterpret_cast<uintptr_t>(lam_state) & 7u)) return GQHIP_ERR_INVALID_ARG;
-  const int64_t K = c / dim, rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
-  if (rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned8(scalars_out) || !aligned8(lam_state)) return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
+  if (g.rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   GaussTrainParams p{};
   p.z = z; p.noise = noise; p.zhat = zhat; p.sd_out = sd_out_or_null; p.kl2row = kl2row;
   p.lv_min = (float)lv_min; p.lv_max = (float)lv_max;
-  p.dim = (int)dim; p.K = (int)K; p.L = (int)L; p.c = (int)c;
-  p.layout = layout == GQHIP_LAYOUT_BCHW ? 1 : 2; p.grouping = grouping;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(zhat) |
-                         reinterpret_cast<uintptr_t>(sd_out_or_null);
-  const int variant = train_variant(layout, grouping, dim, K, L, bits, (long)rows, &p.items);
-  const dim3 grid(train_grid(p.items));
-  switch (variant) {
-    case 1: hipLaunchKernelGGL((gauss_train_fwd_kernel<4, false>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((gauss_train_fwd_kernel<4, true>), grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((gauss_train_fwd_kernel<1, false>), grid, dim3(256), 0, st, p);
-  }
-  int rc = check_launch();
+  p.dim = (int)dim; p.K = (int)g.K; p.L = (int)L; p.c = (int)c;
+  p.layout = g.om.mode; p.grouping = grouping;
+  const int variant = train_variant(layout, grouping, dim, g.K, L, bits(z) | bits(noise) | bits(zhat) | bits(sd_out_or_null),
+                                    (long)g.rows, &p.items);
+  const auto fwd = variant == 1 ? gauss_train_fwd_kernel<4, false> : variant == 2 ? gauss_train_fwd_kernel<4, true> : gauss_train_fwd_kernel<1, false>;
+  const int rc = launch(fwd, dim3(train_grid(p.items)), dim3(256), 0, st, p);
   if (rc != GQHIP_OK) return rc;
-  GaussStatsParams gp{};
-  gp.kl2row = kl2row; gp.rows = (long)rows; gp.lam_state = lam_state; gp.scalars = scalars_out;
-  gp.thr_hi = (float)(log2n + tolerance); gp.thr_lo = (float)(log2n - tolerance); gp.log2n = (float)log2n;
-  gp.lam_factor = lam_factor; gp.lam_lo = lam_lo; gp.lam_hi = lam_hi; gp.lam_max_decreases = lam_max_decreases;
-  gp.loss_divisor = loss_divisor;
-  hipLaunchKernelGGL(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st, gp);      // the second launch: same stream, in order
-  return check_launch();
+  return launch(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st,      // the second launch: same stream, in order
+                gauss_stats_params(kl2row, g.rows, lam_state, scalars_out, log2n, tolerance, lam_factor, lam_lo, lam_hi,
+                                   lam_max_decreases, loss_divisor));
 }
 
 int gq_gauss_backward_f32(const float *z, const float *noise, const float *g_zhat_or_null, const float *g_sd_or_null,
                           const float *g_kl_or_null, const double *lam_before, float *grad_z, int64_t B, int64_t L, int64_t c,
                           int64_t dim, int layout, int grouping, double lv_min, double lv_max, double log2n, double tolerance,
                           double loss_divisor, void *stream) {
-  if (!z || !noise || !lam_before || !grad_z || !train_shape_ok(B, L, c, dim, layout, grouping)) return GQHIP_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(lam_before) & 7u) || (reinterpret_cast<uintptr_t>(g_kl_or_null) & 3u)) return GQHIP_ERR_INVALID_ARG;
-  const int64_t K = c / dim, rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;
-  if (rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
+  ZGeom g;
+  if (!z || !noise || !lam_before || !grad_z || !z_geometry(B, L, c, dim, layout, grouping, &g)) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned8(lam_before) || (bits(g_kl_or_null) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;
+  if (g.rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
   GaussTrainParams p{};
   p.z = z; p.noise = noise; p.g_zhat = g_zhat_or_null; p.g_sd = g_sd_or_null; p.g_kl = g_kl_or_null;
   p.lam_before = lam_before; p.grad_z = grad_z; p.divisor = loss_divisor;
   p.thr_hi = (float)(log2n + tolerance); p.thr_lo = (float)(log2n - tolerance);
   p.lv_min = (float)lv_min; p.lv_max = (float)lv_max;
-  p.dim = (int)dim; p.K = (int)K; p.L = (int)L; p.c = (int)c;
-  p.layout = layout == GQHIP_LAYOUT_BCHW ? 1 : 2; p.grouping = grouping;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(g_zhat_or_null) |
-                         reinterpret_cast<uintptr_t>(g_sd_or_null) | reinterpret_cast<uintptr_t>(grad_z);
-  const int variant = train_variant(layout, grouping, dim, K, L, bits, (long)rows, &p.items);
-  const dim3 grid(train_grid(p.items));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (variant) {
-    case 1: hipLaunchKernelGGL((gauss_train_bwd_kernel<4, false>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((gauss_train_bwd_kernel<4, true>), grid, dim3(256), 0, st, p); break;
-    default: hipLaunchKernelGGL((gauss_train_bwd_kernel<1, false>), grid, dim3(256), 0, st, p);
-  }
-  return check_launch();
+  p.dim = (int)dim; p.K = (int)g.K; p.L = (int)L; p.c = (int)c;
+  p.layout = g.om.mode; p.grouping = grouping;
+  const int variant = train_variant(layout, grouping, dim, g.K, L,
+                                    bits(z) | bits(noise) | bits(g_zhat_or_null) | bits(g_sd_or_null) | bits(grad_z), (long)g.rows, &p.items);
+  const auto bwd = variant == 1 ? gauss_train_bwd_kernel<4, false> : variant == 2 ? gauss_train_bwd_kernel<4, true> : gauss_train_bwd_kernel<1, false>;
+  return launch(bwd, dim3(train_grid(p.items)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 int vq_quantize_z_f32(const float *z, const float *emb, int64_t *idx, float *zq, float *loss2_or_null, int64_t B, int64_t L,
                       int64_t c, int64_t dim, int64_t n, int layout, double beta, int legacy, void *workspace,
                       int64_t workspace_bytes, void *cb_cache_or_null, int64_t cb_cache_bytes, void *stream) {
-  if (!z || !emb || !idx || !zq || B < 0 || L < 1 || c < 1 || dim < 1 || dim > kMaxDim || c % dim != 0)
-    return GQHIP_ERR_INVALID_ARG;
-  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return GQHIP_ERR_INVALID_ARG;
-  const int64_t K = c / dim, rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;
-  if (rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  ZGeom g;                                                                            // channel = d * K + k (vq.py:53): strided
+  if (!z || !emb || !idx || !zq || !z_geometry(B, L, c, dim, layout, GQHIP_GROUP_STRIDED, &g)) return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;
+  if (g.rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   PrepInput in;
-  in.z = z;
-  OutMap om{};
-  om.mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  om.K = (int)K; om.L = (int)L; om.c = (int)c; om.grouping = GQHIP_GROUP_STRIDED;     // channel = d * K + k (vq.py:53)
+  WsLayout w{};
+  in.z = z; in.layout = &w;
   in.ste_kind = 2; in.ste = z;                                                        // z_q = z + (z_q - z) (vq.py:89)
-  int rc = run_argmax<kModeVQ>(in, nullptr, nullptr, nullptr, emb, idx, zq, dim, rows, n, 0.0, workspace, workspace_bytes,
-                               cb_cache_or_null, cb_cache_bytes, om, st);
+  const int rc = run_argmax<kModeVQ>(in, nullptr, nullptr, nullptr, emb, idx, zq, dim, g.rows, n, 0.0, workspace, workspace_bytes,
+                                     cb_cache_or_null, cb_cache_bytes, g.om, st);
   if (rc != GQHIP_OK || !loss2_or_null) return rc;
-  const WsLayout w = ws_layout(rows, n, dim);
   VqLossParams lp{};
   lp.zrows = reinterpret_cast<const float *>(static_cast<char *>(workspace) + w.mu);
   lp.idx = idx; lp.emb = emb; lp.loss = loss2_or_null;
   lp.hdr = reinterpret_cast<WsHeader *>(static_cast<char *>(workspace) + w.hdr);
-  lp.rows = (long)rows; lp.dim = (int)dim; lp.n = (int)n; lp.beta = (float)beta; lp.legacy = legacy; lp.omap = om;
-  int64_t blocks = (rows * dim + 256 * 16 - 1) / (256 * 16);
+  lp.rows = (long)g.rows; lp.dim = (int)dim; lp.n = (int)n; lp.beta = (float)beta; lp.legacy = legacy; lp.omap = g.om;
+  int64_t blocks = (g.rows * dim + 256 * 16 - 1) / (256 * 16);
   blocks = blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);
-  hipLaunchKernelGGL(vq_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, st, lp);
-  return check_launch();
+  return launch(vq_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, st, lp);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,
                    int64_t dim, int64_t n, int layout, int grouping, void *stream) {
-  if (!idx || !cb || !zhat || B < 0 || L < 1 || K < 1 || dim < 1 || n < 1) return GQHIP_ERR_INVALID_ARG;
-  const int64_t rows = B * L * K;
-  if (rows == 0) return GQHIP_OK;
+  ZGeom g;
+  if (!idx || !cb || !zhat || K < 1 || n < 1 || !z_geometry(B, L, K * dim, dim, layout, grouping, &g, /*strict=*/false))
+    return GQHIP_ERR_INVALID_ARG;
+  if (g.rows == 0) return GQHIP_OK;
   DequantParams dp{};
-  dp.idx = idx; dp.cb = cb; dp.zhat = zhat; dp.rows = rows; dp.dim = (int)dim; dp.n = (int)n;
-  dp.omap.mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  dp.omap.K = (int)K; dp.omap.L = (int)L; dp.omap.c = (int)(K * dim); dp.omap.grouping = grouping;
-  hipLaunchKernelGGL(dequant_kernel, dim3((unsigned)((rows * dim + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), dp);
-  return check_launch();
+  dp.idx = idx; dp.cb = cb; dp.zhat = zhat; dp.rows = g.rows; dp.dim = (int)dim; dp.n = (int)n; dp.omap = g.om;
+  return launch(dequant_kernel, dim3((unsigned)((g.rows * dim + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), dp);
 }
 
 int vq_argmin_f32(const float *z, const float *emb, int64_t *idx, float *zq_or_null, int64_t dim,
@@ -953,17 +952,15 @@ int lfq_pack_f32(const float *x, int64_t *idx, float *q_or_null, int64_t rows, i
                  void *stream) {
   if (!x || !idx || rows < 0 || nbits < 1 || nbits > 62) return GQHIP_ERR_INVALID_ARG;
   if (rows == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(lfq_pack_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, idx, q_or_null, (long)rows, (int)nbits);
-  return check_launch();
+  return launch(lfq_pack_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), x, idx, q_or_null, (long)rows, (int)nbits);
 }
 
 int lfq_unpack_f32(const int64_t *idx, float *q, int64_t rows, int64_t nbits, void *stream) {
   if (!idx || !q || rows < 0 || nbits < 1 || nbits > 62) return GQHIP_ERR_INVALID_ARG;
   if (rows == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(lfq_unpack_kernel, dim3((unsigned)((rows * nbits + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), idx, q, (long)rows, (int)nbits);
-  return check_launch();
+  return launch(lfq_unpack_kernel, dim3((unsigned)((rows * nbits + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), idx, q, (long)rows, (int)nbits);
 }
 
 static int fsq_levels(const int32_t *levels_host, int64_t nlev, FsqLevels *L) {
@@ -985,9 +982,8 @@ int fsq_quantize_f32(const float *z, const int32_t *levels_host, int64_t nlev, f
   FsqLevels L;
   if (!z || !idx || rows < 0 || fsq_levels(levels_host, nlev, &L) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
   if (rows == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(fsq_quantize_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), z, L, zhat, idx, (long)rows);
-  return check_launch();
+  return launch(fsq_quantize_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), z, L, zhat, idx, (long)rows);
 }
 
 int fsq_dequant_f32(const int32_t *idx, const int32_t *levels_host, int64_t nlev, float *zhat, int64_t rows,
@@ -995,9 +991,8 @@ int fsq_dequant_f32(const int32_t *idx, const int32_t *levels_host, int64_t nlev
   FsqLevels L;
   if (!idx || !zhat || rows < 0 || fsq_levels(levels_host, nlev, &L) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
   if (rows == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(fsq_dequant_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), idx, L, zhat, (long)rows);
-  return check_launch();
+  return launch(fsq_dequant_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), idx, L, zhat, (long)rows);
 }
 
 int gq_index_histogram(const int64_t *idx, int64_t count, int64_t n, int32_t *hist, void *stream) {
@@ -1007,24 +1002,21 @@ int gq_index_histogram(const int64_t *idx, int64_t count, int64_t n, int32_t *hi
   if (count == 0) return GQHIP_OK;
   int blocks = (int)((count + 255) / 256);
   blocks = blocks > 2048 ? 2048 : blocks;
-  hipLaunchKernelGGL(hist_kernel, dim3(blocks), dim3(256), 0, st, idx, (long)count, (int)n, hist);
-  return check_launch();
+  return launch(hist_kernel, dim3(blocks), dim3(256), 0, st, idx, (long)count, (int)n, hist);
 }
 
 int gq_indices_to_u16(const int64_t *idx, uint16_t *out, int64_t count, void *stream) {
   if (!idx || !out || count < 0) return GQHIP_ERR_INVALID_ARG;
   if (count == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(to_u16_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), idx, out, (long)count);
-  return check_launch();
+  return launch(to_u16_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), idx, out, (long)count);
 }
 
 int gq_indices_from_u16(const uint16_t *in, int64_t *idx, int64_t count, void *stream) {
   if (!in || !idx || count < 0) return GQHIP_ERR_INVALID_ARG;
   if (count == 0) return GQHIP_OK;
-  hipLaunchKernelGGL(from_u16_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), in, idx, (long)count);
-  return check_launch();
+  return launch(from_u16_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0,
+                static_cast<hipStream_t>(stream), in, idx, (long)count);
 }
 
 int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image) {
@@ -1045,8 +1037,7 @@ static int step_record_launch(const float *x, const float *x_rec, const int64_t 
   p.ticket = reinterpret_cast<int *>(static_cast<char *>(workspace_zeroed) + B * p.chunks * 8);
   const int64_t words = (n_idx + 1) / 2;
   const int64_t blocks = p.psnr_blocks + (words + 255) / 256;
-  hipLaunchKernelGGL(step_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-  return check_launch();
+  return launch(step_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
 }
 
 int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
@@ -1136,11 +1127,9 @@ int ssim_launch(const float *x, const float *y, int64_t B, int64_t C, int layout
     if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
     const bool fh = L.H >= gqssim::kWin, fw = L.W >= gqssim::kWin;
     const dim3 grid((unsigned)blocks);
-    if (fh && fw) hipLaunchKernelGGL((gqssim::ssim_level_kernel<true, true>), grid, dim3(256), 0, st, p);
-    else if (fh) hipLaunchKernelGGL((gqssim::ssim_level_kernel<true, false>), grid, dim3(256), 0, st, p);
-    else if (fw) hipLaunchKernelGGL((gqssim::ssim_level_kernel<false, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((gqssim::ssim_level_kernel<false, false>), grid, dim3(256), 0, st, p);
-    const int rc = check_launch();
+    const auto level = fh ? (fw ? gqssim::ssim_level_kernel<true, true> : gqssim::ssim_level_kernel<true, false>)
+                          : (fw ? gqssim::ssim_level_kernel<false, true> : gqssim::ssim_level_kernel<false, false>);
+    const int rc = launch(level, grid, dim3(256), 0, st, p);
     if (rc != GQHIP_OK) return rc;
   }
   return GQHIP_OK;

@@ -54,13 +54,8 @@ int gn_silu_f32(const float *x, const float *gamma, const float *beta, const flo
                        stats_ws, (int)C, (long)HW, (int)cpg, slabs);
     int rc = check_launch();
     if (rc != GQHIP_OK) return rc;
-    if (apply_silu)
-      hipLaunchKernelGGL((gn_apply_nhwc_kernel<1>), dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, gamma, beta, y,
-                         stats_ws, pre_bias_or_null, (int)C, (long)HW, (int)cpg, eps, slabs);
-    else
-      hipLaunchKernelGGL((gn_apply_nhwc_kernel<0>), dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, gamma, beta, y,
-                         stats_ws, pre_bias_or_null, (int)C, (long)HW, (int)cpg, eps, slabs);
-    return check_launch();
+    return launch(apply_silu ? gn_apply_nhwc_kernel<1> : gn_apply_nhwc_kernel<0>, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x,
+                  gamma, beta, y, stats_ws, pre_bias_or_null, (int)C, (long)HW, (int)cpg, eps, slabs);
   }
   if (layout != GQHIP_LAYOUT_NCHW || HW % 4 != 0) return GQHIP_ERR_INVALID_ARG;   // callers fall back to torch
   if (stats_zero(stats_ws, sizeof(int64_t) * kStatWords * bg, st) != hipSuccess) return check_launch();
@@ -75,13 +70,8 @@ int gn_silu_f32(const float *x, const float *gamma, const float *beta, const flo
   int segs = (int)((HW + 8191) / 8192);
   if (segs < 1) segs = 1;
   const dim3 grid((unsigned)(B * C * segs));
-  if (apply_silu)
-    hipLaunchKernelGGL((gn_apply_kernel<1>), grid, dim3(256), 0, st, x, gamma, beta, y, stats_ws, pre_bias_or_null,
-                       (int)C, (long)HW, (int)cpg, eps, segs);
-  else
-    hipLaunchKernelGGL((gn_apply_kernel<0>), grid, dim3(256), 0, st, x, gamma, beta, y, stats_ws, pre_bias_or_null,
-                       (int)C, (long)HW, (int)cpg, eps, segs);
-  return check_launch();
+  return launch(apply_silu ? gn_apply_kernel<1> : gn_apply_kernel<0>, grid, dim3(256), 0, st, x, gamma, beta, y, stats_ws,
+                pre_bias_or_null, (int)C, (long)HW, (int)cpg, eps, segs);
 }
 
 int add_bias_f32(const float *a, const float *b, const float *bias_or_null, float *y, int64_t B, int64_t C,
@@ -123,9 +113,8 @@ int add_bias_stats_f32(const float *a, const float *b, const float *bias_or_null
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups, st) != hipSuccess) return check_launch();
   const int slabs = nhwc_slabs(C, HW);
-  hipLaunchKernelGGL(add_bias_stats_nhwc_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, st, a, b, bias_or_null, y,
-                     stats_out, (int)C, (long)HW, (int)cpg, slabs);
-  return check_launch();
+  return launch(add_bias_stats_nhwc_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, st, a, b, bias_or_null, y,
+                stats_out, (int)C, (long)HW, (int)cpg, slabs);
 }
 
 int gn_apply_f32(const float *x, const float *gamma, const float *beta, float *y, int64_t B, int64_t C, int64_t HW,
@@ -137,13 +126,8 @@ int gn_apply_f32(const float *x, const float *gamma, const float *beta, float *y
   if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int slabs = nhwc_slabs(C, HW);
-  if (apply_silu)
-    hipLaunchKernelGGL((gn_apply_nhwc_kernel<1>), dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, gamma, beta, y, stats,
-                       (const float *)nullptr, (int)C, (long)HW, (int)cpg, eps, slabs);
-  else
-    hipLaunchKernelGGL((gn_apply_nhwc_kernel<0>), dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, gamma, beta, y, stats,
-                       (const float *)nullptr, (int)C, (long)HW, (int)cpg, eps, slabs);
-  return check_launch();
+  return launch(apply_silu ? gn_apply_nhwc_kernel<1> : gn_apply_nhwc_kernel<0>, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x,
+                gamma, beta, y, stats, nullptr, (int)C, (long)HW, (int)cpg, eps, slabs);
 }
 
 int wino_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
@@ -153,9 +137,8 @@ int wino_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, 
   const long tiles = (long)(B * (H / 2) * (W / 2)), total = tiles * (C / 4);
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(wino_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                     (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
-  return check_launch();
+  return launch(wino_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
 }
 
 static int wino_in_f16_impl(int vm, const float *x, void *V, int64_t B, int64_t H, int64_t W, int64_t C, int tile,
@@ -222,9 +205,8 @@ int gn_stats_f32(const float *x, const float *pre_bias_or_null, int64_t B, int64
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups, st) != hipSuccess) return check_launch();
   const int slabs = nhwc_slabs(C, HW);
-  hipLaunchKernelGGL(gn_stats_nhwc_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, pre_bias_or_null, stats_out,
-                     (int)C, (long)HW, (int)cpg, slabs);
-  return check_launch();
+  return launch(gn_stats_nhwc_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, pre_bias_or_null, stats_out,
+                (int)C, (long)HW, (int)cpg, slabs);
 }
 
 static int wino_in_gn_impl(int tile, int f16, const float *x, const float *gamma, const float *beta,
@@ -509,9 +491,8 @@ int wino_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W,
   const long tiles = (long)(B * (H / 2) * (W / 2)), total = tiles * (C / 4);
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(wino_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
-                     (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
-  return check_launch();
+  return launch(wino_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
+                (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
 }
 
 int wino4_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
@@ -521,9 +502,8 @@ int wino4_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W,
   const long tiles = (long)(B * (H / 4) * (W / 4)), total = tiles * (C / 4);
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(wino4_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                     (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
-  return check_launch();
+  return launch(wino4_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
 }
 
 int wino4_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale, void *stream) {
@@ -533,9 +513,8 @@ int wino4_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W
   const long tiles = (long)(B * (H / 4) * (W / 4)), total = tiles * (C / 4);
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(wino4_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
-                     (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
-  return check_launch();
+  return launch(wino4_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
+                (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
 }
 
 int wino_out_res_nhwc_f32(const float *M, const float *res, const float *bias_or_null, float *y, int64_t *stats_out,
@@ -578,10 +557,9 @@ int attn_split_qkv_f16x3(const float *qkv, void *Q3, void *K3, void *V3, int64_t
   const long total = (long)(B * L * (C / 4));
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(attn_split_qkv_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), qkv,
-                     static_cast<_Float16 *>(Q3), static_cast<_Float16 *>(K3), static_cast<_Float16 *>(V3), (long)L,
-                     (int)(C / 4), sq, sv, total);
-  return check_launch();
+  return launch(attn_split_qkv_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), qkv,
+                static_cast<_Float16 *>(Q3), static_cast<_Float16 *>(K3), static_cast<_Float16 *>(V3), (long)L,
+                (int)(C / 4), sq, sv, total);
 }
 
 int attn_softmax_split_f16x3(const float *S, void *P3, int64_t rows, int64_t L, float factor, void *stream) {
@@ -607,9 +585,8 @@ int attn_softmax_split_f16x3(const float *S, void *P3, int64_t rows, int64_t L, 
 int f16_scales_from_gn_stats(const int64_t *stats, int64_t n_bg, double amp, double u_scale, float *scales_out,
                              void *stream) {
   if (!stats || !scales_out || n_bg < 1 || n_bg > 0x7fffffff || !(amp > 0.0) || !(u_scale > 0.0)) return GQHIP_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(f16_scales_from_stats_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), stats, (int)n_bg,
-                     (float)amp, (float)u_scale, scales_out);
-  return check_launch();
+  return launch(f16_scales_from_stats_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), stats, (int)n_bg,
+                (float)amp, (float)u_scale, scales_out);
 }
 
 int upsample2x_nhwc_f32(const float *x, float *y, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
@@ -619,9 +596,8 @@ int upsample2x_nhwc_f32(const float *x, float *y, int64_t B, int64_t H, int64_t 
   const long total = (long)(B * H * W * (C / 4));
   long blocks = (total + 255) / 256;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(upsample2x_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                     y, (int)H, (int)W, (int)(C / 4), total);
-  return check_launch();
+  return launch(upsample2x_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                y, (int)H, (int)W, (int)(C / 4), total);
 }
 
 int gqhip_checksum_tensors(const void *table_dev, int64_t count, uint64_t *sums_dev, void *stream) {
@@ -630,9 +606,8 @@ int gqhip_checksum_tensors(const void *table_dev, int64_t count, uint64_t *sums_
   if (!table_dev || !sums_dev) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (hipMemsetAsync(sums_dev, 0, sizeof(uint64_t) * count, st) != hipSuccess) return check_launch();
-  hipLaunchKernelGGL(checksum_tensors_kernel, dim3((unsigned)count, kChecksumSlices), dim3(256), 0, st,
-                     static_cast<const ChecksumEntry *>(table_dev), reinterpret_cast<unsigned long long *>(sums_dev));
-  return check_launch();
+  return launch(checksum_tensors_kernel, dim3((unsigned)count, kChecksumSlices), dim3(256), 0, st,
+                static_cast<const ChecksumEntry *>(table_dev), reinterpret_cast<unsigned long long *>(sums_dev));
 }
 
 int64_t gq_mha_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H) {
@@ -646,8 +621,7 @@ int gq_mha_fwd_f32(const float *qkv, float *out, int64_t B, int64_t L, int64_t E
   if (B == 0 || L == 0) return GQHIP_OK;
   if (!qkv || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return GQHIP_ERR_INVALID_ARG;
   const dim3 grid((unsigned)((L + kAttnQRows - 1) / kAttnQRows), (unsigned)(B * H));
-  hipLaunchKernelGGL(mha_fwd_f32_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, (int)L, (int)E, (int)H);
-  return check_launch();
+  return launch(mha_fwd_f32_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, (int)L, (int)E, (int)H);
 }
 
 }  // extern "C"

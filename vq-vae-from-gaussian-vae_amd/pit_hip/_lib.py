@@ -284,21 +284,11 @@ def gq_quantize_z(z, cb, dim: int, layout: str, grouping: int, lv_range=(-30.0, 
     zhat): the first launch also writes ``zhat_noquant = mu + noise * sd`` (gaussian.py:121), returned as a third value."""
     z, cb = _dev(z, torch.float32, "z"), _dev(cb, torch.float32, "codebook")
     n = cb.shape[0]
-    if layout == "bchw":
-        B, c2, L = z.shape[0], z.shape[1], int(z[0, 0].numel())
-    else:
-        B, L, c2 = z.shape
-    c = c2 // 2
-    K = c // dim
-    rows = B * L * K
+    B, L, c, K, rows, shape, idx_shape = _z_geometry(z, dim, layout)
     ws = ws or Workspace()
     dev = z.device
-    if layout == "bchw":
-        idx = torch.empty((B, K) + tuple(z.shape[2:]), dtype=torch.int64, device=dev)
-        zhat = torch.empty((B, c) + tuple(z.shape[2:]), dtype=torch.float32, device=dev)
-    else:
-        idx = torch.empty((B, L, K), dtype=torch.int64, device=dev)
-        zhat = torch.empty((B, L, c), dtype=torch.float32, device=dev)
+    idx = torch.empty(idx_shape, dtype=torch.int64, device=dev)
+    zhat = torch.empty(shape, dtype=torch.float32, device=dev)
     noquant = None
     if noise is not None:
         noise = _dev(noise, torch.float32, "noise")
@@ -332,25 +322,13 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
     fresh 64-byte device buffer: float32 view [0:4] = kl_loss, bits-mean, bits-min, bits-max; float64 view of bytes 32..56 = the
     lambdas after the update."""
     z, cb, noise = _dev(z, torch.float32, "z"), _dev(cb, torch.float32, "codebook"), _dev(noise, torch.float32, "noise")
-    if not (lam_state.is_cuda and lam_state.dtype == torch.float64 and lam_state.numel() == 3 and lam_state.is_contiguous()):
-        raise GqHipError("lam_state must be a contiguous float64 [3] tensor on the HIP device")
+    _lam_ok(lam_state, "lam_state")
     n = cb.shape[0]
-    if layout == "bchw":
-        B, c2, L = z.shape[0], z.shape[1], int(z[0, 0].numel())
-        tail = tuple(z.shape[2:])
-    else:
-        B, L, c2 = z.shape
-    c = c2 // 2
-    K = c // dim
-    rows = B * L * K
+    B, L, c, K, rows, shape, idx_shape = _z_geometry(z, dim, layout)
     ws = ws or Workspace()
     dev = z.device
-    if layout == "bchw":
-        idx = torch.empty((B, K) + tail, dtype=torch.int64, device=dev)
-        zhat = torch.empty((B, c) + tail, dtype=torch.float32, device=dev)
-    else:
-        idx = torch.empty((B, L, K), dtype=torch.int64, device=dev)
-        zhat = torch.empty((B, L, c), dtype=torch.float32, device=dev)
+    idx = torch.empty(idx_shape, dtype=torch.int64, device=dev)
+    zhat = torch.empty(shape, dtype=torch.float32, device=dev)
     if tuple(noise.shape) != tuple(zhat.shape):
         raise GqHipError(f"noise must have the shape of zhat {tuple(zhat.shape)}, got {tuple(noise.shape)}")
     noquant = torch.empty_like(zhat)
@@ -369,18 +347,20 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
     return idx, zhat, (pure if use_ste else zhat), noquant, std, scalars
 
 
-def _z_geometry(z, dim: int, layout: str):
-    """(B, L, c, K, rows, shape of zhat) of an encoder output z holding [mu | logvar] in a module layout (gqhip.h)."""
+def _z_geometry(t, dim: int, layout: str, holds: str = "mu|logvar"):
+    """(B, L, c, K, rows, shape of zhat, shape of the indices) of a tensor in a module layout (gqhip.h) whose channel axis holds
+    [mu | logvar] (an encoder output: 2 c channels), "z" (c channels) or "idx" (the indices themselves: K = c / dim channels)."""
     if layout == "bchw":
-        B, c2, L = z.shape[0], z.shape[1], int(z[0, 0].numel())
-        c = c2 // 2
-        shape = (B, c) + tuple(z.shape[2:])
+        B, ch, L = t.shape[0], t.shape[1], int(t[0, 0].numel())
     else:
-        B, L, c2 = z.shape
-        c = c2 // 2
-        shape = (B, L, c)
+        B, L, ch = t.shape
+    c = {"mu|logvar": ch // 2, "z": ch, "idx": ch * dim}[holds]
     K = c // dim
-    return B, L, c, K, B * L * K, shape
+
+    def shape(channels):
+        return ((B, channels) + tuple(t.shape[2:])) if layout == "bchw" else (B, L, channels)
+
+    return B, L, c, K, B * L * K, shape(c), shape(K)
 
 
 def _lam_ok(t, name: str) -> None:
@@ -395,7 +375,7 @@ def gq_gauss_train(z, dim: int, layout: str, grouping: int, noise, lam_state, lo
     scalars) with ``scalars`` as gq_quantize_z_gauss returns it."""
     z, noise = _dev(z, torch.float32, "z"), _dev(noise, torch.float32, "noise")
     _lam_ok(lam_state, "lam_state")
-    B, L, c, K, rows, shape = _z_geometry(z, dim, layout)
+    B, L, c, K, rows, shape, _ = _z_geometry(z, dim, layout)
     if tuple(noise.shape) != shape:
         raise GqHipError(f"noise must have the shape of zhat {shape}, got {tuple(noise.shape)}")
     dev = z.device
@@ -419,7 +399,7 @@ def gq_gauss_backward(z, dim: int, layout: str, grouping: int, noise, lam_before
     gradient that is not contiguous in the layout of zhat is made so.  ``g_kl``: one float32 on the device."""
     z, noise = _dev(z, torch.float32, "z"), _dev(noise, torch.float32, "noise")
     _lam_ok(lam_before, "lam_before")
-    B, L, c, K, rows, shape = _z_geometry(z, dim, layout)
+    B, L, c, K, rows, shape, _ = _z_geometry(z, dim, layout)
 
     def grad(t, name):
         if t is None:
@@ -452,17 +432,12 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     (idx [B, K, ...] / [B, L, K], z_q in the layout of z, loss float32 [2] = {codebook_loss, mean((e - z)^2)})."""
     z, emb = _dev(z, torch.float32, "z"), _dev(emb, torch.float32, "embedding")
     n = emb.shape[0]
-    if layout == "bchw":
-        B, c, L = z.shape[0], z.shape[1], int(z[0, 0].numel())
-    else:
-        B, L, c = z.shape
+    B, L, c, K, rows, _, idx_shape = _z_geometry(z, dim, layout, holds="z")
     if c % dim or emb.shape[1] != dim:
         raise GqHipError("shape mismatch in vq_quantize_z")
-    K = c // dim
-    rows = B * L * K
     ws = ws or Workspace()
     dev = z.device
-    idx = torch.empty(((B, K) + tuple(z.shape[2:])) if layout == "bchw" else (B, L, K), dtype=torch.int64, device=dev)
+    idx = torch.empty(idx_shape, dtype=torch.int64, device=dev)
     zq = torch.empty_like(z)
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -476,12 +451,8 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
 
 def gq_dequant(idx, cb, dim: int, layout: str, grouping: int):
     idx, cb = _dev(idx, torch.int64, "indices"), _dev(cb, torch.float32, "codebook")
-    if layout == "bchw":
-        B, K, L = idx.shape[0], idx.shape[1], int(idx[0, 0].numel())
-        zhat = torch.empty((B, K * dim) + tuple(idx.shape[2:]), dtype=torch.float32, device=idx.device)
-    else:
-        B, L, K = idx.shape
-        zhat = torch.empty((B, L, K * dim), dtype=torch.float32, device=idx.device)
+    B, L, _, K, _, shape, _ = _z_geometry(idx, dim, layout, holds="idx")
+    zhat = torch.empty(shape, dtype=torch.float32, device=idx.device)
     with torch.cuda.device(idx.device):
         _check(lib().gq_dequant_f32(idx.data_ptr(), cb.data_ptr(), zhat.data_ptr(), B, L, K, dim, cb.shape[0],
                                     GQHIP_LAYOUT[layout], grouping, _stream()), "gq_dequant_f32")
