@@ -24,8 +24,8 @@ struct WinoGemm2Params {
   const _Float16 *Wf;   // [P][cin/16][cout/32][2][64][8]  operand-order (U_h, U_l) of U * u_scale
   float *M;             // [P][tiles][cout]
   long tiles;           // a multiple of 256
-  int cin, cout, nnb;   // nnb = cout / 128
-  long mtiles;          // tiles / 256
+  int cin, cout, nnb;   // nnb = cout / columns of a block (128; 256 for wino_gemm_f16x2_k64_kernel)
+  long mtiles;          // tiles / rows of a block (256; 128 for wino_gemm_f16x2_k64_kernel<1>)
   long ntile_total;     // P * mtiles
   long tiles_per_xcd;   // ceil(ntile_total / 8)
 };
@@ -120,30 +120,50 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_f16x2_kernel(const WinoGemm2
     }
 }
 
-// ---- the same GEMM with 256 x 256 block tiles for the 512-channel levels: 8 waves (2 x 4: wave = 128 rows x 64 columns), ONE
-// block per CU, a stage = 64 k of both planes (64 KiB, 96 MFMAs per wave between barriers), double buffered (2 x 64.25 KiB of
-// LDS).  Against the 256 x 128 form: every row tile is read once per TWO column blocks of a 512-column output instead of
-// once per four, the loads of the next stage have 96 instead of 48 MFMAs per wave to land, half the barriers.
-__global__ __launch_bounds__(512, 1) void wino_gemm_f16x2_w8_kernel(const WinoGemm2Params p) {
+// ---- the same GEMM with 256-column block tiles and 64-k stages for the 512-channel levels, in two tilings of one body:
+//   RW = 2: 256 x 256 block, 8 waves (2 x 4: wave = 128 rows x 64 columns), ONE block per CU, 2 x 64.25 KiB of LDS;
+//   RW = 1: 128 x 256 block, 4 waves side by side along the columns (the same wave, wm = 0), TWO independent blocks per CU,
+//           2 x 32.25 KiB of LDS per block (129 KiB for the pair, under the CU's 160 KiB).
+// A stage = 64 k of both planes (96 MFMAs per wave between barriers), double buffered.  Against the 256 x 128 form: every row
+// tile is read once per 256 columns instead of once per 128, the loads of the next stage have 96 instead of 48 MFMAs per wave
+// to land, half the barriers.  Per output element both tilings (and the 256 x 128 form) accumulate in the same order -- k
+// ascending, h U_h, h U_l, l U_h per k-step -- so M is bit-identical whichever runs (tests/test_gpu_wino_gemm_tilings.py).
+//
+// Why two: all blocks of a launch have the same length and start together, so with one block per CU the chip runs in lockstep
+// rounds and the M store (256 KiB per block, 64 MiB per round in one burst: ~15 us at the 4.2-4.5 TB/s the transforms reach)
+// ADDS to the MFMA phase (49 152 MFMA cycles per 256 x 256 x 512 block: ~29 us at ~1.7 GHz) instead of hiding under it: a
+// round measured ~53 us at Cin = 512 and ~31 us at Cin = 256.  Two half-height blocks per CU drift apart in phase, so one
+// block's store and next prologue can run under the other's MFMAs: the model predicts a gain at Cin = 512 (a round could
+// approach max(MFMA, HBM) ~ 29 us) and none at Cin = 256 (HBM-bound already: 128 MiB per round).  Measured (profiles/r12/
+// gemm_ab.txt, the two alternately in one process): RW = 1 is 4-16 % faster in the median at all six shapes of the step, and
+// the Cin = 256 shapes gain as much as the Cin = 512 ones (4.06 against 3.62 TB/s at 36 x 16 384 x 256 -> 256) -- the
+// one-block form was not at the HBM limit there either, its lockstep rounds alternated between reading and writing.  The
+// dispatch (gqhip_unet.hip:wino_gemm_tiling) therefore takes RW = 1 at every shape; RW = 2 stays selectable (GQHIP_WGEMM=w8)
+// until the A/B has been repeated with long windows.
+template <int RW>
+__global__ __launch_bounds__(256 * RW, 3 - RW) void wino_gemm_f16x2_k64_kernel(const WinoGemm2Params p) {
+  static_assert(RW == 1 || RW == 2, "row waves");
   // eight (k16 chunk, plane) regions, 32 bytes apart modulo 256: the loader's ds_write_b128 of 16 lanes (one row: 16 pieces,
-  // two per region) covers all 64 banks
-  constexpr int kPlane = 256 * 32 + 32, kChunk = 2 * kPlane, kStage = 4 * kChunk;
+  // two per region) covers all 64 banks; the rows of a region stay 32 bytes apart with the halves swapped on odd groups of 8
+  // rows, so the waves' ds_read_b128 (32 rows of one region) is conflict-free as well -- neither depends on the block's height
+  constexpr int kRows = 128 * RW, kPlane = kRows * 32 + 32, kChunk = 2 * kPlane, kStage = 4 * kChunk;
   static_assert(kChunk % 256 == 64 && kPlane % 256 == 32, "region stagger");
+  static_assert((3 - RW) * 2 * kStage <= 160 * 1024, "co-resident blocks must fit the CU's LDS");
   __shared__ __attribute__((aligned(16))) unsigned char sA[2 * kStage];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c = lane & 31, h = lane >> 5, wm = wave >> 2, wn = wave & 3;
+  const int c = lane & 31, h = lane >> 5, wm = RW == 2 ? wave >> 2 : 0, wn = wave & 3;
   const long vb = blockIdx.x, kq = vb >> 3;
   const int nb = (int)(kq % p.nnb);                 // nnb = cout / 256 here
   const long tile = (vb & 7) * p.tiles_per_xcd + kq / p.nnb;
   if (tile >= p.ntile_total) return;
-  const long pos = tile / p.mtiles, m0 = (tile % p.mtiles) * 256;
+  const long pos = tile / p.mtiles, m0 = (tile % p.mtiles) * kRows;   // mtiles = tiles / kRows
   const int cin = p.cin, nst = cin / 64;
   // loader: thread -> 16-byte piece w16 = tid & 15 of a row's stage (plane w16 >> 3, k16 chunk (w16 >> 1) & 3, half w16 & 1),
-  // rows (tid >> 4) + 32 i
+  // rows (tid >> 4) + 16 RW i
   const int w16 = tid & 15, r0 = tid >> 4, pl = w16 >> 3, jc = (w16 >> 1) & 3, jh = w16 & 1;
   const _Float16 *src = p.V2 + ((pos * p.tiles + m0 + r0) * 2L * cin) + pl * cin + 16 * jc + 8 * jh;
   const int loff = jc * kChunk + pl * kPlane + r0 * 32 + 16 * (jh ^ ((r0 >> 3) & 1));
-  const long rstride = 64L * cin;   // 32 rows, halfs
+  const long rstride = 32L * RW * cin;   // 16 RW rows, halfs
   f16x8 st[8];
   auto issue = [&](int stage) {
 #pragma unroll
@@ -151,7 +171,7 @@ __global__ __launch_bounds__(512, 1) void wino_gemm_f16x2_w8_kernel(const WinoGe
   };
   auto commit = [&](int buf) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) *reinterpret_cast<f16x8 *>(sA + buf * kStage + loff + i * 1024) = st[i];
+    for (int i = 0; i < 8; ++i) *reinterpret_cast<f16x8 *>(sA + buf * kStage + loff + i * (512 * RW)) = st[i];
   };
   f32x16 acc[4][2];
 #pragma unroll

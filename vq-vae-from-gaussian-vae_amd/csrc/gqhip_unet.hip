@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "gqhip_internal.h"
 #include "gq_unet_aux.h"
@@ -170,6 +171,22 @@ int wino_in_nhwc_f16x2(const float *x, void *V2, int64_t B, int64_t H, int64_t W
   return wino_in_f16_impl(2, x, V2, B, H, W, C, tile, scale, stream);
 }
 
+// The tiling of wino_gemm_f16x2 (gq_wino_gemm.h).  The 256-column tilings need Cin % 64 == 0 and Cout % 256 == 0; every other
+// shape runs 256 x 128.  Among the two, 128 x 256 (two 4-wave blocks per CU) everywhere: alternating with 256 x 256 (one 8-wave
+// block per CU) in one process on MI355X it was the faster of each adjacent pair of windows at all six shapes of the step, by
+// 4-16 % in the median, at Cin = 256 as much as at Cin = 512 (profiles/r12/gemm_ab.txt -- one session with short windows; its
+// caveats are stated there).
+// GQHIP_WGEMM forces one (A/B, tests): 128 = 256 x 128, w8 = 256 x 256, w4 = 128 x 256; read per call, so one process can
+// compare them.  A forced 256-column tiling still yields to 256 x 128 where the shape does not allow it.
+enum class WinoGemmTiling { k256x128, k256x256, k128x256 };
+static WinoGemmTiling wino_gemm_tiling(int64_t Cin, int64_t Cout) {
+  const char *knob = getenv("GQHIP_WGEMM");
+  if (Cin % 64 != 0 || Cout % 256 != 0 || (knob && !strcmp(knob, "128"))) return WinoGemmTiling::k256x128;
+  if (knob && !strcmp(knob, "w8")) return WinoGemmTiling::k256x256;
+  if (knob && !strcmp(knob, "w4")) return WinoGemmTiling::k128x256;
+  return WinoGemmTiling::k128x256;
+}
+
 int wino_gemm_f16x2(const void *V2, const void *Wf, float *M, int64_t P, int64_t tiles, int64_t Cin, int64_t Cout,
                     void *stream) {
   if (P < 1 || tiles < 0 || tiles > 0x3fffffff || tiles % 256 != 0 || Cin < 32 || Cin % 32 != 0 || Cin > 4096 || Cout < 128 ||
@@ -179,19 +196,19 @@ int wino_gemm_f16x2(const void *V2, const void *Wf, float *M, int64_t P, int64_t
   if (!V2 || !Wf || !M) return GQHIP_ERR_INVALID_ARG;
   WinoGemm2Params wp{};
   wp.V2 = static_cast<const _Float16 *>(V2); wp.Wf = static_cast<const _Float16 *>(Wf); wp.M = M; wp.tiles = tiles;
-  wp.cin = (int)Cin; wp.cout = (int)Cout; wp.nnb = (int)(Cout / 128);
-  wp.mtiles = tiles / 256; wp.ntile_total = P * wp.mtiles; wp.tiles_per_xcd = (wp.ntile_total + 7) / 8;
-  // 256 x 256 tiles (8 waves, one block per CU) where the shape allows: Cin % 64 == 0, Cout % 256 == 0; GQHIP_WGEMM=128 keeps
-  // the 256 x 128 form (A/B)
-  static const int env_w = getenv("GQHIP_WGEMM") ? atoi(getenv("GQHIP_WGEMM")) : 0;
-  const bool wide = Cin % 64 == 0 && Cout % 256 == 0 && env_w != 128;
-  if (wide) wp.nnb = (int)(Cout / 256);
+  wp.cin = (int)Cin; wp.cout = (int)Cout;
+  const WinoGemmTiling tiling = wino_gemm_tiling(Cin, Cout);
+  const long rows = tiling == WinoGemmTiling::k128x256 ? 128 : 256, cols = tiling == WinoGemmTiling::k256x128 ? 128 : 256;
+  wp.nnb = (int)(Cout / cols);
+  wp.mtiles = tiles / rows; wp.ntile_total = P * wp.mtiles; wp.tiles_per_xcd = (wp.ntile_total + 7) / 8;
   const long blocks = 8 * wp.tiles_per_xcd * wp.nnb;
   if (blocks > 0x7fffffffL) return GQHIP_ERR_INVALID_ARG;
-  if (wide)
-    hipLaunchKernelGGL(wino_gemm_f16x2_w8_kernel, dim3((unsigned)blocks), dim3(512), 0, static_cast<hipStream_t>(stream), wp);
-  else
-    hipLaunchKernelGGL(wino_gemm_f16x2_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), wp);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (tiling) {
+    case WinoGemmTiling::k128x256: hipLaunchKernelGGL(wino_gemm_f16x2_k64_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, wp); break;
+    case WinoGemmTiling::k256x256: hipLaunchKernelGGL(wino_gemm_f16x2_k64_kernel<2>, dim3((unsigned)blocks), dim3(512), 0, st, wp); break;
+    case WinoGemmTiling::k256x128: hipLaunchKernelGGL(wino_gemm_f16x2_kernel, dim3((unsigned)blocks), dim3(256), 0, st, wp); break;
+  }
   return check_launch();
 }
 

@@ -825,8 +825,9 @@ def attention_f16x3(qkv, q_bound: float, v_bound: float):
 
 
 def own_gemm_fits(positions: int, tiles: int, cout: int, cin: int = 256) -> bool:
-    """Where wino_gemm_f16x2 replaces the library's K-concatenated GEMM: wherever its grid (256 x 256 tiles at Cout % 256 == 0,
-    else 256 x 128) fills whole rounds of the chip reasonably (36 x 1024 tiles x 512 channels = 288 blocks = 1.125 rounds does
+    """Where wino_gemm_f16x2 replaces the library's K-concatenated GEMM: wherever its grid (128 x 256 tiles, two blocks per CU, at
+    Cout % 256 == 0 and Cin % 64 == 0 -- the same number of rounds as the 256 x 256 tiles, one per CU, counted below -- else
+    256 x 128) fills whole rounds of the chip reasonably (36 x 1024 tiles x 512 channels = 288 blocks = 1.125 rounds does
     not).  Alone the kernel is 1.05-1.21x the library at 256 input channels and at 16 x 4096 tiles, 0.91-0.95x at the two largest
     512-channel shapes (tools/wino_gemm2_bench.py) -- but its [h | l] operand also takes a third off what the input transform
     writes, so the step as a whole is faster with it everywhere (33.9 -> 33.4 ms)."""
