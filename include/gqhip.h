@@ -419,10 +419,30 @@ int conv3x3_gn_f16x3(const float *x, const float *gamma, const float *beta, cons
  * power-of-two scale of x + pre_bias comes from
  * scales_dev = {scale, 1 / (scale * u_scale)} in device memory (f16_scales_from_gn_stats) or, when that is NULL, from the
  * `scale` / `mscale` arguments.  Wf [Cin/16, 1, Cout/32, 2, 64, 8] as for conv3x3_gn_f16x3; y = x W * mscale + bias (+ res);
- * stats_out optional.  HW % 256 == 0, Cin % 32 == 0. */
+ * stats_out optional.  HW % 128 == 0, Cin % 32 == 0.  Blocks are 256 pixels x 128 columns, or 128 x 128 where the 256-pixel
+ * grid would leave the chip under-filled (fewer than two blocks per CU, or a last round less than 85 % full) or HW % 256 != 0;
+ * the result does not depend on the tiling.  GQHIP_CONV1_TILE = 128 | 256 in the environment forces one (read per call; a
+ * forced 256 at HW % 256 != 0 is GQHIP_ERR_INVALID_ARG). */
 int conv1x1_f16x3(const float *x, const float *pre_bias_or_null, const void *Wf, const float *scales_dev_or_null, float scale,
                   float mscale, const float *bias_or_null, const float *res_or_null, float *y, gqhip_gnstat_t *stats_out_or_null, int64_t B, int64_t HW,
                   int64_t Cin, int64_t Cout, int64_t groups_out, void *stream);
+/* conv1x1_f16x3 of GroupNorm(x + pre_bias) (no SiLU: the attention block's norm, reference pit/modules/unet.py:185-190) with
+ * the normalisation applied while x is staged, as conv3x3_gn_f16x3 does: the normalised tensor is never written, and the
+ * result is bit for bit that of gn_silu_f32(apply_silu = 0) followed by conv1x1_f16x3.  stats_in: the statistics of
+ * x + pre_bias (gn_stats_f32 / a producer's stats_out); `scale` >= 1 / max|normalised tensor| as a power of two, host side
+ * only.  Cin <= 512, (Cin / groups_in) % 4 == 0. */
+int conv1x1_gn_f16x3(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
+                     const gqhip_gnstat_t *stats_in, int64_t groups_in, double eps, const void *Wf, float scale, float mscale,
+                     const float *bias_or_null, const float *res_or_null, float *y, gqhip_gnstat_t *stats_out_or_null, int64_t B,
+                     int64_t HW, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream);
+/* The attention block's q | k | v projection C -> 3C (Wf [C/16, 1, 3C/32, 2, 64, 8]) writing the operands of the attention
+ * GEMMs itself: Q3, K3, V3 are byte for byte what attn_split_qkv_f16x3(sq, sv) makes of the projection conv1x1_f16x3 (or,
+ * with gamma / beta / stats_in given, conv1x1_gn_f16x3) would have stored, and that fp32 tensor is never written.
+ * x [B * L, C]; C % 128 == 0 (a block's 128 columns lie inside q, k or v), L % 128 == 0; with GroupNorm C <= 512. */
+int conv1x1_qkv_split_f16x3(const float *x, const float *gamma_or_null, const float *beta_or_null, const float *pre_bias_or_null,
+                            const gqhip_gnstat_t *stats_in_or_null, int64_t groups_in, double eps, const void *Wf, float scale,
+                            float mscale, const float *bias_or_null, void *Q3, void *K3, void *V3, float sq, float sv, int64_t B,
+                            int64_t L, int64_t C, void *stream);
 /* 3x3 convolution with stride 2 over x padded by one zero row / column at the bottom / right -- the reference's Downsample
  * (pit/modules/unet.py:76-97: F.pad(x, (0,1,0,1)) + conv stride 2) -- Cin -> Cout (128, 256 or 512), fp16 x 3 on the four
  * phase images of x (nine k-steps per 16 input channels).  x [B, Hin, Win, Cin] fp32 (not normalised; scale as for

@@ -105,11 +105,12 @@ __device__ __forceinline__ void conv3_tap(const unsigned char *A, int dy, const 
 
 // Epilogue: * mscale + bias (+ residual), store, GroupNorm statistics of the result -- through LDS (gq_epilogue.h): lane l of
 // wave (wm, wn) handles channels wn * 64 + 4 (l & 15) .. + 3 of pixels x0 + (l >> 4) + 4 i (i < 8) of rows y0 + 4 wm + rr, so
-// its values fall into one group (cpg is a multiple of 4) and one StatPartial holds them.  `sA` is free: the main loop ended
+// its values fall into one group (cpg is a multiple of 4) and one StatPartial holds them (RR = 4 rows per wave; 2 in the
+// 128-pixel tiling of the 1x1 kernel: rows y0 + 2 wm + rr).  `sA` is free: the main loop ended
 // with a barrier.  COUT is a template parameter: the stride between a lane's pixels (4 COUT) is then a constant.  The lane
 // index is read afresh (mbcnt) rather than kept from the prologue: no VGPR then lives across the main loop for it.
-template <int COUT>
-__device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3Tile &t, const f32x16 (&acc)[4][2], unsigned char *sA,
+template <int COUT, int RR>
+__device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3Tile &t, const f32x16 (&acc)[RR][2], unsigned char *sA,
                                                int64_t *red, int wave, int wm, int wn) {
   constexpr int cout = COUT;
   const int lane = __lane_id(), tid = wave * 64 + lane;
@@ -120,7 +121,7 @@ __device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3
 #pragma unroll
     for (int e = 0; e < 4; ++e) pb[e] = p.bias[t.nb * 128 + n + e];
   }
-  const long o = ((t.b * p.H + t.y0 + 4 * wm) * p.W + t.x0 + (lane >> 4)) * cout + t.nb * 128 + n;
+  const long o = ((t.b * p.H + t.y0 + RR * wm) * p.W + t.x0 + (lane >> 4)) * cout + t.nb * 128 + n;
   const long slice = (long)p.W * cout;
   StatPartial st;
   if (!p.stats) {
@@ -128,9 +129,33 @@ __device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3
     else epi_store<2, false>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
     return;
   }
-  if (p.res) epi_store<3, true>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
-  else epi_store<2, true>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
-  stat_partial_flush(red + kStatWords * (n / p.cpg), st);
+  if constexpr (RR == 4) {
+    if (p.res) epi_store<3, true>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
+    else epi_store<2, true>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
+    stat_partial_flush(red + kStatWords * (n / p.cpg), st);
+  } else {
+    // RR = 2: a record's addends are the partial sums of ONE lane over four rows (StatPartial: shifted fp64 sums, so they
+    // depend on which values a lane holds and in which order).  Rows 2 wm + rr of this block are rows rr' = 0..3 of one wave of
+    // the 256-pixel tiling, so wave row 1 continues the partial of the same lane of wave row 0 -- through LDS, its stores
+    // after the other's -- and flushes the very addend the 256-pixel tiling flushes: the records do not depend on the tiling.
+    // The price: with statistics the two wave rows of a block store one after the other (wave row 1 waits at the barrier
+    // through wave row 0's residual loads and stores), half the epilogue's parallelism within the block; the other blocks
+    // of the CU fill the gap.  proj_out runs this path: 45 -> 39 us at 16 x 32 x 32 x 512 with it (profiles/r13).
+    __shared__ double part[2 * 64 * 4];
+    double *mine = part + (wn * 64 + lane) * 4;
+    if (wm == 0) {
+      if (p.res) epi_store<3, true>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
+      else epi_store<2, true>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
+      mine[0] = st.v0; mine[1] = st.s; mine[2] = st.ss; mine[3] = (double)st.n;
+    }
+    __syncthreads();
+    if (wm == 1) {
+      st.v0 = mine[0]; st.s = mine[1]; st.ss = mine[2]; st.n = (int)mine[3];
+      if (p.res) epi_store<3, true>(acc, stage, lane, p.y, p.res, o, slice, 4 * cout, p.mscale, pb, st);
+      else epi_store<2, true>(acc, stage, lane, p.y, nullptr, o, slice, 4 * cout, p.mscale, pb, st);
+      stat_partial_flush(red + kStatWords * (n / p.cpg), st);
+    }
+  }
   __syncthreads();
   const int gpb = 128 / p.cpg, groups = cout / p.cpg;    // groups per block, per image
   if (tid < kStatWords * gpb) stat_flush_word(p.stats + kStatWords * (t.b * groups + t.nb * gpb) + tid, red[tid]);
@@ -330,42 +355,91 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
 // one line), double buffered: 2 x 32 KB.  x is NOT normalised here (the shortcut takes the raw residual stream): its
 // scale comes from the host (a bound the caller knows) or from device memory (f16_scales_from_gn_stats: no sync).
 struct Conv1Params {
-  Conv3Params c;           // H = HW / 32, W = 32, tiles_x = 1, tiles_y = HW / 256
+  Conv3Params c;           // H = HW / 32, W = 32, tiles_x = 1, tiles_y = HW / (pixels per tile)
   const float *x;          // [B * HW][cin]
   const float *pre_bias;   // [cin] or null: added to x before the split (a bias still pending on x)
   const float *scales_dev; // {scale, 1 / (scale * u_scale)} or null (then c.mscale and `scale` below)
   float scale;
   int cin;
+  // GN variant: the input is GroupNorm(x + pre_bias), no SiLU (the attention block's norm)
+  const float *gamma, *beta;
+  const int64_t *stats_in;   // [B][cin / cpg_in] statistics records of x + pre_bias (gq_stats.h)
+  int cpg_in;
+  double eps;
+  // SPLIT variant: the 3 C columns are q | k | v and leave as the attention GEMMs' operands (gq_epilogue.h: epi_store_split)
+  _Float16 *Q3, *K3, *V3;    // [B][HW][3C], [B][HW][3C], [B][3 HW][C]
+  float sq, sv;
 };
 
-template <int COUT>
+// Variants (all bit-identical per output element: k ascending, h W_h, h W_l, l W_h per k-step, the epilogue's operations):
+//   RR     rows of 32 pixels per wave: 4 = 256 pixels x 128 columns per block, 2 = 128 pixels x 128 columns (stages of
+//          2 x 16 KB) for grids that leave the chip under-filled with 256-pixel tiles (gqhip_unet.hip: conv1_tile_rows);
+//          two blocks per CU either way.
+//   GN     the input is GroupNorm(x + pre_bias) without SiLU: the folded scale and shift of the image's channels are
+//          computed into LDS by the prologue -- the fp64 expressions of conv3x3_gn_f16x3_kernel and gn_apply_nhwc_kernel --
+//          and gn_act<0> is applied in convert(): the normalised tensor is never written (cin <= 512).
+//   SPLIT  the epilogue writes Q3 / K3 / V3 instead of y (COUT = 0: cout = 3 C at run time, C % 128 == 0, so a block's 128
+//          columns lie wholly inside q, k or v); no residual, no statistics.
+template <int COUT, int RR, int GN, int SPLIT>
 __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params pp) {
   typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  static_assert(RR == 4 || RR == 2, "rows of 32 pixels per wave");
+  static_assert((SPLIT != 0) == (COUT == 0), "the split epilogue takes cout at run time");
   Conv3Params p = pp.c;
-  constexpr int kPlane = 256 * 32, kChunk = 2 * kPlane, kStage = 2 * kChunk;   // bytes
+  constexpr int NI = 2 * RR;                                                      // rows of 32 pixels per block
+  constexpr int kPlane = 32 * NI * 32, kChunk = 2 * kPlane, kStage = 2 * kChunk;   // bytes
+  static_assert(2 * kStage >= 4 * kEpiWaveBytes, "the epilogue stages through sA");
   __shared__ __attribute__((aligned(16))) unsigned char sA[2 * kStage];
   __shared__ int64_t red[kStatWords * 32];   // statistics records of the block's <= 32 groups (gq_stats.h)
+  __shared__ __attribute__((aligned(16))) float sAff[2][GN ? 512 : 4];   // GN: folded scale, shift per input channel
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
   Conv3Tile t;
   if (!conv3_tile(p, t)) return;
+  t.y0 = t.y0 / kC3TH * NI;   // conv3_tile counts rows in tiles of kC3TH = 8
   red[tid] = 0;   // kStatWords * 32 = 256 words
   const float scale = pp.scales_dev ? pp.scales_dev[0] : pp.scale;
   if (pp.scales_dev) p.mscale = pp.scales_dev[1];
   const int cin = pp.cin, nst = cin / 32;
+  if constexpr (GN != 0) {
+    const int groups = cin / pp.cpg_in;
+    const double n = (double)pp.cpg_in * (double)p.H * 32.0;
+    for (int ch = tid; ch < cin; ch += 256) {
+      const int g = ch / pp.cpg_in;
+      double st_s, st_ss;
+      stat_load(pp.stats_in + kStatWords * (t.b * groups + g), st_s, st_ss);
+      const double mean = st_s / n;
+      double var = st_ss / n - mean * mean;
+      var = var > 0.0 ? var : 0.0;
+      const double rstd = 1.0 / sqrt(var + pp.eps);
+      const double pbk = pp.pre_bias ? (double)pp.pre_bias[ch] : 0.0;
+      sAff[0][ch] = (float)(rstd * (double)pp.gamma[ch]);
+      sAff[1][ch] = (float)((double)pp.beta[ch] + (pbk - mean) * rstd * (double)pp.gamma[ch]);
+    }
+  }
   // loader: thread -> channel quad w8 = tid & 7 of the stage's 32 channels, rows (tid >> 3) + 32 i
   const int w8 = tid & 7, r0 = tid >> 3;
   const float *xb = pp.x + ((t.b * p.H + t.y0) * 32L + r0) * cin + 4 * w8;
-  const float *pbp = pp.pre_bias ? pp.pre_bias + 4 * w8 : nullptr;
-  f32x4 pb4 = {0.f, 0.f, 0.f, 0.f};
+  const float *pbp = (GN == 0 && pp.pre_bias) ? pp.pre_bias + 4 * w8 : nullptr;
+  f32x4 pb4 = {0.f, 0.f, 0.f, 0.f}, a4 = pb4, sh4 = pb4;
   const int loff = (w8 >> 2) * kChunk + r0 * 32 + 16 * (((w8 >> 1) & 1) ^ ((r0 >> 3) & 1)) + 8 * (w8 & 1);
-  f32x4 st[8];
+  f32x4 st[NI];
   auto issue = [&](int stage) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) st[i] = *reinterpret_cast<const f32x4 *>(xb + (long)(32 * i) * cin + stage * 32);
+    for (int i = 0; i < NI; ++i) st[i] = *reinterpret_cast<const f32x4 *>(xb + (long)(32 * i) * cin + stage * 32);
+  };
+  auto affine = [&](int stage) {           // the per-channel constants of the stage about to be converted
+    if constexpr (GN != 0) {
+      a4 = *reinterpret_cast<const f32x4 *>(&sAff[0][stage * 32 + 4 * w8]);
+      sh4 = *reinterpret_cast<const f32x4 *>(&sAff[1][stage * 32 + 4 * w8]);
+    } else {
+      if (pbp) pb4 = *reinterpret_cast<const f32x4 *>(pbp + stage * 32);
+    }
   };
   auto convert = [&](int i, int buf) {     // rows r0 + 32 i: (r >> 3) & 1 = (r0 >> 3) & 1
-    const f32x4 v = (st[i] + pb4) * scale;
+    f32x4 v;
+    if constexpr (GN != 0) v = gn_act<0>(st[i], a4, sh4) * scale;
+    else v = (st[i] + pb4) * scale;
     f16x4 hi, lo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -376,9 +450,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
     *reinterpret_cast<f16x4 *>(d) = hi;
     *reinterpret_cast<f16x4 *>(d + kPlane) = lo;
   };
-  f32x16 acc[4][2];
-  GQ_C3_ZERO_ACC(acc);
-  const int aoff = (4 * wm) * 1024 + c * 32 + 16 * (h ^ ((c >> 3) & 1));
+  f32x16 acc[RR][2];
+#pragma unroll
+  for (int rr = 0; rr < RR; ++rr)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[rr][j] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int aoff = (RR * wm) * 1024 + c * 32 + 16 * (h ^ ((c >> 3) & 1));
   const unsigned char *wbase = reinterpret_cast<const unsigned char *>(p.Wf) + (4 * t.nb + 2 * wn) * 128 * 16;
   const int wl = lane * 16;
   const long wstep = (long)p.nnb * (512 * 16);
@@ -390,7 +467,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
   };
   auto kstep = [&](const unsigned char *A, const f16x8 (&bq)[4]) {
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
+    for (int rr = 0; rr < RR; ++rr) {
       const f16x8 ah = *reinterpret_cast<const f16x8 *>(A + aoff + rr * 1024);
       const f16x8 al = *reinterpret_cast<const f16x8 *>(A + aoff + rr * 1024 + kPlane);
 #pragma unroll
@@ -404,9 +481,10 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
   const int nks = 2 * nst;
   load_b(0, b0);
   issue(0);
-  if (pbp) pb4 = *reinterpret_cast<const f32x4 *>(pbp);
+  if constexpr (GN != 0) __syncthreads();   // sAff
+  affine(0);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) convert(i, 0);
+  for (int i = 0; i < NI; ++i) convert(i, 0);
   __syncthreads();
   for (int s = 0; s < nst; ++s) {
     const bool more = s + 1 < nst;
@@ -419,14 +497,34 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
     load_b(2 * s + 2 < nks ? 2 * s + 2 : nks - 1, b0);
     kstep(A + kChunk, b1);
     if (more) {
-      if (pbp) pb4 = *reinterpret_cast<const f32x4 *>(pbp + (s + 1) * 32);
+      affine(s + 1);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) convert(i, nbuf);
+      for (int i = 0; i < NI; ++i) convert(i, nbuf);
     }
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
   }
-  conv3_epilogue<COUT>(p, t, acc, sA, red, wave, wm, wn);
+  if constexpr (SPLIT != 0) {
+    // lane l of wave (wm, wn): channels wn * 64 + 4 (l & 15) .. + 3 of the block's 128, tokens 32 (y0 + RR wm + rr) + (l >> 4) + 4 i
+    const int C = p.cout / 3, col = t.nb * 128, third = col / C;
+    const int n = wn * 64 + 4 * (lane & 15), cc = col - third * C + n;
+    const long L = (long)p.H * 32, tok = (long)(t.y0 + RR * wm) * 32 + (lane >> 4);
+    f32x4 pb = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pb[e] = p.bias[col + n + e];
+    }
+    float *stage = reinterpret_cast<float *>(sA + wave * kEpiWaveBytes);
+    if (third < 2) {        // Q3 / K3 [B][L][3C]: the copies C apart within the token's row
+      _Float16 *dst = third == 0 ? pp.Q3 : pp.K3;
+      epi_store_split(acc, stage, lane, dst, (t.b * L + tok) * 3 * C + cc, 32L * 3 * C, 4L * 3 * C, (long)C, third == 0, p.mscale,
+                      pb, pp.sq);
+    } else {                // V3 [B][3L][C]: the copies L rows apart
+      epi_store_split(acc, stage, lane, pp.V3, (t.b * 3 * L + tok) * C + cc, 32L * C, 4L * C, L * C, false, p.mscale, pb, pp.sv);
+    }
+  } else {
+    conv3_epilogue<COUT>(p, t, acc, sA, red, wave, wm, wn);
+  }
 }
 
 // ---- 3x3 convolution with stride 2 on an input padded by one zero row / column at the bottom / right (Downsample,

@@ -42,18 +42,18 @@ __device__ __forceinline__ void epi_transpose(const f32x16 (&a)[2], float *stage
   for (int i = 0; i < 8; ++i) out[i] = s[64 * i];
 }
 
-// The four slices of a wave to y: row (lane >> 4) + 4 i of slice rr, columns 4 (lane & 15) .. + 3 go to
+// The RR (four; two in the 128-pixel tiling of the 1x1 kernel) slices of a wave to y: row (lane >> 4) + 4 i of slice rr, columns 4 (lane & 15) .. + 3 go to
 // y[o + rr * slice + i * step .. + 3] (element offsets; o holds the lane's first row and its column quad), as
 //   MODE 1: acc * mscale + bias                  (upconv)
 //   MODE 2: acc * mscale + bias + 0              (the direct convolutions without a residual: their "+ 0" kept, it turns -0 into +0)
 //   MODE 3: acc * mscale + bias + res            (the direct convolutions with one, read at the same offsets as y)
 // -- per element the fp32 operations of the accumulator-order epilogues, in their order.  STATS: every stored value is
 // also added to st.
-template <int MODE, bool STATS>
-__device__ __forceinline__ void epi_store(const f32x16 (&acc)[4][2], float *stage, int lane, float *y, const float *res,
+template <int MODE, bool STATS, int RR>
+__device__ __forceinline__ void epi_store(const f32x16 (&acc)[RR][2], float *stage, int lane, float *y, const float *res,
                                           long o, long slice, long step, float mscale, f32x4 bias, StatPartial &st) {
 #pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
+  for (int rr = 0; rr < RR; ++rr) {
     __builtin_amdgcn_sched_barrier(0);   // one slice at a time: hoisting the residual loads of later slices spills
     const long orr = o + rr * slice;
     f32x4 rv[8];
@@ -69,6 +69,44 @@ __device__ __forceinline__ void epi_store(const f32x16 (&acc)[4][2], float *stag
       if (MODE >= 2) w = w + rv[i];
       *reinterpret_cast<f32x4 *>(y + orr + i * step) = w;
       if (STATS) stat_partial_add_vec(st, w);
+    }
+  }
+}
+
+// The slices of a wave of the attention block's q | k | v projection, written as the operands of the two attention GEMMs
+// (what attn_split_qkv_kernel makes of the fp32 projection, which is then never stored): the fp32 value of MODE 2 above,
+// times the power of two `s`, as a two-term fp16 split h + l.  h goes to dst[o ..], the second and third copies one and
+// two `plane` elements further: (h, h, l) for q (`second_h`), (h, l, h) for k and v.  A lane's four values are 8 bytes
+// and the 16 lanes of a row cover one 128-byte run of each copy.  h is the conversion of the fp32 product as it stands
+// (kept opaque: see attn_softmax_split_kernel), so h + l is the split the separate pass computes, bit for bit.
+template <int RR>
+__device__ __forceinline__ void epi_store_split(const f32x16 (&acc)[RR][2], float *stage, int lane, _Float16 *dst, long o,
+                                                long slice, long step, long plane, bool second_h, float mscale,
+                                                f32x4 bias, float s) {
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int rr = 0; rr < RR; ++rr) {
+    __builtin_amdgcn_sched_barrier(0);
+    const long orr = o + rr * slice;
+    f32x4 v[8];
+    epi_transpose(acc[rr], stage, lane, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      f32x4 w = v[i];
+      w = w * mscale + bias;
+      w = w + f32x4{0.f, 0.f, 0.f, 0.f};
+      f16x4 h, l;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float x = w[e] * s;
+        asm volatile("" : "+v"(x));
+        h[e] = (_Float16)x;
+        l[e] = (_Float16)(x - (float)h[e]);
+      }
+      _Float16 *d = dst + orr + i * step;
+      *reinterpret_cast<f16x4 *>(d) = h;
+      *reinterpret_cast<f16x4 *>(d + plane) = second_h ? h : l;
+      *reinterpret_cast<f16x4 *>(d + 2 * plane) = second_h ? l : h;
     }
   }
 }

@@ -347,29 +347,127 @@ extern "C" int gqhip_debug_c3_stamps(unsigned long long *out, int64_t words) {  
 }
 #endif
 
+// ---- the 1x1 convolutions (gq_conv3.h: conv1x1_f16x3_kernel) ----
+// Tiling: 256 pixels x 128 columns per block, two blocks per CU = 2 CUs slots.  Where that grid leaves the chip under-filled --
+// fewer blocks than slots, or a last round less than 85 % full (the attention block at 16 x 32 x 32 pixels: q | k | v 768 blocks =
+// 1.5 rounds of 512 slots, proj_out 256 = half a round) -- the 128-pixel tiling doubles the block count instead (1536 = three
+// full rounds, 512 = one); every output bit and statistics record is the same (tests/test_gpu_attn_fused_proj.py).  HW % 256 != 0
+// can only run with 128-pixel tiles.  GQHIP_CONV1_TILE = 128 | 256 forces one (A/B, tests); read per call, as GQHIP_WGEMM is.
+// A forced 256 at HW % 256 != 0 is an invalid argument.  Returns rows of 32 pixels per wave (4 | 2), 0 = invalid.
+// The rule is a heuristic, not a model of the schedule: it counts two slots per CU although some 128-pixel instantiations
+// (the SPLIT ones, which the attention block launches, and <128, 2, 0, 0>) need few enough registers for three (profiles/r13/
+// resource_usage.txt), and it was reasoned through and measured at the benchmark's batch of 16 only, where every nin_shortcut
+// grid is a multiple of 512 blocks and keeps the 256-pixel tiling; at other batch sizes those calls may take 128-pixel tiles too
+// (same results, speed not measured).
+static int conv1_tile_rows(int64_t B, int64_t HW, int64_t Cout) {
+  const char *knob = getenv("GQHIP_CONV1_TILE");
+  if (knob && !strcmp(knob, "128")) return 2;
+  if (knob && !strcmp(knob, "256")) return HW % 256 == 0 ? 4 : 0;
+  if (HW % 256 != 0) return 2;
+  static thread_local int cus_of[64];   // per device; 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 4;
+  if (cus_of[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) return 4;
+    cus_of[dev] = n;
+  }
+  const int64_t slots = 2 * (int64_t)cus_of[dev], blocks = B * (HW / 256) * (Cout / 128);
+  if (blocks < slots) return 2;
+  const int64_t last = blocks % slots;
+  return (last != 0 && last * 100 < slots * 85) ? 2 : 4;
+}
+
+#define GQ_C1_LAUNCH(RR, GN)                                                                                             \
+  do {                                                                                                                   \
+    if (split) hipLaunchKernelGGL((conv1x1_f16x3_kernel<0, RR, GN, 1>), grid, dim3(256), 0, st, gp);                     \
+    else if (Cout == 128) hipLaunchKernelGGL((conv1x1_f16x3_kernel<128, RR, GN, 0>), grid, dim3(256), 0, st, gp);        \
+    else if (Cout == 256) hipLaunchKernelGGL((conv1x1_f16x3_kernel<256, RR, GN, 0>), grid, dim3(256), 0, st, gp);        \
+    else if (Cout == 512) hipLaunchKernelGGL((conv1x1_f16x3_kernel<512, RR, GN, 0>), grid, dim3(256), 0, st, gp);        \
+    else hipLaunchKernelGGL((conv1x1_f16x3_kernel<1536, RR, GN, 0>), grid, dim3(256), 0, st, gp);                        \
+  } while (0)
+
+// One launch path for the three entry points below.  gp: x, pre_bias, scales, and -- for the GroupNorm variant -- gamma, beta,
+// stats_in, cpg_in, eps, and -- for the split epilogue -- Q3, K3, V3, sq, sv already filled in; gp.c filled here.
+static int conv1_launch(Conv1Params &gp, const void *Wf, float mscale, const float *bias, const float *res, float *y,
+                        int64_t *stats_out, int64_t B, int64_t HW, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
+  const bool split = gp.Q3 != nullptr, gn = gp.gamma != nullptr;
+  const int rows = conv1_tile_rows(B, HW, Cout);
+  if (rows == 0) return GQHIP_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (stats_out && stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess) return check_launch();
+  Conv3Params &cp = gp.c;
+  conv3_fill(cp, Wf, bias, res, y, stats_out, B, HW / 32, 32, Cin, Cout, groups_out, mscale);
+  cp.nch = (int)(Cin / 16);
+  cp.tiles_x = 1; cp.tiles_y = (int)(HW / (64 * rows));
+  cp.ntiles = (long)B * cp.tiles_y;
+  cp.tiles_per_xcd = (cp.ntiles + 7) / 8;
+  gp.cin = (int)Cin;
+  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
+  if (rows == 4) {
+    if (gn) GQ_C1_LAUNCH(4, 1); else GQ_C1_LAUNCH(4, 0);
+  } else {
+    if (gn) GQ_C1_LAUNCH(2, 1); else GQ_C1_LAUNCH(2, 0);
+  }
+#undef GQ_C1_LAUNCH
+  return check_launch();
+}
+
+static bool conv1_shape_ok(int64_t B, int64_t HW, int64_t Cin) {
+  return B >= 0 && HW >= 128 && HW % 128 == 0 && Cin >= 32 && Cin % 32 == 0 && HW <= (1 << 24);
+}
+
+static bool conv1_gn_ok(int64_t Cin, int64_t groups_in) {
+  return Cin <= 512 && groups_in >= 1 && Cin % groups_in == 0 && (Cin / groups_in) % 4 == 0;
+}
+
 int conv1x1_f16x3(const float *x, const float *pre_bias_or_null, const void *Wf, const float *scales_dev_or_null, float scale,
                   float mscale, const float *bias_or_null, const float *res_or_null, float *y, int64_t *stats_out_or_null, int64_t B, int64_t HW,
                   int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
-  if (B < 0 || HW < 256 || HW % 256 != 0 || Cin < 32 || Cin % 32 != 0 || (Cout != 128 && Cout != 256 && Cout != 512 && Cout != 1536) ||
-      HW > (1 << 24) || (!scales_dev_or_null && !(scale > 0.f)))
+  if (!conv1_shape_ok(B, HW, Cin) || (Cout != 128 && Cout != 256 && Cout != 512 && Cout != 1536) ||
+      (!scales_dev_or_null && !(scale > 0.f)))
     return GQHIP_ERR_INVALID_ARG;
   if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
   if (B == 0) return GQHIP_OK;
   if (!x || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out_or_null && stats_zero(stats_out_or_null, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess)
-    return check_launch();
   Conv1Params gp{};
-  Conv3Params &cp = gp.c;
-  conv3_fill(cp, Wf, bias_or_null, res_or_null, y, stats_out_or_null, B, HW / 32, 32, Cin, Cout, groups_out, mscale);
-  cp.nch = (int)(Cin / 16);
-  gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scales_dev = scales_dev_or_null; gp.scale = scale; gp.cin = (int)Cin;
-  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
-  if (Cout == 128) hipLaunchKernelGGL(conv1x1_f16x3_kernel<128>, grid, dim3(256), 0, st, gp);
-  else if (Cout == 256) hipLaunchKernelGGL(conv1x1_f16x3_kernel<256>, grid, dim3(256), 0, st, gp);
-  else if (Cout == 512) hipLaunchKernelGGL(conv1x1_f16x3_kernel<512>, grid, dim3(256), 0, st, gp);
-  else hipLaunchKernelGGL(conv1x1_f16x3_kernel<1536>, grid, dim3(256), 0, st, gp);
-  return check_launch();
+  gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scales_dev = scales_dev_or_null; gp.scale = scale;
+  return conv1_launch(gp, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B, HW, Cin, Cout, groups_out, stream);
+}
+
+int conv1x1_gn_f16x3(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
+                     const int64_t *stats_in, int64_t groups_in, double eps, const void *Wf, float scale, float mscale,
+                     const float *bias_or_null, const float *res_or_null, float *y, int64_t *stats_out_or_null, int64_t B,
+                     int64_t HW, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
+  if (!conv1_shape_ok(B, HW, Cin) || !conv1_gn_ok(Cin, groups_in) || (Cout != 128 && Cout != 256 && Cout != 512 && Cout != 1536) ||
+      !(scale > 0.f))
+    return GQHIP_ERR_INVALID_ARG;
+  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0) return GQHIP_OK;
+  if (!x || !gamma || !beta || !stats_in || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
+  Conv1Params gp{};
+  gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scale = scale;
+  gp.gamma = gamma; gp.beta = beta; gp.stats_in = stats_in; gp.cpg_in = (int)(Cin / groups_in); gp.eps = eps;
+  return conv1_launch(gp, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B, HW, Cin, Cout, groups_out, stream);
+}
+
+int conv1x1_qkv_split_f16x3(const float *x, const float *gamma_or_null, const float *beta_or_null, const float *pre_bias_or_null,
+                            const int64_t *stats_in_or_null, int64_t groups_in, double eps, const void *Wf, float scale,
+                            float mscale, const float *bias_or_null, void *Q3, void *K3, void *V3, float sq, float sv, int64_t B,
+                            int64_t L, int64_t C, void *stream) {
+  if (!conv1_shape_ok(B, L, C) || C % 128 != 0 || !(scale > 0.f) || !(sq > 0.f) || !(sv > 0.f))
+    return GQHIP_ERR_INVALID_ARG;
+  if (gamma_or_null && !conv1_gn_ok(C, groups_in)) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0) return GQHIP_OK;
+  if (!x || !Wf || !Q3 || !K3 || !V3 || (gamma_or_null && (!beta_or_null || !stats_in_or_null))) return GQHIP_ERR_INVALID_ARG;
+  Conv1Params gp{};
+  gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scale = scale;
+  if (gamma_or_null) {
+    gp.gamma = gamma_or_null; gp.beta = beta_or_null; gp.stats_in = stats_in_or_null; gp.cpg_in = (int)(C / groups_in); gp.eps = eps;
+  }
+  gp.Q3 = static_cast<_Float16 *>(Q3); gp.K3 = static_cast<_Float16 *>(K3); gp.V3 = static_cast<_Float16 *>(V3);
+  gp.sq = sq; gp.sv = sv;
+  return conv1_launch(gp, Wf, mscale, bias_or_null, nullptr, nullptr, nullptr, B, L, C, 3 * C, 1, stream);
 }
 
 int conv3x3s2_f16x3(const float *x, const void *Wf, const float *scales_dev_or_null, float scale, float mscale,

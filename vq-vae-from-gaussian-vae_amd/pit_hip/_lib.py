@@ -90,6 +90,10 @@ _SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
     "conv1x1_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                       _vp]),
+    "conv1x1_gn_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp,
+                                         _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
+    "conv1x1_qkv_split_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, ctypes.c_float, ctypes.c_float,
+                                                _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _i64, _vp]),
     "conv3x3s2_f16x3": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                         _i64, _vp]),
     "conv3x3_gn_small_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _i64, _i64,
@@ -794,6 +798,37 @@ def bmm_out_dtype_ok(device) -> bool:
 ATTN_L_OK = (64, 256, 1024, 2304, 4096)   # token counts attn_softmax_split_f16x3 is instantiated for
 
 
+def attention_scales(q_bound: float, v_bound: float):
+    """(sq, sv): the powers of two that bring q, k (|.| <= q_bound) and v (<= v_bound) inside fp16's range for attention_f16x3."""
+    pow2 = lambda bound: min(2.0 ** math.floor(math.log2(32768.0 / max(float(bound), 1e-30))), 2.0 ** 14)
+    # q k^T sums C products of scaled operands in fp32: keep sq^2 C q_bound^2 well inside fp32 (it always is: <= 2^30 C)
+    return pow2(q_bound), pow2(v_bound)
+
+
+def attention_operands(B: int, Ltok: int, C: int, device):
+    """Uninitialised (Q3 [B, L, 3C], K3 [B, L, 3C], V3 [B, 3L, C]) fp16: the operands of attention_f16x3's two GEMMs."""
+    return (torch.empty((B, Ltok, 3 * C), dtype=torch.float16, device=device),
+            torch.empty((B, Ltok, 3 * C), dtype=torch.float16, device=device),
+            torch.empty((B, 3 * Ltok, C), dtype=torch.float16, device=device))
+
+
+def attention_from_operands(Q3, K3, V3, sq: float, sv: float):
+    """attention_f16x3 from ready operands (attn_split_qkv_f16x3's, or those the q | k | v projection wrote itself:
+    qkv_split_direct).  Returns (O_raw [B, L, C] fp32, post_scale)."""
+    B, Ltok, C3 = Q3.shape
+    C = C3 // 3
+    if Ltok not in ATTN_L_OK:
+        raise GqHipError("attention_f16x3: token count %d not in %s" % (Ltok, ATTN_L_OK))
+    L_ = lib()
+    with torch.cuda.device(Q3.device):
+        S = torch.bmm(Q3, K3.transpose(1, 2), out_dtype=torch.float32)
+        P3 = torch.empty((B, Ltok, 3 * Ltok), dtype=torch.float16, device=Q3.device)
+        _check(L_.attn_softmax_split_f16x3(S.data_ptr(), P3.data_ptr(), B * Ltok, Ltok, float(C) ** -0.5 / (sq * sq), _stream()),
+               "attn_softmax_split_f16x3")
+        O = torch.bmm(P3, V3, out_dtype=torch.float32)
+    return O, 1.0 / (16384.0 * sv)
+
+
 def attention_f16x3(qkv, q_bound: float, v_bound: float):
     """softmax(q k^T C^-1/2) v for the fused projection qkv [B, L, 3C] fp32 (dense), single head: two library fp16 GEMMs with
     fp32 accumulation over K axes of two-term fp16 splits (gqhip.h:attn_split_qkv_f16x3) -- fp32-grade results at several
@@ -806,22 +841,12 @@ def attention_f16x3(qkv, q_bound: float, v_bound: float):
     C = C3 // 3
     if Ltok not in ATTN_L_OK:
         raise GqHipError("attention_f16x3: token count %d not in %s" % (Ltok, ATTN_L_OK))
-    pow2 = lambda bound: min(2.0 ** math.floor(math.log2(32768.0 / max(float(bound), 1e-30))), 2.0 ** 14)
-    # q k^T sums C products of scaled operands in fp32: keep sq^2 C q_bound^2 well inside fp32 (it always is: <= 2^30 C)
-    sq, sv = pow2(q_bound), pow2(v_bound)
-    L_ = lib()
+    sq, sv = attention_scales(q_bound, v_bound)
     with torch.cuda.device(qkv.device):
-        Q3 = torch.empty((B, Ltok, C3), dtype=torch.float16, device=qkv.device)
-        K3 = torch.empty((B, Ltok, C3), dtype=torch.float16, device=qkv.device)
-        V3 = torch.empty((B, 3 * Ltok, C), dtype=torch.float16, device=qkv.device)
-        _check(L_.attn_split_qkv_f16x3(qkv.data_ptr(), Q3.data_ptr(), K3.data_ptr(), V3.data_ptr(), B, Ltok, C, sq, sv,
-                                       _stream()), "attn_split_qkv_f16x3")
-        S = torch.bmm(Q3, K3.transpose(1, 2), out_dtype=torch.float32)
-        P3 = torch.empty((B, Ltok, 3 * Ltok), dtype=torch.float16, device=qkv.device)
-        _check(L_.attn_softmax_split_f16x3(S.data_ptr(), P3.data_ptr(), B * Ltok, Ltok, float(C) ** -0.5 / (sq * sq), _stream()),
-               "attn_softmax_split_f16x3")
-        O = torch.bmm(P3, V3, out_dtype=torch.float32)
-    return O, 1.0 / (16384.0 * sv)
+        Q3, K3, V3 = attention_operands(B, Ltok, C, qkv.device)
+        _check(lib().attn_split_qkv_f16x3(qkv.data_ptr(), Q3.data_ptr(), K3.data_ptr(), V3.data_ptr(), B, Ltok, C, sq, sv,
+                                          _stream()), "attn_split_qkv_f16x3")
+    return attention_from_operands(Q3, K3, V3, sq, sv)
 
 
 def own_gemm_fits(positions: int, tiles: int, cout: int, cin: int = 256) -> bool:
@@ -850,8 +875,8 @@ def conv3_weights_f16(weight):
     """Operand-order fp16 x 3 weights of a [Cout, Cin, 3, 3] kernel for conv3x3_direct: (Wf [Cin/16, 9, Cout/32, 2, 64, 8]
     fp16, u_scale) -- see gqhip.h:conv3x3_gn_f16x3."""
     cout, cin, kk = weight.shape[0], weight.shape[1], weight.shape[2]
-    if cout not in ((128, 256, 512, 1536) if kk == 1 else (128, 256)) or cin % 16 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)):
-        raise GqHipError("conv3_weights_f16 needs a [128 | 256, Cin % 16 == 0, 3, 3] or [128 | 256 | 512 | 1536, Cin % 16 == 0, 1, 1] kernel")
+    if (cout % 128 if kk == 1 else cout not in (128, 256)) or cin % 16 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)):
+        raise GqHipError("conv3_weights_f16 needs a [128 | 256, Cin % 16 == 0, 3, 3] or [Cout % 128 == 0, Cin % 16 == 0, 1, 1] kernel")
     w = weight.detach().float()
     amax = float(w.abs().max())
     u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
@@ -893,35 +918,75 @@ def conv3x3_direct(x, wf, u_scale: float, x_bound: float, gn, residual=None, bia
     return (y, ostats) if stats_groups else y
 
 
-def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats_groups: int = 0, pre_bias=None,
-                   post_scale: float = 1.0):
-    """1x1 convolution Cin -> Cout (128 | 256) of a channels_last fp32 HIP tensor as an fp16 x 3 GEMM over its pixels with the
-    split of x inside the kernel (gqhip.h:conv1x1_f16x3).  ``wf, u_scale`` from conv3_weights_f16 of the [Cout, Cin, 1, 1]
-    kernel; ``pre_bias``: per-channel bias still pending on x (added before the split); ``scale``: a float bound >=
-    max|x + pre_bias|, or the device float[2] of f16_scales(statistics of x + pre_bias, 1.0, u_scale)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 32 or (x.shape[2] * x.shape[3]) % 256:
-        raise GqHipError("conv1x1_direct needs a dense channels_last fp32 HIP tensor, C % 32 == 0, H * W % 256 == 0")
-    B, C, H, W = x.shape
-    cout = wf.shape[2] * 32
-    if wf.shape[0] * 16 != C or wf.shape[1] != 1:
-        raise GqHipError("conv1x1_direct: weights do not match (need conv3_weights_f16 of a [Cout, %d, 1, 1] kernel)" % C)
-    if residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != (B, cout, H, W)):
-        raise GqHipError("conv1x1_direct: residual must be channels_last [B, Cout, H, W]")
+def _conv1_args(x, wf, scale, gn, post_scale: float, what: str, pre_bias=None):
+    """Shared checks of the 1x1 routes; returns (device scales pointer or None, v_scale)."""
+    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 32 or (x.shape[2] * x.shape[3]) % 128:
+        raise GqHipError(what + " needs a dense channels_last fp32 HIP tensor, C % 32 == 0, H * W % 128 == 0")
+    if wf.shape[0] * 16 != x.shape[1] or wf.shape[1] != 1:
+        raise GqHipError(what + ": weights do not match (need conv3_weights_f16 of a [Cout, %d, 1, 1] kernel)" % x.shape[1])
+    if gn is not None and pre_bias is not None and pre_bias is not gn[6]:
+        raise GqHipError(what + ": with gn the pending bias is gn[6] (the one its statistics include); pre_bias differs from it")
+    if gn is not None and (torch.is_tensor(scale) or gn[4] or x.shape[1] > 512 or (x.shape[1] // gn[2]) % 4):
+        raise GqHipError(what + ": the GroupNorm variant needs a host-side bound, no SiLU, C <= 512 and 4 | channels per group")
     if torch.is_tensor(scale):
         if post_scale != 1.0:
-            raise GqHipError("conv1x1_direct: post_scale needs a host-side scale bound")
-        sdev, v_scale, mscale = scale.data_ptr(), 0.0, 0.0
-    else:
-        v_scale = min(2.0 ** math.floor(math.log2(32768.0 / max(float(scale), 1e-30))), 2.0 ** 14)
-        # post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)
-        sdev, mscale = None, float(post_scale) / (v_scale * u_scale)
+            raise GqHipError(what + ": post_scale needs a host-side scale bound")
+        return scale.data_ptr(), 0.0
+    return None, min(2.0 ** math.floor(math.log2(32768.0 / max(float(scale), 1e-30))), 2.0 ** 14)
+
+
+def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats_groups: int = 0, pre_bias=None,
+                   post_scale: float = 1.0, gn=None):
+    """1x1 convolution Cin -> Cout (128 | 256 | 512 | 1536) of a channels_last fp32 HIP tensor as an fp16 x 3 GEMM over its pixels
+    with the split of x inside the kernel (gqhip.h:conv1x1_f16x3).  ``wf, u_scale`` from conv3_weights_f16 of the [Cout, Cin, 1, 1]
+    kernel; ``pre_bias``: per-channel bias still pending on x (added before the split); ``scale``: a float bound >=
+    max|x + pre_bias|, or the device float[2] of f16_scales(statistics of x + pre_bias, 1.0, u_scale).
+    ``gn`` = (gamma, beta, groups, eps, False, statistics of x + pre_bias, pre_bias) as for conv3x3_direct: the convolution's
+    input is GroupNorm(x + pre_bias), normalised while it is staged (gqhip.h:conv1x1_gn_f16x3); ``scale`` then bounds the
+    normalised tensor."""
+    sdev, v_scale = _conv1_args(x, wf, scale, gn, post_scale, "conv1x1_direct", pre_bias)
+    B, C, H, W = x.shape
+    cout = wf.shape[2] * 32
+    if residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != (B, cout, H, W)):
+        raise GqHipError("conv1x1_direct: residual must be channels_last [B, Cout, H, W]")
+    # post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)
+    mscale = 0.0 if sdev is not None else float(post_scale) / (v_scale * u_scale)
     with torch.cuda.device(x.device):
         y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         ostats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device) if stats_groups else None
-        _check(lib().conv1x1_f16x3(x.data_ptr(), _ptr(pre_bias), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias), _ptr(residual),
-                                   y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1), _stream()),
-               "conv1x1_f16x3")
+        if gn is not None:
+            gamma, beta, groups, eps, _, stats, gn_pb = gn
+            _check(lib().conv1x1_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(gn_pb), stats.data_ptr(), groups,
+                                          float(eps), wf.data_ptr(), float(v_scale), float(mscale), _ptr(bias), _ptr(residual),
+                                          y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1), _stream()),
+                   "conv1x1_gn_f16x3")
+        else:
+            _check(lib().conv1x1_f16x3(x.data_ptr(), _ptr(pre_bias), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias),
+                                       _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1),
+                                       _stream()), "conv1x1_f16x3")
     return (y, ostats) if stats_groups else y
+
+
+def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, bias=None, pre_bias=None, gn=None, out=None):
+    """The attention block's q | k | v projection C -> 3C of conv1x1_direct (same arguments) whose epilogue writes the operands
+    of attention_from_operands itself (gqhip.h:conv1x1_qkv_split_f16x3): (Q3, K3, V3), byte for byte those
+    attn_split_qkv_f16x3(sq, sv) makes of the fp32 projection, which is never stored.  C % 128 == 0.  ``out``: the three
+    operand tensors to fill (attention_operands' shapes, dense fp16) instead of fresh ones."""
+    _, v_scale = _conv1_args(x, wf, float(scale), gn, 1.0, "qkv_split_direct", pre_bias)
+    B, C, H, W = x.shape
+    if wf.shape[2] * 32 != 3 * C or C % 128:
+        raise GqHipError("qkv_split_direct: needs the [3C, C, 1, 1] projection, C % 128 == 0")
+    gamma, beta, groups, eps, _, stats, gn_pb = gn if gn is not None else (None, None, 1, 0.0, False, None, pre_bias)
+    with torch.cuda.device(x.device):
+        Q3, K3, V3 = attention_operands(B, H * W, C, x.device) if out is None else out
+        for t, shape in zip((Q3, K3, V3), ((B, H * W, 3 * C), (B, H * W, 3 * C), (B, 3 * H * W, C))):
+            if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape and t.is_contiguous()):
+                raise GqHipError("qkv_split_direct: out must be dense fp16 [B, L, 3C], [B, L, 3C], [B, 3L, C]")
+        _check(lib().conv1x1_qkv_split_f16x3(x.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(gn_pb), _ptr(stats), groups, float(eps),
+                                             wf.data_ptr(), float(v_scale), 1.0 / (v_scale * u_scale), _ptr(bias), Q3.data_ptr(),
+                                             K3.data_ptr(), V3.data_ptr(), float(sq), float(sv), B, H * W, C, _stream()),
+               "conv1x1_qkv_split_f16x3")
+    return Q3, K3, V3
 
 
 def conv3s2_weights_f16(weight):

@@ -549,6 +549,7 @@ STATS_ARENA = True       # the statistics records of a forward from one arena ze
 CONV_IN_SMALL = True     # the encoder's conv_in (3 -> 128) on libgqhip's fixed-order fp32 kernel (+ bias + statistics), not MIOpen
 GN_GROUPS = 32     # unet.py:54-57: every Normalize is GroupNorm(32, C, eps=1e-6)
 DEFER_BIAS = True
+ATTN_FUSED_PROJ = True   # attention: GroupNorm inside the q | k | v projection's staging, the GEMM operands written by its epilogue
 ATTN_F16X3 = True   # both attention GEMMs as fp16 x 3 library GEMMs (split of q, k, v and softmax + split in libgqhip kernels)
 ATTN_MATH = "auto"  # explicit matmul/softmax/matmul instead of the fused SDPA kernel: "auto" = on HIP devices
 
@@ -668,6 +669,16 @@ class AttnBlock(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape
+        fused = self._fused_proj_attention(x) if ATTN_FUSED_PROJ else None
+        if fused is not None:
+            a, a_scale = fused[0].reshape(b, h, w, c).permute(0, 3, 1, 2), fused[1]
+        else:
+            a, a_scale = self._attention(x)
+        return self._proj_out(x, a, a_scale)
+
+    def _attention(self, x: torch.Tensor):
+        """(attention output [b, c, h, w], power of two still pending on it) of norm -> q, k, v -> softmax(q k^T) v."""
+        b, c, h, w = x.shape
         a_scale = 1.0      # power of two still pending on the attention output (fp16 x 3 route)
         y = _norm_act(self.norm, x, act=False)
         # [b, c, h, w] -> [b, 1, hw, c]
@@ -677,7 +688,7 @@ class AttnBlock(nn.Module):
                 # q, k, v = three 1x1 convolutions of the same tensor = ONE GEMM [b*hw, c] x [c, 3c] with the biases in
                 # its epilogue (instead of 3 MIOpen launches + 3 bias-add passes); the thirds are strided views
                 wqkv, bqkv = self._qkv_weights()
-                if DIRECT_CONV_1X1 and c == 512 and (h * w) % 256 == 0:
+                if self._own_qkv_ok(y):
                     # ... as libgqhip's fp16 x 3 GEMM over the pixels (the fp32 library GEMM runs at ~130 TFLOP/s)
                     from .. import _lib
 
@@ -691,10 +702,10 @@ class AttnBlock(nn.Module):
             else:
                 qkv = None
                 q, k, v = (f(y).permute(0, 2, 3, 1).reshape(b, 1, h * w, c) for f in (self.q, self.k, self.v))
-            if ATTN_F16X3 and qkv is not None and qkv.is_contiguous() and c % 4 == 0 and _f16_gemm_ok(qkv):
+            if qkv is not None and qkv.is_contiguous():
                 from .. import _lib
 
-                if (h * w) in _lib.ATTN_L_OK:
+                if self._f16x3_attention_ok(y):
                     # both attention GEMMs as fp16 GEMMs over K axes of two-term fp16 splits (fp32 accumulation): the fp32
                     # GEMMs are a split-bf16 emulation at ~120 TFLOP/s; operand scales from rigorous bounds (GroupNorm bound x
                     # weight row sums), the softmax writes the split operand of the second GEMM directly
@@ -707,6 +718,11 @@ class AttnBlock(nn.Module):
             q, k, v = (f(y).reshape(b, 1, c, h * w).transpose(2, 3).contiguous() for f in (self.q, self.k, self.v))
             a = _sdpa(q, k, v)
             a = a.transpose(2, 3).reshape(b, c, h, w)
+        return a, a_scale
+
+    def _proj_out(self, x: torch.Tensor, a: torch.Tensor, a_scale: float) -> torch.Tensor:
+        """x + proj_out(a * a_scale)."""
+        c = x.shape[1]
         if (_pointwise_ok(self.proj_out, a) and FUSED_ADD_STATS and x.is_contiguous(memory_format=torch.channels_last)
                 and not x.is_contiguous() and self.proj_out.bias is not None):
             # proj_out + bias + residual add + the next GroupNorm's statistics in one fp16 x 3 GEMM over the pixels.  Scale:
@@ -724,6 +740,46 @@ class AttnBlock(nn.Module):
             a = a * a_scale
         p, pb = _conv(self.proj_out, a)
         return _add(x, p, pb)
+
+    @staticmethod
+    def _own_qkv_ok(y: torch.Tensor) -> bool:
+        """The q | k | v projection of y (the normalised tensor, or x where the GroupNorm runs inside the projection: same shape,
+        layout and dtype) as ONE libgqhip fp16 x 3 GEMM over the pixels.  c = 512: the plain kernel's 3c = 1536 columns."""
+        return (FUSED_QKV and DIRECT_CONV_1X1 and y.is_cuda and y.dtype == torch.float32 and not torch.is_grad_enabled()
+                and y.shape[1] == 512 and (y.shape[2] * y.shape[3]) % 256 == 0
+                and y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous())
+
+    @staticmethod
+    def _f16x3_attention_ok(y: torch.Tensor) -> bool:
+        """Both attention GEMMs as fp16 x 3 library GEMMs (_lib.attention_f16x3 / attention_from_operands)."""
+        from .. import _lib
+
+        return ATTN_F16X3 and y.shape[1] % 4 == 0 and _f16_gemm_ok(y) and (y.shape[2] * y.shape[3]) in _lib.ATTN_L_OK
+
+    def _fused_proj_attention(self, x: torch.Tensor):
+        """The fp16 x 3 attention route below with its two reformatting passes folded into the q | k | v projection
+        (gq_conv3.h: conv1x1_f16x3_kernel, GN + SPLIT): the GroupNorm is applied while x is staged -- the normalised tensor is
+        never written -- and the epilogue stores the operands of the two attention GEMMs, so neither the fp32 q | k | v nor
+        attn_split_qkv's pass over it exists.  Bit for bit the unfused route's result.  Returns (O_raw, scale) or None where
+        that route's own conditions (_own_qkv_ok, _f16x3_attention_ok: shared with _attention, so the two cannot drift apart) or
+        the variant's (a GroupNorm the NHWC kernels take) do not hold.  c = 512 like the route it replaces: at other widths the
+        unfused projection is a library GEMM and "bit for bit" would have nothing to hold against."""
+        b, c, h, w = x.shape
+        if not (self._own_qkv_ok(x) and self._f16x3_attention_ok(x) and _use_fused(x, self.norm)):
+            return None
+        from .. import _lib
+
+        if not _lib.gn_nhwc_ok(c, self.norm.num_groups):
+            return None
+        wqkv, bqkv = self._qkv_weights()
+        qkv_wf, qkv_us = _cached(self, "qkv_wf", _wkey(self.q.weight, self.k.weight, self.v.weight),
+                                 lambda: _lib.conv3_weights_f16(wqkv.t().reshape(3 * c, c, 1, 1)))
+        yb = _gn_act_bound(self.norm, x)
+        sq, sv = _lib.attention_scales(self._qk_bound(yb), self._v_bound(yb))
+        gn = (self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps, False,
+              _stats_of(x, None, self.norm.num_groups), None)
+        q3, k3, v3 = _lib.qkv_split_direct(x, qkv_wf, qkv_us, yb, sq, sv, bias=bqkv, gn=gn)
+        return _lib.attention_from_operands(q3, k3, v3, sq, sv)
 
     def _qk_bound(self, y_bound: float) -> float:
         """max(|q|, |k|) for |y| <= y_bound: q = W_q y + b_q, k = W_k y + b_k."""
