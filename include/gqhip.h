@@ -573,6 +573,24 @@ int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *i
  * Asynchronous on `stream`, no allocation: graph-capturable. */
 int64_t gq_mha_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H);
 int gq_mha_fwd_f32(const float *qkv, float *out, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace, void *stream);
+/* The same forward for training: it also stores lse [B, H, L] fp32 (4-byte aligned), per (batch, head, query row) the
+ * log-sum-exp of the row's scores in the kernel's own units, lse2 = log2 sum_j exp2(s_ij log2(e)) with s = q k^T / sqrt(d)
+ * (lse2 ln 2 is the natural log-sum-exp of s).  `out` is that of gq_mha_fwd_f32 bit for bit. */
+int gq_mha_fwd_lse_f32(const float *qkv, float *out, float *lse, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace,
+                       void *stream);
+/* Fused attention backward (csrc/gq_attn_bwd.h): from qkv, the forward's out and lse, and dout [B, L, E] (the gradient of out)
+ * to dqkv [B, L, 3E], the gradient of qkv in qkv's layout (dq | dk | dv column blocks: what F.linear's backward takes as is).
+ * P = exp2(s2 - lse2) is recomputed and divided by its own row sum (which takes out the rounding of lse2), dV = P^T dout,
+ * dP = dout V^T, delta_i = sum_j P_ij dP_ij (in exact arithmetic sum_d dout_id out_id; taken from the kernels' own P and dP so that
+ * dP - delta cancels on a peaked softmax as an explicit softmax backward does -- `out` is checked like the other tensors and not
+ * read), dS = P o (dP - delta), dQ = dS K / sqrt(d), dK = dS^T Q / sqrt(d).  Same limits and checks as the forward: qkv, out, dout,
+ * dqkv 16-byte aligned, lse and workspace 4-byte aligned, all non-NULL unless B == 0 or L == 0 (GQHIP_OK, nothing launched).
+ * Every element of dqkv is written.  Exact fp32 products on the fp32 matrix cores, fixed-order fp32 sums, no atomics:
+ * bit-reproducible.  workspace: gq_mha_bwd_workspace_bytes(B, L, E, H) bytes (two row sums: 2 B H L floats, rounded up), contents
+ * irrelevant.  Two kernels on `stream`, asynchronous, no allocation: graph-capturable. */
+int64_t gq_mha_bwd_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H);
+int gq_mha_bwd_f32(const float *qkv, const float *out, const float *lse, const float *dout, float *dqkv, int64_t B, int64_t L,
+                   int64_t E, int64_t H, void *workspace, void *stream);
 
 /* ---- profiling recorder ------------------------------------------------------
  * When enabled, every launch of the MFMA filter kernel is bracketed with

@@ -67,9 +67,12 @@ __device__ __forceinline__ void attn_store_tile(const AttnTileRegs &r, float *sK
   }
 }
 
-// grid = (ceil(L / 128), B * H), block = 256
-__global__ __launch_bounds__(256, 2) void mha_fwd_f32_kernel(const float *__restrict__ qkv, float *__restrict__ out, int L,
-                                                              int E, int H) {
+// grid = (ceil(L / 128), B * H), block = 256.  kLse: also store lse[B][H][L] = m + log2(l), the log-sum-exp of the row's scores in
+// the kernel's own units (scores times log2(e) / sqrt(d)) -- what the backward (gq_attn_bwd.h) recomputes P from.  One more store;
+// the arithmetic and `out` are those of the `false` instantiation bit for bit.
+template <bool kLse>
+__global__ __launch_bounds__(256, 2) void mha_fwd_f32_kernel(const float *__restrict__ qkv, float *__restrict__ out,
+                                                              float *__restrict__ lse, int L, int E, int H) {
   __shared__ __attribute__((aligned(16))) float sK[2][kAttnKT * kAttnKS];
   __shared__ __attribute__((aligned(16))) float sV[2][kAttnD * kAttnVS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, r = lane & 31;
@@ -171,6 +174,7 @@ __global__ __launch_bounds__(256, 2) void mha_fwd_f32_kernel(const float *__rest
 
   if (qrow >= L) return;
   const float ll = l + __shfl_xor(l, 32);
+  if (kLse && hi == 0) lse[(long)bh * L + qrow] = m + log2f(ll);
   // lane holds dims attn_crow(i, hi) (+ 32): runs of four consecutive dims -> float4 stores
   float *op = out + ((long)b * L + qrow) * E + (long)h * kAttnD;
 #pragma unroll

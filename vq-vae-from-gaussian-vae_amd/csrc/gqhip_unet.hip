@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <initializer_list>
 #include <cstring>
 
 #include "gqhip_internal.h"
@@ -15,6 +16,7 @@
 #include "gq_conv3.h"
 #include "gq_conv_f32.h"
 #include "gq_attn.h"
+#include "gq_attn_bwd.h"
 
 using namespace gqhip;
 
@@ -730,13 +732,53 @@ int64_t gq_mha_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H) {
   return 0;   // the fp32 route keeps everything on chip: no scratch
 }
 
+// the argument checks shared by the attention entry points: 0 = launch, 1 = nothing to do, -1 = invalid
+static int mha_check(int64_t B, int64_t L, int64_t E, int64_t H, std::initializer_list<const void *> rows16,
+                     std::initializer_list<const void *> words4) {
+  if (B < 0 || L < 0 || H < 1 || E != H * kAttnD || B * H > 65535 || L > (int64_t)0x7fffffff / 3 / E) return -1;
+  if (B == 0 || L == 0) return 1;
+  for (const void *p : rows16)
+    if (!p || ((uintptr_t)p & 15)) return -1;
+  for (const void *p : words4)
+    if (!p || ((uintptr_t)p & 3)) return -1;
+  return 0;
+}
+
 int gq_mha_fwd_f32(const float *qkv, float *out, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace, void *stream) {
   (void)workspace;
-  if (B < 0 || L < 0 || H < 1 || E != H * kAttnD || B * H > 65535 || L > (int64_t)0x7fffffff / 3 / E) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0 || L == 0) return GQHIP_OK;
-  if (!qkv || !out || ((uintptr_t)qkv & 15) || ((uintptr_t)out & 15)) return GQHIP_ERR_INVALID_ARG;
+  const int c = mha_check(B, L, E, H, {qkv, out}, {});
+  if (c) return c < 0 ? GQHIP_ERR_INVALID_ARG : GQHIP_OK;
   const dim3 grid((unsigned)((L + kAttnQRows - 1) / kAttnQRows), (unsigned)(B * H));
-  return launch(mha_fwd_f32_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, (int)L, (int)E, (int)H);
+  return launch(mha_fwd_f32_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, nullptr, (int)L, (int)E,
+                (int)H);
+}
+
+int gq_mha_fwd_lse_f32(const float *qkv, float *out, float *lse, int64_t B, int64_t L, int64_t E, int64_t H, void *workspace,
+                       void *stream) {
+  (void)workspace;
+  const int c = mha_check(B, L, E, H, {qkv, out}, {lse});
+  if (c) return c < 0 ? GQHIP_ERR_INVALID_ARG : GQHIP_OK;
+  const dim3 grid((unsigned)((L + kAttnQRows - 1) / kAttnQRows), (unsigned)(B * H));
+  return launch(mha_fwd_f32_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), qkv, out, lse, (int)L, (int)E, (int)H);
+}
+
+int64_t gq_mha_bwd_workspace_bytes(int64_t B, int64_t L, int64_t E, int64_t H) {
+  (void)E;
+  if (B < 0 || L < 0 || H < 0) return 0;
+  return (2 * B * H * L * (int64_t)sizeof(float) + 255) / 256 * 256;   // n [B][H][L], then D [B][H][L] (gq_attn_bwd.h)
+}
+
+int gq_mha_bwd_f32(const float *qkv, const float *out, const float *lse, const float *dout, float *dqkv, int64_t B, int64_t L,
+                   int64_t E, int64_t H, void *workspace, void *stream) {
+  const int c = mha_check(B, L, E, H, {qkv, out, dout, dqkv}, {lse, workspace});
+  if (c) return c < 0 ? GQHIP_ERR_INVALID_ARG : GQHIP_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((L + kAttnQRows - 1) / kAttnQRows), (unsigned)(B * H));
+  float *rown = static_cast<float *>(workspace), *rowd = rown + B * H * L;
+  // `out` is checked like the other tensors and not read: delta comes from P and dP (gq_attn_bwd.h)
+  const int rc = launch(mha_bwd_dq_f32_kernel, grid, dim3(256), 0, st, qkv, lse, dout, dqkv, rown, rowd, (int)L, (int)E, (int)H);
+  if (rc != GQHIP_OK) return rc;
+  return launch(mha_bwd_dkdv_f32_kernel, grid, dim3(256), 0, st, qkv, lse, dout, rown, rowd, dqkv, (int)L, (int)E, (int)H);
 }
 
 }  // extern "C"

@@ -123,6 +123,9 @@ _SIGNATURES = {
     "gq_step_record_ssim_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
     "gq_mha_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gq_mha_fwd_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "gq_mha_fwd_lse_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "gq_mha_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gq_mha_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "gqhip_profile_enable": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_reserve": (ctypes.c_int, [ctypes.c_int]),
     "gqhip_profile_collect": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
@@ -1304,23 +1307,65 @@ MHA_HEAD_DIMS = (64,)    # head dims gq_mha_fwd_f32 is built for
 _mha_ws: dict = {}
 
 
-def mha_fwd(qkv: torch.Tensor, heads: int) -> torch.Tensor:
-    """softmax(q k^T / sqrt(d)) v per (batch, head) from the in-projection output ``qkv`` [B, L, 3E] fp32 on a HIP device,
-    read in place; returns [B, L, E] with the heads concatenated (gqhip.h: gq_mha_fwd_f32; pit/modules/vit.py:142-151)."""
+def _mha_qkv(qkv: torch.Tensor, heads: int, who: str):
+    """The validation every attention wrapper shares: qkv [B, L, 3E] fp32 on a HIP device, 16-byte aligned, a built head dim."""
     qkv = _dev(qkv, torch.float32, "qkv")
     if qkv.dim() != 3 or qkv.shape[2] % 3 != 0 or heads < 1 or (qkv.shape[2] // 3) % heads != 0:
-        raise GqHipError(f"mha_fwd: qkv must be [B, L, 3E] with E divisible by heads={heads}, got {tuple(qkv.shape)}")
+        raise GqHipError(f"{who}: qkv must be [B, L, 3E] with E divisible by heads={heads}, got {tuple(qkv.shape)}")
     B, L, E3 = qkv.shape
     E = E3 // 3
     if E // heads not in MHA_HEAD_DIMS:
-        raise GqHipError(f"mha_fwd: head dim {E // heads} is not built (built: {MHA_HEAD_DIMS})")
+        raise GqHipError(f"{who}: head dim {E // heads} is not built (built: {MHA_HEAD_DIMS})")
     if qkv.data_ptr() % 16 != 0:
         qkv = qkv.clone()
+    return qkv, B, L, E
+
+
+def mha_fwd(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """softmax(q k^T / sqrt(d)) v per (batch, head) from the in-projection output ``qkv`` [B, L, 3E] fp32 on a HIP device,
+    read in place; returns [B, L, E] with the heads concatenated (gqhip.h: gq_mha_fwd_f32; pit/modules/vit.py:142-151)."""
+    qkv, B, L, E = _mha_qkv(qkv, heads, "mha_fwd")
     out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
     ws = _ssim_ws(_mha_ws, (qkv.device, B, L, E, heads), lib().gq_mha_workspace_bytes(B, L, E, heads), qkv.device)
     with torch.cuda.device(qkv.device):
         _check(lib().gq_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, E, heads, ws.data_ptr(), _stream()), "gq_mha_fwd_f32")
     return out
+
+
+def mha_fwd_lse(qkv: torch.Tensor, heads: int):
+    """``mha_fwd`` for training: (out [B, L, E], lse [B, heads, L]) -- the same ``out`` bit for bit, and per query row the
+    log-sum-exp of its scores in the kernel's units (times ln 2: of q k^T / sqrt(d)), which ``mha_bwd`` recomputes the softmax
+    from (gqhip.h: gq_mha_fwd_lse_f32)."""
+    qkv, B, L, E = _mha_qkv(qkv, heads, "mha_fwd_lse")
+    out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
+    lse = torch.empty(B, heads, L, dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _check(lib().gq_mha_fwd_lse_f32(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, E, heads, None, _stream()),
+               "gq_mha_fwd_lse_f32")
+    return out, lse
+
+
+def mha_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch.Tensor, heads: int) -> torch.Tensor:
+    """The gradient of ``qkv`` [B, L, 3E] (dq | dk | dv in qkv's layout) from ``out``, ``lse`` of ``mha_fwd_lse(qkv, heads)`` and
+    ``dout``, the gradient of ``out`` (gqhip.h: gq_mha_bwd_f32; two kernels, no atomics, bit-reproducible)."""
+    qkv, B, L, E = _mha_qkv(qkv, heads, "mha_bwd")
+    out, lse = _dev(out, torch.float32, "out"), _dev(lse, torch.float32, "lse")
+    dout = _dev(dout, torch.float32, "dout").contiguous()            # autograd hands out expanded (stride 0) gradients
+    if tuple(out.shape) != (B, L, E) or tuple(dout.shape) != (B, L, E) or tuple(lse.shape) != (B, heads, L):
+        raise GqHipError(f"mha_bwd: out / dout must be {(B, L, E)} and lse {(B, heads, L)}, got {tuple(out.shape)}, "
+                         f"{tuple(dout.shape)}, {tuple(lse.shape)}")
+    out, lse = out.contiguous(), lse.contiguous()
+    if out.data_ptr() % 16 != 0:
+        out = out.clone()
+    if dout.data_ptr() % 16 != 0:
+        dout = dout.clone()
+    dqkv = torch.empty(B, L, 3 * E, dtype=torch.float32, device=qkv.device)
+    # delta lives for this call only: from the caching allocator, so that calls on different streams never share it
+    ws = torch.empty(max(lib().gq_mha_bwd_workspace_bytes(B, L, E, heads), 8), dtype=torch.uint8, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        _check(lib().gq_mha_bwd_f32(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), B, L, E,
+                                    heads, ws.data_ptr(), _stream()), "gq_mha_bwd_f32")
+    return dqkv
 
 
 def profile_enable(on: bool) -> None:

@@ -8,16 +8,22 @@ License, Copyright (c) 2024 Yue Zhao): the same classes, constructor keywords, d
 restated locally; einops' patterns are spelled as the reshape / permute / reshape they expand to.
 
 Two routes through every attention layer:
-- the HIP route: CUDA fp32 input, grad disabled, ``mask_type`` "none", a head dim libgqhip is built for (64), no attention
+- the HIP route: CUDA fp32 input, grad disabled (or ``HIP_ATTN_TRAIN`` on, see below), ``mask_type`` "none", a head dim libgqhip is built for (64), no attention
   dropout or drop path in training.  The tokens stay batch-first [B, L, E]: ``F.linear(ln_1(x), in_proj_weight,
   in_proj_bias)`` -> ``_lib.mha_fwd`` (one fused kernel, S never written) -> ``out_proj``.  LayerNorm, the MLP, GELU and the
   residual adds stay ATen ops.
 - otherwise (CPU, autograd, masks, other head dims, ``HIP_ATTN = False``) the reference's exact op sequence: permute to
   seq-first, ``self.attn(x, x, x, need_weights=False)``, permute back -- bit-identical to the reference on CPU.
+
+Training on the HIP route is opt-in (``HIP_ATTN_TRAIN = True`` or ``GQHIP_ATTN_TRAIN=1`` in the environment at import): with grad
+enabled the attention core then is ``_MhaFn`` -- ``_lib.mha_fwd_lse`` forward (the same ``out`` bits, plus the row log-sum-exp),
+``_lib.mha_bwd`` backward (csrc/gq_attn_bwd.h) -- and everything around it stays autograd's.  Off (the default), every grad-enabled
+call takes torch's route exactly as before.
 """
 from __future__ import annotations
 
 import collections.abc
+import os
 from collections import OrderedDict
 from itertools import repeat
 from typing import Callable, Optional, Union
@@ -28,6 +34,7 @@ import torch.nn.functional as F
 from torch.utils.checkpoint import checkpoint
 
 HIP_ATTN = True   # route unmasked fp32 inference attention through libgqhip's fused kernel (False: torch's MHA everywhere)
+HIP_ATTN_TRAIN = os.environ.get("GQHIP_ATTN_TRAIN", "") == "1"   # also with grad enabled (fused forward + backward); default off
 
 
 # ---- timm.models.layers, restated ---------------------------------------------------------------------------------------------
@@ -93,8 +100,13 @@ def _caulsal_mask_impl(sequence_length, device, **kwargs):
 
 def _hip_route(x: torch.Tensor, transformer: "Transformer", mask_type) -> bool:
     """The fused HIP attention applies to every block of ``transformer`` for input ``x`` (see the module docstring)."""
-    if not (HIP_ATTN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 3):
+    if not (HIP_ATTN and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3):
         return False
+    if torch.is_grad_enabled():
+        if not HIP_ATTN_TRAIN:
+            return False
+        if transformer.training and transformer.grad_checkpointing and transformer.selective_checkpointing:
+            return False    # selective checkpointing stays on torch's route
     if not (mask_type is None or str(mask_type).lower() == "none") or len(transformer.resblocks) == 0:
         return False
     from .. import _lib
@@ -106,6 +118,26 @@ def _hip_route(x: torch.Tensor, transformer: "Transformer", mask_type) -> bool:
         if r.training and (a.dropout > 0.0 or isinstance(r.drop_path, DropPath) and r.drop_path.drop_prob > 0.0):
             return False
     return True
+
+
+class _MhaFn(torch.autograd.Function):
+    """The attention core on libgqhip under autograd: qkv [B, L, 3E] -> out [B, L, E]; the backward recomputes P from lse."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        from .. import _lib
+
+        out, lse = _lib.mha_fwd_lse(qkv, heads)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .. import _lib
+
+        qkv, out, lse = ctx.saved_tensors
+        return _lib.mha_bwd(qkv, out, lse, dout, ctx.heads), None
 
 
 # ---- blocks (vit.py:83-279) -----------------------------------------------------------------------------------------------------
@@ -167,7 +199,11 @@ class ResidualAttentionBlock(nn.Module):
 
         a = self.attn
         qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)
-        return F.linear(_lib.mha_fwd(qkv, a.num_heads), a.out_proj.weight, a.out_proj.bias)
+        if torch.is_grad_enabled() and qkv.requires_grad:
+            o = _MhaFn.apply(qkv, a.num_heads)
+        else:
+            o = _lib.mha_fwd(qkv, a.num_heads)
+        return F.linear(o, a.out_proj.weight, a.out_proj.bias)
 
     def checkpoint_forward(self, x: torch.Tensor, attn_mask: Optional[torch.Tensor] = None, is_causal: bool = False):
         state = x
@@ -272,9 +308,12 @@ class Transformer(nn.Module):
         return x
 
     def forward_hip(self, x: torch.Tensor) -> torch.Tensor:
-        """Unmasked forward of batch-first x [B, L, E] (the HIP route; no checkpointing: grad is off)."""
+        """Unmasked forward of batch-first x [B, L, E] (the HIP route), whole-block checkpointing as in forward()."""
         for r in self.resblocks:
-            x = r.forward_hip(x)
+            if self.training and self.grad_checkpointing and torch.is_grad_enabled():
+                x = checkpoint(r.forward_hip, x, **self.grad_checkpointing_params)
+            else:
+                x = r.forward_hip(x)
         return x
 
 
