@@ -77,7 +77,7 @@ def toy():
 
 SWITCHES = ["default", "FUSED_GN", "DEFER_BIAS", "WINOGRAD", "FUSED_WINO_TAIL", "WINOGRAD_F4", "WINOGRAD_F16X3", "WINOGRAD_OWN_GEMM",
             "DIRECT_CONV", "DIRECT_CONV_S2", "DIRECT_CONV_1X1", "FUSED_CONV_OUT", "CONV_F32", "FUSED_WINO_GN", "FUSED_WINO_GN_F4",
-            "DIRECT_UPCONV", "FUSED_QKV", "FUSED_ADD_STATS", "STATS_ARENA", "CONV_IN_SMALL", "ATTN_F16X3"]
+            "DIRECT_UPCONV", "FUSED_QKV", "FUSED_ADD_STATS", "STATS_ARENA", "CONV_IN_SMALL", "ATTN_F16X3", "ATTN_FUSED_PROJ"]
 
 
 @pytest.mark.parametrize("channels_last", [True, False])
@@ -420,3 +420,44 @@ def test_winograd_fused_tail_and_unfused_each_match_fp64():
                     R.lin_gate(yy, ref, mag, c, f"Winograd F({4 if f4 else 2},3) {cin}->{cout}, {name}")
                     yy._gn_stats = (st, 32)
                     _stats_follow_output(yy, name)
+
+
+# ------------------------------------------------------------------------------------------ which kernel serves which layer
+def test_recorded_routes_match_the_committed_route_trace():
+    """tools/convstack/route_trace.py replayed: per case (the toy UNet under every switch and both layouts, the full UNet at the
+    bench shapes and at sizes no tile divides, a ResnetBlock with a pending bias, with and without active dropout) the ordered
+    list of libgqhip / library calls of one forward equals tests/golden/convstack_routes.json -- names, tensor shapes, None-ness
+    and integer / bool / string arguments.  A route that moves shows up here as the first call that differs."""
+    import hashlib
+    import importlib.util
+    import json
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("route_trace", os.path.join(root, "tools", "convstack", "route_trace.py"))
+    rt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rt)
+    assert rt.SWITCHES == SWITCHES and rt.TOY == TOY and rt.FULL == FULL
+    with open(os.path.join(root, "tests", "golden", "convstack_routes.json")) as f:
+        want = json.load(f)
+    env = rt.environment()
+    assert env["bmm_out_dtype_ok"] == want["environment"]["bmm_out_dtype_ok"], (
+        f"the fixture was recorded with bmm_out_dtype_ok = {want['environment']['bmm_out_dtype_ok']} (torch "
+        f"{want['environment']['torch']}); this torch ({env['torch']}) gives {env['bmm_out_dtype_ok']}: the fp16 x 3 library-GEMM "
+        "routes differ, record the fixture again under this build")
+    got = rt.summary(rt.cases())["cases"]
+    assert sorted(got) == sorted(want["cases"])
+    bad = []
+    for name, w in want["cases"].items():
+        g = got[name]
+        if g["sha1"] != w["sha1"]:
+            first = ""
+            if "calls" in w:
+                first = next((f"; first difference at call {i}: {a} != {b}" for i, (a, b) in enumerate(zip(g["calls"], w["calls"])) if a != b),
+                             f"; {len(g['calls'])} calls against {len(w['calls'])}")
+            diff = {k: (g["counts"].get(k, 0), w["counts"].get(k, 0)) for k in set(g["counts"]) | set(w["counts"])
+                    if g["counts"].get(k, 0) != w["counts"].get(k, 0)}
+            bad.append(f"{name}: (got, recorded) counts that differ {diff or 'none: the order or the arguments moved'}{first}")
+        elif "calls" in w:
+            assert hashlib.sha1("\n".join(w["calls"]).encode()).hexdigest() == w["sha1"], name + ": the fixture's own list and hash disagree"
+    assert not bad, "\n".join(bad)

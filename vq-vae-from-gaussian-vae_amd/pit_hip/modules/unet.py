@@ -11,7 +11,8 @@ Two execution paths.  A module left in NCHW runs ATen / MIOpen convolutions with
 kernels (the drop-in default).  A module converted with ``.to(memory_format=torch.channels_last)`` -- the bench
 configuration -- runs every convolution but ``conv_in`` in libgqhip (direct fp16 x 3 implicit GEMMs, Winograd transforms
 around fp16 GEMMs, fp32 matrix-core convolutions for the layers next to z) and is bit-reproducible run to run; which kernel
-serves which layer: profiles/r03/route_table.txt.  Training / autograd / CPU tensors always take the ATen ops.
+serves which layer: tests/golden/convstack_routes.json (the recorded call list of tools/convstack/route_trace.py; every 3x3
+convolution's route is picked in ``_conv3x3``).  Training / autograd / CPU tensors always take the ATen ops.
 
 Only what the shipped SD3-UNet configs use is built: ``attn_type`` "vanilla"
 (single-head SDPA, unet.py:166-206) or "none"; ``temb_channels`` is always 0 on
@@ -21,12 +22,14 @@ from __future__ import annotations
 
 import math
 import os
-
+import threading
 from typing import Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .. import _lib
 
 
 def _gn(ch: int) -> nn.GroupNorm:
@@ -39,14 +42,22 @@ def _silu(x: torch.Tensor) -> torch.Tensor:
     return F.silu(x)
 
 
+def _infer_ok(x: torch.Tensor) -> bool:
+    """Inference on a HIP device, fp32, 4-D: what every libgqhip route asks of its input.  (FUSED_GN is not part of it: the
+    sites that consult that switch name it themselves.)"""
+    return x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
+
+
+def _nhwc(x: torch.Tensor) -> bool:
+    """Dense channels_last (and not NCHW-contiguous as well)."""
+    return _lib.image_layout(x) == 1
+
+
 def _use_fused(x: torch.Tensor, norm: nn.GroupNorm) -> bool:
     """HIP fused GroupNorm(+SiLU) applies to inference on HIP devices, NCHW fp32, HW % 4 == 0;
     training / autograd / CPU tensors stay on the ATen ops (this stack is PyTorch by design)."""
-    if not (FUSED_GN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and x.dim() == 4 and norm.affine):
+    if not (FUSED_GN and _infer_ok(x) and norm.affine):
         return False
-    from .. import _lib
-
     layout = _lib.image_layout(x)
     if layout == 0:
         return (x.shape[2] * x.shape[3]) % 4 == 0
@@ -59,12 +70,12 @@ def _materialize(x: torch.Tensor, pre_bias) -> torch.Tensor:
 
 def _norm_act(norm: nn.GroupNorm, x: torch.Tensor, act: bool = True, pre_bias=None) -> torch.Tensor:
     """GroupNorm followed by swish (unet.py:140-141, :146-147, :432-433) -- one fused HIP pass pair.
-    ``pre_bias``: per-channel bias still pending on ``x`` (see ``_conv``)."""
+    ``pre_bias``: per-channel bias still pending on ``x`` (see ``_conv3x3``)."""
     if _use_fused(x, norm):
-        from .. import _lib
-
         st = getattr(x, "_gn_stats", None)   # left behind by the residual add that produced x (see _add)
-        if st is not None and pre_bias is None and st[1] == norm.num_groups and _lib.image_layout(x) == 1:
+        # producer statistics serve only channels_last, matching groups and no pending bias; gn_silu recomputes them otherwise
+        # (_gn_stats_pb, the memo of _stats_of, is never read here)
+        if st is not None and pre_bias is None and st[1] == norm.num_groups and _nhwc(x):
             y = _lib.gn_apply(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act, st[0])
         else:
             y = _lib.gn_silu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=act, pre_bias=pre_bias)
@@ -76,22 +87,19 @@ def _norm_act(norm: nn.GroupNorm, x: torch.Tensor, act: bool = True, pre_bias=No
 
 
 def _defer_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
-    """Deferred-bias path: inference on HIP, NCHW fp32, zero padding, output HW % 4 == 0."""
-    return (FUSED_GN and DEFER_BIAS and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and conv.bias is not None and conv.padding_mode == "zeros")
+    """Deferred-bias path: inference on HIP, fp32, zero padding."""
+    return FUSED_GN and DEFER_BIAS and _infer_ok(x) and conv.bias is not None and conv.padding_mode == "zeros"
 
 
 def _f16_gemm_ok(x: torch.Tensor) -> bool:
     """The library-GEMM half of the fp16 x 3 routes needs bmm(out_dtype=fp32) (recent PyTorch-ROCm): probed once."""
-    from .. import _lib
-
     return _lib.bmm_out_dtype_ok(x.device)
 
 
 def _f16_args(conv: nn.Conv2d, x: torch.Tensor, f4: bool):
     """(U3, u_scale, bound) for _lib.wino_conv3x3's fp16 x 3 route, or None: needs a rigorous bound on |x| (left on the
     tensor by _norm_act: every Winograd convolution of this UNet is fed by GroupNorm + swish)."""
-    bound = getattr(x, "_act_bound", None)
+    bound = getattr(x, "_act_bound", None)   # there only when _norm_act ran with WINOGRAD_F16X3 set
     if not WINOGRAD_F16X3 or bound is None or not _f16_gemm_ok(x):
         return None
     u3, u_scale, wf2 = _wino_weights_f16(conv, f4)
@@ -100,39 +108,71 @@ def _f16_args(conv: nn.Conv2d, x: torch.Tensor, f4: bool):
 
 def _f16_args_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: torch.Tensor, f4: bool):
     """_f16_args for a convolution whose GroupNorm + swish runs inside the input transform: the bound is that of the
-    activated tensor, which is never materialised."""
+    activated tensor, which is never materialised, so it is computed here."""
     if not WINOGRAD_F16X3 or not _f16_gemm_ok(x):
         return None
     u3, u_scale, wf2 = _wino_weights_f16(conv, f4)
     return u3, u_scale, _gn_act_bound(norm, x), (wf2 if WINOGRAD_OWN_GEMM else None)
 
 
-def _conv(conv: nn.Conv2d, x: torch.Tensor, want_stats: bool = False):
-    """Run ``conv`` and return (y, pending_bias).  ATen's MIOpen path adds the bias in a separate
-    elementwise pass over the whole output; on the deferred path the conv runs bias-free and the
-    bias is handed to the consumer (the next fused GroupNorm or residual add), which folds it in.
-    ``want_stats``: the consumer is a GroupNorm(32) -- on the Winograd path its statistics come with the output."""
-    if _defer_ok(x, conv):
-        if _wino_ok(conv, x):
-            from .. import _lib
+def _conv3x3(conv: nn.Conv2d, x: torch.Tensor, norm=None, pre_bias=None, residual=None, residual_bias=None,
+             want_stats: bool = False):
+    """[residual + residual_bias +] conv(swish(norm(x + pre_bias))) -> (y, pending_bias): the one place that picks a
+    convolution's route.  ATen's MIOpen path adds the bias in a separate elementwise pass over the whole output; on the
+    deferred path the conv runs bias-free and the bias is handed to the consumer (the next fused GroupNorm or residual add),
+    which folds it in.
+    Input: libgqhip's direct fp16 x 3 kernel and the Winograd input transforms (FUSED_WINO_GN / FUSED_WINO_GN_F4) apply
+    ``norm`` + swish while they stage x, so the normalised tensor is never written; where neither takes the layer it is
+    materialised by ``_norm_act`` and the route is picked for that tensor: Winograd (fp16 x 3 or fp32 GEMMs) or the library.
+    Tail: with ``want_stats`` (the consumer is a GroupNorm(32)) or a ``residual`` (conv2 of a ResnetBlock) the kernel's
+    epilogue adds the bias (+ residual + residual_bias) and leaves the next GroupNorm's statistics with the output; a
+    residual it cannot take is added by ``_add``.  ``norm`` None runs any convolution (1x1, stride 2): only marked 3x3
+    stride-1 ones leave the library."""
+    cout = conv.out_channels
+    fuse_in = norm is not None and _defer_ok(x, conv) and _use_fused(x, norm)
+    tail = FUSED_WINO_TAIL and (want_stats or residual is not None) and _lib.gn_nhwc_ok(cout, GN_GROUPS)
+    if residual is not None:
+        # the fused conv2 tail exists only with norm2 handled here, and is gated on _wino_ok for the direct kernel too
+        if not (tail and fuse_in and _wino_ok(conv, x) and residual.shape[1] == cout and _nhwc(residual)):
+            h, bias = _conv3x3(conv, x if norm is None else _norm_act(norm, x, pre_bias=pre_bias))
+            if residual_bias is not None:
+                bias = residual_bias if bias is None else bias + residual_bias
+            return _add(residual, h, bias), None
+    f4 = WINOGRAD_F4 and getattr(conv, "_gq_wino4", False) and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0
+    direct = fuse_in and _direct_ok(conv, x)    # (conv1 takes the direct kernel whatever _wino_ok says)
+    if norm is not None and not direct and not (fuse_in and _wino_ok(conv, x) and (FUSED_WINO_GN_F4 if f4 else FUSED_WINO_GN)):
+        x, norm = _norm_act(norm, x, pre_bias=pre_bias), None
+    if norm is None and residual is None:       # (a fused residual tail has passed both tests on the tensor norm2 read)
+        if not _defer_ok(x, conv):
+            return conv(x), None
+        if not _wino_ok(conv, x):
+            return F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups), conv.bias
+    epilogue = {}
+    if tail:
+        epilogue = dict(residual=residual, bias=conv.bias if residual_bias is None else conv.bias + residual_bias,
+                        stats_groups=GN_GROUPS)
+    if direct:
+        wf, us = _direct_weights(conv)
+        out = _lib.conv3x3_direct(x, wf, us, _gn_act_bound(norm, x), gn=_gn_tuple(norm, x, pre_bias), **epilogue)
+    else:
+        gn = None if norm is None else _gn_tuple(norm, x, pre_bias)
+        f16 = _f16_args(conv, x, f4) if norm is None else _f16_args_gn(conv, norm, x, f4)
+        out = _lib.wino_conv3x3(x, _wino_weights(conv, f4), gn=gn, f16=f16, **epilogue)
+    if not tail:
+        return out, conv.bias
+    out[0]._gn_stats = (out[1], GN_GROUPS)
+    return out[0], None
 
-            f4 = WINOGRAD_F4 and getattr(conv, "_gq_wino4", False) and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0
-            if want_stats and FUSED_WINO_TAIL and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS):
-                # the consumer is a GroupNorm: add the bias here and leave the statistics with the output
-                y, stats = _lib.wino_conv3x3(x, _wino_weights(conv, f4), bias=conv.bias, stats_groups=GN_GROUPS,
-                                             f16=_f16_args(conv, x, f4))
-                y._gn_stats = (stats, GN_GROUPS)
-                return y, None
-            return _lib.wino_conv3x3(x, _wino_weights(conv, f4), f16=_f16_args(conv, x, f4)), conv.bias
-        return F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups), conv.bias
-    return conv(x), None
+
+def _conv(conv: nn.Conv2d, x: torch.Tensor):
+    """Run ``conv`` (any kernel size and stride) and return (y, pending_bias): ``_conv3x3`` without a GroupNorm."""
+    return _conv3x3(conv, x)
 
 
 def _match_layout(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
     """A module converted with ``.to(memory_format=torch.channels_last)`` gets its input in NHWC too (the fast conv
     stack -- Winograd, sub-pixel upsample, NHWC GroupNorm kernels -- is the channels_last one)."""
-    if (x.is_cuda and x.dim() == 4 and conv.weight.is_contiguous(memory_format=torch.channels_last)
-            and not conv.weight.is_contiguous() and not x.is_contiguous(memory_format=torch.channels_last)):
+    if x.is_cuda and x.dim() == 4 and _nhwc(conv.weight) and not x.is_contiguous(memory_format=torch.channels_last):
         return x.contiguous(memory_format=torch.channels_last)
     return x
 
@@ -140,7 +180,7 @@ def _match_layout(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
 def _wino_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return (WINOGRAD and getattr(conv, "_gq_wino", False) and conv.in_channels >= WINOGRAD_MIN_CH
             and conv.out_channels >= WINOGRAD_MIN_CH and conv.out_channels % 4 == 0 and x.shape[2] % 2 == 0
-            and x.shape[3] % 2 == 0 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
+            and x.shape[3] % 2 == 0 and _nhwc(x))
 
 
 def _direct_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -148,25 +188,22 @@ def _direct_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     channels (the 256 x 256 level), where every Winograd route is HBM-bound on its transformed tensors, and -- for modules
     marked F(2x2,3x3)-only (the encoder) -- into 256 channels too (gq_conv3.h)."""
     if not (DIRECT_CONV and getattr(conv, "_gq_wino", False) and conv.in_channels % 16 == 0 and x.shape[2] % 8 == 0
-            and x.shape[3] % 32 == 0 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
+            and x.shape[3] % 32 == 0 and _nhwc(x)):
         return False
     if conv.out_channels == 128:
         return True
+    # 256 output channels only where F(4x4,3x3) would not be used
     return conv.out_channels == 256 and not (WINOGRAD_F4 and getattr(conv, "_gq_wino4", False))
 
 
 def _direct_weights(conv: nn.Conv2d):
     """(Wf, u_scale) of conv3x3_direct / conv1x1_direct, cached until the weight changes."""
-    from .. import _lib
-
     return _cached(conv, "direct_wf", _wkey(conv.weight), lambda: _lib.conv3_weights_f16(conv.weight))
 
 
 def _stats_of(x: torch.Tensor, pre_bias, groups: int):
     """GroupNorm statistics of x + pre_bias: left by the producer of x, computed earlier for the same pending bias, or
     computed (and remembered on x) here."""
-    from .. import _lib
-
     st = getattr(x, "_gn_stats", None)
     if st is not None and pre_bias is None and st[1] == groups:
         return st[0]
@@ -186,11 +223,10 @@ def _gn_tuple(norm: nn.GroupNorm, x: torch.Tensor, pre_bias):
 def _pointwise_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     """1x1 convolutions into 128 / 256 / 512 channels (ResnetBlock shortcuts, attention proj_out) as libgqhip's fp16 x 3
     GEMM over the pixels (gq_conv3.h: conv1x1_f16x3) instead of MIOpen's fp32 implicit GEMM (~100 TFLOP/s)."""
-    return (DIRECT_CONV_1X1 and FUSED_GN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-            and conv.out_channels in (128, 256, 512) and conv.in_channels % 128 == 0 and x.dim() == 4
-            and (x.shape[2] * x.shape[3]) % 256 == 0 and x.is_contiguous(memory_format=torch.channels_last)
-            and not x.is_contiguous())
+    # (HW % 256 and Cin % 128 are asked here although the library takes HW % 128 and Cin % 32)
+    return (DIRECT_CONV_1X1 and FUSED_GN and _infer_ok(x) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.padding == (0, 0) and conv.groups == 1 and conv.out_channels in (128, 256, 512)
+            and conv.in_channels % 128 == 0 and (x.shape[2] * x.shape[3]) % 256 == 0 and _nhwc(x))
 
 
 def _norm_act_conv_small(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, pre_bias=None) -> torch.Tensor:
@@ -199,12 +235,9 @@ def _norm_act_conv_small(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, p
     MIOpen's implicit GEMM (0.2 + 0.96 ms at 16 x 256 x 256 x 128)."""
     if (FUSED_CONV_OUT and _use_fused(x, norm) and conv.out_channels <= 4 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
-            and x.shape[1] % 32 == 0 and x.shape[1] <= 512 and x.shape[2] % 16 == 0 and x.shape[3] % 16 == 0):
-        from .. import _lib
-
-        if _lib.image_layout(x) == 1:
-            ohwi = _cached(conv, "ohwi", _wkey(conv.weight), lambda: conv.weight.detach().permute(0, 2, 3, 1).contiguous())
-            return _lib.conv3x3_gn_small(x, ohwi, conv.bias, _gn_tuple(norm, x, pre_bias))
+            and x.shape[1] % 32 == 0 and x.shape[1] <= 512 and x.shape[2] % 16 == 0 and x.shape[3] % 16 == 0 and _nhwc(x)):
+        ohwi = _cached(conv, "ohwi", _wkey(conv.weight), lambda: conv.weight.detach().permute(0, 2, 3, 1).contiguous())
+        return _lib.conv3x3_gn_small(x, ohwi, conv.bias, _gn_tuple(norm, x, pre_bias))
     return conv(_norm_act(norm, x, pre_bias=pre_bias))
 
 
@@ -226,19 +259,14 @@ def _cached(module: nn.Module, name: str, key, build):
 def _conv_f32_ok(conv: nn.Conv2d, x: torch.Tensor, gn: bool) -> bool:
     """The narrow ends of the stack (encoder conv_out, decoder conv_in) on libgqhip's fp32 matrix-core convolution: a fixed
     summation order, hence bit-reproducible -- MIOpen's pick for 512 -> 32 channels is a split-K kernel with atomics."""
-    if not (CONV_F32 and FUSED_GN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.padding_mode == "zeros" and x.is_contiguous(memory_format=torch.channels_last)
-            and not x.is_contiguous()):
+    if not (CONV_F32 and FUSED_GN and _infer_ok(x) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and _nhwc(x)):
         return False
-    from .. import _lib
-
     return _lib.conv_f32_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], gn)
 
 
 def _conv_f32(conv: nn.Conv2d, x: torch.Tensor, gn=None) -> torch.Tensor:
-    from .. import _lib
-
     wk = _cached(conv, "f32_wk", _wkey(conv.weight), lambda: _lib.conv_f32_weights(conv.weight))
     return _lib.conv3x3_f32(x, wk, conv.out_channels, bias=conv.bias, gn=gn)
 
@@ -248,64 +276,23 @@ def _conv_in_small(conv: nn.Conv2d, x: torch.Tensor):
     fixed-order fp32 kernel with the bias and the first GroupNorm's statistics in its epilogue (round 4; it was the last MIOpen
     convolution of the bench shapes: 0.24 ms per call once MIOpen's CK solver runs, 4 ms for each of a process's first eight
     calls).  Other shapes / layouts: ``_conv``."""
-    if (CONV_IN_SMALL and FUSED_GN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
-            and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.padding_mode == "zeros" and GN_GROUPS == 32):
-        from .. import _lib
-
-        if _lib.image_layout(x) == 1 and _lib.conv_cin_small_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3]):
-            wk = _cached(conv, "cin_small_wk", _wkey(conv.weight), lambda: _lib.conv_cin_small_weights(conv.weight))
-            y, st = _lib.conv3x3_cin_small(x, wk, conv.bias, stats_groups=GN_GROUPS)
-            y._gn_stats = (st, GN_GROUPS)
-            return y, None
+    if (CONV_IN_SMALL and FUSED_GN and _infer_ok(x) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
+            and GN_GROUPS == 32 and _nhwc(x)
+            and _lib.conv_cin_small_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3])):
+        wk = _cached(conv, "cin_small_wk", _wkey(conv.weight), lambda: _lib.conv_cin_small_weights(conv.weight))
+        y, st = _lib.conv3x3_cin_small(x, wk, conv.bias, stats_groups=GN_GROUPS)
+        y._gn_stats = (st, GN_GROUPS)
+        return y, None
     return _conv(conv, x)
 
 
 def _norm_act_conv_f32(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, pre_bias=None) -> torch.Tensor:
     """conv(swish(norm(x + pre_bias))) for the encoder's conv_out (unet.py:432-436): GroupNorm + swish applied while the
     patch is staged, fp32 matrix cores, fixed summation order."""
-    if _conv_f32_ok(conv, x, True) and _use_fused(x, norm):
-        from .. import _lib
-
-        if _lib.image_layout(x) == 1:
-            return _conv_f32(conv, x, gn=_gn_tuple(norm, x, pre_bias))
+    if _conv_f32_ok(conv, x, True) and _use_fused(x, norm):   # (_conv_f32_ok: channels_last)
+        return _conv_f32(conv, x, gn=_gn_tuple(norm, x, pre_bias))
     return conv(_norm_act(norm, x, pre_bias=pre_bias))
-
-
-def _norm_act_conv(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, pre_bias=None, want_stats: bool = False):
-    """conv(swish(norm(x + pre_bias))) -> (y, pending_bias).  The GroupNorm(+SiLU) is applied inside the Winograd input
-    transform, so the normalised tensor is never written (FUSED_WINO_GN / FUSED_WINO_GN_F4)."""
-    if _defer_ok(x, conv) and _direct_ok(conv, x) and _use_fused(x, norm):
-        from .. import _lib
-
-        if _lib.image_layout(x) == 1:
-            wf, us = _direct_weights(conv)
-            gn = _gn_tuple(norm, x, pre_bias)
-            if want_stats and FUSED_WINO_TAIL and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS):
-                y, ostats = _lib.conv3x3_direct(x, wf, us, _gn_act_bound(norm, x), gn=gn, bias=conv.bias,
-                                                stats_groups=GN_GROUPS)
-                y._gn_stats = (ostats, GN_GROUPS)
-                return y, None
-            return _lib.conv3x3_direct(x, wf, us, _gn_act_bound(norm, x), gn=gn), conv.bias
-    if _defer_ok(x, conv) and _wino_ok(conv, x) and _use_fused(x, norm):
-        from .. import _lib
-
-        f4 = WINOGRAD_F4 and getattr(conv, "_gq_wino4", False) and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0
-        if _lib.image_layout(x) == 1 and (FUSED_WINO_GN_F4 if f4 else FUSED_WINO_GN):
-            st = getattr(x, "_gn_stats", None)
-            if st is not None and pre_bias is None and st[1] == norm.num_groups:
-                stats = st[0]
-            else:
-                stats = _lib.gn_stats(x, norm.num_groups, pre_bias)
-            gn = (norm.weight, norm.bias, norm.num_groups, norm.eps, True, stats, pre_bias)
-            U = _wino_weights(conv, f4)
-            f16 = _f16_args_gn(conv, norm, x, f4)
-            if want_stats and FUSED_WINO_TAIL and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS):
-                y, ostats = _lib.wino_conv3x3(x, U, gn=gn, bias=conv.bias, stats_groups=GN_GROUPS, f16=f16)
-                y._gn_stats = (ostats, GN_GROUPS)
-                return y, None
-            return _lib.wino_conv3x3(x, U, gn=gn, f16=f16), conv.bias
-    return _conv(conv, _norm_act(norm, x, pre_bias=pre_bias), want_stats)
 
 
 _WINO_G2 = [[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]]
@@ -339,8 +326,6 @@ def _wino_weights_f16(conv: nn.Conv2d, f4: bool = False):
         l = (us - h.float()).half()
         wf2 = None
         if WINOGRAD_OWN_GEMM and U.shape[1] % 32 == 0 and U.shape[2] % 128 == 0:
-            from .. import _lib
-
             wf2 = _lib.wino_weights_operand_order(h, l)
         return torch.cat([h, l, h], 1).contiguous(), u_scale, wf2
 
@@ -369,8 +354,6 @@ class _WeightGuard:
         self.key = None
 
     def begin(self, module: nn.Module) -> bool:
-        from .. import _lib
-
         params = [p for p in module.parameters()]
         # the checksum kernel reads numel() words from data_ptr(): only DENSE parameters (contiguous, or a dense channels_last
         # layout) -- an expanded or strided view would be read past its own storage, so such a module runs unguarded
@@ -417,10 +400,6 @@ def _with_stats_arena(module: nn.Module, run, x: torch.Tensor):
     forwards take per-call records from the caching allocator, which the capture keeps alive."""
     if not (STATS_ARENA and FUSED_GN and x.is_cuda and not torch.is_grad_enabled()) or torch.cuda.is_current_stream_capturing():
         return run(x)
-    import threading
-
-    from .. import _lib
-
     key = (threading.get_ident(), torch.cuda.current_stream(x.device).cuda_stream)
     arenas = module.__dict__.setdefault("_gq_stats_arenas", {})
     arena = arenas.pop(key, None)
@@ -477,7 +456,7 @@ def _drop_caches_after_load(module, incompatible_keys) -> None:
 
 
 def mark_winograd(module: nn.Module, f4: bool = False) -> None:
-    """Flag the stride-1, padding-1 3x3 convolutions of ``module`` for the Winograd path (see ``_conv``);
+    """Flag the stride-1, padding-1 3x3 convolutions of ``module`` for the Winograd path (see ``_conv3x3``);
     ``f4``: F(4x4,3x3) where the spatial size allows it (decoder only: larger rounding error)."""
     for m in module.modules():
         if (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1)
@@ -488,10 +467,7 @@ def mark_winograd(module: nn.Module, f4: bool = False) -> None:
 
 def _add(a: torch.Tensor, b: torch.Tensor, bias=None) -> torch.Tensor:
     """a + b (+ bias[c]) -- the residual add with the pending biases folded in."""
-    if (bias is not None and a.is_cuda and a.shape == b.shape and a.dtype == torch.float32
-            and not torch.is_grad_enabled()):
-        from .. import _lib
-
+    if bias is not None and _infer_ok(a) and a.shape == b.shape:    # (whatever FUSED_GN says)
         la, lb = _lib.image_layout(a), _lib.image_layout(b)
         if FUSED_ADD_STATS and la == 1 and lb == 1 and _lib.gn_nhwc_ok(a.shape[1], GN_GROUPS):
             # every residual add of this UNet feeds a GroupNorm(32): leave its statistics with the sum, the
@@ -583,66 +559,30 @@ class ResnetBlock(nn.Module):
 
     def forward(self, x: torch.Tensor, pre_bias=None) -> torch.Tensor:
         """``pre_bias``: bias of the conv that produced ``x``, not yet added (deferred path)."""
-        h, b1 = _norm_act_conv(self.norm1, self.conv1, x, pre_bias, want_stats=True)   # norm2 follows
-        if self.in_channels != self.out_channels and _pointwise_ok(self.nin_shortcut, x) and _use_fused(x, self.norm1):
+        h, b1 = _conv3x3(self.conv1, x, self.norm1, pre_bias, want_stats=True)   # norm2 follows
+        xs, bs = self._shortcut(x, pre_bias)
+        if self.dropout.p > 0.0 and self.training:   # active dropout: norm2 is materialised, which leaves conv2's tail unfused
+            return _conv3x3(self.conv2, self.dropout(_norm_act(self.norm2, h, pre_bias=b1)), residual=xs, residual_bias=bs)[0]
+        # dropout is the identity (unet.py:148 with p = 0 / eval)
+        return _conv3x3(self.conv2, h, self.norm2, b1, residual=xs, residual_bias=bs)[0]
+
+    def _shortcut(self, x: torch.Tensor, pre_bias):
+        """(xs, bs) with xs + bs = nin_shortcut(x + pre_bias), or x + pre_bias where the width does not change."""
+        if self.in_channels == self.out_channels:
+            return x, pre_bias
+        nin = self.nin_shortcut
+        if _pointwise_ok(nin, x) and _use_fused(x, self.norm1):
             # nin(x + pb) as one fp16 x 3 GEMM over the pixels; x + pb is split inside the kernel, its power-of-two scale
             # comes (on the device) from the statistics norm1 needed anyway: |x + pb| <= sqrt(group sum of squares)
-            from .. import _lib
-
-            wf, us = _direct_weights(self.nin_shortcut)
+            wf, us = _direct_weights(nin)
             scales = _lib.f16_scales(_stats_of(x, pre_bias, GN_GROUPS), 1.0, us)
-            xs, bs = _lib.conv1x1_direct(x, wf, us, scales, pre_bias=pre_bias), self.nin_shortcut.bias
-        elif self.in_channels != self.out_channels:
-            # nin(x + pb) = nin_nobias(x) + W.pb + nin.bias : every constant goes into the fused add
-            xs, bs = _conv(self.nin_shortcut, x)
-            if pre_bias is not None:
-                wpb = self.nin_shortcut.weight.reshape(self.out_channels, self.in_channels) @ pre_bias
-                bs = wpb if bs is None else bs + wpb
-        else:
-            xs, bs = x, pre_bias
-        if self.dropout.p > 0.0 and self.training:
-            h, bias = _conv(self.conv2, self.dropout(_norm_act(self.norm2, h, pre_bias=b1)))
-        else:   # dropout is the identity (unet.py:148 with p = 0 / eval)
-            if (FUSED_WINO_TAIL and _defer_ok(h, self.conv2) and _wino_ok(self.conv2, h) and _use_fused(h, self.norm2)
-                    and xs.shape[1] == self.out_channels and xs.is_contiguous(memory_format=torch.channels_last)
-                    and not xs.is_contiguous()):
-                from .. import _lib
-
-                if (_direct_ok(self.conv2, h) and _lib.gn_nhwc_ok(self.out_channels, GN_GROUPS)
-                        and _lib.image_layout(h) == 1):
-                    bias = self.conv2.bias if bs is None else self.conv2.bias + bs
-                    wf, us = _direct_weights(self.conv2)
-                    y, ostats = _lib.conv3x3_direct(h, wf, us, _gn_act_bound(self.norm2, h),
-                                                    gn=_gn_tuple(self.norm2, h, b1), residual=xs, bias=bias,
-                                                    stats_groups=GN_GROUPS)
-                    y._gn_stats = (ostats, GN_GROUPS)
-                    return y
-                if _lib.gn_nhwc_ok(self.out_channels, GN_GROUPS) and _lib.image_layout(h) == 1:
-                    # conv2, its bias, the shortcut's constants, the residual add and the next GroupNorm's statistics
-                    # in one output-transform pass (and, with F(4x4,3x3), norm2 + swish inside the input transform)
-                    bias = self.conv2.bias if bs is None else self.conv2.bias + bs
-                    f4 = (WINOGRAD_F4 and getattr(self.conv2, "_gq_wino4", False) and h.shape[2] % 4 == 0
-                          and h.shape[3] % 4 == 0)
-                    if FUSED_WINO_GN_F4 if f4 else FUSED_WINO_GN:
-                        st = getattr(h, "_gn_stats", None)
-                        if st is not None and b1 is None and st[1] == self.norm2.num_groups:
-                            stats = st[0]
-                        else:
-                            stats = _lib.gn_stats(h, self.norm2.num_groups, b1)
-                        gn = (self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, True, stats, b1)
-                        src = h
-                        f16 = _f16_args_gn(self.conv2, self.norm2, h, f4)
-                    else:
-                        gn, src = None, _norm_act(self.norm2, h, pre_bias=b1)
-                        f16 = _f16_args(self.conv2, src, f4)
-                    y, ostats = _lib.wino_conv3x3(src, _wino_weights(self.conv2, f4), gn=gn, residual=xs, bias=bias,
-                                                  stats_groups=GN_GROUPS, f16=f16)
-                    y._gn_stats = (ostats, GN_GROUPS)
-                    return y
-            h, bias = _conv(self.conv2, _norm_act(self.norm2, h, pre_bias=b1))
-        if bs is not None:
-            bias = bs if bias is None else bias + bs
-        return _add(xs, h, bias)
+            return _lib.conv1x1_direct(x, wf, us, scales, pre_bias=pre_bias), nin.bias
+        # nin(x + pb) = nin_nobias(x) + W.pb + nin.bias : every constant goes into the fused add
+        xs, bs = _conv(nin, x)
+        if pre_bias is not None:
+            wpb = nin.weight.reshape(self.out_channels, self.in_channels) @ pre_bias
+            bs = wpb if bs is None else bs + wpb
+        return xs, bs
 
 
 class AttnBlock(nn.Module):
@@ -667,6 +607,14 @@ class AttnBlock(nn.Module):
 
         return _cached(self, "qkv", _wkey(*ps), build)
 
+    def _qkv_weights_f16(self):
+        """(qkv_wf, qkv_us): that matrix as the weight operand of libgqhip's fp16 x 3 GEMM over the pixels; cached likewise."""
+        def build():
+            wqkv = self._qkv_weights()[0]
+            return _lib.conv3_weights_f16(wqkv.t().reshape(wqkv.shape[1], wqkv.shape[0], 1, 1))
+
+        return _cached(self, "qkv_wf", _wkey(self.q.weight, self.k.weight, self.v.weight), build)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape
         fused = self._fused_proj_attention(x) if ATTN_FUSED_PROJ else None
@@ -682,18 +630,15 @@ class AttnBlock(nn.Module):
         a_scale = 1.0      # power of two still pending on the attention output (fp16 x 3 route)
         y = _norm_act(self.norm, x, act=False)
         # [b, c, h, w] -> [b, 1, hw, c]
-        if y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous():
+        if _nhwc(y):
             # channels_last: [b, hw, c] is a free view of the conv output and of the result
-            if FUSED_QKV and y.is_cuda and y.dtype == torch.float32 and not torch.is_grad_enabled():
+            if FUSED_QKV and _infer_ok(y):
                 # q, k, v = three 1x1 convolutions of the same tensor = ONE GEMM [b*hw, c] x [c, 3c] with the biases in
                 # its epilogue (instead of 3 MIOpen launches + 3 bias-add passes); the thirds are strided views
                 wqkv, bqkv = self._qkv_weights()
                 if self._own_qkv_ok(y):
                     # ... as libgqhip's fp16 x 3 GEMM over the pixels (the fp32 library GEMM runs at ~130 TFLOP/s)
-                    from .. import _lib
-
-                    qkv_wf, qkv_us = _cached(self, "qkv_wf", _wkey(self.q.weight, self.k.weight, self.v.weight),
-                                             lambda: _lib.conv3_weights_f16(wqkv.t().reshape(3 * c, c, 1, 1)))
+                    qkv_wf, qkv_us = self._qkv_weights_f16()
                     qkv = _lib.conv1x1_direct(y, qkv_wf, qkv_us, _gn_act_bound(self.norm, x), bias=bqkv)
                     qkv = qkv.permute(0, 2, 3, 1).reshape(b, 1, h * w, 3 * c)
                 else:
@@ -703,8 +648,6 @@ class AttnBlock(nn.Module):
                 qkv = None
                 q, k, v = (f(y).permute(0, 2, 3, 1).reshape(b, 1, h * w, c) for f in (self.q, self.k, self.v))
             if qkv is not None and qkv.is_contiguous():
-                from .. import _lib
-
                 if self._f16x3_attention_ok(y):
                     # both attention GEMMs as fp16 GEMMs over K axes of two-term fp16 splits (fp32 accumulation): the fp32
                     # GEMMs are a split-bf16 emulation at ~120 TFLOP/s; operand scales from rigorous bounds (GroupNorm bound x
@@ -723,14 +666,11 @@ class AttnBlock(nn.Module):
     def _proj_out(self, x: torch.Tensor, a: torch.Tensor, a_scale: float) -> torch.Tensor:
         """x + proj_out(a * a_scale)."""
         c = x.shape[1]
-        if (_pointwise_ok(self.proj_out, a) and FUSED_ADD_STATS and x.is_contiguous(memory_format=torch.channels_last)
-                and not x.is_contiguous() and self.proj_out.bias is not None):
+        if _pointwise_ok(self.proj_out, a) and FUSED_ADD_STATS and _nhwc(x) and self.proj_out.bias is not None:
             # proj_out + bias + residual add + the next GroupNorm's statistics in one fp16 x 3 GEMM over the pixels.  Scale:
             # the attention output is a convex combination of the rows of v, so |a| <= max|v| <= max|y| max_j ||W_v[j]||_1 +
             # max|b_v|, with |y| bounded by the GroupNorm bound
-            from .. import _lib
-
-            if _lib.image_layout(a) == 1 and _lib.gn_nhwc_ok(c, GN_GROUPS):
+            if _lib.gn_nhwc_ok(c, GN_GROUPS):   # (_pointwise_ok: a is channels_last)
                 wf, us = _direct_weights(self.proj_out)
                 out, st = _lib.conv1x1_direct(a, wf, us, self._v_bound(_gn_act_bound(self.norm, x)) / a_scale, residual=x,
                                               bias=self.proj_out.bias, stats_groups=GN_GROUPS, post_scale=a_scale)
@@ -745,15 +685,12 @@ class AttnBlock(nn.Module):
     def _own_qkv_ok(y: torch.Tensor) -> bool:
         """The q | k | v projection of y (the normalised tensor, or x where the GroupNorm runs inside the projection: same shape,
         layout and dtype) as ONE libgqhip fp16 x 3 GEMM over the pixels.  c = 512: the plain kernel's 3c = 1536 columns."""
-        return (FUSED_QKV and DIRECT_CONV_1X1 and y.is_cuda and y.dtype == torch.float32 and not torch.is_grad_enabled()
-                and y.shape[1] == 512 and (y.shape[2] * y.shape[3]) % 256 == 0
-                and y.is_contiguous(memory_format=torch.channels_last) and not y.is_contiguous())
+        return (FUSED_QKV and DIRECT_CONV_1X1 and _infer_ok(y) and y.shape[1] == 512 and (y.shape[2] * y.shape[3]) % 256 == 0
+                and _nhwc(y))    # (whatever FUSED_GN says)
 
     @staticmethod
     def _f16x3_attention_ok(y: torch.Tensor) -> bool:
         """Both attention GEMMs as fp16 x 3 library GEMMs (_lib.attention_f16x3 / attention_from_operands)."""
-        from .. import _lib
-
         return ATTN_F16X3 and y.shape[1] % 4 == 0 and _f16_gemm_ok(y) and (y.shape[2] * y.shape[3]) in _lib.ATTN_L_OK
 
     def _fused_proj_attention(self, x: torch.Tensor):
@@ -767,13 +704,10 @@ class AttnBlock(nn.Module):
         b, c, h, w = x.shape
         if not (self._own_qkv_ok(x) and self._f16x3_attention_ok(x) and _use_fused(x, self.norm)):
             return None
-        from .. import _lib
-
         if not _lib.gn_nhwc_ok(c, self.norm.num_groups):
             return None
-        wqkv, bqkv = self._qkv_weights()
-        qkv_wf, qkv_us = _cached(self, "qkv_wf", _wkey(self.q.weight, self.k.weight, self.v.weight),
-                                 lambda: _lib.conv3_weights_f16(wqkv.t().reshape(3 * c, c, 1, 1)))
+        bqkv = self._qkv_weights()[1]
+        qkv_wf, qkv_us = self._qkv_weights_f16()
         yb = _gn_act_bound(self.norm, x)
         sq, sv = _lib.attention_scales(self._qk_bound(yb), self._v_bound(yb))
         gn = (self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps, False,
@@ -819,15 +753,12 @@ class Downsample(nn.Module):
         if not self.with_conv:
             return F.avg_pool2d(x, 2, 2), None
         conv = self.conv
-        if (DIRECT_CONV_S2 and self.mode == "constant" and FUSED_GN and x.is_cuda and x.dtype == torch.float32
-                and not torch.is_grad_enabled() and conv.out_channels in (128, 256, 512) and conv.in_channels % 16 == 0
-                and conv.bias is not None and x.dim() == 4 and x.shape[2] % 16 == 0 and x.shape[3] % 64 == 0
-                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()):
+        if (DIRECT_CONV_S2 and self.mode == "constant" and FUSED_GN and _infer_ok(x) and conv.out_channels in (128, 256, 512)
+                and conv.in_channels % 16 == 0 and conv.bias is not None and x.shape[2] % 16 == 0 and x.shape[3] % 64 == 0
+                and _nhwc(x)):
             # pad + stride-2 convolution + bias + the next GroupNorm's statistics as ONE fp16 x 3 kernel on the four phase
             # images of x (MIOpen: a padding pass + an fp32 implicit GEMM, 0.7-1.0 ms); the scale of x comes, on the device,
             # from the statistics its producer left behind: |x| <= sqrt(group sum of squares)
-            from .. import _lib
-
             if _lib.gn_nhwc_ok(x.shape[1], GN_GROUPS) and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS):
                 s2_wf, s2_us = _cached(conv, "s2_wf", _wkey(conv.weight), lambda: _lib.conv3s2_weights_f16(conv.weight))
                 scales = _lib.f16_scales(_stats_of(x, None, GN_GROUPS), 1.0, s2_us)
@@ -872,8 +803,7 @@ class Upsample(nn.Module):
 
     def forward(self, x: torch.Tensor):
         """Returns (y, pending_bias) -- see ``_conv``."""
-        fast = (FUSED_GN and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-                and x.shape[1] % 4 == 0 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
+        fast = FUSED_GN and _infer_ok(x) and x.shape[1] % 4 == 0 and _nhwc(x)
         if (fast and DIRECT_UPCONV and self.with_conv and _defer_ok(x, self.conv) and self.conv.kernel_size == (3, 3)
                 and self.conv.stride == (1, 1) and self.conv.padding == (1, 1)):
             # nearest x2 then conv3x3 == four 2x2 convolutions of the low-resolution input (one per output phase): 16 instead
@@ -881,8 +811,6 @@ class Upsample(nn.Module):
             # kernel per Upsample), with the bias added and the statistics of the next ResnetBlock's norm1 left behind; the
             # scale of x comes, on the device, from the statistics its producer left (sqrt of a group's sum of squares bounds
             # its largest element)
-            from .. import _lib
-
             b, c, h, w = x.shape
             st = getattr(x, "_gn_stats", None)
             cout = self.conv.out_channels
@@ -895,8 +823,6 @@ class Upsample(nn.Module):
                 y._gn_stats = (ostats, GN_GROUPS)
                 return y, None
         if fast:   # shapes the direct kernel does not tile: upsample (a plain NHWC copy kernel), then the convolution
-            from .. import _lib
-
             x = _lib.upsample2x_nhwc(x)   # ATen's NHWC nearest kernel runs at ~1.6 TB/s; this one is a plain copy
         else:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
