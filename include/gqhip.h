@@ -537,7 +537,10 @@ int gq_indices_from_u16(const uint16_t *in, int64_t *idx, int64_t count,
  * idx: n_idx values in [0, 65536) (not checked; a wider value is truncated to its low 16 bits).  The squared differences are
  * formed in the reference's fp32 op order and summed in fp64 in a fixed order (bit-reproducible; within 2e-6 of torch's fp32
  * mean).  workspace: gq_step_record_workspace_bytes(B, per_image) bytes, ZERO when first used; every call leaves it zero
- * again, so one allocation serves a stream of calls (one stream at a time).  Asynchronous on `stream`, no allocation. */
+ * again -- every byte of it: the thread that finishes an image stores zeros over the partial sums it has added and over the
+ * image's ticket --, so one allocation serves a stream of calls (one stream at a time) of ANY (B, per_image) whose byte count it
+ * holds: the short last batch of an epoch runs in the buffer that was sized for the full one.  Bytes beyond the call's own
+ * gq_step_record_workspace_bytes are neither read nor written.  Asynchronous on `stream`, no allocation. */
 int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image);
 int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
                        int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
@@ -550,7 +553,10 @@ int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, i
  * (csrc/gq_ssim.h).  A side under 11 is left unfiltered, as pytorch_msssim does.  ssim_out_or_null / msssim_out_or_null: B fp32
  * values each; a NULL msssim_out skips levels 1-4; when H < 256 or W < 256 MS-SSIM is NaN (ssim.py:31-34).  One launch per level,
  * sums in a fixed order: bit-reproducible.  workspace: gq_ssim_workspace_bytes(B, C, H, W) bytes, ZERO when first used; every
- * call leaves it zero again (one stream at a time).  Asynchronous on `stream`, no allocation: graph-capturable. */
+ * call leaves it zero again -- every byte of it: tickets and tile sums are zeroed by the block that finishes an image, and a call
+ * that ran levels 1-4 ends with one more launch that clears the pooled planes --, so one allocation serves a stream of calls (one
+ * stream at a time) of ANY (B, C, H, W) whose byte count it holds.  Bytes beyond the call's own gq_ssim_workspace_bytes are neither
+ * read nor written.  Asynchronous on `stream`, no allocation: graph-capturable. */
 int64_t gq_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_t H, int64_t W, int layout, int zero_mean,
                 float *ssim_out_or_null, float *msssim_out_or_null, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
@@ -558,7 +564,8 @@ int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_
  * format of pit_hip/eval_dist.py:StepRecord with n_metrics = 3:
  *     rec [3 B + (n_idx + 1) / 2] int32 = [ B x (psnr, ssim, ms_ssim) as fp32 bits, image-major | indices as uint16 pairs ].
  * The PSNR words and the index words come from the kernel of gq_step_record_f32 (bit-identical to it), SSIM / MS-SSIM from that
- * of gq_ssim_f32.  workspace: gq_step_record_ssim_workspace_bytes(B, C, H, W) bytes, ZERO when first used, left zero. */
+ * of gq_ssim_f32.  workspace: gq_step_record_ssim_workspace_bytes(B, C, H, W) bytes, ZERO when first used, left zero: every byte, as
+ * by the two calls it is made of, so one allocation serves any stream of shapes that fit. */
 int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
                             int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);

@@ -244,14 +244,15 @@ __global__ __launch_bounds__(256) void from_u16_kernel(const uint16_t *__restric
 // with n_metrics = 1, i.e. what eval.py:165-169 (get_psnr(zero_mean=True), pit/evaluations/psnr.py:17-28) and the index gather
 // of eval.py:152-154 publish per batch.  Blocks [0, B * chunks): one contiguous chunk of one image, the squared differences in
 // the reference's fp32 op order ((x + 1) 127.5 - (x_rec + 1) 127.5, squared), summed in fp64; the LAST block of an image (a ticket
-// per image, reset for the next call) adds the chunk sums in chunk order -- a fixed order: the value is bit-reproducible -- and
+// per image, reset for the next call) adds the chunk sums in chunk order -- a fixed order: the value is bit-reproducible --, stores
+// zeros over them (one thread per image, `chunks` stores: the workspace is all zero between calls whatever B the next one has) and
 // writes 20 log10(255 / sqrt(mse)).  The blocks after those pack the indices.  The three-metric record (gq_step_record_ssim_f32)
 // runs the same kernel with stride 3: [ B x (psnr, ssim, ms_ssim) | indices ], its PSNR words those of stride 1 bit for bit.
 struct StepRecordParams {
   const float *x, *x_rec;     // [B, per_image] in the SAME dense layout
   const int64_t *idx;         // [n_idx]
   int *rec;                   // [B + (n_idx + 1) / 2]
-  double *partial;            // [B, chunks]      (workspace)
+  double *partial;            // [B, chunks]      (workspace; zero between calls, like the tickets)
   int *ticket;                // [B], all zero between calls (workspace)
   long per_image, n_idx;
   int B, chunks, psnr_blocks;
@@ -303,7 +304,11 @@ __global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams
   if (!sh_last || tid != 0) return;
   __threadfence();
   double sum = 0.0;
-  for (int k = 0; k < p.chunks; ++k) sum += __hip_atomic_load(&p.partial[(long)b * p.chunks + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int k = 0; k < p.chunks; ++k) {
+    double *part = &p.partial[(long)b * p.chunks + k];
+    sum += __hip_atomic_load(part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *part = 0.0;                               // the whole workspace is zero again behind the call: a later call may lay it out
+  }                                            // for another B (its tickets then sit where these sums were)
   const float mse = (float)(sum / (double)p.per_image);
   const float psnr = (float)(20.0 * log10(255.0 / sqrt((double)mse)));      // identical images: +inf, like the reference
   p.rec[(long)b * p.stride] = __float_as_int(psnr);

@@ -80,7 +80,9 @@ static_assert(sizeof(GaussStatsParams) == 80, "fits the header's pad");
 
 // Workspace header (first 8 KiB of the caller's workspace).  Everything in it is (re)written by the kernels of ONE
 // call: gq_prep_kernel resets the counters and writes the max|cb| partials, the re-rank reduces them per wave.
-// Nothing here is read across calls.
+// Nothing here is read across calls: the buffer may hold anything on entry (0xFF bytes, another call's leftovers).  The exhaustive
+// path, which has no gq_prep_kernel, fills the header with zeros instead; vq_loss_kernel reads loss_part[k] only for the blocks of its
+// own launch.  Field by field and region by region: the docstring of tests/test_gpu_scratch_contracts.py, which checks it.
 constexpr int kAbsmaxParts = 256;
 struct WsHeader {
   int fb_count;                       // rows the candidates could not decide (finished by the in-block scan; exhaustive kernel: its list)

@@ -7,7 +7,9 @@
 // workspace.  A side shorter than 11 is not filtered (pytorch_msssim skips it): template flags FH / FW.  The blocks after those
 // write the next level's 2 x 2 average pool of X and Y (zero padding on the leading edge of an odd side, divided by 4).  In the
 // level that finishes the call the LAST block of each image (a per-image ticket, left zero for the next call) adds the tile sums
-// of every level in a fixed order, so the values are bit-reproducible, and writes SSIM and MS-SSIM as fp32.
+// of every level in a fixed order, so the values are bit-reproducible, zeroes them and writes SSIM and MS-SSIM as fp32.  A call
+// that pooled (MS-SSIM) ends with one launch of ssim_zero_kernel over the pooled planes: the workspace is ALL zero between calls,
+// so the next call may lay it out for any other shape that fits (its tickets must find zeros wherever they land).
 //
 // Numerics: the scaled inputs are formed in fp32 as the reference does ((x + 1) 127.5 or x 255); from there on everything is
 // fp64 -- at the 0..255 scale G(XX) - mu^2 cancels up to ~16 bits in flat regions, which fp32 (the reference) cannot carry.
@@ -29,7 +31,7 @@ struct Params {
   const float *x, *y;        // level 0: B images, NCHW (layout 0) or NHWC (layout 1), fp32, unscaled
   const double *px, *py;     // level >= 1: this level's planes [B * C, H, W] (workspace)
   double *qx, *qy;           // next level's pooled planes (workspace), NULL: no pooling in this launch
-  double *partial;           // tile sums of every level (workspace)
+  double *partial;           // tile sums of every level (workspace; zeroed again by the block that adds them)
   int *ticket;               // [B], zero between calls (workspace)
   float *ssim_out, *ms_out;  // NULL or per-image values at [b * out_stride]
   long out_stride;
@@ -197,11 +199,13 @@ __global__ __launch_bounds__(256) void ssim_level_kernel(const Params p) {
     for (int l = 0; l < nl; ++l) {
       const Level &M = p.lv[l];
       const int nt = M.tiles_x * M.tiles_y;
-      const double *src = p.partial + (M.part + (long)pl * nt) * 2;
+      double *src = p.partial + (M.part + (long)pl * nt) * 2;
       double s = 0.0, cs = 0.0;
       for (int k = tid; k < nt; k += 64) {
         s += __hip_atomic_load(src + 2 * k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         cs += __hip_atomic_load(src + 2 * k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        src[2 * k] = 0.0;                      // zero behind the call, like the ticket: a later call with another B puts its
+        src[2 * k + 1] = 0.0;                  // tickets where these records were
       }
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
@@ -223,6 +227,11 @@ __global__ __launch_bounds__(256) void ssim_level_kernel(const Params p) {
   if (p.ssim_out) p.ssim_out[(long)b * p.out_stride] = (float)(ssim_img / p.C);
   if (p.ms_out) p.ms_out[(long)b * p.out_stride] = p.nan_ms ? __int_as_float(0x7fc00000) : (float)(ms_img / p.C);
   p.ticket[b] = 0;                             // ready for the next call on this workspace
+}
+
+// The pooled planes of a call that ran more than one level, back to zero (grid-stride, 16-byte stores; n2 = pairs of doubles).
+__global__ __launch_bounds__(256) void ssim_zero_kernel(double2 *dst, long n2) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += (long)gridDim.x * 256) dst[i] = double2{0.0, 0.0};
 }
 
 }  // namespace gqssim

@@ -1132,6 +1132,14 @@ int ssim_launch(const float *x, const float *y, int64_t B, int64_t C, int layout
     const int rc = launch(level, grid, dim3(256), 0, st, p);
     if (rc != GQHIP_OK) return rc;
   }
+  if (levels > 1) {
+    // the pooled planes are the only words still set (tickets and tile records are zeroed by the block that finishes an image): one
+    // fill, and the workspace is all zero for whatever shape the next call lays out in it (p1 | p2 are adjacent, an even count)
+    const int64_t pairs = (pl.p1_doubles + pl.p2_doubles) / 2;
+    const int64_t blocks = (pairs + 255) / 256;
+    return launch(gqssim::ssim_zero_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st,
+                  reinterpret_cast<double2 *>(p1), (long)pairs);
+  }
   return GQHIP_OK;
 }
 }  // namespace
