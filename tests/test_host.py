@@ -92,6 +92,203 @@ def test_invalid_arguments_return_status_not_crash():
     assert L.lfq_pack_f32(None, None, None, 4, 16, None) == 1
 
 
+_NAN = float("nan")
+_GN_C = [dict(C=0), dict(C=96), dict(C=130), dict(C=2048), dict(C=512, groups=64), dict(C=512, groups=128)]
+_GN_G = [dict(groups=0), dict(groups=5), dict(groups=128)]
+_WINO2 = [dict(B=-1), dict(H=0), dict(H=1), dict(H=7), dict(W=1), dict(W=7), dict(C=0), dict(C=2), dict(C=6)]
+_WINO4 = [dict(B=-1), dict(H=2), dict(H=6), dict(W=2), dict(W=6), dict(C=0), dict(C=2), dict(C=6)]
+_TILE = [dict(tile=4), dict(tile=3), dict(tile=0), dict(tile=4, H=6), dict(tile=4, W=6), dict(tile=4, H=2)]
+_SCALE = [dict(scale=0.0), dict(scale=-1.0), dict(scale=_NAN)]
+_SCALE_DEV = _SCALE + [dict(scale=0.0, scales_dev=None), dict(scale=_NAN, scales_dev=None), dict(scales_dev=None)]
+_GOUT = [dict(groups_out=0), dict(groups_out=5), dict(groups_out=64), dict(groups_out=1), dict(groups_out=5, stats_out=None)]
+# The conv-stack entry points of csrc/gqhip_unet.hip: entry: (argument names in the order of the C signature, one
+# valid set of the shape / scalar arguments, perturbations of it).  Pointer arguments are those _SIGNATURES declares void *;
+# a perturbation may null some.  The first argument of _EMPTY that an entry point has is the one whose 0 means "nothing to do".
+_EMPTY = ("B", "rows", "tiles", "count", "n_bg")
+_CABI = {
+    "gn_silu_f32": ("x gamma beta pre_bias y B C HW groups eps apply_silu layout stats_ws stream",
+                    dict(B=1, C=128, HW=64, groups=32, eps=1e-6, apply_silu=1, layout=1),
+                    [dict(B=-1), dict(HW=0), dict(HW=6), dict(layout=0), dict(layout=2), dict(layout=0, HW=6), dict(layout=0, C=96),
+                     dict(apply_silu=0), dict(pre_bias=None)] + _GN_C + _GN_G),
+    "add_bias_f32": ("a b bias y B C HW layout stream", dict(B=1, C=128, HW=64, layout=1),
+                     [dict(B=-1), dict(C=0), dict(C=6), dict(HW=0), dict(HW=6), dict(layout=0), dict(layout=2), dict(layout=0, HW=6),
+                      dict(layout=0, C=6), dict(bias=None)]),
+    "add_bias_stats_f32": ("a b bias y B C HW groups stats_out stream", dict(B=1, C=128, HW=64, groups=32),
+                           [dict(B=-1), dict(HW=0), dict(HW=6), dict(bias=None)] + _GN_C + _GN_G),
+    "gn_apply_f32": ("x gamma beta y B C HW groups eps apply_silu stats stream",
+                     dict(B=1, C=128, HW=64, groups=32, eps=1e-6, apply_silu=1),
+                     [dict(B=-1), dict(HW=0), dict(apply_silu=0)] + _GN_C + _GN_G),
+    "gn_stats_f32": ("x pre_bias B C HW groups stats_out stream", dict(B=1, C=128, HW=64, groups=32),
+                     [dict(B=-1), dict(HW=0), dict(pre_bias=None)] + _GN_C + _GN_G),
+    "wino_in_nhwc_f32": ("x V B H W C stream", dict(B=1, H=8, W=8, C=8), _WINO2 + [dict(H=6)]),
+    "wino4_in_nhwc_f32": ("x V B H W C stream", dict(B=1, H=8, W=8, C=8), _WINO4),
+    "wino_out_nhwc_f32": ("M y B H W C mscale stream", dict(B=1, H=8, W=8, C=8, mscale=1.0), _WINO2 + [dict(mscale=0.0)]),
+    "wino4_out_nhwc_f32": ("M y B H W C mscale stream", dict(B=1, H=8, W=8, C=8, mscale=1.0), _WINO4 + [dict(mscale=0.0)]),
+    "wino_in_nhwc_f16x3": ("x V3 B H W C tile scale stream", dict(B=1, H=8, W=8, C=8, tile=2, scale=1.0), _WINO2 + _TILE + _SCALE),
+    "wino_in_nhwc_f16x2": ("x V2 B H W C tile scale stream", dict(B=1, H=8, W=8, C=8, tile=2, scale=1.0), _WINO2 + _TILE + _SCALE),
+    "wino_gemm_f16x2": ("V2 Wf M P tiles Cin Cout stream", dict(P=16, tiles=256, Cin=64, Cout=256),
+                        [dict(P=0), dict(P=1 << 31), dict(tiles=-256), dict(tiles=128), dict(tiles=0x40000000), dict(Cin=0), dict(Cin=16),
+                         dict(Cin=32), dict(Cin=48), dict(Cin=4128), dict(Cout=0), dict(Cout=64), dict(Cout=128), dict(Cout=192),
+                         dict(Cout=4224)]),
+    "wino_in_gn_nhwc_f32": ("x gamma beta pre_bias stats V B H W C groups eps apply_silu stream",
+                            dict(B=1, H=8, W=8, C=128, groups=32, eps=1e-6, apply_silu=1),
+                            _WINO2 + [dict(groups=0), dict(groups=5), dict(groups=64), dict(apply_silu=0), dict(pre_bias=None)]),
+    "wino4_in_gn_nhwc_f32": ("x gamma beta pre_bias stats V B H W C groups eps apply_silu stream",
+                             dict(B=1, H=8, W=8, C=128, groups=32, eps=1e-6, apply_silu=1),
+                             _WINO4 + [dict(groups=0), dict(groups=5), dict(groups=64), dict(apply_silu=0), dict(pre_bias=None)]),
+    "wino_in_gn_nhwc_f16x3": ("x gamma beta pre_bias stats V3 B H W C groups eps apply_silu tile scale stream",
+                              dict(B=1, H=8, W=8, C=128, groups=32, eps=1e-6, apply_silu=1, tile=2, scale=1.0),
+                              _WINO2 + _TILE + _SCALE + [dict(groups=0), dict(groups=5), dict(groups=64), dict(apply_silu=0),
+                                                         dict(apply_silu=0, tile=4)]),
+    "wino_in_gn_nhwc_f16x2": ("x gamma beta pre_bias stats V2 B H W C groups eps apply_silu tile scale stream",
+                              dict(B=1, H=8, W=8, C=128, groups=32, eps=1e-6, apply_silu=1, tile=2, scale=1.0),
+                              _WINO2 + _TILE + _SCALE + [dict(groups=0), dict(groups=5), dict(groups=64), dict(apply_silu=0),
+                                                         dict(apply_silu=0, tile=4)]),
+    "conv3x3_gn_f16x3": ("x gamma beta pre_bias stats_in groups_in eps apply_silu scale Wf bias res y stats_out B H W Cin Cout "
+                         "groups_out mscale stream",
+                         dict(groups_in=32, eps=1e-6, apply_silu=1, scale=1.0, B=1, H=8, W=32, Cin=64, Cout=128, groups_out=32, mscale=1.0),
+                         [dict(B=-1), dict(H=0), dict(H=4), dict(H=12), dict(H=131080), dict(W=16), dict(W=48), dict(Cin=0), dict(Cin=16),
+                          dict(Cin=48), dict(Cin=544), dict(Cout=64), dict(Cout=256), dict(Cout=512), dict(groups_in=0), dict(groups_in=5),
+                          dict(apply_silu=0), dict(apply_silu=0, Cout=256), dict(bias=None, res=None, pre_bias=None)] + _SCALE + _GOUT),
+    "conv1x1_f16x3": ("x pre_bias Wf scales_dev scale mscale bias res y stats_out B HW Cin Cout groups_out stream",
+                      dict(scale=1.0, mscale=1.0, B=1, HW=256, Cin=64, Cout=128, groups_out=32),
+                      [dict(B=-1), dict(HW=0), dict(HW=64), dict(HW=128), dict(HW=384), dict(HW=512), dict(HW=(1 << 24) + 128), dict(Cin=0),
+                       dict(Cin=16), dict(Cin=48), dict(Cout=64), dict(Cout=256), dict(Cout=512), dict(Cout=1024), dict(Cout=1536),
+                       dict(bias=None, res=None, pre_bias=None)] + _SCALE_DEV + _GOUT),
+    "conv1x1_gn_f16x3": ("x gamma beta pre_bias stats_in groups_in eps Wf scale mscale bias res y stats_out B HW Cin Cout groups_out "
+                         "stream",
+                         dict(groups_in=16, eps=1e-6, scale=1.0, mscale=1.0, B=1, HW=256, Cin=64, Cout=128, groups_out=32),
+                         [dict(B=-1), dict(HW=0), dict(HW=64), dict(HW=128), dict(HW=384), dict(Cin=0), dict(Cin=16), dict(Cin=48),
+                          dict(Cin=544), dict(Cout=64), dict(Cout=256), dict(Cout=512), dict(Cout=1024), dict(Cout=1536), dict(groups_in=0),
+                          dict(groups_in=5), dict(groups_in=32)] + _SCALE + _GOUT),
+    "conv1x1_qkv_split_f16x3": ("x gamma beta pre_bias stats_in groups_in eps Wf scale mscale bias Q3 K3 V3 sq sv B L C stream",
+                                dict(groups_in=32, eps=1e-6, scale=1.0, mscale=1.0, sq=1.0, sv=1.0, B=1, L=256, C=128),
+                                [dict(B=-1), dict(L=0), dict(L=64), dict(L=128), dict(L=384), dict(C=0), dict(C=64), dict(C=192), dict(C=512),
+                                 dict(C=640), dict(groups_in=0), dict(groups_in=5), dict(groups_in=64), dict(sq=0.0), dict(sq=_NAN),
+                                 dict(sv=0.0), dict(sv=_NAN), dict(gamma=None, groups_in=0), dict(gamma=None, C=640),
+                                 dict(gamma=None, beta=None, stats_in=None)] + _SCALE),
+    "conv3x3s2_f16x3": ("x Wf scales_dev scale mscale bias y stats_out B Hin Win Cin Cout groups_out stream",
+                        dict(scale=1.0, mscale=1.0, B=1, Hin=16, Win=64, Cin=16, Cout=128, groups_out=32),
+                        [dict(B=-1), dict(Hin=0), dict(Hin=8), dict(Hin=24), dict(Win=32), dict(Win=96), dict(Win=(1 << 20) + 64),
+                         dict(Cin=0), dict(Cin=8), dict(Cin=24), dict(Cout=64), dict(Cout=256), dict(Cout=512), dict(Cout=1024)]
+                        + _SCALE_DEV + _GOUT),
+    "upconv2x_f16x3": ("x Wf scales_dev scale mscale bias y stats_out B H W Cin Cout groups_out stream",
+                       dict(scale=1.0, mscale=1.0, B=1, H=8, W=32, Cin=16, Cout=128, groups_out=32),
+                       [dict(B=-1), dict(H=0), dict(H=4), dict(H=12), dict(H=131080), dict(W=16), dict(W=48), dict(Cin=0), dict(Cin=8),
+                        dict(Cin=24), dict(Cout=64), dict(Cout=256), dict(Cout=512), dict(Cout=1024)] + _SCALE_DEV + _GOUT),
+    "conv3x3_gn_small_f32": ("x gamma beta pre_bias stats_in groups_in eps apply_silu w_ohwi bias y B H W Cin Cout stream",
+                             dict(groups_in=8, eps=1e-6, apply_silu=1, B=1, H=16, W=16, Cin=32, Cout=3),
+                             [dict(B=-1), dict(B=1 << 31), dict(H=8), dict(H=24), dict(W=8), dict(W=24), dict(Cin=0), dict(Cin=16),
+                              dict(Cin=48), dict(Cin=544), dict(Cout=0), dict(Cout=1), dict(Cout=2), dict(Cout=4), dict(Cout=5),
+                              dict(groups_in=0), dict(groups_in=5), dict(apply_silu=0)]),
+    "conv3x3_cin_small_f32": ("x wk bias y stats_out B H W Cin Cout groups_out stream",
+                              dict(B=1, H=8, W=32, Cin=3, Cout=128, groups_out=32),
+                              [dict(B=-1), dict(B=1 << 31), dict(H=4), dict(H=12), dict(W=16), dict(W=48), dict(Cin=0), dict(Cin=1),
+                               dict(Cin=2), dict(Cin=4), dict(Cin=5), dict(Cout=64), dict(Cout=256), dict(groups_out=16), dict(groups_out=0),
+                               dict(groups_out=16, stats_out=None)]),
+    "conv3x3_f32": ("x gamma beta pre_bias stats groups_in eps apply_silu wk bias y B H W Cin Cout stream",
+                    dict(groups_in=8, eps=1e-6, apply_silu=1, B=1, H=4, W=4, Cin=64, Cout=32),
+                    [dict(B=-1), dict(B=1 << 31), dict(H=0), dict(W=0), dict(Cin=4), dict(Cin=8), dict(Cin=24), dict(Cin=128),
+                     dict(Cin=1088), dict(Cout=0), dict(Cout=2), dict(Cout=4), dict(Cout=6), dict(groups_in=0), dict(groups_in=5),
+                     dict(apply_silu=0), dict(gamma=None), dict(beta=None), dict(stats=None), dict(stats=None, Cin=8),
+                     dict(stats=None, Cin=16), dict(stats=None, Cin=32), dict(stats=None, Cin=24), dict(stats=None, Cin=1088),
+                     dict(stats=None, gamma=None, beta=None, groups_in=0)]),
+    "wino_out_res_nhwc_f32": ("M res bias y stats_out B H W C groups tile mscale stream",
+                              dict(B=1, H=8, W=8, C=128, groups=32, tile=2, mscale=1.0),
+                              _WINO2 + _TILE + _GN_C + _GN_G + [dict(C=64), dict(tile=4, C=1024), dict(tile=4, C=512), dict(res=None),
+                                                                dict(res=None, bias=None)]),
+    "attn_split_qkv_f16x3": ("qkv Q3 K3 V3 B L C sq sv stream", dict(B=1, L=64, C=128, sq=1.0, sv=1.0),
+                             [dict(B=-1), dict(L=0), dict(C=0), dict(C=2), dict(C=6), dict(sq=0.0), dict(sq=_NAN), dict(sv=0.0),
+                              dict(sv=_NAN)]),
+    "attn_softmax_split_f16x3": ("S P3 rows L factor stream", dict(rows=4, L=64, factor=1.0),
+                                 [dict(rows=-1), dict(L=0), dict(L=32), dict(L=96), dict(L=128), dict(L=192), dict(L=256), dict(L=1024),
+                                  dict(L=2304), dict(L=4096), dict(L=4160), dict(factor=0.0), dict(factor=_NAN)]),
+    "f16_scales_from_gn_stats": ("stats n_bg amp u_scale scales_out stream", dict(n_bg=32, amp=1.0, u_scale=1.0),
+                                 [dict(n_bg=-1), dict(n_bg=1 << 31), dict(amp=0.0), dict(amp=_NAN), dict(u_scale=0.0), dict(u_scale=_NAN)]),
+    "upsample2x_nhwc_f32": ("x y B H W C stream", dict(B=1, H=4, W=4, C=8),
+                            [dict(B=-1), dict(H=0), dict(W=0), dict(C=0), dict(C=2), dict(C=6)]),
+    "gqhip_checksum_tensors": ("table count sums stream", dict(count=4), [dict(count=-1), dict(count=65535), dict(count=65536)]),
+}
+# the switches an entry point reads per call, with every value its code tells apart (None: unset)
+_CABI_ENV = {"wino_gemm_f16x2": ("GQHIP_WGEMM", (None, "128", "w8", "w4")),
+             "conv1x1_f16x3": ("GQHIP_CONV1_TILE", (None, "128", "256")),
+             "conv1x1_gn_f16x3": ("GQHIP_CONV1_TILE", (None, "128", "256")),
+             "conv1x1_qkv_split_f16x3": ("GQHIP_CONV1_TILE", (None, "128", "256"))}
+
+
+def _cabi_status_cases(L):
+    """Yields (entry, case id, thunk returning the status) over the families of test_conv_stack_cabi_status_table."""
+    fake = 0x10000          # never dereferenced: see the test's docstring
+    for entry, (names, base, perturbations) in _CABI.items():
+        names = names.split()
+        argtypes = L._SIGNATURES[entry][1]
+        assert len(names) == len(argtypes) and set(base) <= set(names), entry
+        ptrs = [n for n, t in zip(names, argtypes) if t is ctypes.c_void_p and n != "stream"]
+        empty = next(n for n in _EMPTY if n in names)
+        fn = getattr(L.lib(), entry)
+
+        def case(cid, scalars, nulls):
+            vals = dict(base, **{p: (None if p in nulls else fake) for p in ptrs}, stream=None)
+            vals.update(scalars)
+            args = [vals[n] for n in names]
+            return entry, cid, (lambda: fn(*args))
+
+        def ident(p):
+            return ",".join("%s=%r" % kv for kv in p.items()) or "base"
+
+        some = [p for p in perturbations if empty not in p]
+        yield case("empty/null", {empty: 0}, ptrs)
+        for p in some:
+            yield case("empty/null/" + ident(p), dict(p, **{empty: 0}), ptrs)
+        for p in [{}] + some:
+            yield case("empty/fake/" + ident(p), dict(p, **{empty: 0}), ())
+        yield case("one/null", {}, ptrs)
+        for n in ptrs:
+            yield case("one/null:" + n, {}, (n,))
+        for p in [{}] + perturbations:
+            yield case("one/fake/" + ident(p), p, ())
+
+
+def _cabi_status_table(L):
+    rows = []
+    for entry, cid, call in _cabi_status_cases(L):
+        knob, values = _CABI_ENV.get(entry, (None, (None,)))
+        for v in values:
+            old = os.environ.pop(knob, None) if knob else None
+            try:
+                if v is not None:
+                    os.environ[knob] = v
+                rows.append([entry, cid if v is None else "%s/%s=%s" % (cid, knob, v), call()])
+            finally:
+                if knob:
+                    os.environ.pop(knob, None)
+                    if old is not None:
+                        os.environ[knob] = old
+    return rows
+
+
+def test_conv_stack_cabi_status_table():
+    """Every conv-stack entry point of csrc/gqhip_unet.hip returns the status tests/golden/convstack_cabi_status.json records for
+    it (recorded with this generator from the library as it was before the host layer's checks were brought together): with
+    nothing to do and all pointers NULL or all set, with every pointer NULL, with each pointer NULL in turn, and with each
+    shape / scalar argument out of its range in turn -- once per value of the GQHIP_WGEMM / GQHIP_CONV1_TILE switches.  Without a
+    device an entry point that gets past its checks returns 3 ("kernel launch failed": no device) and launches nothing, so 0 / 1 /
+    3 tell "empty", "refused" and "would launch" apart -- the ORDER of the checks included.
+    SAFETY: the pointers passed are made up.  They are never dereferenced only because nothing can launch, so this test must
+    never run where a HIP device is present: it skips there, whatever else is asked of it."""
+    if torch.cuda.is_available():
+        pytest.skip("passes made-up pointers: safe only where no kernel can launch")
+    got = _cabi_status_table(_lib())
+    want = json.load(open(os.path.join(G, "convstack_cabi_status.json")))
+    assert len(got) == len(want) > 300 and {e for e, _, _ in got} == set(_CABI) and len(_CABI) == 31
+    assert {s for _, _, s in got} == {0, 1, 3}
+    diff = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not diff, diff[:20]
+    # the 256-pixel tiling forced where only 128-pixel tiles fit stays an invalid argument
+    assert ["conv1x1_f16x3", "one/fake/HW=384/GQHIP_CONV1_TILE=256", 1] in got
+    assert ["conv1x1_f16x3", "one/fake/HW=384", 3] in got
+
+
 def test_no_cpu_fallback():
     L = _lib()
     mu = torch.zeros(4, 16)
@@ -383,6 +580,60 @@ def test_operand_order_weight_layouts_and_gemm_policy():
     assert _lib.own_gemm_fits(36, 16384, 256, 256) and _lib.own_gemm_fits(36, 4096, 512, 512) and _lib.own_gemm_fits(16, 4096, 512, 512)
     assert _lib.own_gemm_fits(16, 16384, 512, 256) and not _lib.own_gemm_fits(36, 1024, 512, 512) and not _lib.own_gemm_fits(16, 256, 512, 512)
     assert set(_lib.FILTER_KINDS) == {"auto", "fp32", "bf16", "mixed"}
+    # every weight builder's bytes and u_scale, and the operand-scale rule, as recorded before the builders shared one weight
+    # split and one scale helper
+    got = _weight_layout_record(_lib)
+    assert got == _WEIGHT_LAYOUT_RECORD, {k: v for k, v in got.items() if _WEIGHT_LAYOUT_RECORD.get(k) != v}
+
+
+def _weight_layout_record(_lib):
+    def sha(t):
+        assert t.dtype == torch.float16 and t.is_contiguous()
+        return hashlib.sha256(t.numpy().tobytes()).hexdigest()
+
+    def randn(seed, *shape):
+        return torch.from_numpy(np.random.RandomState(seed).standard_normal(shape).astype(np.float32))
+
+    rec = {}
+    builders = {"conv3_3x3": lambda w: _lib.conv3_weights_f16(w), "conv3_1x1": lambda w: _lib.conv3_weights_f16(w[:, :, :1, :1]),
+                "conv3s2": lambda w: _lib.conv3s2_weights_f16(w),
+                "upconv": lambda w: _lib.upconv_weights_f16(w[:, :, :2, :2].permute(2, 3, 1, 0).reshape(4 * 32, 128)[:, None, :]
+                                                            .expand(4 * 32, 4, 128).reshape(4 * 32, 4 * 128), 32, 128)}
+    weights = {"randn": randn(11, 128, 32, 3, 3) * 0.07, "zero": torch.zeros(128, 32, 3, 3),
+               "pow2": (randn(12, 128, 32, 3, 3) * 0.1).clamp(-0.25, 0.25)}      # amax == 0; amax an exact power of two
+    assert float(weights["pow2"].abs().max()) == 0.25 and float(weights["pow2"][:, :, :1, :1].abs().max()) == 0.25
+    for wname, w in weights.items():
+        for bname, build in builders.items():
+            wf, us = build(w)
+            rec["%s/%s" % (bname, wname)] = [sha(wf), us]
+    h, l = randn(13, 3, 64, 256).half(), (randn(14, 3, 64, 256) * 2.0 ** -11).half()
+    rec["wino_operand_order"] = [sha(_lib.wino_weights_operand_order(h, l)), None]
+    for bound in (1e-40, 1.0, 3.0, 32768.0, 1e30):
+        rec["attention_scales/%r" % bound] = list(_lib.attention_scales(bound, 2.0 * bound))
+    return rec
+
+
+# [SHA-256 of the operand's bytes, u_scale]; attention_scales: [sq, sv] at (bound, 2 bound)
+_WEIGHT_LAYOUT_RECORD = {
+    "conv3_3x3/randn": ["43918aca79dada65f4b0fad5c9b448606643f7d9cbd585e1750ec7ff8734b2e2", 32768.0],
+    "conv3_1x1/randn": ["4d4241106379cfafb7a60102e90247025b98059f2f1b72ea05b5dbd7b0f49215", 32768.0],
+    "conv3s2/randn": ["312f60907cf0a6d4cb00f4cb905e1e97cae89cea1efa94ee59211b98e51e4cce", 32768.0],
+    "upconv/randn": ["acf470e8174fa39752d94fd7d1e20e2be1a86de8759e03d163a5f5e274d66521", 32768.0],
+    "conv3_3x3/zero": ["8123c216413f82bbaa0339c27a43d9822c2a043e20662b27c97874429b996e9a", 1.0],
+    "conv3_1x1/zero": ["4fe7b59af6de3b665b67788cc2f99892ab827efae3a467342b3bb4e3bc8e5bfe", 1.0],
+    "conv3s2/zero": ["8123c216413f82bbaa0339c27a43d9822c2a043e20662b27c97874429b996e9a", 1.0],
+    "upconv/zero": ["8a39d2abd3999ab73c34db2476849cddf303ce389b35826850f9a700589b4a90", 1.0],
+    "conv3_3x3/pow2": ["74899470ec9cec3d194a990fc9932afce4408499fe258d928c3c9c14983065c8", 65536.0],
+    "conv3_1x1/pow2": ["c0352f2791dd6edce7d4aa473649ff903a253ee501493cf0c067fafb6df69505", 65536.0],
+    "conv3s2/pow2": ["0c6a657bf8560108fa541f3630176768b6f777298cf03dfa81b3658b2d14376f", 65536.0],
+    "upconv/pow2": ["85a22307a6cda80317b634d70092d0c1a17bebc48d1548ec8b24bffd37cefd1b", 65536.0],
+    "wino_operand_order": ["2a1cbc5d740863c3dcd6b573c8d660108842c3b9600386b908ea60acb3f98d53", None],
+    "attention_scales/1e-40": [16384.0, 16384.0],
+    "attention_scales/1.0": [16384.0, 16384.0],
+    "attention_scales/3.0": [8192.0, 4096.0],
+    "attention_scales/32768.0": [1.0, 0.5],
+    "attention_scales/1e+30": [2.5849394142282115e-26, 1.2924697071141057e-26],
+}
 
 
 def test_fp16_fp8_filter_representation_error_is_inside_the_charged_bound():

@@ -28,6 +28,44 @@ thread_local int g_stats_prezeroed = 0;
 inline hipError_t stats_zero(void *p, size_t bytes, hipStream_t st) {
   return g_stats_prezeroed ? hipSuccess : hipMemsetAsync(p, 0, bytes, st);
 }
+
+// What a check helper returns when the arguments are fine and there is something to do; any other value is the entry point's status.
+constexpr int kGo = -1;
+
+// 256-thread blocks over `total` items, `cap` at the most (the kernels stride over the rest)
+dim3 grid1d(long total, long cap) {
+  const long blocks = (total + 255) / 256;
+  return dim3((unsigned)(blocks > cap ? cap : blocks));
+}
+
+// slabs of ~16 pixels per thread for the NHWC GroupNorm kernels (256 / (C / 4) pixel lanes per block)
+int nhwc_slabs(int64_t C, int64_t HW) {
+  const int lanes = (int)(256 / (C / 4));
+  int slabs = (int)((HW + (int64_t)lanes * 16 - 1) / ((int64_t)lanes * 16));
+  if (slabs > 1024) slabs = 1024;
+  return slabs < 1 ? 1 : slabs;
+}
+
+// The checks of the GroupNorm entry points, in this order: sizes, nothing to do, pointers, and for NHWC the kernels' thread <->
+// channel-quad mapping: cpg % 4 == 0, (C/4) | 256, <= 64 groups.
+int gn_check(int64_t B, int64_t C, int64_t HW, int64_t groups, bool ptrs_ok, bool nhwc) {
+  if (B < 0 || C < 1 || HW < 1 || groups < 1 || C % groups != 0) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0) return GQHIP_OK;
+  if (!ptrs_ok) return GQHIP_ERR_INVALID_ARG;
+  if (nhwc && ((C / groups) % 4 != 0 || 256 % (C / 4) != 0 || groups > 64)) return GQHIP_ERR_INVALID_ARG;
+  return kGo;
+}
+
+// Winograd F(tile x tile, 3x3) on NHWC: whole tiles, channel quads
+bool wino_shape_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t tile) {
+  return (tile == 2 || tile == 4) && B >= 0 && H >= tile && W >= tile && H % tile == 0 && W % tile == 0 && C >= 4 && C % 4 == 0;
+}
+
+bool one_of(int64_t v, std::initializer_list<int64_t> values) {
+  for (int64_t w : values)
+    if (v == w) return true;
+  return false;
+}
 }  // namespace
 
 extern "C" {
@@ -40,19 +78,13 @@ int gqhip_stats_prezeroed(int on) {
 int gn_silu_f32(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null, float *y,
                 int64_t B, int64_t C, int64_t HW, int64_t groups, double eps, int apply_silu, int layout,
                 int64_t *stats_ws, void *stream) {
-  if (B < 0 || C < 1 || HW < 1 || groups < 1 || C % groups != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !gamma || !beta || !y || !stats_ws) return GQHIP_ERR_INVALID_ARG;
+  const bool nhwc = layout == GQHIP_LAYOUT_NHWC;
+  if (int rc = gn_check(B, C, HW, groups, x && gamma && beta && y && stats_ws, nhwc); rc != kGo) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t bg = B * groups, cpg = C / groups, chunk = cpg * HW;
-  if (layout == GQHIP_LAYOUT_NHWC) {
-    // thread <-> channel-quad mapping needs cpg % 4 == 0, (C/4) | 256, <= 64 groups
-    if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
+  if (nhwc) {
     if (stats_zero(stats_ws, sizeof(int64_t) * kStatWords * bg, st) != hipSuccess) return check_launch();
-    const int lanes = (int)(256 / (C / 4));
-    int slabs = (int)((HW + (int64_t)lanes * 16 - 1) / ((int64_t)lanes * 16));   // ~16 pixels per thread
-    if (slabs > 1024) slabs = 1024;
-    if (slabs < 1) slabs = 1;
+    const int slabs = nhwc_slabs(C, HW);
     hipLaunchKernelGGL(gn_stats_nhwc_kernel, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x, pre_bias_or_null,
                        stats_ws, (int)C, (long)HW, (int)cpg, slabs);
     int rc = check_launch();
@@ -83,36 +115,24 @@ int add_bias_f32(const float *a, const float *b, const float *bias_or_null, floa
   if (B == 0) return GQHIP_OK;
   if (!a || !b || !y) return GQHIP_ERR_INVALID_ARG;
   const long total4 = (long)(B * C * HW / 4);
-  long blocks = (total4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
+  const dim3 grid = grid1d(total4, 8192);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (layout == GQHIP_LAYOUT_NHWC) {
     if (C % 4 != 0) return GQHIP_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(add_bias_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, bias_or_null, y, (int)C,
+    hipLaunchKernelGGL(add_bias_nhwc_kernel, grid, dim3(256), 0, st, a, b, bias_or_null, y, (int)C,
                        total4);
   } else {
     if (layout != GQHIP_LAYOUT_NCHW || HW % 4 != 0) return GQHIP_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(add_bias_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, bias_or_null, y, (int)C,
+    hipLaunchKernelGGL(add_bias_kernel, grid, dim3(256), 0, st, a, b, bias_or_null, y, (int)C,
                        (long)HW, total4);
   }
   return check_launch();
 }
 
-// slabs of ~16 pixels per thread, as gn_silu_f32's NHWC path
-static int nhwc_slabs(int64_t C, int64_t HW) {
-  const int lanes = (int)(256 / (C / 4));
-  int slabs = (int)((HW + (int64_t)lanes * 16 - 1) / ((int64_t)lanes * 16));
-  if (slabs > 1024) slabs = 1024;
-  return slabs < 1 ? 1 : slabs;
-}
-
 int add_bias_stats_f32(const float *a, const float *b, const float *bias_or_null, float *y, int64_t B, int64_t C,
                        int64_t HW, int64_t groups, int64_t *stats_out, void *stream) {
-  if (B < 0 || C < 1 || HW < 1 || groups < 1 || C % groups != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!a || !b || !y || !stats_out) return GQHIP_ERR_INVALID_ARG;
+  if (int rc = gn_check(B, C, HW, groups, a && b && y && stats_out, true); rc != kGo) return rc;
   const int64_t cpg = C / groups;
-  if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups, st) != hipSuccess) return check_launch();
   const int slabs = nhwc_slabs(C, HW);
@@ -122,55 +142,43 @@ int add_bias_stats_f32(const float *a, const float *b, const float *bias_or_null
 
 int gn_apply_f32(const float *x, const float *gamma, const float *beta, float *y, int64_t B, int64_t C, int64_t HW,
                  int64_t groups, double eps, int apply_silu, const int64_t *stats, void *stream) {
-  if (B < 0 || C < 1 || HW < 1 || groups < 1 || C % groups != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !gamma || !beta || !y || !stats) return GQHIP_ERR_INVALID_ARG;
+  if (int rc = gn_check(B, C, HW, groups, x && gamma && beta && y && stats, true); rc != kGo) return rc;
   const int64_t cpg = C / groups;
-  if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int slabs = nhwc_slabs(C, HW);
   return launch(apply_silu ? gn_apply_nhwc_kernel<1> : gn_apply_nhwc_kernel<0>, dim3((unsigned)(B * slabs)), dim3(256), 0, st, x,
                 gamma, beta, y, stats, nullptr, (int)C, (long)HW, (int)cpg, eps, slabs);
 }
 
-int wino_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
-  if (B < 0 || H < 2 || W < 2 || H % 2 || W % 2 || C < 4 || C % 4 != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !V) return GQHIP_ERR_INVALID_ARG;
-  const long tiles = (long)(B * (H / 2) * (W / 2)), total = tiles * (C / 4);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(wino_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
-}
-
-static int wino_in_f16_impl(int vm, const float *x, void *V, int64_t B, int64_t H, int64_t W, int64_t C, int tile,
-                            float scale, void *stream) {
-  if ((tile != 2 && tile != 4) || B < 0 || H < tile || W < tile || H % tile || W % tile || C < 4 || C % 4 != 0 ||
-      !(scale > 0.f))
-    return GQHIP_ERR_INVALID_ARG;
+// The plain input transforms: vm = 0 fp32 V, 1 the three-plane fp16 operand, 2 the [h | l] operand (gq_unet_aux.h)
+static int wino_in_impl(int vm, const float *x, void *V, int64_t B, int64_t H, int64_t W, int64_t C, int tile, float scale,
+                        void *stream) {
+  if (!wino_shape_ok(B, H, W, C, tile) || !(scale > 0.f)) return GQHIP_ERR_INVALID_ARG;
   if (B == 0) return GQHIP_OK;
   if (!x || !V) return GQHIP_ERR_INVALID_ARG;
   const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / 4);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-#define GQ_WIN(K, VM) \
-  hipLaunchKernelGGL(K<VM>, dim3((unsigned)blocks), dim3(256), 0, st, x, V, (int)H, (int)W, (int)(C / 4), tiles, total, scale)
-  if (tile == 4) { if (vm == 2) GQ_WIN(wino4_in_nhwc_kernel, 2); else GQ_WIN(wino4_in_nhwc_kernel, 1); }
-  else { if (vm == 2) GQ_WIN(wino_in_nhwc_kernel, 2); else GQ_WIN(wino_in_nhwc_kernel, 1); }
-#undef GQ_WIN
-  return check_launch();
+  const auto kernel = tile == 4 ? (vm == 2 ? wino4_in_nhwc_kernel<2> : vm == 1 ? wino4_in_nhwc_kernel<1> : wino4_in_nhwc_kernel<0>)
+                                : (vm == 2 ? wino_in_nhwc_kernel<2> : vm == 1 ? wino_in_nhwc_kernel<1> : wino_in_nhwc_kernel<0>);
+  return launch(kernel, grid1d(total, 16384), dim3(256), 0, static_cast<hipStream_t>(stream), x, V, (int)H, (int)W, (int)(C / 4),
+                tiles, total, scale);
+}
+
+int wino_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
+  return wino_in_impl(0, x, V, B, H, W, C, 2, 1.0f, stream);
+}
+
+int wino4_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
+  return wino_in_impl(0, x, V, B, H, W, C, 4, 1.0f, stream);
 }
 
 int wino_in_nhwc_f16x3(const float *x, void *V3, int64_t B, int64_t H, int64_t W, int64_t C, int tile, float scale,
                        void *stream) {
-  return wino_in_f16_impl(1, x, V3, B, H, W, C, tile, scale, stream);
+  return wino_in_impl(1, x, V3, B, H, W, C, tile, scale, stream);
 }
 
 int wino_in_nhwc_f16x2(const float *x, void *V2, int64_t B, int64_t H, int64_t W, int64_t C, int tile, float scale,
                        void *stream) {
-  return wino_in_f16_impl(2, x, V2, B, H, W, C, tile, scale, stream);
+  return wino_in_impl(2, x, V2, B, H, W, C, tile, scale, stream);
 }
 
 // The tiling of wino_gemm_f16x2 (gq_wino_gemm.h).  The 256-column tilings need Cin % 64 == 0 and Cout % 256 == 0; every other
@@ -178,14 +186,13 @@ int wino_in_nhwc_f16x2(const float *x, void *V2, int64_t B, int64_t H, int64_t W
 // block per CU) in one process on MI355X it was the faster of each adjacent pair of windows at all six shapes of the step, by
 // 4-16 % in the median, at Cin = 256 as much as at Cin = 512 (profiles/r12/gemm_ab.txt -- one session with short windows; its
 // caveats are stated there).
-// GQHIP_WGEMM forces one (A/B, tests): 128 = 256 x 128, w8 = 256 x 256, w4 = 128 x 256; read per call, so one process can
+// GQHIP_WGEMM forces one (A/B, tests): 128 = 256 x 128, w8 = 256 x 256, anything else (w4) = 128 x 256; read per call, so one process can
 // compare them.  A forced 256-column tiling still yields to 256 x 128 where the shape does not allow it.
 enum class WinoGemmTiling { k256x128, k256x256, k128x256 };
 static WinoGemmTiling wino_gemm_tiling(int64_t Cin, int64_t Cout) {
   const char *knob = getenv("GQHIP_WGEMM");
   if (Cin % 64 != 0 || Cout % 256 != 0 || (knob && !strcmp(knob, "128"))) return WinoGemmTiling::k256x128;
   if (knob && !strcmp(knob, "w8")) return WinoGemmTiling::k256x256;
-  if (knob && !strcmp(knob, "w4")) return WinoGemmTiling::k128x256;
   return WinoGemmTiling::k128x256;
 }
 
@@ -216,11 +223,8 @@ int wino_gemm_f16x2(const void *V2, const void *Wf, float *M, int64_t P, int64_t
 
 int gn_stats_f32(const float *x, const float *pre_bias_or_null, int64_t B, int64_t C, int64_t HW, int64_t groups,
                  int64_t *stats_out, void *stream) {
-  if (B < 0 || C < 1 || HW < 1 || groups < 1 || C % groups != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !stats_out) return GQHIP_ERR_INVALID_ARG;
+  if (int rc = gn_check(B, C, HW, groups, x && stats_out, true); rc != kGo) return rc;
   const int64_t cpg = C / groups;
-  if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups, st) != hipSuccess) return check_launch();
   const int slabs = nhwc_slabs(C, HW);
@@ -231,20 +235,18 @@ int gn_stats_f32(const float *x, const float *pre_bias_or_null, int64_t B, int64
 static int wino_in_gn_impl(int tile, int f16, const float *x, const float *gamma, const float *beta,
                            const float *pre_bias_or_null, const int64_t *stats, void *V, int64_t B, int64_t H, int64_t W,
                            int64_t C, int64_t groups, double eps, int apply_silu, float scale, void *stream) {
-  if (B < 0 || H < tile || W < tile || H % tile || W % tile || C < 4 || C % 4 != 0 || groups < 1 || C % groups != 0 ||
-      (C / groups) % 4 != 0 || !(scale > 0.f))
+  if (!wino_shape_ok(B, H, W, C, tile) || groups < 1 || C % groups != 0 || (C / groups) % 4 != 0 || !(scale > 0.f))
     return GQHIP_ERR_INVALID_ARG;
   if (B == 0) return GQHIP_OK;
   if (!x || !gamma || !beta || !stats || !V) return GQHIP_ERR_INVALID_ARG;
   // F(4x4,3x3) on an fp16 operand: two channels per thread (register pressure: see the kernel); 4 otherwise
   const int vw = (tile == 4 && f16 != 0) ? 2 : 4;
   const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / vw);
-  long blocks = (total + 255) / 256;
-  if (blocks > 32768) blocks = 32768;
+  const dim3 grid = grid1d(total, 32768);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define GQ_WGN(K, ...)                                                                                                  \
-  hipLaunchKernelGGL((K<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, st, x, gamma, beta, pre_bias_or_null, stats, \
-                     V, (int)H, (int)W, (int)(C / vw), (int)(C / groups), eps, tiles, total, scale)
+#define GQ_WGN(K, ...)                                                                                                   \
+  hipLaunchKernelGGL((K<__VA_ARGS__>), grid, dim3(256), 0, st, x, gamma, beta, pre_bias_or_null, stats, V, (int)H, (int)W, \
+                     (int)(C / vw), (int)(C / groups), eps, tiles, total, scale)
   if (tile == 4) {
     if (apply_silu) {
       if (f16 == 2) GQ_WGN(wino4_in_gn_nhwc_kernel, 1, 2, 2); else if (f16 == 1) GQ_WGN(wino4_in_gn_nhwc_kernel, 1, 1, 2);
@@ -281,7 +283,6 @@ int wino4_in_gn_nhwc_f32(const float *x, const float *gamma, const float *beta, 
 int wino_in_gn_nhwc_f16x3(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
                           const int64_t *stats, void *V3, int64_t B, int64_t H, int64_t W, int64_t C, int64_t groups,
                           double eps, int apply_silu, int tile, float scale, void *stream) {
-  if (tile != 2 && tile != 4) return GQHIP_ERR_INVALID_ARG;
   return wino_in_gn_impl(tile, 1, x, gamma, beta, pre_bias_or_null, stats, V3, B, H, W, C, groups, eps, apply_silu, scale,
                          stream);
 }
@@ -289,7 +290,6 @@ int wino_in_gn_nhwc_f16x3(const float *x, const float *gamma, const float *beta,
 int wino_in_gn_nhwc_f16x2(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
                           const int64_t *stats, void *V2, int64_t B, int64_t H, int64_t W, int64_t C, int64_t groups,
                           double eps, int apply_silu, int tile, float scale, void *stream) {
-  if (tile != 2 && tile != 4) return GQHIP_ERR_INVALID_ARG;
   return wino_in_gn_impl(tile, 2, x, gamma, beta, pre_bias_or_null, stats, V2, B, H, W, C, groups, eps, apply_silu, scale,
                          stream);
 }
@@ -300,38 +300,60 @@ static bool conv3_groups_ok(int64_t Cout, int64_t groups_out) {
   return cpg % 4 == 0 && 128 % cpg == 0;
 }
 
-static void conv3_fill(Conv3Params &cp, const void *Wf, const float *bias, const float *res, float *y, int64_t *stats, int64_t B,
-                       int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t groups_out, float mscale) {
+// an operand scale from the host, or the device's (scales_dev: f16_scales_from_gn_stats)
+static bool scale_ok(const float *scales_dev_or_null, float scale) { return scales_dev_or_null || scale > 0.f; }
+
+// What every direct convolution does between its shape checks and its launch, in this order: the groups of the statistics it
+// is to leave (groups_ok only counts when there are statistics; the caller evaluates it either way, so it must be safe for any
+// groups_out: conv3_groups_ok refuses groups_out < 1 before it divides), nothing to do, pointers -- conv_checks -- and then
+// the records are zeroed.  conv1_launch settles its tiling between the two.
+static int conv_checks(int64_t B, bool ptrs_ok, const int64_t *stats_out, bool groups_ok) {
+  if (stats_out && !groups_ok) return GQHIP_ERR_INVALID_ARG;
+  if (B == 0) return GQHIP_OK;
+  return ptrs_ok ? kGo : GQHIP_ERR_INVALID_ARG;
+}
+
+static int conv_stats_zero(int64_t *stats_out, int64_t records, hipStream_t st) {
+  if (stats_out && stats_zero(stats_out, sizeof(int64_t) * kStatWords * records, st) != hipSuccess) return check_launch();
+  return kGo;
+}
+
+static int conv_prologue(int64_t B, bool ptrs_ok, int64_t *stats_out, bool groups_ok, int64_t groups_out, hipStream_t st) {
+  const int rc = conv_checks(B, ptrs_ok, stats_out, groups_ok);
+  return rc != kGo ? rc : conv_stats_zero(stats_out, B * groups_out, st);
+}
+
+// Fills cp for output tiles of tile_h x kC3TW pixels and returns the grid: every XCD walks its share of the tiles per column block.
+static dim3 conv3_fill(Conv3Params &cp, const void *Wf, const float *bias, const float *res, float *y, int64_t *stats, int64_t B,
+                       int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t groups_out, float mscale, int tile_h = kC3TH) {
   cp.Wf = static_cast<const _Float16 *>(Wf);
   cp.bias = bias; cp.res = res; cp.y = y; cp.stats = stats;
   cp.H = (int)H; cp.W = (int)W; cp.nch = (int)(Cin / 16); cp.cpg = stats ? (int)(Cout / groups_out) : 4;
   cp.cout = (int)Cout; cp.nnb = (int)(Cout / 128);
-  cp.tiles_x = (int)(W / kC3TW); cp.tiles_y = (int)(H / kC3TH);
+  cp.tiles_x = (int)(W / kC3TW); cp.tiles_y = (int)(H / tile_h);
   cp.ntiles = (long)B * cp.tiles_x * cp.tiles_y;
   cp.tiles_per_xcd = (cp.ntiles + 7) / 8;
   cp.mscale = mscale;
+  return dim3((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
 }
 
 int conv3x3_gn_f16x3(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
                      const int64_t *stats_in, int64_t groups_in, double eps, int apply_silu, float scale, const void *Wf,
                      const float *bias_or_null, const float *res_or_null, float *y, int64_t *stats_out_or_null, int64_t B,
                      int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t groups_out, float mscale, void *stream) {
-  if (B < 0 || H < kC3TH || W < kC3TW || H % kC3TH || W % kC3TW || Cin < 32 || Cin % 32 != 0 || Cin > 512 || (Cout != 128 && Cout != 256) ||
+  if (B < 0 || H < kC3TH || W < kC3TW || H % kC3TH || W % kC3TW || Cin < 32 || Cin % 32 != 0 || Cin > 512 || !one_of(Cout, {128, 256}) ||
       H * W > (1 << 22) || groups_in < 1 || Cin % groups_in != 0 || !(scale > 0.f))
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !gamma || !beta || !stats_in || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out_or_null && stats_zero(stats_out_or_null, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess)
-    return check_launch();
+  if (int rc = conv_prologue(B, x && gamma && beta && stats_in && Wf && y, stats_out_or_null, conv3_groups_ok(Cout, groups_out),
+                             groups_out, st);
+      rc != kGo)
+    return rc;
   Conv3GnParams gp{};
-  Conv3Params &cp = gp.c;
-  cp.Xs = nullptr;
-  conv3_fill(cp, Wf, bias_or_null, res_or_null, y, stats_out_or_null, B, H, W, Cin, Cout, groups_out, mscale);
+  gp.c.Xs = nullptr;
+  const dim3 grid = conv3_fill(gp.c, Wf, bias_or_null, res_or_null, y, stats_out_or_null, B, H, W, Cin, Cout, groups_out, mscale);
   gp.x = x; gp.gamma = gamma; gp.beta = beta; gp.pre_bias = pre_bias_or_null; gp.stats_in = stats_in;
   gp.cin = (int)Cin; gp.cpg_in = (int)(Cin / groups_in); gp.eps = eps; gp.scale = scale;
-  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
   static const int env_dyn = getenv("GQHIP_C3_DYNLDS") ? atoi(getenv("GQHIP_C3_DYNLDS")) : 0;   // diagnostic: extra LDS -> one block per CU
   if (Cout == 128) {
     if (apply_silu) hipLaunchKernelGGL((conv3x3_gn_f16x3_kernel<1, 128>), grid, dim3(256), env_dyn, st, gp);
@@ -390,22 +412,19 @@ static int conv1_tile_rows(int64_t B, int64_t HW, int64_t Cout) {
   } while (0)
 
 // One launch path for the three entry points below.  gp: x, pre_bias, scales, and -- for the GroupNorm variant -- gamma, beta,
-// stats_in, cpg_in, eps, and -- for the split epilogue -- Q3, K3, V3, sq, sv already filled in; gp.c filled here.
-static int conv1_launch(Conv1Params &gp, const void *Wf, float mscale, const float *bias, const float *res, float *y,
+// stats_in, cpg_in, eps, and -- for the split epilogue -- Q3, K3, V3, sq, sv already filled in; gp.c filled here.  ptrs_ok: the entry
+// point's required pointers are there (checked here, after the groups of the statistics and "nothing to do": conv_checks).
+static int conv1_launch(Conv1Params &gp, bool ptrs_ok, const void *Wf, float mscale, const float *bias, const float *res, float *y,
                         int64_t *stats_out, int64_t B, int64_t HW, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
   const bool split = gp.Q3 != nullptr, gn = gp.gamma != nullptr;
+  if (int rc = conv_checks(B, ptrs_ok, stats_out, conv3_groups_ok(Cout, groups_out)); rc != kGo) return rc;
   const int rows = conv1_tile_rows(B, HW, Cout);
   if (rows == 0) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out && stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess) return check_launch();
-  Conv3Params &cp = gp.c;
-  conv3_fill(cp, Wf, bias, res, y, stats_out, B, HW / 32, 32, Cin, Cout, groups_out, mscale);
-  cp.nch = (int)(Cin / 16);
-  cp.tiles_x = 1; cp.tiles_y = (int)(HW / (64 * rows));
-  cp.ntiles = (long)B * cp.tiles_y;
-  cp.tiles_per_xcd = (cp.ntiles + 7) / 8;
+  if (int rc = conv_stats_zero(stats_out, B * groups_out, st); rc != kGo) return rc;
+  // the pixels as an image of HW / 32 rows of 32: a tile of 64 * rows pixels is 2 * rows of them
+  const dim3 grid = conv3_fill(gp.c, Wf, bias, res, y, stats_out, B, HW / 32, 32, Cin, Cout, groups_out, mscale, 2 * rows);
   gp.cin = (int)Cin;
-  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
   if (rows == 4) {
     if (gn) GQ_C1_LAUNCH(4, 1); else GQ_C1_LAUNCH(4, 0);
   } else {
@@ -426,31 +445,25 @@ static bool conv1_gn_ok(int64_t Cin, int64_t groups_in) {
 int conv1x1_f16x3(const float *x, const float *pre_bias_or_null, const void *Wf, const float *scales_dev_or_null, float scale,
                   float mscale, const float *bias_or_null, const float *res_or_null, float *y, int64_t *stats_out_or_null, int64_t B, int64_t HW,
                   int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
-  if (!conv1_shape_ok(B, HW, Cin) || (Cout != 128 && Cout != 256 && Cout != 512 && Cout != 1536) ||
-      (!scales_dev_or_null && !(scale > 0.f)))
+  if (!conv1_shape_ok(B, HW, Cin) || !one_of(Cout, {128, 256, 512, 1536}) || !scale_ok(scales_dev_or_null, scale))
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
   Conv1Params gp{};
   gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scales_dev = scales_dev_or_null; gp.scale = scale;
-  return conv1_launch(gp, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B, HW, Cin, Cout, groups_out, stream);
+  return conv1_launch(gp, x && Wf && y, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B, HW, Cin, Cout, groups_out,
+                      stream);
 }
 
 int conv1x1_gn_f16x3(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
                      const int64_t *stats_in, int64_t groups_in, double eps, const void *Wf, float scale, float mscale,
                      const float *bias_or_null, const float *res_or_null, float *y, int64_t *stats_out_or_null, int64_t B,
                      int64_t HW, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
-  if (!conv1_shape_ok(B, HW, Cin) || !conv1_gn_ok(Cin, groups_in) || (Cout != 128 && Cout != 256 && Cout != 512 && Cout != 1536) ||
-      !(scale > 0.f))
+  if (!conv1_shape_ok(B, HW, Cin) || !conv1_gn_ok(Cin, groups_in) || !one_of(Cout, {128, 256, 512, 1536}) || !(scale > 0.f))
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !gamma || !beta || !stats_in || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
   Conv1Params gp{};
   gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scale = scale;
   gp.gamma = gamma; gp.beta = beta; gp.stats_in = stats_in; gp.cpg_in = (int)(Cin / groups_in); gp.eps = eps;
-  return conv1_launch(gp, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B, HW, Cin, Cout, groups_out, stream);
+  return conv1_launch(gp, x && gamma && beta && stats_in && Wf && y, Wf, mscale, bias_or_null, res_or_null, y, stats_out_or_null, B,
+                      HW, Cin, Cout, groups_out, stream);
 }
 
 int conv1x1_qkv_split_f16x3(const float *x, const float *gamma_or_null, const float *beta_or_null, const float *pre_bias_or_null,
@@ -460,8 +473,7 @@ int conv1x1_qkv_split_f16x3(const float *x, const float *gamma_or_null, const fl
   if (!conv1_shape_ok(B, L, C) || C % 128 != 0 || !(scale > 0.f) || !(sq > 0.f) || !(sv > 0.f))
     return GQHIP_ERR_INVALID_ARG;
   if (gamma_or_null && !conv1_gn_ok(C, groups_in)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !Wf || !Q3 || !K3 || !V3 || (gamma_or_null && (!beta_or_null || !stats_in_or_null))) return GQHIP_ERR_INVALID_ARG;
+  const bool ptrs_ok = x && Wf && Q3 && K3 && V3 && (!gamma_or_null || (beta_or_null && stats_in_or_null));
   Conv1Params gp{};
   gp.x = x; gp.pre_bias = pre_bias_or_null; gp.scale = scale;
   if (gamma_or_null) {
@@ -469,30 +481,32 @@ int conv1x1_qkv_split_f16x3(const float *x, const float *gamma_or_null, const fl
   }
   gp.Q3 = static_cast<_Float16 *>(Q3); gp.K3 = static_cast<_Float16 *>(K3); gp.V3 = static_cast<_Float16 *>(V3);
   gp.sq = sq; gp.sv = sv;
-  return conv1_launch(gp, Wf, mscale, bias_or_null, nullptr, nullptr, nullptr, B, L, C, 3 * C, 1, stream);
+  return conv1_launch(gp, ptrs_ok, Wf, mscale, bias_or_null, nullptr, nullptr, nullptr, B, L, C, 3 * C, 1, stream);
 }
+
+// the kernels instantiated for 128 | 256 | 512 output channels (conv3x3s2_f16x3, upconv2x_f16x3)
+#define GQ_COUT3_LAUNCH(K)                                                                  \
+  do {                                                                                      \
+    if (Cout == 128) hipLaunchKernelGGL(K<128>, grid, dim3(256), 0, st, gp);                \
+    else if (Cout == 256) hipLaunchKernelGGL(K<256>, grid, dim3(256), 0, st, gp);           \
+    else hipLaunchKernelGGL(K<512>, grid, dim3(256), 0, st, gp);                            \
+  } while (0)
 
 int conv3x3s2_f16x3(const float *x, const void *Wf, const float *scales_dev_or_null, float scale, float mscale,
                     const float *bias_or_null, float *y, int64_t *stats_out_or_null, int64_t B, int64_t Hin, int64_t Win,
                     int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
   // output H = Hin / 2, W = Win / 2 (the reference pads one zero row / column at the bottom / right: unet.py:92-95)
   if (B < 0 || Hin < 2 * kC3TH || Win < 2 * kC3TW || Hin % (2 * kC3TH) || Win % (2 * kC3TW) || Cin < 16 || Cin % 16 != 0 ||
-      (Cout != 128 && Cout != 256 && Cout != 512) || Hin * Win > (1 << 24) || (!scales_dev_or_null && !(scale > 0.f)))
+      !one_of(Cout, {128, 256, 512}) || Hin * Win > (1 << 24) || !scale_ok(scales_dev_or_null, scale))
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out_or_null && stats_zero(stats_out_or_null, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess)
-    return check_launch();
+  if (int rc = conv_prologue(B, x && Wf && y, stats_out_or_null, conv3_groups_ok(Cout, groups_out), groups_out, st); rc != kGo)
+    return rc;
   Conv3S2Params gp{};
-  Conv3Params &cp = gp.c;
-  conv3_fill(cp, Wf, bias_or_null, nullptr, y, stats_out_or_null, B, Hin / 2, Win / 2, Cin, Cout, groups_out, mscale);
+  const dim3 grid = conv3_fill(gp.c, Wf, bias_or_null, nullptr, y, stats_out_or_null, B, Hin / 2, Win / 2, Cin, Cout, groups_out,
+                               mscale);
   gp.x = x; gp.scales_dev = scales_dev_or_null; gp.scale = scale; gp.cin = (int)Cin; gp.Hin = (int)Hin; gp.Win = (int)Win;
-  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb));
-  if (Cout == 128) hipLaunchKernelGGL(conv3x3s2_f16x3_kernel<128>, grid, dim3(256), 0, st, gp);
-  else if (Cout == 256) hipLaunchKernelGGL(conv3x3s2_f16x3_kernel<256>, grid, dim3(256), 0, st, gp);
-  else hipLaunchKernelGGL(conv3x3s2_f16x3_kernel<512>, grid, dim3(256), 0, st, gp);
+  GQ_COUT3_LAUNCH(conv3x3s2_f16x3_kernel);
   return check_launch();
 }
 
@@ -500,24 +514,20 @@ int upconv2x_f16x3(const float *x, const void *Wf, const float *scales_dev_or_nu
                    const float *bias_or_null, float *y, int64_t *stats_out_or_null, int64_t B, int64_t H, int64_t W,
                    int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
   if (B < 0 || H < kC3TH || W < kC3TW || H % kC3TH || W % kC3TW || Cin < 16 || Cin % 16 != 0 ||
-      (Cout != 128 && Cout != 256 && Cout != 512) || H * W > (1 << 22) || (!scales_dev_or_null && !(scale > 0.f)))
+      !one_of(Cout, {128, 256, 512}) || H * W > (1 << 22) || !scale_ok(scales_dev_or_null, scale))
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && !conv3_groups_ok(Cout, groups_out)) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !Wf || !y) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out_or_null && stats_zero(stats_out_or_null, sizeof(int64_t) * kStatWords * B * groups_out, st) != hipSuccess)
-    return check_launch();
+  if (int rc = conv_prologue(B, x && Wf && y, stats_out_or_null, conv3_groups_ok(Cout, groups_out), groups_out, st); rc != kGo)
+    return rc;
   Upconv2Params gp{};
-  Conv3Params &cp = gp.c;
-  conv3_fill(cp, Wf, bias_or_null, nullptr, y, stats_out_or_null, B, H, W, Cin, Cout, groups_out, mscale);
+  dim3 grid = conv3_fill(gp.c, Wf, bias_or_null, nullptr, y, stats_out_or_null, B, H, W, Cin, Cout, groups_out, mscale);
+  grid.y = 4;   // the four sub-pixel phases
   gp.x = x; gp.scales_dev = scales_dev_or_null; gp.scale = scale; gp.cin = (int)Cin;
-  const dim3 grid((unsigned)(8 * cp.tiles_per_xcd * cp.nnb), 4);
-  if (Cout == 128) hipLaunchKernelGGL(upconv2x_f16x3_kernel<128>, grid, dim3(256), 0, st, gp);
-  else if (Cout == 256) hipLaunchKernelGGL(upconv2x_f16x3_kernel<256>, grid, dim3(256), 0, st, gp);
-  else hipLaunchKernelGGL(upconv2x_f16x3_kernel<512>, grid, dim3(256), 0, st, gp);
+  GQ_COUT3_LAUNCH(upconv2x_f16x3_kernel);
   return check_launch();
 }
+
+#undef GQ_COUT3_LAUNCH
 
 int conv3x3_gn_small_f32(const float *x, const float *gamma, const float *beta, const float *pre_bias_or_null,
                          const int64_t *stats_in, int64_t groups_in, double eps, int apply_silu, const float *w_ohwi,
@@ -550,12 +560,8 @@ int conv3x3_cin_small_f32(const float *x, const float *wk, const float *bias_or_
                           int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t groups_out, void *stream) {
   if (B < 0 || H < 8 || W < 32 || H % 8 || W % 32 || Cin < 1 || Cin > 4 || Cout != 128 || B * (H / 8) * (W / 32) > 0x7fffffffL)
     return GQHIP_ERR_INVALID_ARG;
-  if (stats_out_or_null && groups_out != 32) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !wk || !y) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (stats_out_or_null && stats_zero(stats_out_or_null, sizeof(int64_t) * kStatWords * B * 32, st) != hipSuccess)
-    return check_launch();
+  if (int rc = conv_prologue(B, x && wk && y, stats_out_or_null, groups_out == 32, 32, st); rc != kGo) return rc;
   ConvInParams cp{};
   cp.x = x; cp.wk = wk; cp.bias = bias_or_null; cp.y = y; cp.stats = stats_out_or_null; cp.H = (int)H; cp.W = (int)W;
   const dim3 grid((unsigned)(B * (H / 8) * (W / 32)));
@@ -601,49 +607,31 @@ int conv3x3_f32(const float *x, const float *gamma_or_null, const float *beta_or
   return check_launch();
 }
 
-int wino_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale, void *stream) {
-  if (B < 0 || H < 2 || W < 2 || H % 2 || W % 2 || C < 4 || C % 4 != 0) return GQHIP_ERR_INVALID_ARG;
+static int wino_out_impl(int tile, const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale,
+                         void *stream) {
+  if (!wino_shape_ok(B, H, W, C, tile)) return GQHIP_ERR_INVALID_ARG;
   if (B == 0) return GQHIP_OK;
   if (!M || !y) return GQHIP_ERR_INVALID_ARG;
-  const long tiles = (long)(B * (H / 2) * (W / 2)), total = tiles * (C / 4);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(wino_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
-                (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
+  const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / 4);
+  return launch(tile == 4 ? wino4_out_nhwc_kernel : wino_out_nhwc_kernel, grid1d(total, 16384), dim3(256), 0,
+                static_cast<hipStream_t>(stream), M, y, (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
 }
 
-int wino4_in_nhwc_f32(const float *x, float *V, int64_t B, int64_t H, int64_t W, int64_t C, void *stream) {
-  if (B < 0 || H < 4 || W < 4 || H % 4 || W % 4 || C < 4 || C % 4 != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!x || !V) return GQHIP_ERR_INVALID_ARG;
-  const long tiles = (long)(B * (H / 4) * (W / 4)), total = tiles * (C / 4);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(wino4_in_nhwc_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
-                (void *)V, (int)H, (int)W, (int)(C / 4), tiles, total, 1.0f);
+int wino_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale, void *stream) {
+  return wino_out_impl(2, M, y, B, H, W, C, mscale, stream);
 }
 
 int wino4_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale, void *stream) {
-  if (B < 0 || H < 4 || W < 4 || H % 4 || W % 4 || C < 4 || C % 4 != 0) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!M || !y) return GQHIP_ERR_INVALID_ARG;
-  const long tiles = (long)(B * (H / 4) * (W / 4)), total = tiles * (C / 4);
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(wino4_out_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), M, y,
-                (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
+  return wino_out_impl(4, M, y, B, H, W, C, mscale, stream);
 }
 
 int wino_out_res_nhwc_f32(const float *M, const float *res, const float *bias_or_null, float *y, int64_t *stats_out,
                           int64_t B, int64_t H, int64_t W, int64_t C, int64_t groups, int tile, float mscale,
                           void *stream) {
-  if ((tile != 2 && tile != 4) || B < 0 || H < tile || W < tile || H % tile || W % tile || C < 4 || C % 4 != 0 ||
-      groups < 1 || C % groups != 0)
-    return GQHIP_ERR_INVALID_ARG;
-  if (B == 0) return GQHIP_OK;
-  if (!M || !y || !stats_out) return GQHIP_ERR_INVALID_ARG;   // res may be NULL: bias + statistics only
+  if (!wino_shape_ok(B, H, W, C, tile)) return GQHIP_ERR_INVALID_ARG;
+  // res may be NULL: bias + statistics only
+  if (int rc = gn_check(B, C, H * W, groups, M && y && stats_out, true); rc != kGo) return rc;
   const int64_t cpg = C / groups;
-  if (cpg % 4 != 0 || 256 % (C / 4) != 0 || groups > 64) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stats_zero(stats_out, sizeof(int64_t) * kStatWords * B * groups, st) != hipSuccess) return check_launch();
   const long tpi = (long)((H / tile) * (W / tile)), tiles = (long)B * tpi;
@@ -654,16 +642,10 @@ int wino_out_res_nhwc_f32(const float *M, const float *res, const float *bias_or
   if (slabs > 1024) slabs = 1024;
   if (slabs < 1) slabs = 1;
   const dim3 grid((unsigned)(B * slabs));
-  if (tile == 4 && vw == 2)
-    hipLaunchKernelGGL((wino_out_res_nhwc_kernel<4, 2>), grid, dim3(256), 0, st, M, res, bias_or_null, y, stats_out, (int)H,
-                       (int)W, (int)(C / 2), (int)cpg, tiles, (int)slabs, mscale);
-  else if (tile == 4)
-    hipLaunchKernelGGL((wino_out_res_nhwc_kernel<4, 4>), grid, dim3(256), 0, st, M, res, bias_or_null, y, stats_out, (int)H,
-                       (int)W, (int)(C / 4), (int)cpg, tiles, (int)slabs, mscale);
-  else
-    hipLaunchKernelGGL((wino_out_res_nhwc_kernel<2, 4>), grid, dim3(256), 0, st, M, res, bias_or_null, y, stats_out, (int)H,
-                       (int)W, (int)(C / 4), (int)cpg, tiles, (int)slabs, mscale);
-  return check_launch();
+  const auto kernel = tile == 2 ? wino_out_res_nhwc_kernel<2, 4>
+                                : vw == 2 ? wino_out_res_nhwc_kernel<4, 2> : wino_out_res_nhwc_kernel<4, 4>;
+  return launch(kernel, grid, dim3(256), 0, st, M, res, bias_or_null, y, stats_out, (int)H, (int)W, (int)(C / vw), (int)cpg, tiles,
+                (int)slabs, mscale);
 }
 
 int attn_split_qkv_f16x3(const float *qkv, void *Q3, void *K3, void *V3, int64_t B, int64_t L, int64_t C, float sq, float sv,
@@ -672,9 +654,7 @@ int attn_split_qkv_f16x3(const float *qkv, void *Q3, void *K3, void *V3, int64_t
   if (B == 0) return GQHIP_OK;
   if (!qkv || !Q3 || !K3 || !V3) return GQHIP_ERR_INVALID_ARG;
   const long total = (long)(B * L * (C / 4));
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(attn_split_qkv_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), qkv,
+  return launch(attn_split_qkv_kernel, grid1d(total, 16384), dim3(256), 0, static_cast<hipStream_t>(stream), qkv,
                 static_cast<_Float16 *>(Q3), static_cast<_Float16 *>(K3), static_cast<_Float16 *>(V3), (long)L,
                 (int)(C / 4), sq, sv, total);
 }
@@ -711,9 +691,7 @@ int upsample2x_nhwc_f32(const float *x, float *y, int64_t B, int64_t H, int64_t 
   if (B == 0) return GQHIP_OK;
   if (!x || !y) return GQHIP_ERR_INVALID_ARG;
   const long total = (long)(B * H * W * (C / 4));
-  long blocks = (total + 255) / 256;
-  if (blocks > 16384) blocks = 16384;
-  return launch(upsample2x_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+  return launch(upsample2x_nhwc_kernel, grid1d(total, 16384), dim3(256), 0, static_cast<hipStream_t>(stream), x,
                 y, (int)H, (int)W, (int)(C / 4), total);
 }
 

@@ -614,6 +614,62 @@ def gn_nhwc_ok(C: int, groups: int) -> bool:
     return C % groups == 0 and cpg % 4 == 0 and C % 4 == 0 and 256 % (C // 4) == 0 and groups <= 64
 
 
+def _need_nhwc(who: str, x, c: int = 1, h: int = 1, w: int = 1, hw: int = 1) -> None:
+    """The input test of the conv-stack wrappers: ``x`` is a dense channels_last fp32 HIP tensor whose C, H, W and H * W are
+    multiples of ``c``, ``h``, ``w`` and ``hw``; the error names ``who`` and what it needs."""
+    if (image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % c or x.shape[2] % h or x.shape[3] % w
+            or (x.shape[2] * x.shape[3]) % hw):
+        needs = [f"{name} % {m} == 0" for name, m in (("C", c), ("H", h), ("W", w), ("H * W", hw)) if m > 1]
+        raise GqHipError(f"{who} needs a dense channels_last fp32 HIP tensor" + (" with " + ", ".join(needs) if needs else ""))
+
+
+def _need_residual(who: str, residual, shape) -> None:
+    if residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != tuple(shape)):
+        raise GqHipError(f"{who}: residual must be channels_last [B, Cout, H, W]")
+
+
+def _out_nhwc(x, C: int, H: int, W: int):
+    """An uninitialised channels_last [B, C, H, W] result for the input x."""
+    return torch.empty((x.shape[0], C, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+
+
+def _out_and_stats(x, C: int, H: int, W: int, stats_groups: int):
+    """(_out_nhwc, the statistics records of its ``stats_groups`` GroupNorm groups or None).  Call it right before the library
+    call that fills the records: _stats_records tells the library whether they are zero already, and the flag is the thread's."""
+    y = _out_nhwc(x, C, H, W)
+    return y, (_stats_records(GNSTAT_WORDS * x.shape[0] * stats_groups, x.device) if stats_groups else None)
+
+
+def _y_or_both(y, ostats):
+    return y if ostats is None else (y, ostats)
+
+
+def _pow2_scale(bound, amp: float = 1.0) -> float:
+    """The operand scale of the fp16 x 3 routes: the largest power of two, 2^14 at the most, that keeps amp * bound inside 32768
+    (half of fp16's range: headroom for the rounding of the split)."""
+    return min(2.0 ** math.floor(math.log2(32768.0 / (amp * max(float(bound), 1e-30)))), 2.0 ** 14)
+
+
+def _operand_scales(scale, u_scale: float, post_scale: float = 1.0):
+    """(device scales pointer or None, v_scale, mscale) of a direct fp16 x 3 convolution: ``scale`` is a float bound of the
+    activation, or the device float[2] of f16_scales -- the kernel then reads both factors there, and 0.0 goes in their place."""
+    if torch.is_tensor(scale):
+        return scale.data_ptr(), 0.0, 0.0
+    v_scale = _pow2_scale(scale)
+    return None, v_scale, float(post_scale) / (v_scale * u_scale)
+
+
+def _split_f16(w):
+    """(hi, lo, u_scale): the two-term fp16 split hi + lo of w * u_scale, u_scale the power of two that brings max|w| into
+    (8192, 16384] (1.0 for an all-zero w)."""
+    w = w.detach().float()
+    amax = float(w.abs().max())
+    u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
+    ws = w * u_scale
+    hi = ws.half()
+    return hi, (ws - hi.float()).half(), u_scale
+
+
 def gn_silu(x, gamma, beta, groups: int, eps: float, silu: bool = True, pre_bias=None):
     """Fused GroupNorm(+SiLU) on an NCHW or channels_last fp32 HIP tensor (see gqhip.h:gn_silu_f32)."""
     layout = image_layout(x)
@@ -647,7 +703,8 @@ def add_bias(a, b, bias=None):
 
 def add_bias_stats(a, b, bias, groups: int):
     """channels_last only: (a + b (+ bias[c]), GroupNorm statistics of that sum [2 * B * groups] fp64)."""
-    if image_layout(a) != 1 or image_layout(b) != 1 or not a.is_cuda or a.dtype != torch.float32 or not gn_nhwc_ok(a.shape[1], groups):
+    _need_nhwc("add_bias_stats", a)
+    if image_layout(b) != 1 or not gn_nhwc_ok(a.shape[1], groups):
         raise GqHipError("add_bias_stats needs two dense channels_last fp32 HIP tensors with a GroupNorm-compatible C")
     B, C = a.shape[0], a.shape[1]
     HW = a.shape[2] * a.shape[3]
@@ -661,8 +718,7 @@ def add_bias_stats(a, b, bias, groups: int):
 
 def gn_apply(x, gamma, beta, groups: int, eps: float, silu: bool, stats):
     """channels_last only: GroupNorm(+SiLU) of x from statistics computed by add_bias_stats."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32:
-        raise GqHipError("gn_apply needs a dense channels_last fp32 HIP tensor")
+    _need_nhwc("gn_apply", x)
     B, C = x.shape[0], x.shape[1]
     HW = x.shape[2] * x.shape[3]
     y = torch.empty_like(x)
@@ -686,8 +742,9 @@ def gn_stats_values(stats):
 
 def gn_stats(x, groups: int, pre_bias=None):
     """channels_last only: GroupNorm statistics of x (+ pre_bias[c]) as [2 * B * groups] fp64 (sum, sum of squares)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or not gn_nhwc_ok(x.shape[1], groups):
-        raise GqHipError("gn_stats needs a dense channels_last fp32 HIP tensor with a GroupNorm-compatible C")
+    _need_nhwc("gn_stats", x)
+    if not gn_nhwc_ok(x.shape[1], groups):
+        raise GqHipError("gn_stats needs a GroupNorm-compatible C")
     B, C = x.shape[0], x.shape[1]
     stats = _stats_records(GNSTAT_WORDS * B * groups, x.device)
     with torch.cuda.device(x.device):
@@ -697,7 +754,8 @@ def gn_stats(x, groups: int, pre_bias=None):
 
 
 def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0, f16=None):
-    """3x3 stride-1 padding-1 convolution of a channels_last fp32 HIP tensor by Winograd F(2x2, 3x3):
+    """3x3 stride-1 padding-1 convolution of a channels_last fp32 HIP tensor by Winograd F(2x2, 3x3) in three stages (input
+    transform, GEMMs, output transform):
     U [16, Cin, Cout] = G g G^T (see unet._wino_weights).  Returns [B, Cout, H, W] channels_last, no bias.
     ``gn`` = (gamma, beta, groups, eps, silu, stats, pre_bias): the convolution's input is SiLU(GroupNorm(x + pre_bias)),
     applied inside the input transform (the normalised tensor is never materialised).
@@ -706,79 +764,69 @@ def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0,
     ``f16`` = (U3, u_scale, x_bound): run the 16 / 36 GEMMs as ONE fp16 batched GEMM with fp32 accumulation over a K axis
     that carries the three products of two-term fp16 splits (see gqhip.h:wino_in_nhwc_f16x3): U3 [T, 3 Cin, Cout] fp16 =
     [U_h; U_l; U_h] of U * u_scale, x_bound >= max|x| (guarantees the scaled transform stays inside fp16's range)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 4 or x.shape[2] % 2 or x.shape[3] % 2:
-        raise GqHipError("wino_conv3x3 needs a dense channels_last fp32 HIP tensor, C % 4 == 0, even H and W")
+    _need_nhwc("wino_conv3x3", x, c=4, h=2, w=2)
     B, C, H, W = x.shape
-    cout = U.shape[2]
-    f4 = U.shape[0] == 36                                     # F(4x4,3x3): 6x6 tiles, 36 GEMMs
+    T, cout = U.shape[0], U.shape[2]
+    f4 = T == 36                                              # F(4x4,3x3): 6x6 tiles, 36 GEMMs
     if f4 and (H % 4 or W % 4):
         raise GqHipError("F(4x4,3x3) needs H, W multiples of 4")
     t = 4 if f4 else 2
     tiles = B * (H // t) * (W // t)
+    # the operand V of the GEMMs: fp32 [T, tiles, C] (planes = 0), or -- f16 -- the two-term split of the transform times v_scale as [h | l]
+    # (2 C wide, for our own GEMM kernel, which forms the three products itself: wino_gemm_f16x2, weights in operand order) or
+    # as the three planes the library's K-concatenated GEMM wants (3 C wide)
+    planes, v_scale, mscale = 0, 1.0, 1.0
+    if f16 is not None:
+        U3, u_scale, x_bound = f16[:3]
+        # |B^T d B| <= amp * max|d| (amp = squared max abs row sum of B^T: 100 for F(4x4,3x3), 4 for F(2x2,3x3)); with gn, x_bound
+        # bounds SiLU(GroupNorm(x)), the tensor the transform actually sees
+        v_scale = _pow2_scale(x_bound, 100.0 if f4 else 4.0)
+        use_own = len(f16) > 3 and f16[3] is not None and tiles % 256 == 0 and own_gemm_fits(T, tiles, cout, C)
+        planes, mscale = 2 if use_own else 3, 1.0 / (v_scale * u_scale)
     L = lib()
-    mscale = 1.0
     with torch.cuda.device(x.device):
-        if f16 is not None:
-            U3, u_scale, x_bound = f16[:3]
-            # |B^T d B| <= amp * max|d| (amp = squared max abs row sum of B^T: 100 for F(4x4,3x3), 4 for F(2x2,3x3))
-            amp = 100.0 if f4 else 4.0
-            v_scale = 2.0 ** math.floor(math.log2(32768.0 / (amp * max(float(x_bound), 1e-30))))
-            v_scale = min(v_scale, 2.0 ** 14)
-            use_own = len(f16) > 3 and f16[3] is not None and tiles % 256 == 0 and own_gemm_fits(U.shape[0], tiles, cout, C)
-            if use_own:
-                # [h | l] operand (4 bytes per element) + our own GEMM kernel forming the three products (wino_gemm_f16x2:
-                # weights in operand order)
-                V = torch.empty((U.shape[0], tiles, 2 * C), dtype=torch.float16, device=x.device)
-                if gn is not None:
-                    gamma, beta, groups, eps, silu, stats, pre_bias = gn
-                    _check(L.wino_in_gn_nhwc_f16x2(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias),
-                                                   stats.data_ptr(), V.data_ptr(), B, H, W, C, groups, float(eps),
-                                                   1 if silu else 0, t, float(v_scale), _stream()), "wino_in_gn_nhwc_f16x2")
-                else:
-                    _check(L.wino_in_nhwc_f16x2(x.data_ptr(), V.data_ptr(), B, H, W, C, t, float(v_scale), _stream()),
-                           "wino_in_nhwc_f16x2")
-                M = torch.empty((U.shape[0], tiles, cout), dtype=torch.float32, device=x.device)
-                _check(L.wino_gemm_f16x2(V.data_ptr(), f16[3].data_ptr(), M.data_ptr(), U.shape[0], tiles, C, cout,
-                                         _stream()), "wino_gemm_f16x2")
-                V = None
-            else:
-                V = torch.empty((U.shape[0], tiles, 3 * C), dtype=torch.float16, device=x.device)
-            if V is None:
-                pass
-            elif gn is not None:     # x_bound then bounds SiLU(GroupNorm(x)), the tensor the transform actually sees
-                gamma, beta, groups, eps, silu, stats, pre_bias = gn
-                _check(L.wino_in_gn_nhwc_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias),
-                                               stats.data_ptr(), V.data_ptr(), B, H, W, C, groups, float(eps),
-                                               1 if silu else 0, t, float(v_scale), _stream()), "wino_in_gn_nhwc_f16x3")
-            else:
-                _check(L.wino_in_nhwc_f16x3(x.data_ptr(), V.data_ptr(), B, H, W, C, t, float(v_scale), _stream()),
-                       "wino_in_nhwc_f16x3")
-            if V is not None:
-                M = torch.bmm(V, U3, out_dtype=torch.float32)     # ONE fp16 GEMM per tile position, fp32 accumulate
-            mscale = 1.0 / (v_scale * u_scale)
+        # 1. input transform (with the GroupNorm + SiLU of gn applied on the way)
+        V = torch.empty((T, tiles, (planes or 1) * C), dtype=torch.float16 if planes else x.dtype, device=x.device)
+        _wino_in(L, x, V, gn, t, planes, v_scale)
+        # 2. the 16 / 36 GEMMs [tiles, Cin] x [Cin, Cout], fp32 accumulation
+        if planes == 2:
+            M = torch.empty((T, tiles, cout), dtype=torch.float32, device=x.device)
+            _check(L.wino_gemm_f16x2(V.data_ptr(), f16[3].data_ptr(), M.data_ptr(), T, tiles, C, cout, _stream()), "wino_gemm_f16x2")
+            del V                                             # (this route has always freed its operand before y is taken)
+        elif planes == 3:
+            M = torch.bmm(V, U3, out_dtype=torch.float32)     # ONE fp16 GEMM per tile position
         else:
-            V = torch.empty((U.shape[0], tiles, C), dtype=x.dtype, device=x.device)
-            if gn is not None:
-                gamma, beta, groups, eps, silu, stats, pre_bias = gn
-                _check((L.wino4_in_gn_nhwc_f32 if f4 else L.wino_in_gn_nhwc_f32)(
-                    x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(), V.data_ptr(), B, H, W, C,
-                    groups, float(eps), 1 if silu else 0, _stream()), "wino_in_gn_nhwc_f32")
-            else:
-                _check((L.wino4_in_nhwc_f32 if f4 else L.wino_in_nhwc_f32)(x.data_ptr(), V.data_ptr(), B, H, W, C, _stream()),
-                       "wino_in_nhwc_f32")
-            M = torch.bmm(V, U)                               # 16 / 36 GEMMs [tiles, Cin] x [Cin, Cout] (hipBLASLt)
-        y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+            M = torch.bmm(V, U)                               # hipBLASLt
+        # 3. output transform (with bias, residual and the statistics of the result when asked for)
         if stats_groups:
-            if (residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != tuple(y.shape))) \
-                    or not gn_nhwc_ok(cout, stats_groups):
-                raise GqHipError("fused Winograd tail needs a channels_last residual of the output shape and a GroupNorm-compatible C")
-            stats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device)
+            _need_residual("wino_conv3x3", residual, (B, cout, H, W))
+            if not gn_nhwc_ok(cout, stats_groups):
+                raise GqHipError("wino_conv3x3: the fused tail needs a GroupNorm-compatible Cout")
+            y, stats = _out_and_stats(x, cout, H, W, stats_groups)
             _check(L.wino_out_res_nhwc_f32(M.data_ptr(), _ptr(residual), _ptr(bias), y.data_ptr(), stats.data_ptr(),
                                            B, H, W, cout, stats_groups, t, float(mscale), _stream()), "wino_out_res_nhwc_f32")
             return y, stats
+        y = _out_nhwc(x, cout, H, W)
         _check((L.wino4_out_nhwc_f32 if f4 else L.wino_out_nhwc_f32)(M.data_ptr(), y.data_ptr(), B, H, W, cout,
                                                                      float(mscale), _stream()), "wino_out_nhwc_f32")
     return y
+
+
+def _wino_in(L, x, V, gn, t: int, planes: int, v_scale: float) -> None:
+    """wino_conv3x3's input transform of F(t x t, 3x3) into V, by one of six entry points: fp32 (``planes`` 0), or the fp16
+    operand of 2 | 3 planes scaled by v_scale; ``gn``: with the GroupNorm in front."""
+    B, C, H, W = x.shape
+    f16_args = (t, float(v_scale)) if planes else ()
+    if gn is None:
+        name = {0: "wino4_in_nhwc_f32" if t == 4 else "wino_in_nhwc_f32", 2: "wino_in_nhwc_f16x2", 3: "wino_in_nhwc_f16x3"}[planes]
+        rc = getattr(L, name)(x.data_ptr(), V.data_ptr(), B, H, W, C, *f16_args, _stream())
+    else:
+        name = {0: "wino4_in_gn_nhwc_f32" if t == 4 else "wino_in_gn_nhwc_f32", 2: "wino_in_gn_nhwc_f16x2",
+                3: "wino_in_gn_nhwc_f16x3"}[planes]
+        gamma, beta, groups, eps, silu, stats, pre_bias = gn
+        rc = getattr(L, name)(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(), V.data_ptr(), B, H, W,
+                              C, groups, float(eps), 1 if silu else 0, *f16_args, _stream())
+    _check(rc, name)
 
 
 _BMM_OUT_DTYPE = None
@@ -803,9 +851,8 @@ ATTN_L_OK = (64, 256, 1024, 2304, 4096)   # token counts attn_softmax_split_f16x
 
 def attention_scales(q_bound: float, v_bound: float):
     """(sq, sv): the powers of two that bring q, k (|.| <= q_bound) and v (<= v_bound) inside fp16's range for attention_f16x3."""
-    pow2 = lambda bound: min(2.0 ** math.floor(math.log2(32768.0 / max(float(bound), 1e-30))), 2.0 ** 14)
     # q k^T sums C products of scaled operands in fp32: keep sq^2 C q_bound^2 well inside fp32 (it always is: <= 2^30 C)
-    return pow2(q_bound), pow2(v_bound)
+    return _pow2_scale(q_bound), _pow2_scale(v_bound)
 
 
 def attention_operands(B: int, Ltok: int, C: int, device):
@@ -880,12 +927,7 @@ def conv3_weights_f16(weight):
     cout, cin, kk = weight.shape[0], weight.shape[1], weight.shape[2]
     if (cout % 128 if kk == 1 else cout not in (128, 256)) or cin % 16 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)):
         raise GqHipError("conv3_weights_f16 needs a [128 | 256, Cin % 16 == 0, 3, 3] or [Cout % 128 == 0, Cin % 16 == 0, 1, 1] kernel")
-    w = weight.detach().float()
-    amax = float(w.abs().max())
-    u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
-    ws = w * u_scale
-    hi = ws.half()
-    lo = (ws - hi.float()).half()
+    hi, lo, u_scale = _split_f16(weight)
     planes = torch.stack([hi, lo], 0)                                    # [plane, n, k, ky, kx]
     # n = 32 tile + c, k = 16 chunk + 8 h + e  ->  [chunk, ky, kx, tile, plane, h, c, e]
     p7 = planes.reshape(2, cout // 32, 32, cin // 16, 2, 8, kk, kk).permute(3, 6, 7, 1, 0, 4, 2, 5)
@@ -897,45 +939,39 @@ def conv3x3_direct(x, wf, u_scale: float, x_bound: float, gn, residual=None, bia
     a direct (implicit GEMM) fp16 x 3 convolution with the normalisation applied while the patch is staged
     (gqhip.h:conv3x3_gn_f16x3); ``wf, u_scale`` from conv3_weights_f16, ``x_bound`` >= max|activated tensor|, ``gn`` as in
     wino_conv3x3.  Returns y, or (y, statistics of y) when ``stats_groups`` > 0 (+ bias, + residual in either case)."""
-    if (image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 32 or x.shape[1] > 512 or x.shape[2] % 8
-            or x.shape[3] % 32 or gn is None):
-        raise GqHipError("conv3x3_direct needs a dense channels_last fp32 HIP tensor, C % 32 == 0, C <= 512, H % 8 == 0, W % 32 == 0, "
-                         "and the GroupNorm that feeds the convolution")
+    _need_nhwc("conv3x3_direct", x, c=32, h=8, w=32)
+    if x.shape[1] > 512 or gn is None:
+        raise GqHipError("conv3x3_direct needs C <= 512 and the GroupNorm that feeds the convolution")
     B, C, H, W = x.shape
     cout = wf.shape[2] * 32
     if wf.shape[0] * 16 != C:
         raise GqHipError("conv3x3_direct: weights are for %d input channels, x has %d" % (wf.shape[0] * 16, C))
-    if residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != (B, cout, H, W)):
-        raise GqHipError("conv3x3_direct: residual must be channels_last [B, Cout, H, W]")
-    v_scale = min(2.0 ** math.floor(math.log2(32768.0 / max(float(x_bound), 1e-30))), 2.0 ** 14)
-    L = lib()
+    _need_residual("conv3x3_direct", residual, (B, cout, H, W))
+    v_scale = _pow2_scale(x_bound)
+    mscale = 1.0 / (v_scale * u_scale)
+    gamma, beta, groups, eps, silu, stats, pre_bias = gn
     with torch.cuda.device(x.device):
-        y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        ostats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device) if stats_groups else None
-        mscale = 1.0 / (v_scale * u_scale)
-        gamma, beta, groups, eps, silu, stats, pre_bias = gn
-        _check(L.conv3x3_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(),
-                                  groups, float(eps), 1 if silu else 0, float(v_scale), wf.data_ptr(), _ptr(bias),
-                                  _ptr(residual), y.data_ptr(), _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1),
-                                  mscale, _stream()), "conv3x3_gn_f16x3")
-    return (y, ostats) if stats_groups else y
+        y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
+        _check(lib().conv3x3_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(),
+                                      groups, float(eps), 1 if silu else 0, float(v_scale), wf.data_ptr(), _ptr(bias),
+                                      _ptr(residual), y.data_ptr(), _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1),
+                                      mscale, _stream()), "conv3x3_gn_f16x3")
+    return _y_or_both(y, ostats)
 
 
-def _conv1_args(x, wf, scale, gn, post_scale: float, what: str, pre_bias=None):
-    """Shared checks of the 1x1 routes; returns (device scales pointer or None, v_scale)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 32 or (x.shape[2] * x.shape[3]) % 128:
-        raise GqHipError(what + " needs a dense channels_last fp32 HIP tensor, C % 32 == 0, H * W % 128 == 0")
+def _conv1_args(x, wf, u_scale: float, scale, gn, post_scale: float, what: str, pre_bias=None):
+    """Shared checks of the 1x1 routes; returns _operand_scales' (device scales pointer or None, v_scale, mscale).
+    post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)."""
+    _need_nhwc(what, x, c=32, hw=128)
     if wf.shape[0] * 16 != x.shape[1] or wf.shape[1] != 1:
         raise GqHipError(what + ": weights do not match (need conv3_weights_f16 of a [Cout, %d, 1, 1] kernel)" % x.shape[1])
     if gn is not None and pre_bias is not None and pre_bias is not gn[6]:
         raise GqHipError(what + ": with gn the pending bias is gn[6] (the one its statistics include); pre_bias differs from it")
     if gn is not None and (torch.is_tensor(scale) or gn[4] or x.shape[1] > 512 or (x.shape[1] // gn[2]) % 4):
         raise GqHipError(what + ": the GroupNorm variant needs a host-side bound, no SiLU, C <= 512 and 4 | channels per group")
-    if torch.is_tensor(scale):
-        if post_scale != 1.0:
-            raise GqHipError(what + ": post_scale needs a host-side scale bound")
-        return scale.data_ptr(), 0.0
-    return None, min(2.0 ** math.floor(math.log2(32768.0 / max(float(scale), 1e-30))), 2.0 ** 14)
+    if torch.is_tensor(scale) and post_scale != 1.0:
+        raise GqHipError(what + ": post_scale needs a host-side scale bound")
+    return _operand_scales(scale, u_scale, post_scale)
 
 
 def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats_groups: int = 0, pre_bias=None,
@@ -947,16 +983,12 @@ def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats
     ``gn`` = (gamma, beta, groups, eps, False, statistics of x + pre_bias, pre_bias) as for conv3x3_direct: the convolution's
     input is GroupNorm(x + pre_bias), normalised while it is staged (gqhip.h:conv1x1_gn_f16x3); ``scale`` then bounds the
     normalised tensor."""
-    sdev, v_scale = _conv1_args(x, wf, scale, gn, post_scale, "conv1x1_direct", pre_bias)
+    sdev, v_scale, mscale = _conv1_args(x, wf, u_scale, scale, gn, post_scale, "conv1x1_direct", pre_bias)
     B, C, H, W = x.shape
     cout = wf.shape[2] * 32
-    if residual is not None and (image_layout(residual) != 1 or tuple(residual.shape) != (B, cout, H, W)):
-        raise GqHipError("conv1x1_direct: residual must be channels_last [B, Cout, H, W]")
-    # post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)
-    mscale = 0.0 if sdev is not None else float(post_scale) / (v_scale * u_scale)
+    _need_residual("conv1x1_direct", residual, (B, cout, H, W))
     with torch.cuda.device(x.device):
-        y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        ostats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device) if stats_groups else None
+        y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
         if gn is not None:
             gamma, beta, groups, eps, _, stats, gn_pb = gn
             _check(lib().conv1x1_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(gn_pb), stats.data_ptr(), groups,
@@ -967,7 +999,7 @@ def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats
             _check(lib().conv1x1_f16x3(x.data_ptr(), _ptr(pre_bias), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias),
                                        _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1),
                                        _stream()), "conv1x1_f16x3")
-    return (y, ostats) if stats_groups else y
+    return _y_or_both(y, ostats)
 
 
 def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, bias=None, pre_bias=None, gn=None, out=None):
@@ -975,7 +1007,7 @@ def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, 
     of attention_from_operands itself (gqhip.h:conv1x1_qkv_split_f16x3): (Q3, K3, V3), byte for byte those
     attn_split_qkv_f16x3(sq, sv) makes of the fp32 projection, which is never stored.  C % 128 == 0.  ``out``: the three
     operand tensors to fill (attention_operands' shapes, dense fp16) instead of fresh ones."""
-    _, v_scale = _conv1_args(x, wf, float(scale), gn, 1.0, "qkv_split_direct", pre_bias)
+    _, v_scale, mscale = _conv1_args(x, wf, u_scale, float(scale), gn, 1.0, "qkv_split_direct", pre_bias)
     B, C, H, W = x.shape
     if wf.shape[2] * 32 != 3 * C or C % 128:
         raise GqHipError("qkv_split_direct: needs the [3C, C, 1, 1] projection, C % 128 == 0")
@@ -986,7 +1018,7 @@ def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, 
             if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape and t.is_contiguous()):
                 raise GqHipError("qkv_split_direct: out must be dense fp16 [B, L, 3C], [B, L, 3C], [B, 3L, C]")
         _check(lib().conv1x1_qkv_split_f16x3(x.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(gn_pb), _ptr(stats), groups, float(eps),
-                                             wf.data_ptr(), float(v_scale), 1.0 / (v_scale * u_scale), _ptr(bias), Q3.data_ptr(),
+                                             wf.data_ptr(), float(v_scale), mscale, _ptr(bias), Q3.data_ptr(),
                                              K3.data_ptr(), V3.data_ptr(), float(sq), float(sv), B, H * W, C, _stream()),
                "conv1x1_qkv_split_f16x3")
     return Q3, K3, V3
@@ -998,12 +1030,7 @@ def conv3s2_weights_f16(weight):
     cout, cin = weight.shape[0], weight.shape[1]
     if cout not in (128, 256, 512) or cin % 16 or tuple(weight.shape[2:]) != (3, 3):
         raise GqHipError("conv3s2_weights_f16 needs a [128 | 256 | 512, Cin % 16 == 0, 3, 3] kernel")
-    w = weight.detach().float()
-    amax = float(w.abs().max())
-    u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
-    ws = w * u_scale
-    hi = ws.half()
-    lo = (ws - hi.float()).half()
+    hi, lo, u_scale = _split_f16(weight)
     planes = torch.stack([hi, lo], 0)                                    # [plane, n, k, ky, kx]
     std = planes.reshape(2, cout // 32, 32, cin // 16, 2, 8, 3, 3).permute(3, 6, 7, 1, 0, 4, 2, 5)   # [chunk, ky, kx, tile, plane, h, c, e]
     steps = []
@@ -1020,23 +1047,17 @@ def conv3x3s2_direct(x, wf, u_scale: float, scale, bias=None, stats_groups: int 
     as an fp16 x 3 convolution on the four phase images (gqhip.h:conv3x3s2_f16x3).  ``wf, u_scale`` from conv3s2_weights_f16;
     ``scale``: a float bound >= max|x| or the device float[2] of f16_scales.  Returns y [B, Cout, H/2, W/2] (+ bias), or
     (y, statistics of y)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 16 or x.shape[2] % 16 or x.shape[3] % 64:
-        raise GqHipError("conv3x3s2_direct needs a dense channels_last fp32 HIP tensor, C % 16 == 0, H % 16 == 0, W % 64 == 0")
+    _need_nhwc("conv3x3s2_direct", x, c=16, h=16, w=64)
     B, C, H, W = x.shape
     cout = wf.shape[1] * 32
     if wf.shape[0] != 9 * (C // 16):
         raise GqHipError("conv3x3s2_direct: weights do not match the input channels")
-    if torch.is_tensor(scale):
-        sdev, v_scale, mscale = scale.data_ptr(), 0.0, 0.0
-    else:
-        v_scale = min(2.0 ** math.floor(math.log2(32768.0 / max(float(scale), 1e-30))), 2.0 ** 14)
-        sdev, mscale = None, 1.0 / (v_scale * u_scale)
+    sdev, v_scale, mscale = _operand_scales(scale, u_scale)
     with torch.cuda.device(x.device):
-        y = torch.empty((B, cout, H // 2, W // 2), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        ostats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device) if stats_groups else None
+        y, ostats = _out_and_stats(x, cout, H // 2, W // 2, stats_groups)
         _check(lib().conv3x3s2_f16x3(x.data_ptr(), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias), y.data_ptr(),
                                      _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1), _stream()), "conv3x3s2_f16x3")
-    return (y, ostats) if stats_groups else y
+    return _y_or_both(y, ostats)
 
 
 def upconv_weights_f16(phase_matrix, cin: int, cout: int):
@@ -1045,12 +1066,7 @@ def upconv_weights_f16(phase_matrix, cin: int, cout: int):
     [column tile][plane][lane (hh, c)][e] = plane[tap, 16 chunk + 8 hh + e, phase, 32 tile + c] --, u_scale)."""
     if cout not in (128, 256, 512) or cin % 16 or tuple(phase_matrix.shape) != (4 * cin, 4 * cout):
         raise GqHipError("upconv_weights_f16 needs the [4 Cin, 4 Cout] phase matrix, Cin % 16 == 0, Cout in (128, 256, 512)")
-    w = phase_matrix.detach().float()
-    amax = float(w.abs().max())
-    u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
-    ws = w * u_scale
-    hi = ws.half()
-    lo = (ws - hi.float()).half()
+    hi, lo, u_scale = _split_f16(phase_matrix)
     planes = torch.stack([hi, lo], 0).reshape(2, 4, cin // 16, 2, 8, 4, cout // 32, 32)   # [pl, tap, chunk, hh, e, phase, nt, c]
     wf = planes.permute(5, 2, 1, 6, 0, 3, 7, 4).reshape(4, 4 * (cin // 16), cout // 32, 2, 64, 8)
     return wf.contiguous(), u_scale
@@ -1060,36 +1076,29 @@ def upconv2x_direct(x, wf, u_scale: float, scale, bias=None, stats_groups: int =
     """The reference's Upsample (nearest x2 + conv 3x3) of a channels_last fp32 HIP tensor as the direct sub-pixel fp16 x 3
     convolution (gqhip.h:upconv2x_f16x3).  ``wf, u_scale`` from upconv_weights_f16; ``scale``: a float bound >= max|x| or the
     device float[2] of f16_scales.  Returns y [B, Cout, 2H, 2W] (+ bias), or (y, statistics of y)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 16 or x.shape[2] % 8 or x.shape[3] % 32:
-        raise GqHipError("upconv2x_direct needs a dense channels_last fp32 HIP tensor, C % 16 == 0, H % 8 == 0, W % 32 == 0")
+    _need_nhwc("upconv2x_direct", x, c=16, h=8, w=32)
     B, C, H, W = x.shape
     cout = wf.shape[2] * 32
     if wf.shape[0] != 4 or wf.shape[1] != 4 * (C // 16):
         raise GqHipError("upconv2x_direct: weights do not match the input channels")
-    if torch.is_tensor(scale):
-        sdev, v_scale, mscale = scale.data_ptr(), 0.0, 0.0
-    else:
-        v_scale = min(2.0 ** math.floor(math.log2(32768.0 / max(float(scale), 1e-30))), 2.0 ** 14)
-        sdev, mscale = None, 1.0 / (v_scale * u_scale)
+    sdev, v_scale, mscale = _operand_scales(scale, u_scale)
     with torch.cuda.device(x.device):
-        y = torch.empty((B, cout, 2 * H, 2 * W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        ostats = _stats_records(GNSTAT_WORDS * B * stats_groups, x.device) if stats_groups else None
+        y, ostats = _out_and_stats(x, cout, 2 * H, 2 * W, stats_groups)
         _check(lib().upconv2x_f16x3(x.data_ptr(), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias), y.data_ptr(),
                                     _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1), _stream()), "upconv2x_f16x3")
-    return (y, ostats) if stats_groups else y
+    return _y_or_both(y, ostats)
 
 
 def conv3x3_gn_small(x, w_ohwi, bias, gn):
     """conv3x3(SiLU(GroupNorm(x))) into 1..4 channels (gqhip.h:conv3x3_gn_small_f32): x channels_last fp32 [B, Cin, H, W],
     w_ohwi [Cout, 3, 3, Cin] fp32 contiguous, ``gn`` = (gamma, beta, groups, eps, silu, stats, pre_bias)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 32 or x.shape[2] % 16 or x.shape[3] % 16:
-        raise GqHipError("conv3x3_gn_small needs a dense channels_last fp32 HIP tensor, C % 32 == 0, H % 16 == 0, W % 16 == 0")
+    _need_nhwc("conv3x3_gn_small", x, c=32, h=16, w=16)
     B, C, H, W = x.shape
     cout = w_ohwi.shape[0]
     if tuple(w_ohwi.shape) != (cout, 3, 3, C) or not w_ohwi.is_contiguous() or w_ohwi.dtype != torch.float32:
         raise GqHipError("conv3x3_gn_small: weights must be fp32 [Cout, 3, 3, Cin] contiguous")
     gamma, beta, groups, eps, silu, stats, pre_bias = gn
-    y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = _out_nhwc(x, cout, H, W)
     with torch.cuda.device(x.device):
         _check(lib().conv3x3_gn_small_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(),
                                           groups, float(eps), 1 if silu else 0, w_ohwi.data_ptr(), _ptr(bias), y.data_ptr(),
@@ -1137,12 +1146,11 @@ def conv3x3_f32(x, wk, cout: int, bias=None, gn=None):
     """3x3 convolution (stride 1, padding 1) of a channels_last fp32 HIP tensor on the fp32 matrix cores with a fixed summation
     order (gqhip.h:conv3x3_f32: bit-reproducible).  ``wk`` from conv_f32_weights; ``gn`` = (gamma, beta, groups, eps, silu, stats,
     pre_bias): the input is act(GroupNorm(x + pre_bias)), applied while the patch is staged."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32:
-        raise GqHipError("conv3x3_f32 needs a dense channels_last fp32 HIP tensor")
+    _need_nhwc("conv3x3_f32", x)
     B, C, H, W = x.shape
     if not conv_f32_ok(C, cout, H, W, gn is not None) or wk.numel() != ((cout + 31) // 32) * 9 * (C // 8) * 256:
         raise GqHipError(f"conv3x3_f32: shape {tuple(x.shape)} -> {cout} channels is not tiled by the kernel")
-    y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = _out_nhwc(x, cout, H, W)
     gamma = beta = stats = pre_bias = None
     groups, eps, silu = 1, 0.0, False
     if gn is not None:
@@ -1168,17 +1176,15 @@ def conv_cin_small_weights(weight):
 def conv3x3_cin_small(x, wk, bias=None, stats_groups: int = 0):
     """The encoder's conv_in on libgqhip (gqhip.h:conv3x3_cin_small_f32): 3x3 / stride 1 / pad 1, Cin <= 4 -> 128 channels of a
     channels_last fp32 HIP image, fp32 FMAs in a fixed order, bias added; ``stats_groups`` = 32: returns (y, statistics of y)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32:
-        raise GqHipError("conv3x3_cin_small needs a dense channels_last fp32 HIP tensor")
+    _need_nhwc("conv3x3_cin_small", x)
     B, C, H, W = x.shape
     if not conv_cin_small_ok(C, wk.shape[1], H, W) or wk.shape[0] != 9 * C or stats_groups not in (0, 32):
         raise GqHipError(f"conv3x3_cin_small: shape {tuple(x.shape)} is not tiled by the kernel")
     with torch.cuda.device(x.device):
-        y = torch.empty((B, 128, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        ostats = _stats_records(GNSTAT_WORDS * B * 32, x.device) if stats_groups else None
+        y, ostats = _out_and_stats(x, 128, H, W, 32 if stats_groups else 0)
         _check(lib().conv3x3_cin_small_f32(x.data_ptr(), wk.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(ostats), B, H, W, C, 128,
                                            32, _stream()), "conv3x3_cin_small_f32")
-    return (y, ostats) if stats_groups else y
+    return _y_or_both(y, ostats)
 
 
 def f16_scales(stats, amp: float, u_scale: float):
@@ -1196,10 +1202,9 @@ def f16_scales(stats, amp: float, u_scale: float):
 
 def upsample2x_nhwc(x):
     """Nearest x2 upsample of a channels_last fp32 HIP tensor [B, C, H, W] -> [B, C, 2H, 2W] (channels_last)."""
-    if image_layout(x) != 1 or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] % 4:
-        raise GqHipError("upsample2x_nhwc needs a dense channels_last fp32 HIP tensor with C % 4 == 0")
+    _need_nhwc("upsample2x_nhwc", x, c=4)
     B, C, H, W = x.shape
-    y = torch.empty((B, C, 2 * H, 2 * W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+    y = _out_nhwc(x, C, 2 * H, 2 * W)
     with torch.cuda.device(x.device):
         _check(lib().upsample2x_nhwc_f32(x.data_ptr(), y.data_ptr(), B, H, W, C, _stream()), "upsample2x_nhwc_f32")
     return y
