@@ -198,6 +198,42 @@ def test_fused_groupnorm_transforms_bit_identical_on_the_f16_routes():
 
 
 @pytest.mark.convstack
+def test_fused_groupnorm_consumers_equal_gn_apply_then_their_plain_twins():
+    """One statistics tensor, no pending bias: a consumer with the GroupNorm fused in writes the bits of gn_apply followed by its
+    plain twin.  Asserted with torch.equal for three pairs: the fp32 operand V of wino_in_gn_nhwc_f32 and wino4_in_gn_nhwc_f32
+    (the f16 operands are covered above), compared as written, image borders included (12 x 20 pixels), with and without SiLU;
+    and conv1x1_gn_f16x3 against conv1x1_f16x3 of gn_apply(silu=False) at the same operand scale (8 x 32 pixels: the 1x1
+    kernel's rows are 32 pixels wide).  None is gated against fp64 instead."""
+    from pit_hip import _lib
+
+    torch.manual_seed(15)
+    C, eps = 128, 1e-6
+    norm = torch.nn.GroupNorm(32, C, eps=eps).to(DEV)
+    with torch.no_grad():
+        norm.weight.normal_(); norm.bias.normal_()
+        L = _lib.lib()
+        x = (3 * torch.randn(2, C, 12, 20)).to(DEV).contiguous(memory_format=torch.channels_last)
+        stats = _lib.gn_stats(x, 32)
+        for silu in (True, False):
+            xn = _lib.gn_apply(x, norm.weight, norm.bias, 32, eps, silu, stats)
+            for t in (2, 4):
+                shape = ((t + 2) ** 2, 2 * (12 // t) * (20 // t), C)
+                fused, plain = torch.empty(shape, device=DEV), torch.empty(shape, device=DEV)
+                _lib._wino_in(L, x, fused, (norm.weight, norm.bias, 32, eps, silu, stats, None), t, 0, 1.0)
+                _lib._wino_in(L, xn, plain, None, t, 0, 1.0)
+                assert torch.equal(fused, plain), (t, silu, float((fused - plain).abs().max()))
+        conv = torch.nn.Conv2d(C, 128, 1).to(DEV).to(memory_format=torch.channels_last)
+        x = (3 * torch.randn(2, C, 8, 32)).to(DEV).contiguous(memory_format=torch.channels_last)
+        stats = _lib.gn_stats(x, 32)
+        xn = _lib.gn_apply(x, norm.weight, norm.bias, 32, eps, False, stats)
+        wf, us = _lib.conv3_weights_f16(conv.weight)
+        bound = float(xn.abs().max())
+        fused = _lib.conv1x1_direct(x, wf, us, bound, bias=conv.bias, gn=(norm.weight, norm.bias, 32, eps, False, stats, None))
+        plain = _lib.conv1x1_direct(xn, wf, us, bound, bias=conv.bias)
+        assert torch.equal(fused, plain), float((fused - plain).abs().max())
+
+
+@pytest.mark.convstack
 def test_silu_is_accurate_and_finite_at_the_extremes():
     """libgqhip's one SiLU (Newton-refined reciprocal): within 4e-7 relative of fp64 on ordinary inputs; -0 / x at the
     ends of the range (e^-x overflows for x < -88.7: the IEEE quotient there is -0, and so is ours -- no NaN; where

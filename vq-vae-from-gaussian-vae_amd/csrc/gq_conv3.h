@@ -203,16 +203,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
     const int groups = cin / pp.cpg_in;
     const double n = (double)pp.cpg_in * (double)H * (double)W;
     for (int ch = tid; ch < cin; ch += 256) {
-      const int g = ch / pp.cpg_in;
-      double st_s, st_ss;
-      stat_load(pp.stats_in + kStatWords * (t.b * groups + g), st_s, st_ss);
-      const double mean = st_s / n;
-      double var = st_ss / n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      const double rstd = 1.0 / sqrt(var + pp.eps);
-      const double pbk = pp.pre_bias ? (double)pp.pre_bias[ch] : 0.0;
-      sAff[0][ch] = (float)(rstd * (double)pp.gamma[ch]);
-      sAff[1][ch] = (float)((double)pp.beta[ch] + (pbk - mean) * rstd * (double)pp.gamma[ch]);
+      const GnAffine f = gn_channel(gn_group(pp.stats_in + kStatWords * (t.b * groups + ch / pp.cpg_in), n, pp.eps), pp.gamma, pp.beta, pp.pre_bias, ch);
+      sAff[0][ch] = f.a;
+      sAff[1][ch] = f.sh;
     }
   }
   // loader bookkeeping: thread -> channel quad w = tid & 3 of patch pixels q = (tid >> 2) + 64 i (i < 6, q < 340)
@@ -226,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
     const int R = q / kC3PW, px = q % kC3PW;
     const int gy = t.y0 - 1 + R, gx = t.x0 - 1 + px;
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-    const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), cx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+    const int cy = clamp_index(gy, H), cx = clamp_index(gx, W);
     goff[i] = (cy * W + cx) * cin + 4 * w;                      // floats, within the image
     inb |= (unsigned)(in ? 1 : 0) << i;
   }
@@ -376,7 +369,7 @@ struct Conv1Params {
 //          2 x 16 KB) for grids that leave the chip under-filled with 256-pixel tiles (gqhip_unet.hip: conv1_tile_rows);
 //          two blocks per CU either way.
 //   GN     the input is GroupNorm(x + pre_bias) without SiLU: the folded scale and shift of the image's channels are
-//          computed into LDS by the prologue -- the fp64 expressions of conv3x3_gn_f16x3_kernel and gn_apply_nhwc_kernel --
+//          computed into LDS by the prologue (gq_stats.h: gn_group / gn_channel, the fold every consumer shares)
 //          and gn_act<0> is applied in convert(): the normalised tensor is never written (cin <= 512).
 //   SPLIT  the epilogue writes Q3 / K3 / V3 instead of y (COUT = 0: cout = 3 C at run time, C % 128 == 0, so a block's 128
 //          columns lie wholly inside q, k or v); no residual, no statistics.
@@ -405,16 +398,9 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
     const int groups = cin / pp.cpg_in;
     const double n = (double)pp.cpg_in * (double)p.H * 32.0;
     for (int ch = tid; ch < cin; ch += 256) {
-      const int g = ch / pp.cpg_in;
-      double st_s, st_ss;
-      stat_load(pp.stats_in + kStatWords * (t.b * groups + g), st_s, st_ss);
-      const double mean = st_s / n;
-      double var = st_ss / n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      const double rstd = 1.0 / sqrt(var + pp.eps);
-      const double pbk = pp.pre_bias ? (double)pp.pre_bias[ch] : 0.0;
-      sAff[0][ch] = (float)(rstd * (double)pp.gamma[ch]);
-      sAff[1][ch] = (float)((double)pp.beta[ch] + (pbk - mean) * rstd * (double)pp.gamma[ch]);
+      const GnAffine f = gn_channel(gn_group(pp.stats_in + kStatWords * (t.b * groups + ch / pp.cpg_in), n, pp.eps), pp.gamma, pp.beta, pp.pre_bias, ch);
+      sAff[0][ch] = f.a;
+      sAff[1][ch] = f.sh;
     }
   }
   // loader: thread -> channel quad w8 = tid & 7 of the stage's 32 channels, rows (tid >> 3) + 32 i
@@ -819,16 +805,9 @@ __global__ __launch_bounds__(256) void conv3x3_gn_small_kernel(const float *__re
     const int groups = C / cpg;
     const double n = (double)cpg * (double)H * (double)W;
     for (int ch = tid; ch < C; ch += 256) {
-      const int g = ch / cpg;
-      double st_s, st_ss;
-      stat_load(stats + kStatWords * (b * groups + g), st_s, st_ss);
-      const double mean = st_s / n;
-      double var = st_ss / n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      const double rstd = 1.0 / sqrt(var + eps);
-      const double pbk = pre_bias ? (double)pre_bias[ch] : 0.0;
-      sAff[0][ch] = (float)(rstd * (double)gamma[ch]);
-      sAff[1][ch] = (float)((double)beta[ch] + (pbk - mean) * rstd * (double)gamma[ch]);
+      const GnAffine f = gn_channel(gn_group(stats + kStatWords * (b * groups + ch / cpg), n, eps), gamma, beta, pre_bias, ch);
+      sAff[0][ch] = f.a;
+      sAff[1][ch] = f.sh;
     }
   }
   float acc[COUT];
@@ -843,7 +822,7 @@ __global__ __launch_bounds__(256) void conv3x3_gn_small_kernel(const float *__re
       const int R = px / PW, X = px % PW;
       const int gy = y0 - 1 + R, gx = x0 - 1 + X;
       const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-      const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), cx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
+      const int cy = clamp_index(gy, H), cx = clamp_index(gx, W);
       const f32x4 v = *reinterpret_cast<const f32x4 *>(xb + ((long)cy * W + cx) * C + c0 + 4 * q);
       const f32x4 a4 = *reinterpret_cast<const f32x4 *>(&sAff[0][c0 + 4 * q]);
       const f32x4 sh4 = *reinterpret_cast<const f32x4 *>(&sAff[1][c0 + 4 * q]);

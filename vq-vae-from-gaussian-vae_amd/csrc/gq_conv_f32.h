@@ -69,16 +69,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_f32_ksplit_kernel(const ConvF3
     const int groups = C / p.cpg;
     const double n = (double)p.cpg * (double)p.H * (double)p.W;
     for (int ch = tid; ch < C; ch += 256) {
-      const int g = ch / p.cpg;
-      double st_s, st_ss;
-      stat_load(p.stats + kStatWords * (b * groups + g), st_s, st_ss);
-      const double mean = st_s / n;
-      double var = st_ss / n - mean * mean;
-      var = var > 0.0 ? var : 0.0;
-      const double rstd = 1.0 / sqrt(var + p.eps);
-      const double pbk = p.pre_bias ? (double)p.pre_bias[ch] : 0.0;
-      sAff[0][ch] = (float)(rstd * (double)p.gamma[ch]);
-      sAff[1][ch] = (float)((double)p.beta[ch] + (pbk - mean) * rstd * (double)p.gamma[ch]);
+      const GnAffine f = gn_channel(gn_group(p.stats + kStatWords * (b * groups + ch / p.cpg), n, p.eps), p.gamma, p.beta, p.pre_bias, ch);
+      sAff[0][ch] = f.a;
+      sAff[1][ch] = f.sh;
     }
     __syncthreads();
   }

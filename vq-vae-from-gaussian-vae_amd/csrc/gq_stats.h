@@ -154,4 +154,32 @@ __device__ __forceinline__ void stat_load(const int64_t *rec, double &s, double 
   }
 }
 
+// ---- the GroupNorm fold: THE definition every consumer of a record calls, so the fused consumers (Winograd input
+// transforms, direct convolutions) and gn_apply + their plain twins see the same bits of a and sh by construction.
+// Record -> (mean, rstd) of the group's n values: fp64, the variance clamped at zero, eps inside the root.
+struct GnGroup {
+  double mean, rstd;
+};
+__device__ __forceinline__ GnGroup gn_group(const int64_t *rec, double n, double eps) {
+  double s, ss;
+  stat_load(rec, s, ss);
+  const double mean = s / n;
+  double var = ss / n - mean * mean;
+  var = var > 0.0 ? var : 0.0;
+  return {mean, 1.0 / sqrt(var + eps)};
+}
+// Channel c: y = a x + sh is gamma (x + pre_bias - mean) rstd + beta (pre_bias nullable: a bias still pending on x).  Every
+// operation in fp64 (-ffp-contract=off: no fused multiply-add), one rounding to fp32 each; the order is load pre_bias, a, sh.
+struct GnAffine {
+  float a, sh;
+};
+__device__ __forceinline__ GnAffine gn_channel(const GnGroup g, const float *gamma, const float *beta, const float *pre_bias,
+                                               int c) {
+  const double pbk = pre_bias ? (double)pre_bias[c] : 0.0;
+  GnAffine f;
+  f.a = (float)(g.rstd * (double)gamma[c]);
+  f.sh = (float)((double)beta[c] + (pbk - g.mean) * g.rstd * (double)gamma[c]);
+  return f;
+}
+
 }  // namespace gqhip

@@ -22,6 +22,18 @@ __device__ __forceinline__ float silu_f32(float x) {
   return d > 1e37f ? q : q1;
 }
 
+// SiLU(GroupNorm(x)) of a thread's channels: a, sh = the folded per-channel scale and shift (gq_stats.h: gn_channel).  EVERY
+// consumer of a GroupNorm applies them through this function -- gn_apply as its own pass and every kernel with the producer
+// fused in -- so the fused transforms write bit-for-bit the V of the two-pass route.
+template <int SILU, typename VEC>
+__device__ __forceinline__ VEC gn_act(VEC v, VEC a, VEC sh) {
+  v = v * a + sh;
+  if (SILU) {
+#pragma unroll
+    for (int e = 0; e < (int)(sizeof(VEC) / sizeof(float)); ++e) v[e] = silu_f32(v[e]);
+  }
+  return v;
+}
 // ---- NHWC (channels_last) variants: x[b][hw][c], the layout MIOpen's fp32 igemm kernels want ----
 // A block owns a slab of pixels of one image and ALL channels: thread -> channel quad q = tid % (C/4)
 // (4 consecutive channels of ONE group since cpg % 4 == 0), pixel lane = tid / (C/4).
@@ -62,33 +74,18 @@ __global__ __launch_bounds__(256) void gn_apply_nhwc_kernel(const float *__restr
   const long lo = slab * per, hi = lo + per < HW ? lo + per : HW;
   const int q = threadIdx.x % quads, pl = threadIdx.x / quads;
   const int g = (4 * q) / cpg;
-  const double n = (double)cpg * (double)HW;
-  double st_s, st_ss;
-  stat_load(stats + kStatWords * (b * groups + g), st_s, st_ss);
-  const double mean = st_s / n;
-  double var = st_ss / n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + eps);
+  const GnGroup gg = gn_group(stats + kStatWords * (b * groups + g), (double)cpg * (double)HW, eps);
   f32x4 a, sh;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int c = 4 * q + k;
-    const double pbk = pre_bias ? (double)pre_bias[c] : 0.0;
-    a[k] = (float)(rstd * (double)gamma[c]);
-    sh[k] = (float)((double)beta[c] + (pbk - mean) * rstd * (double)gamma[c]);
+    const GnAffine f = gn_channel(gg, gamma, beta, pre_bias, 4 * q + k);
+    a[k] = f.a;
+    sh[k] = f.sh;
   }
   const float *xi = x + (b * HW) * C + 4 * q;
   float *yo = y + (b * HW) * C + 4 * q;
-  for (long p = lo + pl; p < hi; p += lanes) {
-    f32x4 v = *reinterpret_cast<const f32x4 *>(xi + p * C) * a + sh;
-    if (SILU) {
-      v.x = silu_f32(v.x);
-      v.y = silu_f32(v.y);
-      v.z = silu_f32(v.z);
-      v.w = silu_f32(v.w);
-    }
-    *reinterpret_cast<f32x4 *>(yo + p * C) = v;
-  }
+  for (long p = lo + pl; p < hi; p += lanes)
+    *reinterpret_cast<f32x4 *>(yo + p * C) = gn_act<SILU>(*reinterpret_cast<const f32x4 *>(xi + p * C), a, sh);
 }
 
 __global__ __launch_bounds__(256) void add_bias_nhwc_kernel(const float *__restrict__ a, const float *__restrict__ b,
@@ -194,166 +191,20 @@ __device__ __forceinline__ void wino_store_v(void *V, int k, long tiles, long ti
   }
 }
 
-template <int F16X3>
-__global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
-                                                           int C4, long tiles, long total, float scale) {
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const int q = (int)(t % C4);
-    const long tile = t / C4;
-    const int tw = (int)(tile % (W / 2));
-    const long r = tile / (W / 2);
-    const int th = (int)(r % (H / 2));
-    const long b = r / (H / 2);
-    f32x4 d[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sy = 2 * th - 1 + i, sx = 2 * tw - 1 + j;
-        d[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (sy >= 0 && sy < H && sx >= 0 && sx < W)
-          d[i][j] = reinterpret_cast<const f32x4 *>(x)[((b * H + sy) * W + sx) * C4 + q];
-      }
-    f32x4 w[4][4];   // B^T d
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      w[0][j] = d[0][j] - d[2][j];
-      w[1][j] = d[1][j] + d[2][j];
-      w[2][j] = d[2][j] - d[1][j];
-      w[3][j] = d[1][j] - d[3][j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {   // (B^T d) B
-      wino_store_v<F16X3>(V, 4 * i + 0, tiles, tile, C4, q, w[i][0] - w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 1, tiles, tile, C4, q, w[i][1] + w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 2, tiles, tile, C4, q, w[i][2] - w[i][1], scale);
-      wino_store_v<F16X3>(V, 4 * i + 3, tiles, tile, C4, q, w[i][1] - w[i][3], scale);
-    }
-  }
-}
-
-// SiLU(GroupNorm(x)) of four channels: a, sh = the folded per-channel scale and shift.  The same arithmetic as
-// gn_apply_nhwc_kernel, so the fused transforms write bit-for-bit the V of the two-pass route.
-template <int SILU, typename VEC>
-__device__ __forceinline__ VEC gn_act(VEC v, VEC a, VEC sh) {
-  v = v * a + sh;
-  if (SILU) {
-#pragma unroll
-    for (int e = 0; e < (int)(sizeof(VEC) / sizeof(float)); ++e) v[e] = silu_f32(v[e]);
-  }
-  return v;
-}
-
-// Input transform with the producer fused in: the conv input is GroupNorm(+SiLU) of x (unet.py:140-142, :146-149), so
-// the normalisation is applied to the 16 loaded values on the fly (statistics from gn_stats / add_bias_stats) and the
-// normalised tensor is never written: saves gn_apply's write and this kernel's read of it.  Zero padding applies to the
-// ACTIVATED tensor, so out-of-bounds taps stay exactly 0.
-template <int SILU, int F16X3>
-__global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta,
-                                                              const float *__restrict__ pre_bias,
-                                                              const int64_t *__restrict__ stats, void *__restrict__ V,
-                                                              int H, int W, int C4, int cpg, double eps, long tiles,
-                                                              long total, float scale) {
-  const int groups = 4 * C4 / cpg;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const int q = (int)(t % C4);
-    const long tile = t / C4;
-    const int tw = (int)(tile % (W / 2));
-    const long r = tile / (W / 2);
-    const int th = (int)(r % (H / 2));
-    const long b = r / (H / 2);
-    const int g = (4 * q) / cpg;
-    const double n = (double)cpg * (double)H * (double)W;
-    double st_s, st_ss;
-    stat_load(stats + kStatWords * (b * groups + g), st_s, st_ss);
-    const double mean = st_s / n;
-    double var = st_ss / n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
-    f32x4 a, sh;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = 4 * q + k;
-      const double pbk = pre_bias ? (double)pre_bias[c] : 0.0;
-      a[k] = (float)(rstd * (double)gamma[c]);
-      sh[k] = (float)((double)beta[c] + (pbk - mean) * rstd * (double)gamma[c]);
-    }
-    f32x4 d[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        // no branch around the load: the 16 loads must all be in flight before the first activation (with the
-        // activation inside an `if` hipcc keeps 16 load -> wait -> compute rounds: measured 965 vs 765 us); taps outside
-        // the image read a clamped address and are zeroed afterwards
-        const int sy = 2 * th - 1 + i, sx = 2 * tw - 1 + j;
-        const int cy = sy < 0 ? 0 : (sy >= H ? H - 1 : sy), cx = sx < 0 ? 0 : (sx >= W ? W - 1 : sx);
-        d[i][j] = reinterpret_cast<const f32x4 *>(x)[((b * H + cy) * W + cx) * C4 + q];
-      }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int sy = 2 * th - 1 + i, sx = 2 * tw - 1 + j;
-        const float inb = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? 1.f : 0.f;
-        d[i][j] = gn_act<SILU>(d[i][j], a, sh) * inb;
-      }
-    f32x4 w[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      w[0][j] = d[0][j] - d[2][j];
-      w[1][j] = d[1][j] + d[2][j];
-      w[2][j] = d[2][j] - d[1][j];
-      w[3][j] = d[1][j] - d[3][j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      wino_store_v<F16X3>(V, 4 * i + 0, tiles, tile, C4, q, w[i][0] - w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 1, tiles, tile, C4, q, w[i][1] + w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 2, tiles, tile, C4, q, w[i][2] - w[i][1], scale);
-      wino_store_v<F16X3>(V, 4 * i + 3, tiles, tile, C4, q, w[i][1] - w[i][3], scale);
-    }
-  }
-}
-
-// `mscale`: M came out of a GEMM on scaled operands (the f16x3 path): y = mscale * (A^T M A); 1 otherwise (a power of two).
-__global__ __launch_bounds__(256) void wino_out_nhwc_kernel(const float *__restrict__ M, float *__restrict__ y, int H, int W,
-                                                            int C4, long tiles, long total, float mscale) {
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const int q = (int)(t % C4);
-    const long tile = t / C4;
-    const int tw = (int)(tile % (W / 2));
-    const long r = tile / (W / 2);
-    const int th = (int)(r % (H / 2));
-    const long b = r / (H / 2);
-    const f32x4 *mi = reinterpret_cast<const f32x4 *>(M) + tile * C4 + q;
-    const long plane = tiles * C4;
-    f32x4 m[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) m[i][j] = mi[(4 * i + j) * plane];
-    f32x4 u[2][4];   // A^T m
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      u[0][j] = m[0][j] + m[1][j] + m[2][j];
-      u[1][j] = m[1][j] - m[2][j] - m[3][j];
-    }
-    f32x4 *o = reinterpret_cast<f32x4 *>(y) + ((b * H + 2 * th) * W + 2 * tw) * C4 + q;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      o[(long)i * W * C4] = (u[i][0] + u[i][1] + u[i][2]) * mscale;
-      o[(long)i * W * C4 + C4] = (u[i][1] - u[i][2] - u[i][3]) * mscale;
-    }
-  }
-}
-
 // ---- Winograd F(4x4, 3x3): 6x6 input tiles (stride 4), 36 GEMMs, 4x4 output tiles: 36 multiplies per 16 outputs (4x
 // fewer than direct, 1.78x fewer than F(2x2,3x3)) and V / M are 2.25x the activation instead of 4x.  Larger transform
 // constants (up to 8) cost ~10x the rounding error of F(2x2,3x3): used in the decoder only.
 //   B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
 //   A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
+//
+// ---- The pieces the seven transform kernels share.  T = 2: F(2x2,3x3), 4: F(4x4,3x3); N = T + 2 = the transform size.
+// The 1-D transforms of one column or row: A^T m of both sizes (wino_at<T>) and F(4x4,3x3)'s B^T d; F(2x2,3x3)'s B^T d is
+// written out in its two input kernels, each value formed in its store's argument (fewer registers: profiles/r17).
+template <typename V>
+__device__ __forceinline__ void wino2_at(const V (&m)[4], V (&o)[2]) {
+  o[0] = m[0] + m[1] + m[2];
+  o[1] = m[1] - m[2] - m[3];
+}
 template <typename V>
 __device__ __forceinline__ void wino4_bt(const V (&d)[6], V (&o)[6]) {
   o[0] = 4.f * d[0] - 5.f * d[2] + d[4];
@@ -371,28 +222,140 @@ __device__ __forceinline__ void wino4_at(const V (&m)[6], V (&o)[4]) {
   o[2] = s12 + 4.f * s34;
   o[3] = d12 + 8.f * d34 + m[5];
 }
+template <int T, typename V>
+__device__ __forceinline__ void wino_at(const V (&m)[T + 2], V (&o)[T]) {
+  if constexpr (T == 4) wino4_at(m, o); else wino2_at(m, o);
+}
+
+// Item t of a grid-stride transform -> channel vector q (of CV per pixel) of tile (b, th, tw); `tile` counts over all images.
+struct WinoTile {
+  int q, th, tw;
+  long tile, b;
+};
+template <int T>
+__device__ __forceinline__ WinoTile wino_tile(long t, int CV, int H, int W) {
+  WinoTile w;
+  w.q = (int)(t % CV);
+  w.tile = t / CV;
+  w.tw = (int)(w.tile % (W / T));
+  const long r = w.tile / (W / T);
+  w.th = (int)(r % (H / T));
+  w.b = r / (H / T);
+  return w;
+}
+
+// The four input transforms keep a loop body each, so that hipcc keeps all loads of a tile (F(4x4,3x3): of all columns) in
+// flight: do not wrap the gather in a function shared by the plain and the fused kernels (profiles/r17).
+template <int F16X3>
+__global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
+                                                           int C4, long tiles, long total, float scale) {
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const WinoTile wt = wino_tile<2>(t, C4, H, W);
+    f32x4 d[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sy = 2 * wt.th - 1 + i, sx = 2 * wt.tw - 1 + j;
+        d[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (sy >= 0 && sy < H && sx >= 0 && sx < W)
+          d[i][j] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + sy) * W + sx) * C4 + wt.q];
+      }
+    f32x4 w[4][4];   // B^T d
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[0][j] = d[0][j] - d[2][j];
+      w[1][j] = d[1][j] + d[2][j];
+      w[2][j] = d[2][j] - d[1][j];
+      w[3][j] = d[1][j] - d[3][j];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {   // (B^T d) B, each value stored as it is formed
+      wino_store_v<F16X3>(V, 4 * i + 0, tiles, wt.tile, C4, wt.q, w[i][0] - w[i][2], scale);
+      wino_store_v<F16X3>(V, 4 * i + 1, tiles, wt.tile, C4, wt.q, w[i][1] + w[i][2], scale);
+      wino_store_v<F16X3>(V, 4 * i + 2, tiles, wt.tile, C4, wt.q, w[i][2] - w[i][1], scale);
+      wino_store_v<F16X3>(V, 4 * i + 3, tiles, wt.tile, C4, wt.q, w[i][1] - w[i][3], scale);
+    }
+  }
+}
+
+// Input transform with the producer fused in: the conv input is GroupNorm(+SiLU) of x (unet.py:140-142, :146-149), so
+// the normalisation is applied to the 16 loaded values on the fly (statistics from gn_stats / add_bias_stats) and the
+// normalised tensor is never written: saves gn_apply's write and this kernel's read of it.  Zero padding applies to the
+// ACTIVATED tensor, so out-of-bounds taps stay exactly 0.
+template <int SILU, int F16X3>
+__global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta,
+                                                              const float *__restrict__ pre_bias,
+                                                              const int64_t *__restrict__ stats, void *__restrict__ V,
+                                                              int H, int W, int C4, int cpg, double eps, long tiles,
+                                                              long total, float scale) {
+  const int groups = 4 * C4 / cpg;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const WinoTile wt = wino_tile<2>(t, C4, H, W);
+    const int g = (4 * wt.q) / cpg;
+    const GnGroup gg = gn_group(stats + kStatWords * (wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
+    f32x4 a, sh;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const GnAffine f = gn_channel(gg, gamma, beta, pre_bias, 4 * wt.q + k);
+      a[k] = f.a;
+      sh[k] = f.sh;
+    }
+    f32x4 d[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // no branch around the load: the 16 loads must all be in flight before the first activation (with the
+        // activation inside an `if` hipcc keeps 16 load -> wait -> compute rounds: measured 965 vs 765 us); taps outside
+        // the image read a clamped address and are zeroed afterwards
+        const int sy = 2 * wt.th - 1 + i, sx = 2 * wt.tw - 1 + j;
+        const int cy = clamp_index(sy, H), cx = clamp_index(sx, W);
+        d[i][j] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + cy) * W + cx) * C4 + wt.q];
+      }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int sy = 2 * wt.th - 1 + i, sx = 2 * wt.tw - 1 + j;
+        const float inb = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? 1.f : 0.f;
+        d[i][j] = gn_act<SILU>(d[i][j], a, sh) * inb;
+      }
+    f32x4 w[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[0][j] = d[0][j] - d[2][j];
+      w[1][j] = d[1][j] + d[2][j];
+      w[2][j] = d[2][j] - d[1][j];
+      w[3][j] = d[1][j] - d[3][j];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      wino_store_v<F16X3>(V, 4 * i + 0, tiles, wt.tile, C4, wt.q, w[i][0] - w[i][2], scale);
+      wino_store_v<F16X3>(V, 4 * i + 1, tiles, wt.tile, C4, wt.q, w[i][1] + w[i][2], scale);
+      wino_store_v<F16X3>(V, 4 * i + 2, tiles, wt.tile, C4, wt.q, w[i][2] - w[i][1], scale);
+      wino_store_v<F16X3>(V, 4 * i + 3, tiles, wt.tile, C4, wt.q, w[i][1] - w[i][3], scale);
+    }
+  }
+}
 
 template <int F16X3>
 __global__ __launch_bounds__(256) void wino4_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
                                                             int C4, long tiles, long total, float scale) {
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const int q = (int)(t % C4);
-    const long tile = t / C4;
-    const int tw = (int)(tile % (W / 4));
-    const long r = tile / (W / 4);
-    const int th = (int)(r % (H / 4));
-    const long b = r / (H / 4);
+    const WinoTile wt = wino_tile<4>(t, C4, H, W);
     f32x4 w[6][6];   // B^T d, column by column
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       f32x4 col[6], o[6];
-      const int sx = 4 * tw - 1 + j;
+      const int sx = 4 * wt.tw - 1 + j;
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int sy = 4 * th - 1 + i;
+        const int sy = 4 * wt.th - 1 + i;
         col[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (sy >= 0 && sy < H && sx >= 0 && sx < W)
-          col[i] = reinterpret_cast<const f32x4 *>(x)[((b * H + sy) * W + sx) * C4 + q];
+          col[i] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + sy) * W + sx) * C4 + wt.q];
       }
       wino4_bt(col, o);
 #pragma unroll
@@ -403,7 +366,7 @@ __global__ __launch_bounds__(256) void wino4_in_nhwc_kernel(const float *__restr
       f32x4 o[6];
       wino4_bt(w[i], o);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, tile, C4, q, o[j], scale);
+      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, wt.tile, C4, wt.q, o[j], scale);
     }
   }
 }
@@ -422,42 +385,30 @@ __global__ __launch_bounds__(256) void wino4_in_gn_nhwc_kernel(const float *__re
   typedef float vec __attribute__((ext_vector_type(VW)));
   const int groups = VW * CV / cpg;
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const int q = (int)(t % CV);
-    const long tile = t / CV;
-    const int tw = (int)(tile % (W / 4));
-    const long r = tile / (W / 4);
-    const int th = (int)(r % (H / 4));
-    const long b = r / (H / 4);
-    const int g = (VW * q) / cpg;
-    const double n = (double)cpg * (double)H * (double)W;
-    double st_s, st_ss;
-    stat_load(stats + kStatWords * (b * groups + g), st_s, st_ss);
-    const double mean = st_s / n;
-    double var = st_ss / n - mean * mean;
-    var = var > 0.0 ? var : 0.0;
-    const double rstd = 1.0 / sqrt(var + eps);
+    const WinoTile wt = wino_tile<4>(t, CV, H, W);
+    const int g = (VW * wt.q) / cpg;
+    const GnGroup gg = gn_group(stats + kStatWords * (wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
     vec a, sh;
 #pragma unroll
     for (int k = 0; k < VW; ++k) {
-      const int c = VW * q + k;
-      const double pbk = pre_bias ? (double)pre_bias[c] : 0.0;
-      a[k] = (float)(rstd * (double)gamma[c]);
-      sh[k] = (float)((double)beta[c] + (pbk - mean) * rstd * (double)gamma[c]);
+      const GnAffine f = gn_channel(gg, gamma, beta, pre_bias, VW * wt.q + k);
+      a[k] = f.a;
+      sh[k] = f.sh;
     }
     vec w[6][6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       vec col[6], o[6];
-      const int sx = 4 * tw - 1 + j;
+      const int sx = 4 * wt.tw - 1 + j;
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int sy = 4 * th - 1 + i;   // branch-free: see wino_in_gn_nhwc_kernel
-        const int cy = sy < 0 ? 0 : (sy >= H ? H - 1 : sy), cx = sx < 0 ? 0 : (sx >= W ? W - 1 : sx);
-        col[i] = reinterpret_cast<const vec *>(x)[((b * H + cy) * W + cx) * CV + q];
+        const int sy = 4 * wt.th - 1 + i;   // branch-free: see wino_in_gn_nhwc_kernel
+        const int cy = clamp_index(sy, H), cx = clamp_index(sx, W);
+        col[i] = reinterpret_cast<const vec *>(x)[((wt.b * H + cy) * W + cx) * CV + wt.q];
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int sy = 4 * th - 1 + i;
+        const int sy = 4 * wt.th - 1 + i;
         const float inb = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? 1.f : 0.f;
         col[i] = gn_act<SILU>(col[i], a, sh) * inb;
       }
@@ -470,11 +421,54 @@ __global__ __launch_bounds__(256) void wino4_in_gn_nhwc_kernel(const float *__re
       vec o[6];
       wino4_bt(w[i], o);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, tile, CV, q, o[j], scale);
+      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, wt.tile, CV, wt.q, o[j], scale);
     }
   }
 }
 
+// "Load M, A^T M" of one output tile, shared by the three output transforms: the N x N values M of the tile (mi = its channel
+// vector in plane 0, `plane` vectors per plane) -> u = A^T M; the caller finishes y = u A row by row (wino_at on u[i]) as it
+// stores.  NJ = columns of M loaded before they are transformed: all N in the plain F(2x2,3x3) kernel, 1 (column by column)
+// elsewhere -- the order each kernel had, which is the order hipcc schedules by.
+template <int T, int NJ, typename VEC>
+__device__ __forceinline__ void wino_out_cols(const VEC *mi, long plane, VEC (&u)[T][T + 2]) {
+  constexpr int N = T + 2;
+#pragma unroll
+  for (int j0 = 0; j0 < N; j0 += NJ) {
+    VEC m[NJ][N];   // NJ columns
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) m[j][i] = mi[(N * i + j0 + j) * plane];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      VEC o[T];
+      wino_at<T>(m[j], o);
+#pragma unroll
+      for (int i = 0; i < T; ++i) u[i][j0 + j] = o[i];
+    }
+  }
+}
+
+// The plain output transforms.  `mscale`: M came out of a GEMM on scaled operands (the f16x3 path): y = mscale * (A^T M A);
+// 1 otherwise (a power of two).
+__global__ __launch_bounds__(256) void wino_out_nhwc_kernel(const float *__restrict__ M, float *__restrict__ y, int H, int W,
+                                                            int C4, long tiles, long total, float mscale) {
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const WinoTile wt = wino_tile<2>(t, C4, H, W);
+    f32x4 u[2][4];   // A^T m
+    wino_out_cols<2, 4>(reinterpret_cast<const f32x4 *>(M) + wt.tile * C4 + wt.q, tiles * C4, u);
+    f32x4 *out = reinterpret_cast<f32x4 *>(y) + ((wt.b * H + 2 * wt.th) * W + 2 * wt.tw) * C4 + wt.q;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      f32x4 o[2];
+      wino2_at(u[i], o);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) out[((long)i * W + j) * C4] = o[j] * mscale;
+    }
+  }
+}
+// (decode written out: wino_tile costs this kernel, at 254 VGPRs, a scalar register -- profiles/r17)
 __global__ __launch_bounds__(256) void wino4_out_nhwc_kernel(const float *__restrict__ M, float *__restrict__ y, int H, int W,
                                                              int C4, long tiles, long total, float mscale) {
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
@@ -486,16 +480,8 @@ __global__ __launch_bounds__(256) void wino4_out_nhwc_kernel(const float *__rest
     const long b = r / (H / 4);
     const f32x4 *mi = reinterpret_cast<const f32x4 *>(M) + tile * C4 + q;
     const long plane = tiles * C4;
-    f32x4 u[4][6];   // A^T m, column by column
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      f32x4 col[6], o[4];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) col[i] = mi[(6 * i + j) * plane];
-      wino4_at(col, o);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) u[i][j] = o[i];
-    }
+    f32x4 u[4][6];   // A^T m
+    wino_out_cols<4, 1>(mi, plane, u);
     f32x4 *out = reinterpret_cast<f32x4 *>(y) + ((b * H + 4 * th) * W + 4 * tw) * C4 + q;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -520,7 +506,6 @@ __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__r
                                                                 int64_t *__restrict__ stats, int H, int W, int CV,
                                                                 int cpg, long tiles, int slabs, float mscale) {
   typedef float vec __attribute__((ext_vector_type(VW)));
-  constexpr int NI = T + 2;   // transform size (4 or 6)
   __shared__ int64_t red[kStatWords * 64];   // per-group statistics records (gq_stats.h)
   const int groups = VW * CV / cpg, lanes = 256 / CV;
   const long b = blockIdx.x / slabs;
@@ -551,31 +536,12 @@ __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__r
 #pragma unroll
         for (int j = 0; j < T; ++j) r[i][j] = (vec)(0.f);
     }
-    vec u[T][NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      if constexpr (T == 4) {
-        vec col[6], o[4];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) col[i] = mi[(6 * i + j) * plane];
-        wino4_at(col, o);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) u[i][j] = o[i];
-      } else {
-        const vec m0 = mi[(0 + j) * plane], m1 = mi[(4 + j) * plane], m2 = mi[(8 + j) * plane], m3 = mi[(12 + j) * plane];
-        u[0][j] = m0 + m1 + m2;
-        u[1][j] = m1 - m2 - m3;
-      }
-    }
+    vec u[T][T + 2];
+    wino_out_cols<T, 1>(mi, plane, u);
 #pragma unroll
     for (int i = 0; i < T; ++i) {
       vec o[T];
-      if constexpr (T == 4) {
-        wino4_at(u[i], o);
-      } else {
-        o[0] = u[i][0] + u[i][1] + u[i][2];
-        o[1] = u[i][1] - u[i][2] - u[i][3];
-      }
+      wino_at<T>(u[i], o);
 #pragma unroll
       for (int j = 0; j < T; ++j) {
         const long off = pix0 + ((long)i * W + j) * CV;
@@ -680,31 +646,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *__restrict__
   const int c = (int)(row % C);
   const long b = row / C;
   const long bg = b * (C / cpg) + c / cpg;
-  const double n = (double)cpg * (double)HW;
-  double st_s, st_ss;
-  stat_load(stats + kStatWords * bg, st_s, st_ss);
-  const double mean = st_s / n;
-  double var = st_ss / n - mean * mean;
-  var = var > 0.0 ? var : 0.0;
-  const double rstd = 1.0 / sqrt(var + eps);
-  const float a = (float)(rstd * (double)gamma[c]);
-  const double pb = pre_bias ? (double)pre_bias[c] : 0.0;
-  const float sh = (float)((double)beta[c] + (pb - mean) * rstd * (double)gamma[c]);
+  const GnAffine f = gn_channel(gn_group(stats + kStatWords * bg, (double)cpg * (double)HW, eps), gamma, beta, pre_bias, c);
   const long per = ((HW / 4 + segs - 1) / segs) * 4;
   const long lo = seg * per, hi = lo + per < HW ? lo + per : HW;
   const float *xi = x + row * HW;
   float *yo = y + row * HW;
-  for (long i = lo + threadIdx.x * 4; i + 3 < hi; i += 256 * 4) {
-    f32x4 v = *reinterpret_cast<const f32x4 *>(xi + i);
-    v = v * a + sh;
-    if (SILU) {
-      v.x = silu_f32(v.x);
-      v.y = silu_f32(v.y);
-      v.z = silu_f32(v.z);
-      v.w = silu_f32(v.w);
-    }
-    *reinterpret_cast<f32x4 *>(yo + i) = v;
-  }
+  for (long i = lo + threadIdx.x * 4; i + 3 < hi; i += 256 * 4)
+    *reinterpret_cast<f32x4 *>(yo + i) = gn_act<SILU>(*reinterpret_cast<const f32x4 *>(xi + i), (f32x4)(f.a), (f32x4)(f.sh));
 }
 
 // ---- single-head attention of the deepest level (pit/modules/unet.py:185-206) on the fp16 matrix cores, fp32 results:
