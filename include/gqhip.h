@@ -27,6 +27,7 @@
  *                    train()) and the autograd backward of it and of GaussianQuantRegularizer2.forward.
  *   vq_argmin_f32    pit/quantization/vq.py:58-73.
  *   vq_quantize_z_f32 pit/quantization/vq.py:39-96 (VQQuantizer.forward, eval).
+ *   vq_backward_f32  the autograd backward of pit/quantization/vq.py:39-96 (VQQuantizer.forward in train()).
  *   lfq_pack_f32     pit/quantization/lfq.py:147-158.
  *   lfq_unpack_f32   pit/quantization/lfq.py:210-228 (also BSQ: pit/quantization/bsq.py:85-156).
  *   fsq_quantize_f32 / fsq_dequant_f32  pit/quantization/fsq.py:29-89.
@@ -56,7 +57,8 @@ extern "C" {
                                *    statistics and lambda state on the device) and VQQuantizer (vq_quantize_z_f32: layouts, straight-through
                                *    value and codebook loss inside the launches); additive since, the version unchanged: per-image SSIM /
                                *    MS-SSIM (gq_ssim_f32), the three-metric step record (gq_step_record_ssim_f32), the train-mode step of the Gaussian
-                               *    regularizers (gq_gauss_train_f32, gq_gauss_backward_f32) */
+                               *    regularizers (gq_gauss_train_f32, gq_gauss_backward_f32), the backward of VQQuantizer's train step
+                               *    (vq_backward_f32, vq_backward_workspace_bytes) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -284,6 +286,30 @@ int vq_argmin_f32(const float *z, const float *emb, int64_t *idx,
 int vq_quantize_z_f32(const float *z, const float *emb, int64_t *idx, float *zq, float *loss2_or_null, int64_t B, int64_t L,
                       int64_t c, int64_t dim, int64_t n, int layout, double beta, int legacy, void *workspace,
                       int64_t workspace_bytes, void *cb_cache_or_null, int64_t cb_cache_bytes, void *stream);
+
+/* ---- the backward of VQQuantizer.forward's train step (vq.py:78-89; the forward is vq_quantize_z_f32 without a cache) in ONE call.
+ *   z, emb, idx, layouts and the channel rule: vq_quantize_z_f32's.  Item p = (b L + l) K + k, e_p = emb[idx_p], N = B L c;
+ *   (a, b) = (1, beta) when legacy != 0, (beta, 1) otherwise.
+ *   g_zq_or_null (layout of z): the gradient arriving at zq; g_loss_or_null: ONE float on the device (4-byte aligned), the gradient
+ *   arriving at codebook_loss; NULL = zero.
+ *   grad_z_or_null (layout of z) = g_zq + (g_loss a 2 / N) (z - e): the difference in fp32, the rest in fp64, rounded once (the
+ *   straight-through value hands g_zq to z and nothing to e).  16-byte accesses when z, g_zq and grad_z are 16-byte aligned and
+ *   L % 4 == 0 (BCHW) / c % 4 == 0 (BLC), 4-byte accesses otherwise.
+ *   grad_emb_or_null [n, dim], written WHOLE (exact +0.0 for a code no item chose):
+ *       grad_emb[j][d] = (float)((g_loss b 2 / N) * sum over p with idx_p = j, ascending p, of (double)fl32(e_p[d] - z_p[d]))
+ *   with the sum and the product in fp64.  A code chosen by more than 128 items (kVqChunk, csrc/vq_train.h) is summed as partials
+ *   of 128 consecutive items of its ascending list each, added in chunk order.  The order of every sum depends on idx and the
+ *   shape alone: no float atomics, results are bit-identical from run to run.  (Built from a stable radix sort of the items by
+ *   code in the workspace; integer atomics only where their result is order-free.)
+ *   An idx value outside [0, n) is checked before it addresses anything: that item adds nothing to grad_emb, and its elements of
+ *   grad_z are g_zq alone.
+ *   workspace: vq_backward_workspace_bytes(B L K, n, dim) bytes (-1: unsupported shape), 16-byte aligned, contents don't-care on entry -- the call
+ *   rebuilds all of it; NULL or short -> GQHIP_ERR_WORKSPACE.  No items: GQHIP_OK after zeroing grad_emb.  Reads nothing back to
+ *   the host: graph-capturable. */
+int64_t vq_backward_workspace_bytes(int64_t items, int64_t n, int64_t dim);
+int vq_backward_f32(const float *z, const float *emb, const int64_t *idx, const float *g_zq_or_null, const float *g_loss_or_null,
+                    float *grad_z_or_null, float *grad_emb_or_null, int64_t B, int64_t L, int64_t c, int64_t dim, int64_t n,
+                    int layout, double beta, int legacy, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- LFQ: sign quantisation + big-endian bit pack -------------------------- */
 int lfq_pack_f32(const float *x, int64_t *idx, float *q_or_null, int64_t rows,

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""Time one training step (forward + backward) through the Gaussian regularizers alone, on the device.
+"""Time one training step (forward + backward) through the Gaussian regularizers, or through VQQuantizer, alone on the device.
 
     python tools/bench_train_step.py [--root TREE] [--iters 200] [--warmup 20] [--label NAME]
 
 Modules: GaussianQuantRegularizer("bchw", 65536, group=16) in train() and GaussianQuantRegularizer2(16, 65536) under autograd, on
 z = [16, 32, 32, 32] and [16, 32, 64, 64] (gq_0.25 at 256^2 and 512^2), NCHW and channels_last.  A step is
     zhat, info = m(z);  ((zhat * w).sum() + 0.37 * info["kl_loss"]).backward()
+With `--only vq` (VQ cases run only when asked for by name): VQQuantizer("bchw", 65536, 16) in train() with a trained-like codebook
+(codes ~ N(0, 1) * 0.5) on z = [16, 16, 32, 32] and [16, 16, 64, 64] (sd3unet_vq_16 at 256^2 and 512^2), NCHW and channels_last; a step is
+    zq, info = m(z);  ((zq * w).sum() + 0.37 * info["codebook_loss"]).backward()
+with z.grad and embedding.weight.grad both wanted.
 `--iters` timed steps after `--warmup`, in 10 batches, each between two device events (the time between the events includes whatever
 the host makes the device wait for, which is the point: the op-by-op path stops the host three times per step).  Prints one JSON line
 per (module, shape, layout): median / min / max over the batches of the per-step time in microseconds.
@@ -26,7 +30,7 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--label", default="")
-    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'")
+    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'; 'vq' runs the VQ cases instead")
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(a.root, "vq-vae-from-gaussian-vae_amd"))
     import torch
@@ -37,6 +41,48 @@ def main() -> int:
     dev = torch.device("cuda:0")
     batches = 10
     per = max(1, a.iters // batches)
+
+    def timed(step):
+        for _ in range(a.warmup):
+            step()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(batches):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per):
+                step()
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1) * 1e3 / per)
+        return times
+
+    if a.only == "vq":
+        from pit_hip.quantization.vq import VQQuantizer
+
+        for hw in (32, 64):
+            for channels_last in (False, True):
+                g = torch.Generator().manual_seed(hw)
+                z, w = 0.5 * torch.randn(16, 16, hw, hw, generator=g).to(dev), torch.randn(16, 16, hw, hw, generator=g).to(dev)
+                if channels_last:
+                    z, w = z.contiguous(memory_format=torch.channels_last), w.contiguous(memory_format=torch.channels_last)
+                z.requires_grad_(True)
+                m = VQQuantizer("bchw", 65536, 16)
+                m.embedding.weight.data = 0.5 * torch.randn(65536, 16, generator=g)
+                m = m.to(dev).train()
+
+                def step():
+                    z.grad = None
+                    m.embedding.weight.grad = None
+                    zq, info = m(z)
+                    ((zq * w).sum() + 0.37 * info["codebook_loss"]).backward()
+
+                times = timed(step)
+                print(json.dumps({"label": a.label, "module": "vq", "z": [16, 16, hw, hw], "channels_last": channels_last,
+                                  "steps": per * batches, "us_median": round(statistics.median(times), 2),
+                                  "us_min": round(min(times), 2), "us_max": round(max(times), 2),
+                                  "fused": os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"}), flush=True)
+        return 0
     for kind in ("gq1", "gq2"):
         if a.only and a.only not in kind:
             continue
@@ -56,18 +102,7 @@ def main() -> int:
                     zhat, info = m(z)
                     ((zhat * w).sum() + 0.37 * info["kl_loss"]).backward()
 
-                for _ in range(a.warmup):
-                    step()
-                torch.cuda.synchronize()
-                times = []
-                for _ in range(batches):
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(per):
-                        step()
-                    e1.record()
-                    e1.synchronize()
-                    times.append(e0.elapsed_time(e1) * 1e3 / per)
+                times = timed(step)
                 print(json.dumps({"label": a.label, "module": kind, "z": [16, 32, hw, hw], "channels_last": channels_last,
                                   "steps": per * batches, "us_median": round(statistics.median(times), 2),
                                   "us_min": round(min(times), 2), "us_max": round(max(times), 2),

@@ -24,6 +24,7 @@
 #include "gq_scores.h"
 #include "gq_scores_f16.h"
 #include "gq_ssim.h"
+#include "vq_train.h"
 
 using namespace gqhip;
 
@@ -926,6 +927,83 @@ int vq_quantize_z_f32(const float *z, const float *emb, int64_t *idx, float *zq,
   int64_t blocks = (g.rows * dim + 256 * 16 - 1) / (256 * 16);
   blocks = blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks);
   return launch(vq_loss_kernel, dim3((unsigned)blocks), dim3(256), 0, st, lp);
+}
+
+// ---- the backward of VQQuantizer's train step (vq_train.h) ----
+namespace {
+struct VqBwdLayout {
+  int64_t keys[2], vals[2], table, partial, flag, total;
+  int tiles, passes;
+};
+static bool vq_backward_layout(int64_t items, int64_t n, int64_t dim, VqBwdLayout *w) {
+  if (items < 0 || items > 0x3fffffff || n < 1 || n > 0x7fffffff || dim < 1 || dim > kMaxDim) return false;
+  int bits = 0;
+  while (((int64_t)1 << bits) < n) ++bits;
+  w->passes = bits <= 8 ? 1 : (bits + 7) / 8;
+  w->tiles = (int)((items + kVqSortTile - 1) / kVqSortTile);
+  int64_t off = 0;
+  for (int i = 0; i < 2; ++i) {
+    w->keys[i] = off; off += align256(items * 4);
+    w->vals[i] = off; off += align256(items * 4);
+  }
+  w->table = off;   off += align256((int64_t)256 * w->tiles * 4);
+  w->partial = off; off += align256(2 * ((items + kVqChunk - 1) / kVqChunk) * dim * 8);
+  w->flag = off;    off += 256;
+  w->total = off;
+  return true;
+}
+}  // namespace
+
+int64_t vq_backward_workspace_bytes(int64_t items, int64_t n, int64_t dim) {
+  VqBwdLayout w;
+  return vq_backward_layout(items, n, dim, &w) ? w.total : -1;
+}
+
+int vq_backward_f32(const float *z, const float *emb, const int64_t *idx, const float *g_zq_or_null, const float *g_loss_or_null,
+                    float *grad_z_or_null, float *grad_emb_or_null, int64_t B, int64_t L, int64_t c, int64_t dim, int64_t n,
+                    int layout, double beta, int legacy, void *workspace, int64_t workspace_bytes, void *stream) {
+  ZGeom g;
+  VqBwdLayout w;
+  if (!z || !emb || !idx || !z_geometry(B, L, c, dim, layout, GQHIP_GROUP_STRIDED, &g)) return GQHIP_ERR_INVALID_ARG;
+  if (!vq_backward_layout(g.rows, n, dim, &w) || (bits(g_loss_or_null) & 3u) || (bits(workspace) & 15u)) return GQHIP_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (g.rows > 0 && (!workspace || workspace_bytes < w.total)) return GQHIP_ERR_WORKSPACE;
+  if (grad_emb_or_null && hipMemsetAsync(grad_emb_or_null, 0, sizeof(float) * n * dim, st) != hipSuccess) return check_launch();
+  if (g.rows == 0) return GQHIP_OK;
+  char *ws = static_cast<char *>(workspace);
+  const int last = (w.passes - 1) & 1;                           // pass i writes buffer pair i & 1
+  VqBwdParams p{};
+  p.z = z; p.emb = emb; p.idx = idx; p.g_zq = g_zq_or_null; p.g_loss = g_loss_or_null;
+  p.grad_z = grad_z_or_null; p.grad_emb = grad_emb_or_null;
+  p.keys = reinterpret_cast<const unsigned *>(ws + w.keys[last]); p.vals = reinterpret_cast<const unsigned *>(ws + w.vals[last]);
+  p.partial = reinterpret_cast<double *>(ws + w.partial); p.flag = reinterpret_cast<int *>(ws + w.flag);
+  p.items = (long)g.rows; p.total = (long)(B * L * c);
+  p.cz = (legacy ? 1.0 : beta) * 2.0 / (double)p.total; p.ce = (legacy ? beta : 1.0) * 2.0 / (double)p.total;
+  p.dim = (int)dim; p.n = (int)n; p.omap = g.om;
+  if (grad_z_or_null) {
+    const bool wide = ((bits(z) | bits(g_zq_or_null) | bits(grad_z_or_null)) & 15u) == 0 && (layout == GQHIP_LAYOUT_BCHW ? L : c) % 4 == 0;
+    const long threads = wide ? p.total / 4 : p.total;
+    const int rc = launch(wide ? vq_grad_z_kernel<4> : vq_grad_z_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
+    if (rc != GQHIP_OK) return rc;
+  }
+  if (!grad_emb_or_null || !g_loss_or_null) return GQHIP_OK;    // no gradient arrives at the loss: grad_emb stays the zeros above
+  VqSortParams sp{};
+  sp.idx = idx; sp.table = reinterpret_cast<int *>(ws + w.table); sp.flag = p.flag;
+  sp.items = p.items; sp.tiles = w.tiles; sp.n = p.n; sp.omap = g.om;
+  for (int pass = 0; pass < w.passes; ++pass) {
+    sp.first = pass == 0; sp.shift = 8 * pass;
+    sp.keys_in = reinterpret_cast<const unsigned *>(ws + w.keys[(pass + 1) & 1]); sp.vals_in = reinterpret_cast<const unsigned *>(ws + w.vals[(pass + 1) & 1]);
+    sp.keys_out = reinterpret_cast<unsigned *>(ws + w.keys[pass & 1]); sp.vals_out = reinterpret_cast<unsigned *>(ws + w.vals[pass & 1]);
+    int rc = launch(vq_sort_count_kernel, dim3((unsigned)w.tiles), dim3(64), 0, st, sp);
+    if (rc == GQHIP_OK) rc = launch(vq_sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp.table, (long)256 * w.tiles);
+    if (rc == GQHIP_OK) rc = launch(vq_sort_place_kernel, dim3((unsigned)w.tiles), dim3(64), 0, st, sp);
+    if (rc != GQHIP_OK) return rc;
+  }
+  const int64_t blocks = (g.rows * dim + 255) / 256;
+  if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
+  const int rc = launch(vq_emb_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+  if (rc != GQHIP_OK) return rc;
+  return launch(vq_emb_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,

@@ -59,6 +59,9 @@ _SIGNATURES = {
                                              _vp]),
     "vq_quantize_z_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
                                          ctypes.c_int, _vp, _i64, _vp, _i64, _vp]),
+    "vq_backward_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "vq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
+                                       ctypes.c_int, _vp, _i64, _vp]),
     "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                       ctypes.c_int, _vp]),
     "vq_argmin_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -434,9 +437,10 @@ def gq_gauss_backward(z, dim: int, layout: str, grouping: int, noise, lam_before
     return grad_z
 
 
-def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: Optional[Workspace] = None):
-    """VQQuantizer's eval forward in one call (gqhip.h: vq_quantize_z_f32): z [B, c, ...] ("bchw") or [B, L, c] ("blc") ->
-    (idx [B, K, ...] / [B, L, K], z_q in the layout of z, loss float32 [2] = {codebook_loss, mean((e - z)^2)})."""
+def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: Optional[Workspace] = None, use_cache: bool = True):
+    """VQQuantizer's forward in one call (gqhip.h: vq_quantize_z_f32): z [B, c, ...] ("bchw") or [B, L, c] ("blc") ->
+    (idx [B, K, ...] / [B, L, K], z_q in the layout of z, loss float32 [2] = {codebook_loss, mean((e - z)^2)}).
+    ``use_cache=False``: no codebook cache in this call, as in vq_argmin (a codebook that changes every step)."""
     z, emb = _dev(z, torch.float32, "z"), _dev(emb, torch.float32, "embedding")
     n = emb.shape[0]
     B, L, c, K, rows, _, idx_shape = _z_geometry(z, dim, layout, holds="z")
@@ -449,11 +453,64 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, dev)
-        cptr, cbytes = ws.cache(n, dim, dev)
+        cptr, cbytes = ws.cache(n, dim, dev) if use_cache else (None, 0)
         _check(lib().vq_quantize_z_f32(z.data_ptr(), emb.data_ptr(), idx.data_ptr(), zq.data_ptr(), loss.data_ptr(), B, L, c, dim,
                                        n, GQHIP_LAYOUT[layout], float(beta), 1 if legacy else 0, wptr, wbytes, cptr, cbytes,
                                        _stream()), "vq_quantize_z_f32")
     return idx, zq, loss
+
+
+class VqBackwardWorkspace:
+    """Scratch of vq_backward (gqhip.h: vq_backward_workspace_bytes), grown on demand and reused across calls; its contents never
+    matter on entry.  One per stream at a time.  Graph captures: the rules of ``Workspace`` -- never replaced during or after one."""
+
+    def __init__(self) -> None:
+        self.buf: Optional[torch.Tensor] = None
+        self._pinned = False
+
+    def get(self, items: int, n: int, dim: int, device) -> Tuple[int, int]:
+        need = lib().vq_backward_workspace_bytes(items, n, dim)
+        if need < 0:
+            raise GqHipError(f"unsupported shape items={items} n={n} dim={dim}")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
+            if capturing or self._pinned:
+                raise GqHipError("vq_backward's workspace would have to grow during / after a HIP graph capture that uses it: "
+                                 "run a warm-up step of the largest shape before capturing")
+            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+        if capturing:
+            self._pinned = True
+        return self.buf.data_ptr(), self.buf.numel()
+
+
+def vq_backward(z, emb, idx, dim: int, layout: str, beta: float, legacy: bool, g_zq=None, g_loss=None, want_grad_z: bool = True,
+                want_grad_emb: bool = True, ws: Optional[VqBackwardWorkspace] = None):
+    """The backward of VQQuantizer's train step in one call (gqhip.h: vq_backward_f32).  z, emb, idx: the forward's operands and
+    indices; ``g_zq`` (shape of z; made contiguous in z's layout when it is not) and ``g_loss`` (one float32 on the device) are
+    the gradients arriving at z_q and codebook_loss, None = zero.  Returns (grad_z or None, grad_emb [n, dim] or None)."""
+    z, emb, idx = _dev(z, torch.float32, "z"), _dev(emb, torch.float32, "embedding"), _dev(idx, torch.int64, "indices")
+    n = emb.shape[0]
+    B, L, c, K, items, _, idx_shape = _z_geometry(z, dim, layout, holds="z")
+    if c % dim or emb.shape[1] != dim or tuple(idx.shape) != idx_shape:
+        raise GqHipError("shape mismatch in vq_backward")
+    if g_zq is not None:
+        g_zq = _dev(g_zq, torch.float32, "g_zq")
+        if g_zq.shape != z.shape:
+            raise GqHipError(f"g_zq must have the shape of z {tuple(z.shape)}, got {tuple(g_zq.shape)}")
+    if g_loss is not None:
+        g_loss = _dev(g_loss, torch.float32, "g_loss")
+        if g_loss.numel() != 1:
+            raise GqHipError("g_loss must hold one float")
+    ws = ws or VqBackwardWorkspace()
+    dev = z.device
+    grad_z = torch.empty_like(z) if want_grad_z else None
+    grad_emb = torch.empty_like(emb) if want_grad_emb else None
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(items, n, dim, dev)
+        _check(lib().vq_backward_f32(z.data_ptr(), emb.data_ptr(), idx.data_ptr(), _ptr(g_zq), _ptr(g_loss), _ptr(grad_z),
+                                     _ptr(grad_emb), B, L, c, dim, n, GQHIP_LAYOUT[layout], float(beta), 1 if legacy else 0,
+                                     wptr, wbytes, _stream()), "vq_backward_f32")
+    return grad_z, grad_emb
 
 
 def gq_dequant(idx, cb, dim: int, layout: str, grouping: int):
