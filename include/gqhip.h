@@ -29,6 +29,7 @@
  *   vq_quantize_z_f32 pit/quantization/vq.py:39-96 (VQQuantizer.forward, eval).
  *   vq_backward_f32  the autograd backward of pit/quantization/vq.py:39-96 (VQQuantizer.forward in train()).
  *   lfq_pack_f32     pit/quantization/lfq.py:147-158.
+ *   lfq_train_f32 / lfq_backward_f32  pit/quantization/lfq.py:56-76, 160-208 (LFQQuantizer.forward in train()) and its autograd backward.
  *   lfq_unpack_f32   pit/quantization/lfq.py:210-228 (also BSQ: pit/quantization/bsq.py:85-156).
  *   fsq_quantize_f32 / fsq_dequant_f32  pit/quantization/fsq.py:29-89.
  *   gn_silu_f32      pit/modules/unet.py:49-57 (Normalize + nonlinearity pairs).
@@ -58,7 +59,8 @@ extern "C" {
                                *    value and codebook loss inside the launches); additive since, the version unchanged: per-image SSIM /
                                *    MS-SSIM (gq_ssim_f32), the three-metric step record (gq_step_record_ssim_f32), the train-mode step of the Gaussian
                                *    regularizers (gq_gauss_train_f32, gq_gauss_backward_f32), the backward of VQQuantizer's train step
-                               *    (vq_backward_f32, vq_backward_workspace_bytes) */
+                               *    (vq_backward_f32, vq_backward_workspace_bytes), LFQQuantizer's train step
+                               *    (lfq_train_f32, lfq_backward_f32, lfq_train_workspace_bytes) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -316,6 +318,35 @@ int lfq_pack_f32(const float *x, int64_t *idx, float *q_or_null, int64_t rows,
                  int64_t nbits, void *stream);
 int lfq_unpack_f32(const int64_t *idx, float *q, int64_t rows, int64_t nbits,
                    void *stream);
+
+/* ---- LFQQuantizer's train step (lfq.py:56-76, 160-208) in ONE forward and ONE backward call, without the [rows, 2^d] logits.
+ *   x: [B, C, L] (layout 0, BCHW) or [B, L, C] (layout 1, BLC; also channels_last memory), C = nc d, d in 1..16, nc d <= 62.
+ *   Row r = (b L + l) nc + ci holds channels ci d + i; R = B L nc rows.  T = 0.01, eps = 1e-5, s = 400 x, p = sigma(s), q = 1 - p:
+ *   the row's softmax over {-1,+1}^d is the product of d Bernoullis, so with the low dl = d / 2 bits as v, the high dh = d - dl
+ *   bits as u and the per-row tables A_r[u], B_r[v] of those products, avg[u 2^dl + v] = (1 / R) sum_r A_r[u] B_r[v] (code j has
+ *   +1 in dimension i when bit i of j is set: the order of the reference's avg_probs).
+ * lfq_train_f32 writes
+ *   quantized (layout of x) = x + (q - x), q = x > 0 ? 1 : -1, two rounded fp32 operations;
+ *   idx [B L] = the big-endian pack of the C sign bits of a position (lfq_pack_f32's value);
+ *   avg [2^d] floats, kept by the caller for the backward;
+ *   scalars [4] floats ON THE DEVICE = {entropy_aux_loss = w_s per_sample_entropy - w_b codebook_entropy, per_sample_entropy =
+ *     mean_r sum_i (log1p(e) + |s| e / (1 + e)) with e = exp(-|s|), codebook_entropy = -sum avg log(avg + eps), commit_loss =
+ *     mean((x - q)^2)}.
+ * lfq_backward_f32, with the gradients arriving at quantized (g_q, layout of x) and at entropy_aux_loss / commit_loss (ONE float
+ * each ON THE DEVICE), NULL = zero, writes grad_x (layout of x) =
+ *     g_q + g_commit 2 (x - q) / (B L C) + g_aux 400 (w_s / R (-s p q) - w_b d codebook_entropy / d s)
+ *   from x and avg alone (G = -(log(avg + eps) + avg / (avg + eps)); for a high bit i,
+ *   d codebook_entropy / d s_i = (1 / R) sum_u (G B_r)[u] A_r[u] (bit_i(u) ? q_i : -p_i); low bits: G^T A_r and B_r).
+ * The GEMMs run on v_mfma_f32_32x32x2_f32.  Rows are summed in chunks of 256 (csrc/lfq_train.h: kLfqChunk) added in chunk
+ * order: no float atomics, bit-identical from run to run.  Neither call reads the host or synchronises; both are ordered on
+ * `stream`.  workspace: lfq_train_workspace_bytes(R, d) bytes (-1: rows < 0 or too many, d outside 1..16), 16-byte aligned, contents
+ * don't-care on entry, nothing in it is kept between calls; NULL, misaligned or short -> GQHIP_ERR_WORKSPACE.  B L = 0: GQHIP_OK. */
+int64_t lfq_train_workspace_bytes(int64_t rows, int64_t d);
+int lfq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, float *scalars, int64_t B, int64_t L, int64_t C,
+                  int64_t nc, int64_t d, int layout, float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream);
+int lfq_backward_f32(const float *x, const float *avg, const float *g_q_or_null, const float *g_aux_or_null,
+                     const float *g_commit_or_null, float *grad_x, int64_t B, int64_t L, int64_t C, int64_t nc, int64_t d, int layout,
+                     float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---- FSQ: tanh-bounded rounding + mixed-radix pack (pit/quantization/fsq.py:29-89) ----
  * z, zhat [rows, nlev] fp32; idx [rows] int32 (the reference's dtype); levels_host: nlev (<= 16)

@@ -10,6 +10,11 @@ With `--only vq` (VQ cases run only when asked for by name): VQQuantizer("bchw",
 (codes ~ N(0, 1) * 0.5) on z = [16, 16, 32, 32] and [16, 16, 64, 64] (sd3unet_vq_16 at 256^2 and 512^2), NCHW and channels_last; a step is
     zq, info = m(z);  ((zq * w).sum() + 0.37 * info["codebook_loss"]).backward()
 with z.grad and embedding.weight.grad both wanted.
+With `--only lfq`: LFQQuantizer("bchw", 256, 2) (sd3unet_lfq_16) and LFQQuantizer("bchw", 65536, 1) in train() on
+z = [16, 16, 32, 32] ~ 0.02 N(0, 1) (entropies not saturated), NCHW and channels_last; a step is
+    q, info = m(z);  ((q * w).sum() + 0.37 * info["entropy_aux_loss"] + 1.3 * info["commit_loss"]).backward()
+(the op-by-op path of the 65 536-code case builds the [16 384, 65 536] logits: several GB and tens of ms per step, so time it with a
+small `--iters`).
 `--iters` timed steps after `--warmup`, in 10 batches, each between two device events (the time between the events includes whatever
 the host makes the device wait for, which is the point: the op-by-op path stops the host three times per step).  Prints one JSON line
 per (module, shape, layout): median / min / max over the batches of the per-step time in microseconds.
@@ -30,7 +35,7 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--label", default="")
-    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'; 'vq' runs the VQ cases instead")
+    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'; 'vq' / 'lfq' run the VQ / LFQ cases instead")
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(a.root, "vq-vae-from-gaussian-vae_amd"))
     import torch
@@ -81,6 +86,31 @@ def main() -> int:
                 print(json.dumps({"label": a.label, "module": "vq", "z": [16, 16, hw, hw], "channels_last": channels_last,
                                   "steps": per * batches, "us_median": round(statistics.median(times), 2),
                                   "us_min": round(min(times), 2), "us_max": round(max(times), 2),
+                                  "fused": os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"}), flush=True)
+        return 0
+    if a.only == "lfq":
+        from pit_hip.quantization.lfq import LFQQuantizer
+
+        for size, nc in ((256, 2), (65536, 1)):
+            for channels_last in (False, True):
+                g = torch.Generator().manual_seed(size)
+                z, w = 0.02 * torch.randn(16, 16, 32, 32, generator=g).to(dev), torch.randn(16, 16, 32, 32, generator=g).to(dev)
+                if channels_last:
+                    z, w = z.contiguous(memory_format=torch.channels_last), w.contiguous(memory_format=torch.channels_last)
+                z.requires_grad_(True)
+                m = LFQQuantizer("bchw", size, nc).to(dev).train()
+
+                def step():
+                    z.grad = None
+                    q, info = m(z)
+                    ((q * w).sum() + 0.37 * info["entropy_aux_loss"] + 1.3 * info["commit_loss"]).backward()
+
+                torch.cuda.reset_peak_memory_stats()
+                times = timed(step)
+                print(json.dumps({"label": a.label, "module": f"lfq_{size}x{nc}", "z": [16, 16, 32, 32], "channels_last": channels_last,
+                                  "steps": per * batches, "us_median": round(statistics.median(times), 2),
+                                  "us_min": round(min(times), 2), "us_max": round(max(times), 2),
+                                  "peak_mb": round(torch.cuda.max_memory_allocated() / 1e6, 1),
                                   "fused": os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"}), flush=True)
         return 0
     for kind in ("gq1", "gq2"):

@@ -25,6 +25,7 @@
 #include "gq_scores_f16.h"
 #include "gq_ssim.h"
 #include "vq_train.h"
+#include "lfq_train.h"
 
 using namespace gqhip;
 
@@ -1004,6 +1005,111 @@ int vq_backward_f32(const float *z, const float *emb, const int64_t *idx, const 
   const int rc = launch(vq_emb_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
   if (rc != GQHIP_OK) return rc;
   return launch(vq_emb_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+}
+
+// ---- LFQQuantizer's train step (lfq_train.h) ----
+namespace {
+struct LfqLayout {
+  int64_t elem_part, part, ent_part, G, GT, total;
+  int chunks, Mpad, Npad, elem_blocks, avg_blocks, wide;
+};
+static bool lfq_layout(int64_t rows, int64_t d, LfqLayout *w) {
+  if (rows < 0 || rows > 0x3fffffff || d < 1 || d > kLfqMaxD) return false;
+  const int dl = (int)d / 2, dh = (int)d - dl;
+  w->wide = (1 << dl) >= 128;                                    // 128 x 128 block tiles from d = 14 on, 64 x 64 below
+  const int T = w->wide ? 128 : 64;
+  w->Mpad = (1 << dh) > T ? (1 << dh) : T;
+  w->Npad = (1 << dl) > T ? (1 << dl) : T;
+  w->chunks = (int)((rows + kLfqChunk - 1) / kLfqChunk);
+  w->elem_blocks = (int)((rows + 255) / 256);                    // positions <= rows
+  w->avg_blocks = (int)((((int64_t)1 << d) + 255) / 256);
+  int64_t off = 0;
+  w->elem_part = off; off += align256((int64_t)w->elem_blocks * 16);
+  w->part = off;      off += align256((int64_t)w->chunks * w->Mpad * w->Npad * 4);
+  w->ent_part = off;  off += align256((int64_t)w->avg_blocks * 8);
+  w->G = off;         off += align256(((int64_t)4) << d);
+  w->GT = off;        off += align256(((int64_t)4) << d);
+  w->total = off;
+  return true;
+}
+static bool lfq_geometry(int64_t B, int64_t L, int64_t C, int64_t nc, int64_t d, int layout, LfqGeom *g) {
+  if (B < 0 || L < 0 || nc < 1 || d < 1 || d > kLfqMaxD || nc * d > 62 || C != nc * d) return false;
+  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return false;
+  if (B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff || B * L * nc > 0x3fffffff) return false;
+  g->P = (long)(B * L); g->R = (long)(B * L * nc); g->L = (long)L;
+  g->nc = (int)nc; g->d = (int)d; g->dl = (int)d / 2; g->dh = (int)d - g->dl; g->C = (int)C;
+  g->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  return true;
+}
+}  // namespace
+
+int64_t lfq_train_workspace_bytes(int64_t rows, int64_t d) {
+  LfqLayout w;
+  return lfq_layout(rows, d, &w) ? w.total : -1;
+}
+
+int lfq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, float *scalars, int64_t B, int64_t L, int64_t C,
+                  int64_t nc, int64_t d, int layout, float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream) {
+  LfqGeom g;
+  LfqLayout w;
+  if (!x || !quantized || !idx || !avg || !scalars || !lfq_geometry(B, L, C, nc, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
+  if (!lfq_layout(g.R, d, &w) || ((bits(avg) | bits(scalars)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (g.R == 0) return GQHIP_OK;
+  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char *ws = static_cast<char *>(workspace);
+  LfqFwdParams p{};
+  p.x = x; p.quant = quantized; p.idx = idx; p.avg = avg; p.scalars = scalars;
+  p.elem_part = reinterpret_cast<double *>(ws + w.elem_part); p.part = reinterpret_cast<float *>(ws + w.part);
+  p.ent_part = reinterpret_cast<double *>(ws + w.ent_part);
+  p.g = g; p.ws = w_s; p.wb = w_b;
+  p.chunks = w.chunks; p.Mpad = w.Mpad; p.Npad = w.Npad; p.avg_blocks = w.avg_blocks;
+  p.elem_blocks = (int)((g.P + 255) / 256);
+  int rc = launch(lfq_elem_kernel, dim3((unsigned)p.elem_blocks), dim3(256), 0, st, p);
+  if (rc != GQHIP_OK) return rc;
+  const int T = w.wide ? 128 : 64;
+  const dim3 grid((unsigned)w.chunks, (unsigned)((w.Mpad / T) * (w.Npad / T)));
+  rc = launch(w.wide ? lfq_avg_gemm_kernel<2> : lfq_avg_gemm_kernel<1>, grid, dim3(256), 0, st, p);
+  if (rc != GQHIP_OK) return rc;
+  rc = launch(lfq_avg_reduce_kernel, dim3((unsigned)w.avg_blocks), dim3(256), 0, st, p);
+  if (rc != GQHIP_OK) return rc;
+  return launch(lfq_finish_kernel, dim3(1), dim3(256), 0, st, p);
+}
+
+namespace {
+using LfqBwdKernel = void (*)(const LfqBwdParams);
+static LfqBwdKernel lfq_bwd_choice(int dh) {
+  switch (dh <= 5 ? 1 : 1 << (dh - 5)) {
+    case 1: return lfq_bwd_kernel<1>;
+    case 2: return lfq_bwd_kernel<2>;
+    case 4: return lfq_bwd_kernel<4>;
+    case 8: return lfq_bwd_kernel<8>;
+  }
+  return nullptr;
+}
+}  // namespace
+
+int lfq_backward_f32(const float *x, const float *avg, const float *g_q_or_null, const float *g_aux_or_null,
+                     const float *g_commit_or_null, float *grad_x, int64_t B, int64_t L, int64_t C, int64_t nc, int64_t d, int layout,
+                     float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream) {
+  LfqGeom g;
+  LfqLayout w;
+  if (!x || !avg || !grad_x || !lfq_geometry(B, L, C, nc, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
+  if (!lfq_layout(g.R, d, &w) || ((bits(avg) | bits(g_aux_or_null) | bits(g_commit_or_null)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (g.R == 0) return GQHIP_OK;
+  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  char *ws = static_cast<char *>(workspace);
+  LfqBwdParams p{};
+  p.x = x; p.avg = avg; p.g_q = g_q_or_null; p.g_aux = g_aux_or_null; p.g_commit = g_commit_or_null; p.grad_x = grad_x;
+  p.G = reinterpret_cast<float *>(ws + w.G); p.GT = reinterpret_cast<float *>(ws + w.GT);
+  p.g = g; p.ws = w_s; p.wb = w_b;
+  if (g_aux_or_null) {
+    const int rc = launch(lfq_g_kernel, dim3((unsigned)w.avg_blocks), dim3(256), 0, st, p);
+    if (rc != GQHIP_OK) return rc;
+  }
+  const int64_t blocks = (g.R + 32 * kLfqBwdWaves - 1) / (32 * kLfqBwdWaves);
+  return launch(lfq_bwd_choice(g.dh), dim3((unsigned)blocks), dim3(64 * kLfqBwdWaves), 0, st, p);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,

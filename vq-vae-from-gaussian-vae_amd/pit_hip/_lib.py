@@ -62,6 +62,11 @@ _SIGNATURES = {
     "vq_backward_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "vq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
                                        ctypes.c_int, _vp, _i64, _vp]),
+    "lfq_train_workspace_bytes": (_i64, [_i64, _i64]),
+    "lfq_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
+                                     ctypes.c_float, _vp, _i64, _vp]),
+    "lfq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
+                                        ctypes.c_float, _vp, _i64, _vp]),
     "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                       ctypes.c_int, _vp]),
     "vq_argmin_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -548,6 +553,95 @@ def lfq_pack(x):
     with torch.cuda.device(x.device):
         _check(lib().lfq_pack_f32(x.data_ptr(), idx.data_ptr(), q.data_ptr(), rows, nbits, _stream()), "lfq_pack_f32")
     return idx, q
+
+
+class LfqTrainWorkspace:
+    """Scratch of lfq_train / lfq_backward (gqhip.h: lfq_train_workspace_bytes), grown on demand and reused across calls; its
+    contents never matter on entry.  One per stream at a time.  Graph captures: the rules of ``Workspace`` -- never replaced during
+    or after one."""
+
+    def __init__(self) -> None:
+        self.buf: Optional[torch.Tensor] = None
+        self._pinned = False
+
+    def get(self, rows: int, d: int, device) -> Tuple[int, int]:
+        need = lib().lfq_train_workspace_bytes(rows, d)
+        if need < 0:
+            raise GqHipError(f"unsupported shape rows={rows} d={d}")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
+            if capturing or self._pinned:
+                raise GqHipError("the LFQ train step's workspace would have to grow during / after a HIP graph capture that uses "
+                                 "it: run a warm-up step of the largest shape before capturing")
+            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+        if capturing:
+            self._pinned = True
+        return self.buf.data_ptr(), self.buf.numel()
+
+
+def _lfq_geometry(x, num_codebooks: int, dim: int, layout: str):
+    """(B, L, C) of x in a module layout: [B, C, ...] ("bchw") or [B, L, C] ("blc"), C = num_codebooks * dim."""
+    if layout not in GQHIP_LAYOUT or x.dim() < 3 or (layout == "blc" and x.dim() != 3):
+        raise GqHipError(f"x must be [B, C, ...] (bchw) or [B, L, C] (blc), got {tuple(x.shape)} as {layout!r}")
+    if layout == "bchw":
+        B, C, L = x.shape[0], x.shape[1], int(x[0, 0].numel())
+    else:
+        B, L, C = x.shape
+    if C != num_codebooks * dim:
+        raise GqHipError(f"{C} channels do not hold {num_codebooks} codebooks of {dim} bits")
+    return B, L, C
+
+
+def lfq_train(x, num_codebooks: int, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0,
+              ws: Optional[LfqTrainWorkspace] = None):
+    """LFQQuantizer's train-mode forward in one call (gqhip.h: lfq_train_f32): x [B, C, ...] ("bchw") or [B, L, C] ("blc") ->
+    (quantized in the layout of x, indices int64 [B, 1, ...] / [B, L, 1], avg float32 [2^dim] (for lfq_backward), scalars
+    float32 [4] on the device = {entropy_aux_loss, per_sample_entropy, codebook_entropy, commit_loss})."""
+    x = _dev(x, torch.float32, "x")
+    B, L, C = _lfq_geometry(x, num_codebooks, dim, layout)
+    ws = ws or LfqTrainWorkspace()
+    dev = x.device
+    quantized = torch.empty_like(x)
+    idx = torch.empty(((B, 1) + tuple(x.shape[2:])) if layout == "bchw" else (B, L, 1), dtype=torch.int64, device=dev)
+    avg = torch.empty(1 << dim if 1 <= dim <= 16 else 1, dtype=torch.float32, device=dev)
+    scalars = torch.empty(4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
+        _check(lib().lfq_train_f32(x.data_ptr(), quantized.data_ptr(), idx.data_ptr(), avg.data_ptr(), scalars.data_ptr(), B, L, C,
+                                   num_codebooks, dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()),
+               "lfq_train_f32")
+    return quantized, idx, avg, scalars
+
+
+def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0, g_q=None, g_aux=None,
+                 g_commit=None, ws: Optional[LfqTrainWorkspace] = None):
+    """The backward of LFQQuantizer's train step in one call (gqhip.h: lfq_backward_f32).  x, avg: the forward's operand and its
+    ``avg``; ``g_q`` (shape of x; made contiguous in x's layout when it is not), ``g_aux`` and ``g_commit`` (one float32 on the
+    device each) are the gradients arriving at quantized, entropy_aux_loss and commit_loss, None = zero.  Returns grad_x."""
+    x, avg = _dev(x, torch.float32, "x"), _dev(avg, torch.float32, "avg")
+    B, L, C = _lfq_geometry(x, num_codebooks, dim, layout)
+    if avg.numel() != (1 << dim if 1 <= dim <= 16 else 1):
+        raise GqHipError(f"avg must hold 2^{dim} floats, got {avg.numel()}")
+    if g_q is not None:
+        g_q = _dev(g_q, torch.float32, "g_q")
+        if g_q.shape != x.shape:
+            raise GqHipError(f"g_q must have the shape of x {tuple(x.shape)}, got {tuple(g_q.shape)}")
+    scal = []
+    for name, t in (("g_aux", g_aux), ("g_commit", g_commit)):
+        if t is not None:
+            t = _dev(t, torch.float32, name)
+            if t.numel() != 1:
+                raise GqHipError(f"{name} must hold one float")
+        scal.append(t)
+    ws = ws or LfqTrainWorkspace()
+    dev = x.device
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
+        _check(lib().lfq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(scal[0]), _ptr(scal[1]), grad_x.data_ptr(), B, L,
+                                      C, num_codebooks, dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()),
+               "lfq_backward_f32")
+    return grad_x
 
 
 def lfq_unpack(idx, nbits: int):

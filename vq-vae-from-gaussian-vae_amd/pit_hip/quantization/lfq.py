@@ -3,9 +3,17 @@
 Lookup-free quantisation is the closed form of the arg-min over the implicit
 {-1,+1}^d codebook: bit_i = (x_i > 0), index = big-endian pack (channel 0 = MSB).
 Eval returns the same ``info`` keys as the reference with zero losses
-(lfq.py:170-183); the training-only entropy/commit losses are plain torch."""
+(lfq.py:170-183).  In ``train()`` a HIP tensor takes ONE forward library call
+(``lfq_train_f32``) and, under autograd, ONE backward call (``lfq_backward_f32``):
+the softmax over the product codebook factorises into d Bernoullis per row, so the
+``[rows, 2^d]`` logits matrix of lfq.py:63-69 is never built (the batch-average
+distribution is a 2^dh x rows x 2^dl GEMM of per-row probability tables); neither
+call reads the host.  ``GQHIP_TRAIN_FUSED=0`` in the environment (read per call,
+the switch of the Gaussian and VQ train steps) selects the plain torch losses
+instead; CPU tensors always take them."""
 from __future__ import annotations
 
+import os
 from math import log2
 
 import torch
@@ -28,6 +36,37 @@ def lfq_entropy_loss(logits, temperature=0.01, sample_minimization_weight=1.0, b
     return sample_entropy, avg_entropy, loss
 
 
+def _train_fused() -> bool:
+    """False when GQHIP_TRAIN_FUSED=0 asks for the op-by-op torch path of the train step (read per call)."""
+    return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
+
+
+class _LFQTrainFn(torch.autograd.Function):
+    """One forward library call and one backward library call for LFQQuantizer's train step under autograd.
+
+    ``xv`` is x in a library layout; ``cfg`` = (num_codebooks, codebook_dim, layout, w_s, w_b, workspace).  Differentiable
+    outputs: quantized, entropy_aux_loss and commit_loss; the indices and the two entropies are not.  Saved: x and the
+    batch-average distribution ``avg`` (2^d floats) -- the backward rebuilds every probability from x."""
+
+    @staticmethod
+    def forward(ctx, xv, cfg):
+        nc, d, layout, w_s, w_b, ws = cfg
+        quantized, ind, avg, scal = _lib.lfq_train(xv, nc, d, layout, w_s, w_b, ws)
+        aux, sample, batch, commit = scal.unbind(0)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xv, avg)
+        ctx.mark_non_differentiable(ind, sample, batch)
+        return quantized, ind, aux, sample, batch, commit
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_q, _g_ind, g_aux, _g_sample, _g_batch, g_commit):
+        xv, avg = ctx.saved_tensors
+        nc, d, layout, w_s, w_b, ws = ctx.cfg
+        return _lib.lfq_backward(xv, avg, nc, d, layout, w_s, w_b, g_q=g_q, g_aux=g_aux, g_commit=g_commit, ws=ws), None
+
+
 class LFQQuantizer(Module):
     def __init__(self, format, codebook_size=None, num_codebooks=1, sample_minimization_weight=1.0,
                  batch_maximization_weight=1.0):
@@ -43,12 +82,35 @@ class LFQQuantizer(Module):
         self.register_buffer("zero", torch.tensor(0.0), persistent=False)
         bits = self.indices_to_bits(torch.arange(codebook_size))
         self.register_buffer("codebook", bits * 2.0 - 1.0, persistent=False)
+        self._tws = _lib.LfqTrainWorkspace()
 
     def indices_to_bits(self, x):
         mask = 2 ** torch.arange(self.codebook_dim, device=x.device, dtype=torch.long)
         return (x.unsqueeze(-1) & mask) != 0
 
+    def _forward_fused(self, x):
+        """lfq.py:160-208 in train() as one call.  A channels_last x (what the NHWC conv stack hands over) is read, and quantized
+        / indices are written, in that memory layout: NHWC memory of [B, c, h, w] IS the "blc" layout (the permuted views are
+        autograd's own, they copy nothing in either direction)."""
+        xv, layout, as_module = x.float(), self.format, lambda t: t
+        if self.format == "bchw" and not xv.is_contiguous() and xv.is_contiguous(memory_format=torch.channels_last):
+            b, c, h, w = xv.shape
+            xv, layout = xv.permute(0, 2, 3, 1).reshape(b, h * w, c), "blc"          # a view of the same memory
+            as_module = lambda t: t.view(b, h, w, -1).permute(0, 3, 1, 2)
+        cfg = (self.num_codebooks, self.codebook_dim, layout, self.sample_minimization_weight, self.batch_maximization_weight,
+               self._tws)
+        if torch.is_grad_enabled() and xv.requires_grad:
+            quantized, ind, aux, sample, batch, commit = _LFQTrainFn.apply(xv, cfg)
+        else:
+            quantized, ind, _, scal = _lib.lfq_train(xv, *cfg)
+            aux, sample, batch, commit = scal.unbind(0)
+        info = {"indices": as_module(ind), "entropy_aux_loss": aux, "per_sample_entropy": sample.detach(),
+                "codebook_entropy": batch.detach(), "commit_loss": commit}
+        return as_module(quantized).to(x.dtype), info
+
     def forward(self, x):
+        if x.is_cuda and self.training and _train_fused():
+            return self._forward_fused(x)
         if self.format == "bchw":
             b, c, h, w = x.shape
             xf = x.reshape(b, c, h * w).transpose(1, 2)
