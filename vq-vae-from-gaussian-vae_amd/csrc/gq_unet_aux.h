@@ -1,6 +1,8 @@
-// gq_unet_aux.h -- the HBM-bound kernels of the conv stack around the matrix-core kernels: fused GroupNorm (+ SiLU),
+// gq_unet_aux.h -- the kernels of the conv stack around the matrix-core kernels: fused GroupNorm (+ SiLU),
 // residual adds that leave the next GroupNorm's statistics behind, the Winograd F(2x2,3x3) / F(4x4,3x3) data transforms,
-// the sub-pixel upsample glue and the operand splits of the attention GEMMs (pit/modules/unet.py:49-206).
+// the sub-pixel upsample glue and the operand splits of the attention GEMMs (pit/modules/unet.py:49-206).  One pass over
+// memory each; the GroupNorm-fused Winograd input transforms are nevertheless bound by vector issue, not by HBM (their VALU is
+// busy 57-64 % of the kernel's time, 68-73 % before their index arithmetic was taken out of the tile loops: profiles/r20).
 #pragma once
 #include "gq_common.h"
 #include "gq_stats.h"
@@ -164,8 +166,36 @@ __global__ __launch_bounds__(256) void upsample2x_nhwc_kernel(const float *__res
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 // F16X3 = 2 ("f16x2"): V2 [k][tile][2C] = [ h | l ] only -- the operand of wino_gemm_f16x2_kernel / wino_gemm_f16x2_k64_kernel (gq_wino_gemm.h), which form the
 // three products itself (4 instead of 6 bytes per element).
+//
+// ---- Addressing of the transform kernels.  Every address is a base plus a BYTE offset of type OFF, and the offsets of an item
+// are formed once per item, not once per access (hipcc does not strength-reduce `x[((b * H + y) * W + x) * CV + q]` in `long`: it
+// multiplies again for each of the 36 loads and 72 stores of an F(4x4,3x3) item -- profiles/r20):
+//   x / y / res   the tensor's base (the kernel argument: wave-uniform) + row offset + column offset: N offsets per axis, clamps
+//                 included; the row offsets carry the item's image and channel vector
+//   V / M         the plane's base (wave-uniform, advanced plane by plane on the scalar side) + the item's offset in a plane
+// so an access is `global_load / global_store v_offset, s[base]` with at most one 32-bit add in front.
+// OFF = uint32_t in the kernels proper: the host launches them only where every such offset is below 2^32
+// (gq_wino_range.h: wino_offsets_fit_u32).  OFF = uint64_t in their *_wide_kernel twins, which take every other shape.
+// Four kernels keep the per-access 64-bit indexing, each for the reason given where it stands: wino_in_nhwc_kernel<0>,
+// wino4_in_gn_nhwc_kernel<*, 0, 4>, wino4_out_nhwc_kernel and wino_out_res_nhwc_kernel<4, *>.
+// amdgpu_waves_per_eu on the two fused input kernels: with the cheaper addresses hipcc aims at one wave per SIMD more than it can
+// use and pays with the load schedule (wino_in_gn: three loads in flight instead of 16; wino4_in_gn: 163 registers = three waves).
+// The ranges name the occupancy each kernel has anyway (98-108 registers: four waves) and leave the loads as written.
 template <int F16X3, typename VEC>
-__device__ __forceinline__ void wino_store_v(void *V, int k, long tiles, long tile, int CV, int q, VEC v, float scale) {
+struct WinoVRow {   // one item's vector in a row of V: VB bytes in each of the row's PARTS parts of CV vectors ([v], [h | h | l], [h | l])
+  static constexpr int VB = F16X3 ? sizeof(VEC) / 2 : sizeof(VEC), PARTS = F16X3 == 1 ? 3 : F16X3 == 2 ? 2 : 1;
+};
+// Plane 0 of V / M for one item.  The plane bases do not depend on the item, so hipcc would form all N * N of them ahead of the item
+// loop (72 scalar registers for F(4x4,3x3): it spills them); through this the planes are walked by scalar additions item by item.
+template <typename P>
+__device__ __forceinline__ P *wino_plane0(P *p) {
+  uint64_t zero = 0;   // (the pointer itself stays the kernel argument: a global address)
+  asm volatile("" : "+s"(zero));
+  return p + zero;
+}
+// plane = base of the value's plane k, at = byte offset of the item's vector in part 0 of its row, part = bytes per part
+template <int F16X3, typename VEC, typename OFF>
+__device__ __forceinline__ void wino_store_v(char *plane, OFF at, OFF part, VEC v, float scale) {
   constexpr int VW = sizeof(VEC) / sizeof(float);          // channels per thread (4, or 2 in the two-channel kernels)
   typedef _Float16 hvec __attribute__((ext_vector_type(VW)));
   if constexpr (F16X3 != 0) {
@@ -176,18 +206,15 @@ __device__ __forceinline__ void wino_store_v(void *V, int k, long tiles, long ti
       h[e] = (_Float16)v[e];
       l[e] = (_Float16)(v[e] - (float)h[e]);
     }
+    *reinterpret_cast<hvec *>(plane + at) = h;
     if constexpr (F16X3 == 2) {
-      hvec *row = reinterpret_cast<hvec *>(V) + ((long)k * tiles + tile) * (2 * CV);
-      row[q] = h;
-      row[CV + q] = l;
+      *reinterpret_cast<hvec *>(plane + (OFF)(at + part)) = l;
     } else {
-      hvec *row = reinterpret_cast<hvec *>(V) + ((long)k * tiles + tile) * (3 * CV);
-      row[q] = h;
-      row[CV + q] = h;
-      row[2 * CV + q] = l;
+      *reinterpret_cast<hvec *>(plane + (OFF)(at + part)) = h;
+      *reinterpret_cast<hvec *>(plane + (OFF)(at + 2 * part)) = l;
     }
   } else {
-    reinterpret_cast<VEC *>(V)[((long)k * tiles + tile) * CV + q] = v;
+    *reinterpret_cast<VEC *>(plane + at) = v;
   }
 }
 
@@ -228,29 +255,97 @@ __device__ __forceinline__ void wino_at(const V (&m)[T + 2], V (&o)[T]) {
 }
 
 // Item t of a grid-stride transform -> channel vector q (of CV per pixel) of tile (b, th, tw); `tile` counts over all images.
+// IDX = the type the item counts in: OFF (an item count is below the byte count of a plane).
+template <typename IDX>
 struct WinoTile {
   int q, th, tw;
-  long tile, b;
+  IDX tile, b;
 };
-template <int T>
-__device__ __forceinline__ WinoTile wino_tile(long t, int CV, int H, int W) {
-  WinoTile w;
-  w.q = (int)(t % CV);
-  w.tile = t / CV;
-  w.tw = (int)(w.tile % (W / T));
-  const long r = w.tile / (W / T);
-  w.th = (int)(r % (H / T));
-  w.b = r / (H / T);
+template <int T, typename IDX>
+__device__ __forceinline__ WinoTile<IDX> wino_tile(IDX t, int CV, int H, int W) {
+  WinoTile<IDX> w;
+  w.q = (int)(t % (IDX)CV);
+  w.tile = t / (IDX)CV;
+  w.tw = (int)(w.tile % (IDX)(W / T));
+  const IDX r = w.tile / (IDX)(W / T);
+  w.th = (int)(r % (IDX)(H / T));
+  w.b = r / (IDX)(H / T);
   return w;
 }
-
+// The N taps of one axis of an input tile whose first tap is `first` (-1 in the first tile: the padding), once per item: the byte
+// offset of each tap's CLAMPED index (`stride` bytes per step along the axis) and whether the tap lies inside the image (MASK =
+// float: 1.f / 0.f, the factor of the fused kernels, where the product of a row's and a column's factor is exact; bool: the plain
+// kernels' branch).
+template <int N, typename OFF, typename MASK>
+__device__ __forceinline__ void wino_taps(int first, int extent, OFF stride, OFF origin, OFF (&off)[N], MASK (&in)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const int s = first + i;
+    off[i] = origin + (OFF)clamp_index(s, extent) * stride;
+    in[i] = (MASK)(s >= 0 && s < extent);
+  }
+}
+// The T output positions of one axis of output tile `t`
+template <int T, typename OFF>
+__device__ __forceinline__ void wino_outs(int t, OFF stride, OFF origin, OFF (&off)[T]) {
+#pragma unroll
+  for (int i = 0; i < T; ++i) off[i] = origin + (OFF)(T * t + i) * stride;
+}
 // The four input transforms keep a loop body each, so that hipcc keeps all loads of a tile (F(4x4,3x3): of all columns) in
-// flight: do not wrap the gather in a function shared by the plain and the fused kernels (profiles/r17).
-template <int F16X3>
-__global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
-                                                           int C4, long tiles, long total, float scale) {
+// flight: do not wrap the gather in a function shared by the plain and the fused kernels (profiles/r17).  Each body is a
+// function of OFF, called by the kernel (uint32_t) and by its wide twin (uint64_t).
+template <int F16X3, typename OFF>
+__device__ __forceinline__ void wino_in_items(const float *__restrict__ x, void *__restrict__ V, int H, int W, int C4, long tiles,
+                                              long total, float scale) {
+  typedef WinoVRow<F16X3, f32x4> VR;
+  const OFF px = (OFF)C4 * sizeof(f32x4), row = (OFF)W * px;          // bytes per pixel, per image row
+  const OFF part = (OFF)C4 * VR::VB;
+  const uint64_t plane = (uint64_t)tiles * VR::PARTS * part;
+  const char *xb = reinterpret_cast<const char *>(x);
+  for (OFF t = (OFF)blockIdx.x * 256 + threadIdx.x; t < (OFF)total; t += (OFF)gridDim.x * 256) {
+    const WinoTile<OFF> wt = wino_tile<2>(t, C4, H, W);
+    char *vk = wino_plane0(static_cast<char *>(V));
+    const OFF xq = wt.b * ((OFF)H * row) + (OFF)wt.q * sizeof(f32x4);   // the item's image and channel vector
+    OFF ro[4], co[4];
+    bool rin[4], cin[4];
+    wino_taps<4>(2 * wt.th - 1, H, row, xq, ro, rin);
+    wino_taps<4>(2 * wt.tw - 1, W, px, (OFF)0, co, cin);
+    f32x4 d[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        d[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (rin[i] && cin[j]) d[i][j] = *reinterpret_cast<const f32x4 *>(xb + (OFF)(ro[i] + co[j]));
+      }
+    f32x4 w[4][4];   // B^T d
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      w[0][j] = d[0][j] - d[2][j];
+      w[1][j] = d[1][j] + d[2][j];
+      w[2][j] = d[2][j] - d[1][j];
+      w[3][j] = d[1][j] - d[3][j];
+    }
+    const OFF at = wt.tile * (VR::PARTS * part) + (OFF)wt.q * VR::VB;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {   // (B^T d) B, each value stored as it is formed; vk walks the planes 4 i + j
+      wino_store_v<F16X3>(vk, at, part, w[i][0] - w[i][2], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][1] + w[i][2], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][2] - w[i][1], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][1] - w[i][3], scale);
+      vk += plane;
+    }
+  }
+}
+// fp32 V (F16X3 = 0) keeps the per-access 64-bit indexing at every shape, in the kernel and in its wide twin: with the offsets of an item formed once hipcc takes 81
+// instead of 79 registers for this kernel, a wave per SIMD fewer (profiles/r20).
+__device__ __forceinline__ void wino_in_items_f32(const float *__restrict__ x, float *__restrict__ V, int H, int W, int C4,
+                                                  long tiles, long total) {
   for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const WinoTile wt = wino_tile<2>(t, C4, H, W);
+    const WinoTile<long> wt = wino_tile<2>(t, C4, H, W);
     f32x4 d[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -261,7 +356,7 @@ __global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restri
         if (sy >= 0 && sy < H && sx >= 0 && sx < W)
           d[i][j] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + sy) * W + sx) * C4 + wt.q];
       }
-    f32x4 w[4][4];   // B^T d
+    f32x4 w[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       w[0][j] = d[0][j] - d[2][j];
@@ -269,32 +364,49 @@ __global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restri
       w[2][j] = d[2][j] - d[1][j];
       w[3][j] = d[1][j] - d[3][j];
     }
+    f32x4 *v = reinterpret_cast<f32x4 *>(V);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // (B^T d) B, each value stored as it is formed
-      wino_store_v<F16X3>(V, 4 * i + 0, tiles, wt.tile, C4, wt.q, w[i][0] - w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 1, tiles, wt.tile, C4, wt.q, w[i][1] + w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 2, tiles, wt.tile, C4, wt.q, w[i][2] - w[i][1], scale);
-      wino_store_v<F16X3>(V, 4 * i + 3, tiles, wt.tile, C4, wt.q, w[i][1] - w[i][3], scale);
+    for (int i = 0; i < 4; ++i) {
+      v[((long)(4 * i + 0) * tiles + wt.tile) * C4 + wt.q] = w[i][0] - w[i][2];
+      v[((long)(4 * i + 1) * tiles + wt.tile) * C4 + wt.q] = w[i][1] + w[i][2];
+      v[((long)(4 * i + 2) * tiles + wt.tile) * C4 + wt.q] = w[i][2] - w[i][1];
+      v[((long)(4 * i + 3) * tiles + wt.tile) * C4 + wt.q] = w[i][1] - w[i][3];
     }
   }
+}
+template <int F16X3>
+__global__ __launch_bounds__(256) void wino_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
+                                                           int C4, long tiles, long total, float scale) {
+  if constexpr (F16X3 == 0) wino_in_items_f32(x, static_cast<float *>(V), H, W, C4, tiles, total);
+  else wino_in_items<F16X3, uint32_t>(x, V, H, W, C4, tiles, total, scale);
+}
+template <int F16X3>
+__global__ __launch_bounds__(256) void wino_in_nhwc_wide_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
+                                                                int C4, long tiles, long total, float scale) {
+  if constexpr (F16X3 == 0) wino_in_items_f32(x, static_cast<float *>(V), H, W, C4, tiles, total);
+  else wino_in_items<F16X3, uint64_t>(x, V, H, W, C4, tiles, total, scale);
 }
 
 // Input transform with the producer fused in: the conv input is GroupNorm(+SiLU) of x (unet.py:140-142, :146-149), so
 // the normalisation is applied to the 16 loaded values on the fly (statistics from gn_stats / add_bias_stats) and the
 // normalised tensor is never written: saves gn_apply's write and this kernel's read of it.  Zero padding applies to the
 // ACTIVATED tensor, so out-of-bounds taps stay exactly 0.
-template <int SILU, int F16X3>
-__global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
-                                                              const float *__restrict__ beta,
-                                                              const float *__restrict__ pre_bias,
-                                                              const int64_t *__restrict__ stats, void *__restrict__ V,
-                                                              int H, int W, int C4, int cpg, double eps, long tiles,
-                                                              long total, float scale) {
+template <int SILU, int F16X3, typename OFF>
+__device__ __forceinline__ void wino_in_gn_items(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                 const float *__restrict__ beta, const float *__restrict__ pre_bias,
+                                                 const int64_t *__restrict__ stats, void *__restrict__ V, int H, int W, int C4,
+                                                 int cpg, double eps, long tiles, long total, float scale) {
+  typedef WinoVRow<F16X3, f32x4> VR;
   const int groups = 4 * C4 / cpg;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const WinoTile wt = wino_tile<2>(t, C4, H, W);
+  const OFF px = (OFF)C4 * sizeof(f32x4), row = (OFF)W * px;
+  const OFF part = (OFF)C4 * VR::VB;
+  const uint64_t plane = (uint64_t)tiles * VR::PARTS * part;
+  const char *xb = reinterpret_cast<const char *>(x);
+  for (OFF t = (OFF)blockIdx.x * 256 + threadIdx.x; t < (OFF)total; t += (OFF)gridDim.x * 256) {
+    const WinoTile<OFF> wt = wino_tile<2>(t, C4, H, W);
+    char *vk = wino_plane0(static_cast<char *>(V));
     const int g = (4 * wt.q) / cpg;
-    const GnGroup gg = gn_group(stats + kStatWords * (wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
+    const GnGroup gg = gn_group(stats + kStatWords * ((long)wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
     f32x4 a, sh;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -302,6 +414,11 @@ __global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__res
       a[k] = f.a;
       sh[k] = f.sh;
     }
+    const OFF xq = wt.b * ((OFF)H * row) + (OFF)wt.q * sizeof(f32x4);   // the item's image and channel vector
+    OFF ro[4], co[4];
+    float rin[4], cin[4];
+    wino_taps<4>(2 * wt.th - 1, H, row, xq, ro, rin);
+    wino_taps<4>(2 * wt.tw - 1, W, px, (OFF)0, co, cin);
     f32x4 d[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -310,16 +427,13 @@ __global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__res
         // no branch around the load: the 16 loads must all be in flight before the first activation (with the
         // activation inside an `if` hipcc keeps 16 load -> wait -> compute rounds: measured 965 vs 765 us); taps outside
         // the image read a clamped address and are zeroed afterwards
-        const int sy = 2 * wt.th - 1 + i, sx = 2 * wt.tw - 1 + j;
-        const int cy = clamp_index(sy, H), cx = clamp_index(sx, W);
-        d[i][j] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + cy) * W + cx) * C4 + wt.q];
+        d[i][j] = *reinterpret_cast<const f32x4 *>(xb + (OFF)(ro[i] + co[j]));
       }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int sy = 2 * wt.th - 1 + i, sx = 2 * wt.tw - 1 + j;
-        const float inb = (sy >= 0 && sy < H && sx >= 0 && sx < W) ? 1.f : 0.f;
+        const float inb = rin[i] * cin[j];   // 1.f or 0.f, exactly
         d[i][j] = gn_act<SILU>(d[i][j], a, sh) * inb;
       }
     f32x4 w[4][4];
@@ -330,64 +444,107 @@ __global__ __launch_bounds__(256) void wino_in_gn_nhwc_kernel(const float *__res
       w[2][j] = d[2][j] - d[1][j];
       w[3][j] = d[1][j] - d[3][j];
     }
+    const OFF at = wt.tile * (VR::PARTS * part) + (OFF)wt.q * VR::VB;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      wino_store_v<F16X3>(V, 4 * i + 0, tiles, wt.tile, C4, wt.q, w[i][0] - w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 1, tiles, wt.tile, C4, wt.q, w[i][1] + w[i][2], scale);
-      wino_store_v<F16X3>(V, 4 * i + 2, tiles, wt.tile, C4, wt.q, w[i][2] - w[i][1], scale);
-      wino_store_v<F16X3>(V, 4 * i + 3, tiles, wt.tile, C4, wt.q, w[i][1] - w[i][3], scale);
+      wino_store_v<F16X3>(vk, at, part, w[i][0] - w[i][2], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][1] + w[i][2], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][2] - w[i][1], scale);
+      vk += plane;
+      wino_store_v<F16X3>(vk, at, part, w[i][1] - w[i][3], scale);
+      vk += plane;
     }
   }
 }
+#define GQ_WINO_GN_ARGS                                                                                                        \
+  const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,                               \
+      const float *__restrict__ pre_bias, const int64_t *__restrict__ stats, void *__restrict__ V, int H, int W, int CV, int cpg, \
+      double eps, long tiles, long total, float scale
+template <int SILU, int F16X3>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void wino_in_gn_nhwc_kernel(GQ_WINO_GN_ARGS) {
+  wino_in_gn_items<SILU, F16X3, uint32_t>(x, gamma, beta, pre_bias, stats, V, H, W, CV, cpg, eps, tiles, total, scale);
+}
+template <int SILU, int F16X3>
+__global__ __launch_bounds__(256) void wino_in_gn_nhwc_wide_kernel(GQ_WINO_GN_ARGS) {
+  wino_in_gn_items<SILU, F16X3, uint64_t>(x, gamma, beta, pre_bias, stats, V, H, W, CV, cpg, eps, tiles, total, scale);
+}
 
-template <int F16X3>
-__global__ __launch_bounds__(256) void wino4_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
-                                                            int C4, long tiles, long total, float scale) {
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const WinoTile wt = wino_tile<4>(t, C4, H, W);
+template <int F16X3, typename OFF>
+__device__ __forceinline__ void wino4_in_items(const float *__restrict__ x, void *__restrict__ V, int H, int W, int C4, long tiles,
+                                               long total, float scale) {
+  typedef WinoVRow<F16X3, f32x4> VR;
+  const OFF px = (OFF)C4 * sizeof(f32x4), row = (OFF)W * px;
+  const OFF part = (OFF)C4 * VR::VB;
+  const uint64_t plane = (uint64_t)tiles * VR::PARTS * part;
+  const char *xb = reinterpret_cast<const char *>(x);
+  for (OFF t = (OFF)blockIdx.x * 256 + threadIdx.x; t < (OFF)total; t += (OFF)gridDim.x * 256) {
+    const WinoTile<OFF> wt = wino_tile<4>(t, C4, H, W);
+    char *vk = wino_plane0(static_cast<char *>(V));
+    const OFF xq = wt.b * ((OFF)H * row) + (OFF)wt.q * sizeof(f32x4);   // the item's image and channel vector
+    OFF ro[6], co[6];
+    bool rin[6], cin[6];
+    wino_taps<6>(4 * wt.th - 1, H, row, xq, ro, rin);
+    wino_taps<6>(4 * wt.tw - 1, W, px, (OFF)0, co, cin);
     f32x4 w[6][6];   // B^T d, column by column
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       f32x4 col[6], o[6];
-      const int sx = 4 * wt.tw - 1 + j;
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int sy = 4 * wt.th - 1 + i;
         col[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (sy >= 0 && sy < H && sx >= 0 && sx < W)
-          col[i] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + sy) * W + sx) * C4 + wt.q];
+        if (rin[i] && cin[j]) col[i] = *reinterpret_cast<const f32x4 *>(xb + (OFF)(ro[i] + co[j]));
       }
       wino4_bt(col, o);
 #pragma unroll
       for (int i = 0; i < 6; ++i) w[i][j] = o[i];
     }
+    const OFF at = wt.tile * (VR::PARTS * part) + (OFF)wt.q * VR::VB;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {   // (B^T d) B, row by row
+    for (int i = 0; i < 6; ++i) {   // (B^T d) B, row by row; vk walks the planes 6 i + j
       f32x4 o[6];
       wino4_bt(w[i], o);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, wt.tile, C4, wt.q, o[j], scale);
+      for (int j = 0; j < 6; ++j) {
+        wino_store_v<F16X3>(vk, at, part, o[j], scale);
+        vk += plane;
+      }
     }
   }
+}
+template <int F16X3>
+__global__ __launch_bounds__(256) void wino4_in_nhwc_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
+                                                            int C4, long tiles, long total, float scale) {
+  wino4_in_items<F16X3, uint32_t>(x, V, H, W, C4, tiles, total, scale);
+}
+template <int F16X3>
+__global__ __launch_bounds__(256) void wino4_in_nhwc_wide_kernel(const float *__restrict__ x, void *__restrict__ V, int H, int W,
+                                                                 int C4, long tiles, long total, float scale) {
+  wino4_in_items<F16X3, uint64_t>(x, V, H, W, C4, tiles, total, scale);
 }
 
 // wino4_in_nhwc_kernel with the producer fused in (see wino_in_gn_nhwc_kernel): every pixel is activated by the 2.25 tiles
 // that overlap it.  VW = channels per thread: with 4 the 36 x 4 values of a tile plus the activation's temporaries take
 // ~250 registers (two waves per SIMD, the activations' VALU time shows: 399 vs 304 us for the plain transform); with 2
 // (whenever a 256-thread block still spans whole pixels) twice the waves hide it.
-template <int SILU, int F16X3, int VW>
-__global__ __launch_bounds__(256) void wino4_in_gn_nhwc_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
-                                                               const float *__restrict__ beta,
-                                                               const float *__restrict__ pre_bias,
-                                                               const int64_t *__restrict__ stats, void *__restrict__ V,
-                                                               int H, int W, int CV, int cpg, double eps, long tiles,
-                                                               long total, float scale) {
+template <int SILU, int F16X3, int VW, typename OFF>
+__device__ __forceinline__ void wino4_in_gn_items(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                  const float *__restrict__ beta, const float *__restrict__ pre_bias,
+                                                  const int64_t *__restrict__ stats, void *__restrict__ V, int H, int W, int CV,
+                                                  int cpg, double eps, long tiles, long total, float scale) {
   typedef float vec __attribute__((ext_vector_type(VW)));
+  typedef WinoVRow<F16X3, vec> VR;
   const int groups = VW * CV / cpg;
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const WinoTile wt = wino_tile<4>(t, CV, H, W);
+  const OFF px = (OFF)CV * sizeof(vec), row = (OFF)W * px;
+  const OFF part = (OFF)CV * VR::VB;
+  const uint64_t plane = (uint64_t)tiles * VR::PARTS * part;
+  const char *xb = reinterpret_cast<const char *>(x);
+  for (OFF t = (OFF)blockIdx.x * 256 + threadIdx.x; t < (OFF)total; t += (OFF)gridDim.x * 256) {
+    const WinoTile<OFF> wt = wino_tile<4>(t, CV, H, W);
+    char *vk = wino_plane0(static_cast<char *>(V));
     const int g = (VW * wt.q) / cpg;
-    const GnGroup gg = gn_group(stats + kStatWords * (wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
+    const GnGroup gg = gn_group(stats + kStatWords * ((long)wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
     vec a, sh;
 #pragma unroll
     for (int k = 0; k < VW; ++k) {
@@ -395,16 +552,76 @@ __global__ __launch_bounds__(256) void wino4_in_gn_nhwc_kernel(const float *__re
       a[k] = f.a;
       sh[k] = f.sh;
     }
+    const OFF xq = wt.b * ((OFF)H * row) + (OFF)wt.q * sizeof(vec);   // the item's image and channel vector
+    OFF ro[6], co[6];
+    float rin[6], cin[6];
+    wino_taps<6>(4 * wt.th - 1, H, row, xq, ro, rin);
+    wino_taps<6>(4 * wt.tw - 1, W, px, (OFF)0, co, cin);
     vec w[6][6];
+    vec nxt[6];   // column j + 1 is loaded before column j is activated: six loads in flight under every activation
+#pragma unroll
+    for (int i = 0; i < 6; ++i) nxt[i] = *reinterpret_cast<const vec *>(xb + (OFF)(ro[i] + co[0]));   // branch-free: see wino_in_gn_nhwc_kernel
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       vec col[6], o[6];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) col[i] = nxt[i];
+      if (j + 1 < 6) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) nxt[i] = *reinterpret_cast<const vec *>(xb + (OFF)(ro[i] + co[j + 1]));
+      }
+      __builtin_amdgcn_sched_barrier(0);   // (hipcc otherwise sinks the loads into the activation: two or three in flight)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const float inb = rin[i] * cin[j];   // 1.f or 0.f, exactly
+        col[i] = gn_act<SILU>(col[i], a, sh) * inb;
+      }
+      wino4_bt(col, o);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) w[i][j] = o[i];
+    }
+    const OFF at = wt.tile * (VR::PARTS * part) + (OFF)wt.q * VR::VB;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      vec o[6];
+      wino4_bt(w[i], o);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        wino_store_v<F16X3>(vk, at, part, o[j], scale);
+        vk += plane;
+      }
+    }
+  }
+}
+// fp32 V (F16X3 = 0, four channels per thread) keeps the per-access 64-bit indexing at every shape, in the kernel and in its wide twin: with the offsets of an item
+// formed once hipcc takes 235-251 instead of 173 registers for this kernel (profiles/r20).
+template <int SILU>
+__device__ __forceinline__ void wino4_in_gn_items_f32(const float *__restrict__ x, const float *__restrict__ gamma,
+                                                      const float *__restrict__ beta, const float *__restrict__ pre_bias,
+                                                      const int64_t *__restrict__ stats, float *__restrict__ V, int H, int W,
+                                                      int CV, int cpg, double eps, long tiles, long total) {
+  const int groups = 4 * CV / cpg;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const WinoTile<long> wt = wino_tile<4>(t, CV, H, W);
+    const int g = (4 * wt.q) / cpg;
+    const GnGroup gg = gn_group(stats + kStatWords * (wt.b * groups + g), (double)cpg * (double)H * (double)W, eps);
+    f32x4 a, sh;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const GnAffine f = gn_channel(gg, gamma, beta, pre_bias, 4 * wt.q + k);
+      a[k] = f.a;
+      sh[k] = f.sh;
+    }
+    f32x4 w[6][6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      f32x4 col[6], o[6];
       const int sx = 4 * wt.tw - 1 + j;
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const int sy = 4 * wt.th - 1 + i;   // branch-free: see wino_in_gn_nhwc_kernel
+        const int sy = 4 * wt.th - 1 + i;
         const int cy = clamp_index(sy, H), cx = clamp_index(sx, W);
-        col[i] = reinterpret_cast<const vec *>(x)[((wt.b * H + cy) * W + cx) * CV + wt.q];
+        col[i] = reinterpret_cast<const f32x4 *>(x)[((wt.b * H + cy) * W + cx) * CV + wt.q];
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
@@ -418,18 +635,65 @@ __global__ __launch_bounds__(256) void wino4_in_gn_nhwc_kernel(const float *__re
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      vec o[6];
+      f32x4 o[6];
       wino4_bt(w[i], o);
 #pragma unroll
-      for (int j = 0; j < 6; ++j) wino_store_v<F16X3>(V, 6 * i + j, tiles, wt.tile, CV, wt.q, o[j], scale);
+      for (int j = 0; j < 6; ++j) reinterpret_cast<f32x4 *>(V)[((long)(6 * i + j) * tiles + wt.tile) * CV + wt.q] = o[j];
     }
   }
 }
+template <int SILU, int F16X3, int VW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VW == 2 ? (SILU ? 3 : 4) : 1, VW == 2 ? 4 : 8))) void wino4_in_gn_nhwc_kernel(GQ_WINO_GN_ARGS) {
+  if constexpr (F16X3 == 0)
+    wino4_in_gn_items_f32<SILU>(x, gamma, beta, pre_bias, stats, static_cast<float *>(V), H, W, CV, cpg, eps, tiles, total);
+  else
+    wino4_in_gn_items<SILU, F16X3, VW, uint32_t>(x, gamma, beta, pre_bias, stats, V, H, W, CV, cpg, eps, tiles, total, scale);
+}
+template <int SILU, int F16X3, int VW>
+__global__ __launch_bounds__(256) void wino4_in_gn_nhwc_wide_kernel(GQ_WINO_GN_ARGS) {
+  if constexpr (F16X3 == 0)
+    wino4_in_gn_items_f32<SILU>(x, gamma, beta, pre_bias, stats, static_cast<float *>(V), H, W, CV, cpg, eps, tiles, total);
+  else
+    wino4_in_gn_items<SILU, F16X3, VW, uint64_t>(x, gamma, beta, pre_bias, stats, V, H, W, CV, cpg, eps, tiles, total, scale);
+}
+#undef GQ_WINO_GN_ARGS
 
 // "Load M, A^T M" of one output tile, shared by the three output transforms: the N x N values M of the tile (mi = its channel
 // vector in plane 0, `plane` vectors per plane) -> u = A^T M; the caller finishes y = u A row by row (wino_at on u[i]) as it
 // stores.  NJ = columns of M loaded before they are transformed: all N in the plain F(2x2,3x3) kernel, 1 (column by column)
 // elsewhere -- the order each kernel had, which is the order hipcc schedules by.
+// Addressing: m0 = plane 0 of M, at = the item's byte offset in a plane, plane = bytes per plane; the plane pointers cj (plane
+// j0), pi (plane N i + j0) and pk are wave-uniform and advance by additions.
+template <int T, int NJ, typename VEC, typename OFF>
+__device__ __forceinline__ void wino_out_cols(const char *m0, OFF at, uint64_t plane, VEC (&u)[T][T + 2]) {
+  constexpr int N = T + 2;
+  const char *cj = m0;
+#pragma unroll
+  for (int j0 = 0; j0 < N; j0 += NJ) {
+    VEC m[NJ][N];   // NJ columns
+    const char *pi = cj;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const char *pk = pi;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        m[j][i] = *reinterpret_cast<const VEC *>(pk + at);
+        pk += plane;
+      }
+      pi += N * plane;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      VEC o[T];
+      wino_at<T>(m[j], o);
+#pragma unroll
+      for (int i = 0; i < T; ++i) u[i][j0 + j] = o[i];
+    }
+    cj += NJ * plane;
+  }
+}
+// The same with per-access 64-bit indexing (mi = the item's channel vector in plane 0, `plane` vectors per plane), for the output
+// kernels that keep it: wino4_out_nhwc_kernel and wino_out_res_nhwc_kernel<4, *>.
 template <int T, int NJ, typename VEC>
 __device__ __forceinline__ void wino_out_cols(const VEC *mi, long plane, VEC (&u)[T][T + 2]) {
   constexpr int N = T + 2;
@@ -452,22 +716,38 @@ __device__ __forceinline__ void wino_out_cols(const VEC *mi, long plane, VEC (&u
 
 // The plain output transforms.  `mscale`: M came out of a GEMM on scaled operands (the f16x3 path): y = mscale * (A^T M A);
 // 1 otherwise (a power of two).
-__global__ __launch_bounds__(256) void wino_out_nhwc_kernel(const float *__restrict__ M, float *__restrict__ y, int H, int W,
-                                                            int C4, long tiles, long total, float mscale) {
-  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
-    const WinoTile wt = wino_tile<2>(t, C4, H, W);
-    f32x4 u[2][4];   // A^T m
-    wino_out_cols<2, 4>(reinterpret_cast<const f32x4 *>(M) + wt.tile * C4 + wt.q, tiles * C4, u);
-    f32x4 *out = reinterpret_cast<f32x4 *>(y) + ((wt.b * H + 2 * wt.th) * W + 2 * wt.tw) * C4 + wt.q;
+template <int T, int NJ, typename OFF>
+__device__ __forceinline__ void wino_out_items(const float *__restrict__ M, float *__restrict__ y, int H, int W, int C4, long tiles,
+                                               long total, float mscale) {
+  const OFF px = (OFF)C4 * sizeof(f32x4), row = (OFF)W * px;
+  const uint64_t plane = (uint64_t)tiles * px;
+  char *yb = reinterpret_cast<char *>(y);
+  for (OFF t = (OFF)blockIdx.x * 256 + threadIdx.x; t < (OFF)total; t += (OFF)gridDim.x * 256) {
+    const WinoTile<OFF> wt = wino_tile<T>(t, C4, H, W);
+    f32x4 u[T][T + 2];   // A^T m
+    wino_out_cols<T, NJ>(wino_plane0(reinterpret_cast<const char *>(M)), (OFF)(wt.tile * px + (OFF)wt.q * sizeof(f32x4)), plane, u);
+    OFF ro[T], co[T];
+    wino_outs<T>(wt.th, row, (OFF)(wt.b * ((OFF)H * row) + (OFF)wt.q * sizeof(f32x4)), ro);
+    wino_outs<T>(wt.tw, px, (OFF)0, co);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      f32x4 o[2];
-      wino2_at(u[i], o);
+    for (int i = 0; i < T; ++i) {
+      f32x4 o[T];
+      wino_at<T>(u[i], o);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) out[((long)i * W + j) * C4] = o[j] * mscale;
+      for (int j = 0; j < T; ++j) *reinterpret_cast<f32x4 *>(yb + (OFF)(ro[i] + co[j])) = o[j] * mscale;
     }
   }
 }
+#define GQ_WINO_OUT_ARGS const float *__restrict__ M, float *__restrict__ y, int H, int W, int C4, long tiles, long total, float mscale
+__global__ __launch_bounds__(256) void wino_out_nhwc_kernel(GQ_WINO_OUT_ARGS) {
+  wino_out_items<2, 4, uint32_t>(M, y, H, W, C4, tiles, total, mscale);
+}
+__global__ __launch_bounds__(256) void wino_out_nhwc_wide_kernel(GQ_WINO_OUT_ARGS) {
+  wino_out_items<2, 4, uint64_t>(M, y, H, W, C4, tiles, total, mscale);
+}
+#undef GQ_WINO_OUT_ARGS
+// F(4x4,3x3) keeps the per-access 64-bit indexing at every shape (no wide twin): re-addressed, hipcc ran it at 161 registers with
+// 16 + 6 loads in flight where this form has 31 at 254 -- fewer loads in flight per SIMD, and bench.py has no call of it to time.
 // (decode written out: wino_tile costs this kernel, at 254 VGPRs, a scalar register -- profiles/r17)
 __global__ __launch_bounds__(256) void wino4_out_nhwc_kernel(const float *__restrict__ M, float *__restrict__ y, int H, int W,
                                                              int C4, long tiles, long total, float mscale) {
@@ -500,6 +780,79 @@ __global__ __launch_bounds__(256) void wino4_out_nhwc_kernel(const float *__rest
 // values and the 16 residual loads of a tile do not fit 256 registers, the residual is loaded late, one wave per SIMD
 // waits for it 16 times (585 us at 16 x 256 x 256 x 128, 3.9 TB/s); with 2 everything is in flight at once at two waves
 // per SIMD and an access of a wave is still whole 128-byte lines (64 lanes x 8 bytes = the 128 channels of a pixel).
+// Addressing: the image is the block's, so the image bases of res and y are wave-uniform like the planes of M and advance row by
+// row on the scalar side; a thread keeps the offset of its tile in a plane of M and T column offsets (its channel vector included).
+template <int T, int VW, typename OFF>
+__device__ __forceinline__ void wino_out_res_items(const float *__restrict__ M, const float *__restrict__ res,
+                                                   const float *__restrict__ bias, float *__restrict__ y,
+                                                   int64_t *__restrict__ stats, int H, int W, int CV, int cpg, long tiles, int slabs,
+                                                   float mscale) {
+  typedef float vec __attribute__((ext_vector_type(VW)));
+  __shared__ int64_t red[kStatWords * 64];   // per-group statistics records (gq_stats.h)
+  const int groups = VW * CV / cpg, lanes = 256 / CV;
+  const long b = blockIdx.x / slabs;
+  const int slab = blockIdx.x % slabs;
+  const long tpi = (long)(H / T) * (W / T);           // tiles per image
+  const long per = (tpi + slabs - 1) / slabs;
+  const long lo = slab * per, hi = lo + per < tpi ? lo + per : tpi;
+  const int q = threadIdx.x % CV, tl = threadIdx.x / CV;
+  for (int w = threadIdx.x; w < kStatWords * groups; w += 256) red[w] = 0;
+  __syncthreads();
+  vec pb = (vec)(0.f);
+  if (bias) pb = reinterpret_cast<const vec *>(bias)[q];
+  const OFF px = (OFF)CV * sizeof(vec), row = (OFF)W * px;
+  const uint64_t plane = (uint64_t)tiles * px, image = (uint64_t)H * row;
+  const char *resb = reinterpret_cast<const char *>(res) + (uint64_t)b * image;
+  char *yb = reinterpret_cast<char *>(y) + (uint64_t)b * image;
+  const OFF qb = (OFF)q * sizeof(vec), mrow = (OFF)(b * tpi) * px + qb;   // tile 0 of the image in a plane of M
+  StatPartial st;
+  for (OFF ti = (OFF)(lo + tl); ti < (OFF)hi; ti += (OFF)lanes) {
+    const int tw = (int)(ti % (OFF)(W / T)), th = (int)(ti / (OFF)(W / T));
+    const char *m0 = wino_plane0(reinterpret_cast<const char *>(M));
+    OFF pj[T];   // the tile's first row, its column j, the thread's channel vector
+#pragma unroll
+    for (int j = 0; j < T; ++j) pj[j] = (OFF)(T * th) * row + (OFF)(T * tw + j) * px + qb;
+    vec r[T][T];
+    if (res) {   // wave-uniform; issued ahead of M so that nothing waits for it at the end
+#pragma unroll
+      for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+          r[i][j] = *reinterpret_cast<const vec *>(resb + (uint64_t)i * row + pj[j]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < T; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j) r[i][j] = (vec)(0.f);
+    }
+    vec u[T][T + 2];
+    wino_out_cols<T, 1>(m0, (OFF)(mrow + ti * px), plane, u);
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+      vec o[T];
+      wino_at<T>(u[i], o);
+#pragma unroll
+      for (int j = 0; j < T; ++j) {
+        vec v = o[j] * mscale + pb;
+        if (res) v = v + r[i][j];
+        *reinterpret_cast<vec *>(yb + (uint64_t)i * row + pj[j]) = v;
+        stat_partial_add_vec(st, v);
+      }
+    }
+  }
+  const int g = (VW * q) / cpg;
+  stat_partial_flush(red + kStatWords * g, st);
+  __syncthreads();
+  for (int w = threadIdx.x; w < kStatWords * groups; w += 256) stat_flush_word(stats + kStatWords * (b * groups) + w, red[w]);
+}
+#define GQ_WINO_RES_ARGS                                                                                                        \
+  const float *__restrict__ M, const float *__restrict__ res, const float *__restrict__ bias, float *__restrict__ y,          \
+      int64_t *__restrict__ stats, int H, int W, int CV, int cpg, long tiles, int slabs, float mscale
+// F(4x4,3x3) keeps the per-access 64-bit indexing -- the kernel template below, as it was; it has no wide twin: with the offsets
+// formed once wino_out_res_nhwc_kernel<4, 2> was not faster on MI355X (98.2 against 98.0-100.2 us per call, whether its 52 loads
+// were all in flight at three waves per SIMD or column by column at four: profiles/r20/kernel_times.txt) -- its VALU is idle 85 %
+// of the time (profiles/r20/pmc_before.txt) -- and <4, 4> is not run by the step.  (The body stands in the kernel, not in a
+// function the kernel calls: called, hipcc gives <4, 4> 306 instead of 276 registers and 14 spills.)
 template <int T, int VW>
 __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__restrict__ M, const float *__restrict__ res,
                                                                 const float *__restrict__ bias, float *__restrict__ y,
@@ -557,6 +910,17 @@ __global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel(const float *__r
   __syncthreads();
   for (int w = threadIdx.x; w < kStatWords * groups; w += 256) stat_flush_word(stats + kStatWords * (b * groups) + w, red[w]);
 }
+// F(2x2,3x3): the strength-reduced form
+template <>
+__global__ __launch_bounds__(256) void wino_out_res_nhwc_kernel<2, 4>(GQ_WINO_RES_ARGS) {
+  wino_out_res_items<2, 4, uint32_t>(M, res, bias, y, stats, H, W, CV, cpg, tiles, slabs, mscale);
+}
+template <int T, int VW>
+__global__ __launch_bounds__(256) void wino_out_res_nhwc_wide_kernel(GQ_WINO_RES_ARGS) {
+  static_assert(T == 2, "F(4x4,3x3) has one kernel");
+  wino_out_res_items<T, VW, uint64_t>(M, res, bias, y, stats, H, W, CV, cpg, tiles, slabs, mscale);
+}
+#undef GQ_WINO_RES_ARGS
 
 // scales[0] = v_scale = the largest power of two with amp * bound * v_scale <= 32768, bound = sqrt(max over (image,
 // group) of the sum of squares) >= max|x| (rigorous: the L2 norm of a group bounds its largest element), from the

@@ -12,6 +12,7 @@
 
 #include "gqhip_internal.h"
 #include "gq_unet_aux.h"
+#include "gq_wino_range.h"
 #include "gq_wino_gemm.h"
 #include "gq_conv3.h"
 #include "gq_conv_f32.h"
@@ -59,6 +60,13 @@ int gn_check(int64_t B, int64_t C, int64_t HW, int64_t groups, bool ptrs_ok, boo
 // Winograd F(tile x tile, 3x3) on NHWC: whole tiles, channel quads
 bool wino_shape_ok(int64_t B, int64_t H, int64_t W, int64_t C, int64_t tile) {
   return (tile == 2 || tile == 4) && B >= 0 && H >= tile && W >= tile && H % tile == 0 && W % tile == 0 && C >= 4 && C % 4 == 0;
+}
+// Beside it: wino_offsets_fit_u32 (gq_wino_range.h) -- a shape it accepts runs the transform kernels with 32-bit offsets, any other
+// their *_wide_kernel twins; no accepted shape is refused for its size.  GQHIP_WINO_WIDE=1 forces the wide twins at every shape
+// (tests: no test tensor passes 4 GiB); read per call, so one process can run both.
+bool wino_u32(int64_t B, int64_t H, int64_t W, int64_t C, int64_t tile, int64_t plane_bytes_per_channel) {
+  const char *knob = getenv("GQHIP_WINO_WIDE");
+  return !(knob && !strcmp(knob, "1")) && wino_offsets_fit_u32(B, H, W, C, tile, plane_bytes_per_channel);
 }
 
 bool one_of(int64_t v, std::initializer_list<int64_t> values) {
@@ -157,8 +165,12 @@ static int wino_in_impl(int vm, const float *x, void *V, int64_t B, int64_t H, i
   if (B == 0) return GQHIP_OK;
   if (!x || !V) return GQHIP_ERR_INVALID_ARG;
   const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / 4);
-  const auto kernel = tile == 4 ? (vm == 2 ? wino4_in_nhwc_kernel<2> : vm == 1 ? wino4_in_nhwc_kernel<1> : wino4_in_nhwc_kernel<0>)
-                                : (vm == 2 ? wino_in_nhwc_kernel<2> : vm == 1 ? wino_in_nhwc_kernel<1> : wino_in_nhwc_kernel<0>);
+  const bool u32 = wino_u32(B, H, W, C, tile, vm == 1 ? 6 : 4);
+  const auto kernel =
+      u32 ? (tile == 4 ? (vm == 2 ? wino4_in_nhwc_kernel<2> : vm == 1 ? wino4_in_nhwc_kernel<1> : wino4_in_nhwc_kernel<0>)
+                       : (vm == 2 ? wino_in_nhwc_kernel<2> : vm == 1 ? wino_in_nhwc_kernel<1> : wino_in_nhwc_kernel<0>))
+          : (tile == 4 ? (vm == 2 ? wino4_in_nhwc_wide_kernel<2> : vm == 1 ? wino4_in_nhwc_wide_kernel<1> : wino4_in_nhwc_wide_kernel<0>)
+                       : (vm == 2 ? wino_in_nhwc_wide_kernel<2> : vm == 1 ? wino_in_nhwc_wide_kernel<1> : wino_in_nhwc_wide_kernel<0>));
   return launch(kernel, grid1d(total, 16384), dim3(256), 0, static_cast<hipStream_t>(stream), x, V, (int)H, (int)W, (int)(C / 4),
                 tiles, total, scale);
 }
@@ -244,24 +256,25 @@ static int wino_in_gn_impl(int tile, int f16, const float *x, const float *gamma
   const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / vw);
   const dim3 grid = grid1d(total, 32768);
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define GQ_WGN(K, ...)                                                                                                   \
-  hipLaunchKernelGGL((K<__VA_ARGS__>), grid, dim3(256), 0, st, x, gamma, beta, pre_bias_or_null, stats, V, (int)H, (int)W, \
-                     (int)(C / vw), (int)(C / groups), eps, tiles, total, scale)
+  const bool u32 = wino_u32(B, H, W, C, tile, f16 == 1 ? 6 : 4);
+#define GQ_WGN(K, ...)                                                                                                       \
+  hipLaunchKernelGGL((u32 ? K##_kernel<__VA_ARGS__> : K##_wide_kernel<__VA_ARGS__>), grid, dim3(256), 0, st, x, gamma, beta, \
+                     pre_bias_or_null, stats, V, (int)H, (int)W, (int)(C / vw), (int)(C / groups), eps, tiles, total, scale)
   if (tile == 4) {
     if (apply_silu) {
-      if (f16 == 2) GQ_WGN(wino4_in_gn_nhwc_kernel, 1, 2, 2); else if (f16 == 1) GQ_WGN(wino4_in_gn_nhwc_kernel, 1, 1, 2);
-      else GQ_WGN(wino4_in_gn_nhwc_kernel, 1, 0, 4);
+      if (f16 == 2) GQ_WGN(wino4_in_gn_nhwc, 1, 2, 2); else if (f16 == 1) GQ_WGN(wino4_in_gn_nhwc, 1, 1, 2);
+      else GQ_WGN(wino4_in_gn_nhwc, 1, 0, 4);
     } else {
-      if (f16 == 2) GQ_WGN(wino4_in_gn_nhwc_kernel, 0, 2, 2); else if (f16 == 1) GQ_WGN(wino4_in_gn_nhwc_kernel, 0, 1, 2);
-      else GQ_WGN(wino4_in_gn_nhwc_kernel, 0, 0, 4);
+      if (f16 == 2) GQ_WGN(wino4_in_gn_nhwc, 0, 2, 2); else if (f16 == 1) GQ_WGN(wino4_in_gn_nhwc, 0, 1, 2);
+      else GQ_WGN(wino4_in_gn_nhwc, 0, 0, 4);
     }
   } else {
     if (apply_silu) {
-      if (f16 == 2) GQ_WGN(wino_in_gn_nhwc_kernel, 1, 2); else if (f16 == 1) GQ_WGN(wino_in_gn_nhwc_kernel, 1, 1);
-      else GQ_WGN(wino_in_gn_nhwc_kernel, 1, 0);
+      if (f16 == 2) GQ_WGN(wino_in_gn_nhwc, 1, 2); else if (f16 == 1) GQ_WGN(wino_in_gn_nhwc, 1, 1);
+      else GQ_WGN(wino_in_gn_nhwc, 1, 0);
     } else {
-      if (f16 == 2) GQ_WGN(wino_in_gn_nhwc_kernel, 0, 2); else if (f16 == 1) GQ_WGN(wino_in_gn_nhwc_kernel, 0, 1);
-      else GQ_WGN(wino_in_gn_nhwc_kernel, 0, 0);
+      if (f16 == 2) GQ_WGN(wino_in_gn_nhwc, 0, 2); else if (f16 == 1) GQ_WGN(wino_in_gn_nhwc, 0, 1);
+      else GQ_WGN(wino_in_gn_nhwc, 0, 0);
     }
   }
 #undef GQ_WGN
@@ -613,8 +626,10 @@ static int wino_out_impl(int tile, const float *M, float *y, int64_t B, int64_t 
   if (B == 0) return GQHIP_OK;
   if (!M || !y) return GQHIP_ERR_INVALID_ARG;
   const long tiles = (long)(B * (H / tile) * (W / tile)), total = tiles * (C / 4);
-  return launch(tile == 4 ? wino4_out_nhwc_kernel : wino_out_nhwc_kernel, grid1d(total, 16384), dim3(256), 0,
-                static_cast<hipStream_t>(stream), M, y, (int)H, (int)W, (int)(C / 4), tiles, total, mscale);
+  // F(4x4,3x3) indexes in 64 bits at every shape (gq_unet_aux.h); F(2x2,3x3) has a wide twin
+  const auto kernel = tile == 4 ? wino4_out_nhwc_kernel : wino_u32(B, H, W, C, tile, 4) ? wino_out_nhwc_kernel : wino_out_nhwc_wide_kernel;
+  return launch(kernel, grid1d(total, 16384), dim3(256), 0, static_cast<hipStream_t>(stream), M, y, (int)H, (int)W, (int)(C / 4),
+                tiles, total, mscale);
 }
 
 int wino_out_nhwc_f32(const float *M, float *y, int64_t B, int64_t H, int64_t W, int64_t C, float mscale, void *stream) {
@@ -642,8 +657,10 @@ int wino_out_res_nhwc_f32(const float *M, const float *res, const float *bias_or
   if (slabs > 1024) slabs = 1024;
   if (slabs < 1) slabs = 1;
   const dim3 grid((unsigned)(B * slabs));
-  const auto kernel = tile == 2 ? wino_out_res_nhwc_kernel<2, 4>
-                                : vw == 2 ? wino_out_res_nhwc_kernel<4, 2> : wino_out_res_nhwc_kernel<4, 4>;
+  // F(4x4,3x3) indexes in 64 bits at every shape (gq_unet_aux.h); F(2x2,3x3) has a wide twin
+  const auto kernel = tile == 4 ? (vw == 2 ? wino_out_res_nhwc_kernel<4, 2> : wino_out_res_nhwc_kernel<4, 4>)
+                                : wino_u32(B, H, W, C, tile, 4) ? wino_out_res_nhwc_kernel<2, 4>
+                                                                            : wino_out_res_nhwc_wide_kernel<2, 4>;
   return launch(kernel, grid, dim3(256), 0, st, M, res, bias_or_null, y, stats_out, (int)H, (int)W, (int)(C / vw), (int)cpg, tiles,
                 (int)slabs, mscale);
 }
