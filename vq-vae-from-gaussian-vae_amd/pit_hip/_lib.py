@@ -199,22 +199,60 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-class Workspace:
+class _Scratch:
+    """A grow-only device buffer that is never replaced during or after a HIP graph capture that used it: a captured graph has
+    the pointer baked in, so growing the buffer then -- or after the capture, by an eager call with a bigger shape -- would leave
+    the graph writing into freed memory.  It grows when a request exceeds it (or names another device), refuses to while the
+    current stream is capturing or once pinned, and pins itself when it is used under capture; size it with a warm-up call first.
+    ``zeroed``: new memory comes from torch.zeros.  ``pin``: the pin of another scratch, to share it (buffers that one capture
+    uses together); a one-element list, so that sharing it ties no reference cycle around the buffers."""
+
+    _what = "scratch"
+
+    def __init__(self, what: Optional[str] = None, zeroed: bool = False, pin: Optional[list] = None) -> None:
+        self.buf: Optional[torch.Tensor] = None
+        self._pin = [False] if pin is None else pin      # [True] once a graph capture has used the buffer: never replaced again
+        self._what = what or self._what
+        self._new = torch.zeros if zeroed else torch.empty
+
+    def _take(self, need: int, device, shape: str = "", stale: bool = False) -> Tuple[int, int]:
+        """(pointer, bytes) of at least ``need`` bytes on ``device``; ``need`` < 0 is the library's "unsupported shape"."""
+        if need < 0:
+            raise GqHipError(f"unsupported shape {shape}")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self.buf is None or stale or self.buf.numel() < need or self.buf.device != device:
+            if capturing or self._pin[0]:
+                raise GqHipError(f"{self._what} would have to grow during / after a HIP graph capture that uses it: "
+                                 "run a warm-up call of the largest shape before capturing, or use a separate one")
+            self.buf = self._new(need, dtype=torch.uint8, device=device)
+        if capturing:
+            self._pin[0] = True
+        return self.buf.data_ptr(), self.buf.numel()
+
+
+class Workspace(_Scratch):
     """Caller-owned scratch, grown on demand and reused across calls, plus the persistent CODEBOOK CACHE of the shapes that keep
     one (gqhip.h: gqhip_cb_cache_bytes -- dims 4 / 8: the spatial index of the pruned search; the library validates it against a
     content hash of the codebook on every call and rebuilds it in-stream when it is stale, so nothing here has to track the
-    codebook).  One workspace serves one stream at a time (its header carries the per-call counters).  While a HIP graph is being
-    captured the buffers are never replaced: a captured graph has the pointers baked in, so growing them then -- or after the
-    capture, by an eager call with a bigger shape -- would leave the graph writing into freed memory; size them with a warm-up
-    call first (``reserve``), and a capture that would need to grow raises instead."""
+    codebook).  One workspace serves one stream at a time (its header carries the per-call counters).  Graph captures: the rule
+    of ``_Scratch``, one pin for both buffers; size them with a warm-up call first (``reserve``)."""
+
+    _what = "workspace"
 
     def __init__(self) -> None:
-        self.buf: Optional[torch.Tensor] = None
-        self.cache_buf: Optional[torch.Tensor] = None
+        super().__init__()
+        self._cache = _Scratch("the codebook cache", zeroed=True, pin=self._pin)    # zeros: no stamp -> built by the first call
         self._cache_key = None
         self._cache_calls = 0     # calls that were handed the current cache buffer
         self.no_search = False    # the dim-4 index of this codebook was found degenerate (gqhip_cb_cache_degenerate): dense path from then on
-        self._pinned = False      # True once a graph capture has used this buffer: it must never be replaced
+
+    @property
+    def cache_buf(self) -> Optional[torch.Tensor]:
+        return self._cache.buf
+
+    @cache_buf.setter
+    def cache_buf(self, t: Optional[torch.Tensor]) -> None:
+        self._cache.buf = t
 
     def cache(self, n: int, dim: int, device) -> Tuple[Optional[int], int]:
         """(pointer, bytes) of the codebook cache for (n, dim), or (None, 0) for shapes that keep none."""
@@ -222,11 +260,9 @@ class Workspace:
         if need <= 0 or self.no_search:
             return None, 0
         key = (n, dim, device)
-        if self.cache_buf is None or self._cache_key != key or self.cache_buf.numel() < need:
-            if torch.cuda.is_current_stream_capturing() or self._pinned:
-                raise GqHipError("the codebook cache would have to be (re)allocated during / after a HIP graph capture that uses "
-                                 "this Workspace: run a warm-up call of the same codebook shape before capturing")
-            self.cache_buf = torch.zeros(need, dtype=torch.uint8, device=device)    # zeros: no stamp -> built by the first call
+        old = self._cache.buf
+        out = self._cache._take(need, device, stale=self._cache_key != key)
+        if self._cache.buf is not old:
             self._cache_key = key
             self._cache_calls = 0
         # ONE look at what the index builder found, at the call after the one that built it (a 4-KiB synchronous copy, once per
@@ -235,10 +271,10 @@ class Workspace:
         # back to the dense path for good (always exact; a codebook that changes every step should not pass a cache at all: vq.py).
         self._cache_calls += 1
         if self._cache_calls == 2 and lib().gqhip_grid_search_applies(n, dim) and not torch.cuda.is_current_stream_capturing():
-            if lib().gqhip_cb_cache_degenerate(self.cache_buf.data_ptr(), n, dim) == 1:
+            if lib().gqhip_cb_cache_degenerate(out[0], n, dim) == 1:
                 self.no_search = True
                 return None, 0
-        return self.cache_buf.data_ptr(), self.cache_buf.numel()
+        return out
 
     def reserve(self, rows: int, n: int, dim: int, device) -> None:
         """Size the scratch and the codebook cache for a shape ahead of a graph capture."""
@@ -246,18 +282,7 @@ class Workspace:
         self.cache(n, dim, device)
 
     def get(self, rows: int, n: int, dim: int, device) -> Tuple[int, int]:
-        need = lib().gqhip_workspace_bytes(rows, n, dim)
-        if need < 0:
-            raise GqHipError(f"unsupported shape rows={rows} n={n} dim={dim}")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
-            if capturing or self._pinned:
-                raise GqHipError("workspace would have to grow during / after a HIP graph capture that uses it: "
-                                 "run a warm-up call of the largest shape before capturing, or use a separate Workspace")
-            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
-        if capturing:
-            self._pinned = True
-        return self.buf.data_ptr(), self.buf.numel()
+        return self._take(lib().gqhip_workspace_bytes(rows, n, dim), device, f"rows={rows} n={n} dim={dim}")
 
 
 def gq_scores(mu, sd, cb, out, beta: float = 1.0) -> None:
@@ -365,6 +390,8 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
 def _z_geometry(t, dim: int, layout: str, holds: str = "mu|logvar"):
     """(B, L, c, K, rows, shape of zhat, shape of the indices) of a tensor in a module layout (gqhip.h) whose channel axis holds
     [mu | logvar] (an encoder output: 2 c channels), "z" (c channels) or "idx" (the indices themselves: K = c / dim channels)."""
+    if layout not in GQHIP_LAYOUT or t.dim() < 3 or (layout == "blc" and t.dim() != 3):
+        raise GqHipError(f"expected [B, C, ...] (bchw) or [B, L, C] (blc), got {tuple(t.shape)} as {layout!r}")
     if layout == "bchw":
         B, ch, L = t.shape[0], t.shape[1], int(t[0, 0].numel())
     else:
@@ -376,6 +403,26 @@ def _z_geometry(t, dim: int, layout: str, holds: str = "mu|logvar"):
         return ((B, channels) + tuple(t.shape[2:])) if layout == "bchw" else (B, L, channels)
 
     return B, L, c, K, B * L * K, shape(c), shape(K)
+
+
+def _grad_of(t, shape, name: str, of: str):
+    """A gradient that must have ``shape`` (that of ``of``): None passes through, fp32 on the device, contiguous."""
+    if t is None:
+        return None
+    t = _dev(t, torch.float32, name)
+    if tuple(t.shape) != tuple(shape):
+        raise GqHipError(f"{name} must have the shape of {of} {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _grad_scalar(t, name: str):
+    """A gradient that holds one float: None passes through, fp32 on the device."""
+    if t is None:
+        return None
+    t = _dev(t, torch.float32, name)
+    if t.numel() != 1:
+        raise GqHipError(f"{name} must hold one float")
+    return t
 
 
 def _lam_ok(t, name: str) -> None:
@@ -415,24 +462,13 @@ def gq_gauss_backward(z, dim: int, layout: str, grouping: int, noise, lam_before
     z, noise = _dev(z, torch.float32, "z"), _dev(noise, torch.float32, "noise")
     _lam_ok(lam_before, "lam_before")
     B, L, c, K, rows, shape, _ = _z_geometry(z, dim, layout)
-
-    def grad(t, name):
-        if t is None:
-            return None
-        t = _dev(t, torch.float32, name)
-        if tuple(t.shape) != shape:
-            raise GqHipError(f"{name} must have the shape of zhat {shape}, got {tuple(t.shape)}")
-        return t
-
-    g_zhat, g_zhat_noquant, g_std = grad(g_zhat, "g_zhat"), grad(g_zhat_noquant, "g_zhat_noquant"), grad(g_std, "g_std")
+    g_zhat, g_zhat_noquant, g_std = (_grad_of(t, shape, name, "zhat") for t, name in
+                                     ((g_zhat, "g_zhat"), (g_zhat_noquant, "g_zhat_noquant"), (g_std, "g_std")))
     if g_zhat is not None and g_zhat_noquant is not None:
         g_zhat = g_zhat + g_zhat_noquant
     elif g_zhat is None:
         g_zhat = g_zhat_noquant
-    if g_kl is not None:
-        g_kl = _dev(g_kl, torch.float32, "g_kl")
-        if g_kl.numel() != 1:
-            raise GqHipError("g_kl must hold one float")
+    g_kl = _grad_scalar(g_kl, "g_kl")
     grad_z = torch.empty_like(z)
     with torch.cuda.device(z.device):
         _check(lib().gq_gauss_backward_f32(z.data_ptr(), noise.data_ptr(), _ptr(g_zhat), _ptr(g_std), _ptr(g_kl),
@@ -465,27 +501,14 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     return idx, zq, loss
 
 
-class VqBackwardWorkspace:
+class VqBackwardWorkspace(_Scratch):
     """Scratch of vq_backward (gqhip.h: vq_backward_workspace_bytes), grown on demand and reused across calls; its contents never
-    matter on entry.  One per stream at a time.  Graph captures: the rules of ``Workspace`` -- never replaced during or after one."""
+    matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
 
-    def __init__(self) -> None:
-        self.buf: Optional[torch.Tensor] = None
-        self._pinned = False
+    _what = "vq_backward's workspace"
 
     def get(self, items: int, n: int, dim: int, device) -> Tuple[int, int]:
-        need = lib().vq_backward_workspace_bytes(items, n, dim)
-        if need < 0:
-            raise GqHipError(f"unsupported shape items={items} n={n} dim={dim}")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
-            if capturing or self._pinned:
-                raise GqHipError("vq_backward's workspace would have to grow during / after a HIP graph capture that uses it: "
-                                 "run a warm-up step of the largest shape before capturing")
-            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
-        if capturing:
-            self._pinned = True
-        return self.buf.data_ptr(), self.buf.numel()
+        return self._take(lib().vq_backward_workspace_bytes(items, n, dim), device, f"items={items} n={n} dim={dim}")
 
 
 def vq_backward(z, emb, idx, dim: int, layout: str, beta: float, legacy: bool, g_zq=None, g_loss=None, want_grad_z: bool = True,
@@ -498,14 +521,7 @@ def vq_backward(z, emb, idx, dim: int, layout: str, beta: float, legacy: bool, g
     B, L, c, K, items, _, idx_shape = _z_geometry(z, dim, layout, holds="z")
     if c % dim or emb.shape[1] != dim or tuple(idx.shape) != idx_shape:
         raise GqHipError("shape mismatch in vq_backward")
-    if g_zq is not None:
-        g_zq = _dev(g_zq, torch.float32, "g_zq")
-        if g_zq.shape != z.shape:
-            raise GqHipError(f"g_zq must have the shape of z {tuple(z.shape)}, got {tuple(g_zq.shape)}")
-    if g_loss is not None:
-        g_loss = _dev(g_loss, torch.float32, "g_loss")
-        if g_loss.numel() != 1:
-            raise GqHipError("g_loss must hold one float")
+    g_zq, g_loss = _grad_of(g_zq, z.shape, "g_zq", "z"), _grad_scalar(g_loss, "g_loss")
     ws = ws or VqBackwardWorkspace()
     dev = z.device
     grad_z = torch.empty_like(z) if want_grad_z else None
@@ -555,38 +571,19 @@ def lfq_pack(x):
     return idx, q
 
 
-class LfqTrainWorkspace:
+class LfqTrainWorkspace(_Scratch):
     """Scratch of lfq_train / lfq_backward (gqhip.h: lfq_train_workspace_bytes), grown on demand and reused across calls; its
-    contents never matter on entry.  One per stream at a time.  Graph captures: the rules of ``Workspace`` -- never replaced during
-    or after one."""
+    contents never matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
 
-    def __init__(self) -> None:
-        self.buf: Optional[torch.Tensor] = None
-        self._pinned = False
+    _what = "the LFQ train step's workspace"
 
     def get(self, rows: int, d: int, device) -> Tuple[int, int]:
-        need = lib().lfq_train_workspace_bytes(rows, d)
-        if need < 0:
-            raise GqHipError(f"unsupported shape rows={rows} d={d}")
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
-            if capturing or self._pinned:
-                raise GqHipError("the LFQ train step's workspace would have to grow during / after a HIP graph capture that uses "
-                                 "it: run a warm-up step of the largest shape before capturing")
-            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
-        if capturing:
-            self._pinned = True
-        return self.buf.data_ptr(), self.buf.numel()
+        return self._take(lib().lfq_train_workspace_bytes(rows, d), device, f"rows={rows} d={d}")
 
 
 def _lfq_geometry(x, num_codebooks: int, dim: int, layout: str):
     """(B, L, C) of x in a module layout: [B, C, ...] ("bchw") or [B, L, C] ("blc"), C = num_codebooks * dim."""
-    if layout not in GQHIP_LAYOUT or x.dim() < 3 or (layout == "blc" and x.dim() != 3):
-        raise GqHipError(f"x must be [B, C, ...] (bchw) or [B, L, C] (blc), got {tuple(x.shape)} as {layout!r}")
-    if layout == "bchw":
-        B, C, L = x.shape[0], x.shape[1], int(x[0, 0].numel())
-    else:
-        B, L, C = x.shape
+    B, L, C = _z_geometry(x, 1, layout, holds="z")[:3]
     if C != num_codebooks * dim:
         raise GqHipError(f"{C} channels do not hold {num_codebooks} codebooks of {dim} bits")
     return B, L, C
@@ -622,23 +619,13 @@ def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float =
     B, L, C = _lfq_geometry(x, num_codebooks, dim, layout)
     if avg.numel() != (1 << dim if 1 <= dim <= 16 else 1):
         raise GqHipError(f"avg must hold 2^{dim} floats, got {avg.numel()}")
-    if g_q is not None:
-        g_q = _dev(g_q, torch.float32, "g_q")
-        if g_q.shape != x.shape:
-            raise GqHipError(f"g_q must have the shape of x {tuple(x.shape)}, got {tuple(g_q.shape)}")
-    scal = []
-    for name, t in (("g_aux", g_aux), ("g_commit", g_commit)):
-        if t is not None:
-            t = _dev(t, torch.float32, name)
-            if t.numel() != 1:
-                raise GqHipError(f"{name} must hold one float")
-        scal.append(t)
+    g_q, g_aux, g_commit = _grad_of(g_q, x.shape, "g_q", "x"), _grad_scalar(g_aux, "g_aux"), _grad_scalar(g_commit, "g_commit")
     ws = ws or LfqTrainWorkspace()
     dev = x.device
     grad_x = torch.empty_like(x)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
-        _check(lib().lfq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(scal[0]), _ptr(scal[1]), grad_x.data_ptr(), B, L,
+        _check(lib().lfq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(g_aux), _ptr(g_commit), grad_x.data_ptr(), B, L,
                                       C, num_codebooks, dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()),
                "lfq_backward_f32")
     return grad_x
@@ -1389,6 +1376,15 @@ def indices_from_u16(u16):
     return out
 
 
+def _zeroed_ws(ws_cache: dict, key, need: int, device):
+    """The zero-in / zero-out scratch of a metric call, kept in the caller's dict under ``key``: zeroed once, left zero by every
+    call that uses it."""
+    ws = ws_cache.get(key)
+    if ws is None:
+        ws = ws_cache[key] = torch.zeros(max(need, 8), dtype=torch.uint8, device=device)
+    return ws
+
+
 def step_record_ok(x, x_rec, idx) -> bool:
     """gq_step_record_f32 applies: fp32 HIP images of one dense layout (NCHW or channels_last), int64 indices on the same device."""
     if not (x.is_cuda and x_rec.is_cuda and idx.is_cuda and x.dtype == torch.float32 and x_rec.dtype == torch.float32
@@ -1405,11 +1401,7 @@ def step_record(x, x_rec, idx, rec, ws_cache: dict):
     B = x.shape[0]
     per = x[0].numel()
     idx = idx.contiguous()      # (any memory order of the SAME logical [B, K, h, w] order is fine for the caller; contiguous = logical order)
-    need = lib().gq_step_record_workspace_bytes(B, per)
-    key = (x.device, B, per)
-    ws = ws_cache.get(key)
-    if ws is None:
-        ws = ws_cache[key] = torch.zeros(max(need, 8), dtype=torch.uint8, device=x.device)
+    ws = _zeroed_ws(ws_cache, (x.device, B, per), lib().gq_step_record_workspace_bytes(B, per), x.device)
     with torch.cuda.device(x.device):
         _check(lib().gq_step_record_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, per, idx.numel(),
                                         ws.data_ptr(), ws.numel(), _stream()), "gq_step_record_f32")
@@ -1425,13 +1417,6 @@ def ssim_ok(x, x_rec) -> bool:
     return la is not None and la == lb
 
 
-def _ssim_ws(ws_cache: dict, key, need: int, device):
-    ws = ws_cache.get(key)
-    if ws is None:
-        ws = ws_cache[key] = torch.zeros(max(need, 8), dtype=torch.uint8, device=device)   # zeroed once, left zero by every call
-    return ws
-
-
 def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
     """Per-image (SSIM, MS-SSIM or None) as fp32 [B] tensors on x's device (gqhip.h: gq_ssim_f32; pit/evaluations/ssim.py:5-63).
     MS-SSIM is NaN when a side is under 256.  ``ws_cache``: the caller's dict that keeps the self-resetting workspace."""
@@ -1439,7 +1424,7 @@ def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
     layout = image_layout(x)
     ssim = torch.empty(B, dtype=torch.float32, device=x.device)
     ms = torch.empty(B, dtype=torch.float32, device=x.device) if msssim else None
-    ws = _ssim_ws(ws_cache, ("ssim", x.device, B, C, H, W), lib().gq_ssim_workspace_bytes(B, C, H, W), x.device)
+    ws = _zeroed_ws(ws_cache, ("ssim", x.device, B, C, H, W), lib().gq_ssim_workspace_bytes(B, C, H, W), x.device)
     with torch.cuda.device(x.device):
         _check(lib().gq_ssim_f32(x.data_ptr(), x_rec.data_ptr(), B, C, H, W, layout, 1 if zero_mean else 0, ssim.data_ptr(),
                                  ms.data_ptr() if ms is not None else None, ws.data_ptr(), ws.numel(), _stream()), "gq_ssim_f32")
@@ -1451,7 +1436,7 @@ def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
     gq_step_record_ssim_f32; eval.py:152-154,165-178): the PSNR and index words are those of step_record bit for bit."""
     B, C, H, W = x.shape
     idx = idx.contiguous()
-    ws = _ssim_ws(ws_cache, ("rec3", x.device, B, C, H, W), lib().gq_step_record_ssim_workspace_bytes(B, C, H, W), x.device)
+    ws = _zeroed_ws(ws_cache, ("rec3", x.device, B, C, H, W), lib().gq_step_record_ssim_workspace_bytes(B, C, H, W), x.device)
     with torch.cuda.device(x.device):
         _check(lib().gq_step_record_ssim_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
                                              image_layout(x), idx.numel(), ws.data_ptr(), ws.numel(), _stream()),
@@ -1460,7 +1445,6 @@ def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
 
 
 MHA_HEAD_DIMS = (64,)    # head dims gq_mha_fwd_f32 is built for
-_mha_ws: dict = {}
 
 
 def _mha_qkv(qkv: torch.Tensor, heads: int, who: str):
@@ -1482,9 +1466,10 @@ def mha_fwd(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     read in place; returns [B, L, E] with the heads concatenated (gqhip.h: gq_mha_fwd_f32; pit/modules/vit.py:142-151)."""
     qkv, B, L, E = _mha_qkv(qkv, heads, "mha_fwd")
     out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
-    ws = _ssim_ws(_mha_ws, (qkv.device, B, L, E, heads), lib().gq_mha_workspace_bytes(B, L, E, heads), qkv.device)
+    need = lib().gq_mha_workspace_bytes(B, L, E, heads)         # 0 today: no scratch; otherwise per call, as in mha_bwd
+    ws = torch.empty(need, dtype=torch.uint8, device=qkv.device) if need > 0 else None
     with torch.cuda.device(qkv.device):
-        _check(lib().gq_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, E, heads, ws.data_ptr(), _stream()), "gq_mha_fwd_f32")
+        _check(lib().gq_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, E, heads, _ptr(ws), _stream()), "gq_mha_fwd_f32")
     return out
 
 

@@ -54,6 +54,7 @@ import torch.nn as nn
 from torch.distributions import Normal
 
 from .. import _lib
+from ._fused import axis_view, format_view, mu_shape, positions_view, train_fused
 
 
 def prior_samples(n_samples: int, n_variable: int, seed_rec: int) -> torch.Tensor:
@@ -71,11 +72,6 @@ def prior_samples(n_samples: int, n_variable: int, seed_rec: int) -> torch.Tenso
 
 def _kl_bits(mu: torch.Tensor, var: torch.Tensor, logvar: torch.Tensor) -> torch.Tensor:
     return 1.4426 * 0.5 * (torch.pow(mu, 2) + var - 1.0 - logvar)
-
-
-def _train_fused() -> bool:
-    """False when GQHIP_TRAIN_FUSED=0 asks for the op-by-op torch path of the train-mode step (read per call)."""
-    return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
 
 
 class _GaussTrainFn(torch.autograd.Function):
@@ -210,27 +206,15 @@ class GaussianQuantRegularizer(_GaussianQuantBase):
         """Eval branch (gaussian.py:120-160) as ONE call: chunk / clamp / exp, the group permutes, zhat_noquant, the
         rows x n score matrix, arg-max and gather all happen inside libgqhip's three launches.  A channels_last z
         (what the NHWC conv stack hands over) is read, and zhat / indices / zhat_noquant are written, in that memory
-        layout directly: NHWC memory of [B, C, h, w] IS the "blc" layout with L = h * w, so nothing is transposed."""
+        layout directly (_fused.format_view), so nothing is transposed."""
         z = z.float()
-        if self.format == "bchw":
-            b, c2, h, w = z.shape
-            shape_n = (b, c2 // 2, h, w)
-            if not z.is_contiguous() and z.is_contiguous(memory_format=torch.channels_last):
-                zmem = z.permute(0, 2, 3, 1).reshape(b, h * w, c2)   # a view of the same memory
-                # one draw of the size of mu (advances the generator like gaussian.py:121)
-                noise = torch.randn((b, h * w, c2 // 2), dtype=torch.float32, device=z.device)
-                ind, zhat, noq = _lib.gq_quantize_z(zmem, self.prior_samples, self.group, "blc", _lib.GQHIP_GROUP_STRIDED,
-                                                    self.logvar_range, self.beta, self._ws, noise=noise)
-                as_bchw = lambda t: t.view(b, h, w, -1).permute(0, 3, 1, 2)   # logical [B, C, h, w], NHWC memory
-                return as_bchw(zhat), {"indices": as_bchw(ind), "zhat_noquant": as_bchw(noq)}
-        else:
-            b, l, c2 = z.shape
-            shape_n = (b, l, c2 // 2)
-        noise = torch.randn(shape_n, dtype=torch.float32, device=z.device)
-        indices, zhat, zhat_noquant = _lib.gq_quantize_z(z, self.prior_samples, self.group, self.format,
-                                                         _lib.GQHIP_GROUP_STRIDED, self.logvar_range, self.beta,
-                                                         self._ws, noise=noise)
-        return zhat, {"indices": indices, "zhat_noquant": zhat_noquant}
+        assert z.dim() == (4 if self.format == "bchw" else 3)
+        zv, layout, restore = format_view(z, self.format)
+        # one draw of the size of mu (advances the generator like gaussian.py:121)
+        noise = torch.randn(mu_shape(zv, layout), dtype=torch.float32, device=z.device)
+        indices, zhat, zhat_noquant = _lib.gq_quantize_z(zv, self.prior_samples, self.group, layout, _lib.GQHIP_GROUP_STRIDED,
+                                                         self.logvar_range, self.beta, self._ws, noise=noise)
+        return restore(zhat), {"indices": restore(indices), "zhat_noquant": restore(zhat_noquant)}
 
     def _forward_train_fused(self, z):
         """Train branch (gaussian.py:77-119) as ONE forward library call (gq_gauss_train_f32: sample, per-row KL bits, statistics,
@@ -239,19 +223,10 @@ class GaussianQuantRegularizer(_GaussianQuantBase):
         -max (0-d fp32, detached: INTEGRATION.md), lam (0-d fp32, the value after the update).  Nothing is read back: m.lam,
         m.lam_min, m.lam_max pull the device state when somebody looks."""
         z = z.float()
-        restore = lambda t: t
-        if self.format == "bchw":
-            b, c2, h, w = z.shape
-            if not z.is_contiguous() and z.is_contiguous(memory_format=torch.channels_last):
-                zv, layout = z.permute(0, 2, 3, 1).reshape(b, h * w, c2), "blc"      # a view of the same memory
-                shape_n = (b, h * w, c2 // 2)
-                restore = lambda t: t.view(b, h, w, -1).permute(0, 3, 1, 2)          # logical [B, C, h, w], NHWC memory
-            else:
-                zv, layout, shape_n = z.contiguous(), "bchw", (b, c2 // 2, h, w)
-        else:
-            b, l, c2 = z.shape
-            zv, layout, shape_n = z.contiguous(), "blc", (b, l, c2 // 2)
-        noise = torch.randn(shape_n, dtype=torch.float32, device=z.device)
+        assert z.dim() == (4 if self.format == "bchw" else 3)
+        zv, layout, restore = format_view(z, self.format)
+        b = z.shape[0]
+        noise = torch.randn(mu_shape(zv, layout), dtype=torch.float32, device=z.device)
 
         def run(zv_, noise_, lam_state):
             zhat, _, _, sc = _lib.gq_gauss_train(zv_, self.group, layout, _lib.GQHIP_GROUP_STRIDED, noise_, lam_state,
@@ -270,7 +245,7 @@ class GaussianQuantRegularizer(_GaussianQuantBase):
     def forward(self, z):
         if not self.training and not self._compat():
             return self._forward_fused(z)
-        if self.training and z.is_cuda and z.numel() > 0 and _train_fused():
+        if self.training and z.is_cuda and z.numel() > 0 and train_fused():
             return self._forward_train_fused(z)
         z = z.float()
         if self.format == "bchw":
@@ -371,25 +346,6 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         indices = self._restore(indices, z_shape)
         return zhat, {"indices": indices, "zhat_quant": zhat}
 
-    def _fused_view(self, z):
-        """z as (tensor, layout, restore) for the module-level kernels without a copy where its memory allows: a contiguous z is
-        [outer, 2C, inner] = the "bchw" layout for any dim_idx; a channels_last 4-d z with dim_idx 1 is the "blc" layout."""
-        d = self.dim_idx % z.dim()
-        if z.is_contiguous():
-            outer = int(math.prod(z.shape[:d]))
-            inner = int(math.prod(z.shape[d + 1:]))
-            if inner == 1:
-                zv = z.reshape(1, outer, z.shape[d])
-                return zv, "blc", lambda t: t.reshape(*z.shape[:d], -1, *z.shape[d + 1:])
-            zv = z.reshape(outer, z.shape[d], inner)
-            return zv, "bchw", lambda t: t.reshape(*z.shape[:d], -1, *z.shape[d + 1:])
-        zl = torch.movedim(z, d, -1)
-        if not zl.is_contiguous():
-            zl = zl.contiguous()
-        lead = zl.shape[:-1]
-        zv = zl.reshape(1, -1, zl.shape[-1])
-        return zv, "blc", lambda t: torch.movedim(t.reshape(*lead, -1), -1, d)
-
     def _forward_fused(self, z, autograd=False):
         """Eval forward (gaussian.py:333-345) as ONE library call: quant_gaussian's sample, statistics, re-weighted loss and lambda
         update, quant_vq's arg-max and gather, and the straight-through mix all happen in gq_quantize_z_gauss_f32's launches.  The
@@ -401,10 +357,9 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         nothing flows through it.  The noise is one torch.randn draw in the shape and memory layout of zhat."""
         z = z.float()
         assert z.shape[self.dim_idx] % (self.dim * 2) == 0
-        zv, layout, restore = self._fused_view(z)
-        c = zv.shape[1 if layout == "bchw" else 2] // 2
-        shape_n = (zv.shape[0], c, zv.shape[2]) if layout == "bchw" else (zv.shape[0], zv.shape[1], c)
-        noise = torch.randn(shape_n, dtype=torch.float32, device=z.device)     # one draw of the size of mu (gaussian.py:222)
+        zv, layout, restore = axis_view(z, self.dim_idx)
+        # one draw of the size of mu (gaussian.py:222)
+        noise = torch.randn(mu_shape(zv, layout), dtype=torch.float32, device=z.device)
 
         def run(zv_, noise_, lam_state):
             ind, zhat, zq, noq, std, sc = _lib.gq_quantize_z_gauss(
@@ -437,7 +392,7 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         if z.is_cuda and not self._compat():
             if not (torch.is_grad_enabled() and z.requires_grad):
                 return self._forward_fused(z)
-            if _train_fused() and z.numel() > 0:
+            if train_fused() and z.numel() > 0:
                 return self._forward_fused(z, autograd=True)
         zhat_g, info_g = self.quant_gaussian(z)
         with torch.no_grad():
@@ -449,11 +404,8 @@ class GaussianQuantRegularizer2(_GaussianQuantBase):
         return zhat, info_g | info_v
 
     def dequant(self, indices):
-        ind = torch.movedim(indices, self.dim_idx, -1)
-        i_shape = ind.shape
-        flat = ind.reshape(1, -1, i_shape[-1]).contiguous()
-        zhat = _lib.gq_dequant(flat, self.prior_samples, self.dim, "blc", _lib.GQHIP_GROUP_CONTIGUOUS)[0]
-        return torch.movedim(zhat.reshape(*i_shape[:-1], -1), -1, self.dim_idx)
+        flat, layout, restore = positions_view(indices, self.dim_idx % indices.dim())
+        return restore(_lib.gq_dequant(flat, self.prior_samples, self.dim, layout, _lib.GQHIP_GROUP_CONTIGUOUS))
 
 
 class IdentityRegularizer(nn.Module):

@@ -8,12 +8,11 @@ Eval returns the same ``info`` keys as the reference with zero losses
 the softmax over the product codebook factorises into d Bernoullis per row, so the
 ``[rows, 2^d]`` logits matrix of lfq.py:63-69 is never built (the batch-average
 distribution is a 2^dh x rows x 2^dl GEMM of per-row probability tables); neither
-call reads the host.  ``GQHIP_TRAIN_FUSED=0`` in the environment (read per call,
-the switch of the Gaussian and VQ train steps) selects the plain torch losses
-instead; CPU tensors always take them."""
+call reads the host.  ``GQHIP_TRAIN_FUSED=0`` in the environment (read per call:
+``_fused.train_fused``, the one switch of every fused train step) selects the plain
+torch losses instead; CPU tensors always take them."""
 from __future__ import annotations
 
-import os
 from math import log2
 
 import torch
@@ -22,6 +21,7 @@ from torch import einsum
 from torch.nn import Module
 
 from .. import _lib
+from ._fused import format_view, train_fused
 
 
 def lfq_entropy_loss(logits, temperature=0.01, sample_minimization_weight=1.0, batch_maximization_weight=1.0,
@@ -34,11 +34,6 @@ def lfq_entropy_loss(logits, temperature=0.01, sample_minimization_weight=1.0, b
     sample_entropy = torch.mean(-torch.sum(probs * log_probs, -1))
     loss = sample_minimization_weight * sample_entropy - batch_maximization_weight * avg_entropy
     return sample_entropy, avg_entropy, loss
-
-
-def _train_fused() -> bool:
-    """False when GQHIP_TRAIN_FUSED=0 asks for the op-by-op torch path of the train step (read per call)."""
-    return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
 
 
 class _LFQTrainFn(torch.autograd.Function):
@@ -90,13 +85,9 @@ class LFQQuantizer(Module):
 
     def _forward_fused(self, x):
         """lfq.py:160-208 in train() as one call.  A channels_last x (what the NHWC conv stack hands over) is read, and quantized
-        / indices are written, in that memory layout: NHWC memory of [B, c, h, w] IS the "blc" layout (the permuted views are
-        autograd's own, they copy nothing in either direction)."""
-        xv, layout, as_module = x.float(), self.format, lambda t: t
-        if self.format == "bchw" and not xv.is_contiguous() and xv.is_contiguous(memory_format=torch.channels_last):
-            b, c, h, w = xv.shape
-            xv, layout = xv.permute(0, 2, 3, 1).reshape(b, h * w, c), "blc"          # a view of the same memory
-            as_module = lambda t: t.view(b, h, w, -1).permute(0, 3, 1, 2)
+        / indices are written, in that memory layout (_fused.format_view; the permuted views are autograd's own, they copy
+        nothing in either direction)."""
+        xv, layout, as_module = format_view(x.float(), self.format)
         cfg = (self.num_codebooks, self.codebook_dim, layout, self.sample_minimization_weight, self.batch_maximization_weight,
                self._tws)
         if torch.is_grad_enabled() and xv.requires_grad:
@@ -109,7 +100,7 @@ class LFQQuantizer(Module):
         return as_module(quantized).to(x.dtype), info
 
     def forward(self, x):
-        if x.is_cuda and self.training and _train_fused():
+        if x.is_cuda and self.training and train_fused():
             return self._forward_fused(x)
         if self.format == "bchw":
             b, c, h, w = x.shape

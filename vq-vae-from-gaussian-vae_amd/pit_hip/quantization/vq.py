@@ -10,23 +10,18 @@ lookup, straight-through value, the two MSE means -- is ONE library call
 ``torch.autograd.Function`` whose backward is ONE library call as well
 (``vq_backward_f32``: grad_z elementwise, grad of the codebook as a bit-reproducible
 scatter-reduce, no float atomics); neither reads the host.  ``GQHIP_TRAIN_FUSED=0``
-in the environment (read per call, the switch of the Gaussian train step) selects
-the op-by-op path instead: the arg-min in the library (``vq_argmin_f32``), the
-differentiable glue in torch.  CPU tensors always take that path."""
+in the environment (read per call: ``_fused.train_fused``, the one switch of every
+fused train step) selects the op-by-op path instead: the arg-min in the library
+(``vq_argmin_f32``), the differentiable glue in torch.  CPU tensors always take that
+path."""
 from __future__ import annotations
-
-import os
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib
-
-
-def _train_fused() -> bool:
-    """False when GQHIP_TRAIN_FUSED=0 asks for the op-by-op torch path of the train step (read per call)."""
-    return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
+from ._fused import format_view, train_fused
 
 
 class _VQTrainFn(torch.autograd.Function):
@@ -85,8 +80,8 @@ class VQQuantizer(nn.Module):
 
     def _forward_fused(self, z, recording=False):
         """vq.py:39-96 as one call.  A channels_last z (what the NHWC conv stack hands over) is read, and z_q / indices are written,
-        in that memory layout: NHWC memory of [B, c, h, w] IS the "blc" layout.  ``recording``: autograd records, so the call goes
-        through _VQTrainFn (the permuted views below are autograd's own, they copy nothing in either direction)."""
+        in that memory layout (_fused.format_view).  ``recording``: autograd records, so the call goes through _VQTrainFn (the
+        permuted views are autograd's own, they copy nothing in either direction)."""
         z = z.float()
 
         def run(zv, layout):
@@ -101,23 +96,18 @@ class VQQuantizer(nn.Module):
 
         if self.format == "bchw":
             b, c, h, wd = z.shape
-            assert self.dim * self.codebook_num == c
-            if not z.is_contiguous() and z.is_contiguous(memory_format=torch.channels_last):
-                zmem = z.permute(0, 2, 3, 1).reshape(b, h * wd, c)          # a view of the same memory
-                zq, ind, loss = run(zmem, "blc")
-                as_bchw = lambda t: t.view(b, h, wd, -1).permute(0, 3, 1, 2)
-                return as_bchw(zq), {"indices": as_bchw(ind), "codebook_loss": loss}
         else:
             b, l, c = z.shape
             h = int(np.sqrt(l))
             assert h * h == l, "Input length must be a perfect square for blc format"
-            assert self.dim * self.codebook_num == c
-        zq, ind, loss = run(z, self.format)
-        return zq, {"indices": ind, "codebook_loss": loss}
+        assert self.dim * self.codebook_num == c
+        zv, layout, restore = format_view(z, self.format)
+        zq, ind, loss = run(zv, layout)
+        return restore(zq), {"indices": restore(ind), "codebook_loss": loss}
 
     def forward(self, z):
         recording = torch.is_grad_enabled() and (z.requires_grad or self.embedding.weight.requires_grad)
-        if z.is_cuda and (not recording or _train_fused()):
+        if z.is_cuda and (not recording or train_fused()):
             return self._forward_fused(z, recording)
         z = self._to_bhwc(z)
         assert self.dim * self.codebook_num == z.shape[-1]
