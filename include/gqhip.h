@@ -60,7 +60,9 @@ extern "C" {
                                *    MS-SSIM (gq_ssim_f32), the three-metric step record (gq_step_record_ssim_f32), the train-mode step of the Gaussian
                                *    regularizers (gq_gauss_train_f32, gq_gauss_backward_f32), the backward of VQQuantizer's train step
                                *    (vq_backward_f32, vq_backward_workspace_bytes), LFQQuantizer's train step
-                               *    (lfq_train_f32, lfq_backward_f32, lfq_train_workspace_bytes) */
+                               *    (lfq_train_f32, lfq_backward_f32, lfq_train_workspace_bytes), the bit-packed index wire format for any
+                               *    codebook size (gq_indices_pack_bits, gq_indices_unpack_bits, gq_index_histogram_packed,
+                               *    gq_step_record_bits_f32, gq_step_record_ssim_bits_f32 and their two _workspace_bytes functions) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -626,6 +628,45 @@ int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_
 int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
 int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
                             int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream);
+
+/* ---- the bit-packed index wire format: any codebook size up to 2^32 ---------
+ * Index k -- its low w = index_bits bits (1 <= w <= 32), the value taken as unsigned 32-bit -- occupies bits [k w, (k + 1) w) of a
+ * little-endian bit stream laid over int32 words: stream bit p is bit p mod 32 of word p div 32, and the stream is zero-padded to
+ * a whole word, ceil(count w / 32) words.  An index straddles two words when 32 % w != 0.  w = 16 is exactly the "uint16 pairs,
+ * low half first" format above.  n_codes (1 <= n_codes <= 2^w, else GQHIP_ERR_INVALID_ARG) is the codebook size: an index outside
+ * [0, n_codes) is a VIOLATION -- it is packed as its low w bits and counted.  Every word is written by one thread with a plain
+ * store, from indices read with coalesced loads through LDS (csrc/gq_aux.h); the counts are summed per block and added with one
+ * integer atomic per block.  All calls here are asynchronous on `stream`, allocate nothing and are graph-capturable.
+ *
+ * gq_indices_pack_bits: words[ceil(count w / 32)] <- idx[count]; violations_or_null: one int32 that receives the number of
+ *   violations, saturated at 2^31 - 1 (zeroed in-stream by the call, then added to).
+ * gq_indices_unpack_bits: n_records packed fields of `count` indices each, field r at records + r stride_words + offset_words
+ *   (stride_words - offset_words >= ceil(count w / 32)) -> idx[n_records, count], each value in [0, 2^w).  One field: n_records 1.
+ * gq_index_histogram_packed: hist[v] += 1 (int64 hist[n]; it ADDS: a running histogram over many calls, zeroed by the caller)
+ *   for every value v < n of the same fields, read from the packed words -- no int64 indices are formed; values >= n are skipped.
+ *   Integer atomics only: the result is exact whatever the order. */
+int gq_indices_pack_bits(const int64_t *idx, int32_t *words, int64_t count, int index_bits, int64_t n_codes,
+                         int32_t *violations_or_null, void *stream);
+int gq_indices_unpack_bits(const int32_t *records, int64_t *idx, int64_t n_records, int64_t stride_words, int64_t offset_words,
+                           int64_t count, int index_bits, void *stream);
+int gq_index_histogram_packed(const int32_t *records, int64_t n_records, int64_t stride_words, int64_t offset_words, int64_t count,
+                              int index_bits, int64_t n, int64_t *hist, void *stream);
+/* The step records with bit-packed indices -- pit_hip/eval_dist.py:StepRecord(n_codes=...):
+ *     rec [B m + ceil(n_idx w / 32) + 1] int32 = [ the metric words of gq_step_record_f32 (m = 1) / gq_step_record_ssim_f32 (m = 3),
+ *                                                  from the same code, bit-identical | the packed index words | 1 violations word ].
+ * The violations word is this record's number of indices outside [0, n_codes), saturated at 2^31 - 1, written with a plain store
+ * by the last packing block (the per-block counts meet in the workspace: no atomics on the record); it is written when n_idx = 0
+ * too.  workspace: gq_step_record_bits_workspace_bytes(B, per_image) / gq_step_record_ssim_bits_workspace_bytes(B, C, H, W) bytes
+ * (8 more than the uint16 records need: the violations count and its ticket; required for every call), under the contract of
+ * gq_step_record_f32: ZERO when first used, every byte left zero, any later shape whose byte count it holds. */
+int64_t gq_step_record_bits_workspace_bytes(int64_t B, int64_t per_image);
+int gq_step_record_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                            int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int64_t workspace_bytes,
+                            void *stream);
+int64_t gq_step_record_ssim_bits_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int gq_step_record_ssim_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
+                                 int64_t W, int layout, int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed,
+                                 int64_t workspace_bytes, void *stream);
 
 /* Fused multi-head self-attention forward -- pit/modules/vit.py:142-151 (nn.MultiheadAttention(x, x, x, need_weights=False):
  * softmax(q k^T / sqrt(d)) v per (batch, head), no mask, no dropout; csrc/gq_attn.h).

@@ -5,7 +5,9 @@ encode -> quantize -> decode per rank, ONE packed all_gather per step, rank 0 pr
 
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 tools/eval_sharded.py \
       --base configs/sd3unet_gq_0.25.yaml [--ckpt model.ckpt] [--dataset DIR|list.txt] --img_size 256 --bs 16 \
-      [--metrics psnr,ssim,ms_ssim]
+      [--metrics psnr,ssim,ms_ssim] [--n_codes N]
+--n_codes N: the bit-packed index record for a codebook of N entries (any size up to 2^32; without it indices must be < 65536):
+no host read per step, usage / entropy from the histogram accumulated over the whole run.
 Without --dataset a seeded synthetic image bank is used (no data offline)."""
 import argparse
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--bs", type=int, default=1)
     ap.add_argument("--num", type=int, default=64, help="synthetic images when no --dataset is given")
     ap.add_argument("--metrics", default="psnr", help="psnr, or psnr,ssim,ms_ssim (eval.py:165-178)")
+    ap.add_argument("--n_codes", type=int, default=0, help="codebook size: selects the bit-packed index record (default: uint16 record)")
     a = ap.parse_args()
     env = init_from_env(a.dist_backend)
     rank, world = env["rank"], env["world"]
@@ -55,7 +58,7 @@ def main():
     with torch.no_grad():  # tokens per image from a probe (depends on the config's downsampling and K)
         tokens = model.encode(images_for([0]).to(device), return_reg_log=True)[1]["indices"][0].numel()
     metrics = tuple(m.strip() for m in a.metrics.split(",") if m.strip())
-    out = evaluate_sharded(model, images_for, n, a.bs, rank, world, device, tokens, metrics=metrics)
+    out = evaluate_sharded(model, images_for, n, a.bs, rank, world, device, tokens, metrics=metrics, n_codes=a.n_codes or None)
     if rank == 0 and out is not None:
         psnr = out["psnr"].float()
         print(f"PSNR: {psnr.mean():.4f} (±{psnr.std(unbiased=False):.4f})  over {psnr.numel()} images")
@@ -63,8 +66,11 @@ def main():
             if key in out:
                 v = out[key].float()
                 print(f"{label}: {v.mean():.4f} (±{v.std(unbiased=False):.4f})")
-        n_codes = getattr(model.regularization, "n_samples", 65536)
-        _, usage, ent = codebook_usage(out["indices"].to(device), n_codes)   # eval.py:137-141
+        if "hist" in out:
+            usage, ent = out["usage"], out["entropy"]
+        else:
+            n_codes = getattr(model.regularization, "n_samples", 65536)
+            _, usage, ent = codebook_usage(out["indices"].to(device), n_codes)   # eval.py:137-141
         print(f"codebook usage: {usage:.4f}  entropy: {ent:.3f} bits")
     if world > 1:
         import torch.distributed as dist

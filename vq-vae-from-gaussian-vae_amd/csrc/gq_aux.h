@@ -1,7 +1,7 @@
 // gq_aux.h -- the small HBM-bound kernels around the filter: codebook abs-max,
 // workspace header init, operand prep from the encoder output, dequant gather,
 // the reference-compatible score-matrix op, LFQ bit pack/unpack, index
-// histogram and the u16 wire format.
+// histogram, the u16 wire format and the bit-packed one for any codebook size.
 #pragma once
 #include "gq_common.h"
 #include "gq_rerank.h"
@@ -260,18 +260,10 @@ struct StepRecordParams {
 };
 constexpr int kPsnrChunk = 256 * 4 * 8;      // floats per block: eight 16-byte loads per thread
 
-__global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams p) {
+// PSNR block `blk` of [0, B * chunks): shared by the uint16 record and the bit-packed one, so their metric words are the same code.
+__device__ __forceinline__ void step_record_psnr_block(const StepRecordParams &p, const int blk) {
   const int tid = threadIdx.x;
-  if ((int)blockIdx.x >= p.psnr_blocks) {
-    const long w = (long)(blockIdx.x - p.psnr_blocks) * 256 + tid;        // one packed word per thread
-    if (2 * w < p.n_idx) {
-      const unsigned lo = (unsigned)p.idx[2 * w] & 0xffffu;
-      const unsigned hi = 2 * w + 1 < p.n_idx ? (unsigned)p.idx[2 * w + 1] & 0xffffu : 0u;
-      p.rec[(long)p.B * p.stride + w] = (int)(lo | (hi << 16));
-    }
-    return;
-  }
-  const int b = blockIdx.x / p.chunks, ch = blockIdx.x % p.chunks;
+  const int b = blk / p.chunks, ch = blk % p.chunks;
   const long e0 = (long)ch * kPsnrChunk, e1 = e0 + kPsnrChunk < p.per_image ? e0 + kPsnrChunk : p.per_image;
   const float *xa = p.x + (long)b * p.per_image, *xb = p.x_rec + (long)b * p.per_image;
   double acc = 0.0;
@@ -313,6 +305,149 @@ __global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams
   const float psnr = (float)(20.0 * log10(255.0 / sqrt((double)mse)));      // identical images: +inf, like the reference
   p.rec[(long)b * p.stride] = __float_as_int(psnr);
   p.ticket[b] = 0;                             // ready for the next call on this workspace
+}
+
+__global__ __launch_bounds__(256) void step_record_kernel(const StepRecordParams p) {
+  if ((int)blockIdx.x >= p.psnr_blocks) {
+    const long w = (long)(blockIdx.x - p.psnr_blocks) * 256 + threadIdx.x;        // one packed word per thread
+    if (2 * w < p.n_idx) {
+      const unsigned lo = (unsigned)p.idx[2 * w] & 0xffffu;
+      const unsigned hi = 2 * w + 1 < p.n_idx ? (unsigned)p.idx[2 * w + 1] & 0xffffu : 0u;
+      p.rec[(long)p.B * p.stride + w] = (int)(lo | (hi << 16));
+    }
+    return;
+  }
+  step_record_psnr_block(p, (int)blockIdx.x);
+}
+
+// ---- the bit-packed index wire format: any codebook size up to 2^32 ----------------------------------------------------------------
+// Index k -- its low w bits, the value taken as unsigned 32-bit -- occupies bits [k w, (k + 1) w) of a little-endian bit stream over
+// int32 words (stream bit p = bit p mod 32 of word p div 32), zero-padded to a whole word; w = 16 is the uint16 pair format above.
+// A block owns 256 consecutive words = stream bits [8192 blk, 8192 (blk + 1)).  It reads the indices that touch those bits with
+// coalesced 8-byte loads (lane i takes index base + i), kBitsTile at a time, leaves their masked values in LDS, and every thread
+// ORs its own word together from the at most ceil(32 / w) + 1 of them that touch it: one plain store per word, no atomics on the
+// stream.  An index outside [0, n_codes) is counted by the block that owns its FIRST bit (so once), the counts are summed per
+// block, and the sum is returned to thread 0.
+constexpr int kBitsTile = 2048 + 64;          // indices per LDS pass: w >= 4 needs one pass (8192 / 4 + 2)
+struct PackBitsParams {
+  const int64_t *idx;         // [n_idx]
+  int *words;                 // [n_words]
+  long n_idx, n_words;        // n_words = ceil(n_idx w / 32)
+  int64_t n_codes;
+  int w;                      // 1..32
+};
+
+__device__ __forceinline__ int pack_bits_block(const PackBitsParams &p, const long blk) {
+  __shared__ unsigned s_val[kBitsTile];
+  __shared__ int s_viol[4];
+  const int tid = threadIdx.x;
+  const unsigned mask = p.w == 32 ? 0xffffffffu : (1u << p.w) - 1u;
+  const long bit0 = blk * 8192;                                     // the block's first stream bit
+  const long k_lo = bit0 / p.w;                                     // first index with a bit in the block
+  long k_hi = (bit0 + 8191) / p.w;                                  // last one
+  k_hi = k_hi < p.n_idx ? k_hi : p.n_idx - 1;
+  const long word = blk * 256 + tid, p0 = word * 32;                // this thread's word, its first stream bit
+  const long k0 = p0 / p.w;
+  long k1 = (p0 + 31) / p.w;
+  k1 = k1 < p.n_idx ? k1 : p.n_idx - 1;
+  unsigned out = 0u;
+  int viol = 0;
+  for (long base = k_lo; base <= k_hi; base += kBitsTile) {
+    if (base != k_lo) __syncthreads();                              // the previous pass has been read
+    for (int i = tid; i < kBitsTile && base + i <= k_hi; i += 256) {
+      const int64_t v = p.idx[base + i];
+      s_val[i] = (unsigned)v & mask;
+      viol += ((v < 0 || v >= p.n_codes) && (base + i) * p.w >= bit0) ? 1 : 0;
+    }
+    __syncthreads();
+    const long lo = k0 > base ? k0 : base, hi = k1 < base + kBitsTile - 1 ? k1 : base + kBitsTile - 1;
+    for (long k = lo; k <= hi; ++k) {
+      const int sh = (int)(k * p.w - p0);                           // in (-w, 32)
+      const unsigned v = s_val[k - base];
+      out |= sh >= 0 ? v << sh : v >> -sh;
+    }
+  }
+  if (word < p.n_words) p.words[word] = (int)out;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) viol += __shfl_xor(viol, o);
+  if ((tid & 63) == 0) s_viol[tid >> 6] = viol;
+  __syncthreads();
+  return (s_viol[0] + s_viol[1]) + (s_viol[2] + s_viol[3]);
+}
+
+// *p = min(*p + v, 2^31 - 1) for v >= 0: the one integer atomic a block spends on its violations
+__device__ __forceinline__ void saturating_add(int *p, const int v) {
+  int old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), seen;
+  do {
+    seen = old;
+    old = atomicCAS(p, seen, seen > 0x7fffffff - v ? 0x7fffffff : seen + v);
+  } while (old != seen);
+}
+
+// gq_indices_pack_bits: violations (or NULL) was zeroed in-stream by the entry point
+__global__ __launch_bounds__(256) void pack_bits_kernel(const PackBitsParams p, int *__restrict__ violations) {
+  const int viol = pack_bits_block(p, (long)blockIdx.x);
+  if (threadIdx.x == 0 && violations && viol) saturating_add(violations, viol);
+}
+
+// value k of a bit-packed field (the inverse of the above)
+__device__ __forceinline__ unsigned unpack_bits_at(const int *__restrict__ field, const long k, const int w) {
+  const long p = k * w;
+  const long wd = p >> 5;
+  const int off = (int)(p & 31);
+  unsigned v = (unsigned)field[wd] >> off;
+  if (off + w > 32) v |= (unsigned)field[wd + 1] << (32 - off);      // the index straddles two words (then off > 0)
+  return w == 32 ? v : v & ((1u << w) - 1u);
+}
+
+// n_records fields of `count` indices each, field r at records + r * stride + offset (words): one index per thread, 8-byte
+// coalesced stores; neighbouring lanes read the same or neighbouring words.
+__global__ __launch_bounds__(256) void unpack_bits_kernel(const int *__restrict__ records, int64_t *__restrict__ idx, long n_records,
+                                                          long stride, long offset, long count, int w) {
+  const long total = n_records * count;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / count, k = i - r * count;
+    idx[i] = (int64_t)unpack_bits_at(records + r * stride + offset, k, w);
+  }
+}
+
+// hist[v] += 1 for every packed value v < n of the same fields: integer atomics only, so the sums are exact whatever the order
+__global__ __launch_bounds__(256) void hist_packed_kernel(const int *__restrict__ records, long n_records, long stride, long offset,
+                                                          long count, int w, int64_t n, unsigned long long *__restrict__ hist) {
+  const long total = n_records * count;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long r = i / count, k = i - r * count;
+    const unsigned v = unpack_bits_at(records + r * stride + offset, k, w);
+    if ((int64_t)v < n) atomicAdd(&hist[v], 1ull);
+  }
+}
+
+// ---- the step record with bit-packed indices: [ metrics as in step_record_kernel | n_words index words | 1 violations word ] -------
+// Blocks [0, pack_blocks) pack (first, so the short ones are not the kernel's tail), the rest are step_record_psnr_block.  The
+// violations count goes through ONE 64-bit workspace word behind the PSNR workspace, zero between calls like the rest: bits 0..39
+// the running count, bits 40..63 a ticket.  A packing block adds (1 << 40) + its count with one integer atomic; the block whose
+// add returns ticket pack_blocks - 1 has the other blocks' total in the same returned value, stores the sum (saturated) into the
+// record with a plain store and zeroes the word.  pack_blocks < 2^24 (the host checks), so the count stays below 2^37.
+constexpr int kViolTicketShift = 40;
+struct StepRecordBitsParams {
+  StepRecordParams r;         // r.rec, r.B, r.stride: the metric block; r.idx / r.n_idx: the indices
+  PackBitsParams k;           // k.words = r.rec + B * stride
+  unsigned long long *viol;   // workspace: count | ticket << 40
+  int pack_blocks;            // >= 1: the violations word is written even when there are no indices
+};
+
+__global__ __launch_bounds__(256) void step_record_bits_kernel(const StepRecordBitsParams p) {
+  if ((int)blockIdx.x >= p.pack_blocks) {
+    step_record_psnr_block(p.r, (int)blockIdx.x - p.pack_blocks);
+    return;
+  }
+  const int viol = pack_bits_block(p.k, (long)blockIdx.x);
+  if (threadIdx.x != 0) return;
+  const unsigned long long old = atomicAdd(p.viol, (1ull << kViolTicketShift) + (unsigned long long)viol);
+  if ((int)(old >> kViolTicketShift) != p.pack_blocks - 1) return;
+  const unsigned long long total = (old & ((1ull << kViolTicketShift) - 1)) + (unsigned long long)viol;
+  p.k.words[p.k.n_words] = total > 0x7fffffffull ? 0x7fffffff : (int)total;
+  *p.viol = 0ull;                               // ready for the next call on this workspace
 }
 
 // ---- VQ's codebook loss in eval (pit/quantization/vq.py:78-86): mean((z_q - z)^2) over every element --------------------------

@@ -1233,6 +1233,101 @@ int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, i
   return step_record_launch(x, x_rec, idx, rec, B, per_image, n_idx, workspace_zeroed, 1, static_cast<hipStream_t>(stream));
 }
 
+// ---- the bit-packed index wire format (csrc/gq_aux.h) ----------------------------------------------------------------------------
+namespace {
+// 1 <= index_bits <= 32 and 1 <= n_codes <= 2^index_bits: every in-range index survives the packing
+bool bits_args_ok(int index_bits, int64_t n_codes) {
+  return index_bits >= 1 && index_bits <= 32 && n_codes >= 1 && n_codes <= ((int64_t)1 << index_bits);
+}
+// the stream of `count` indices in words; -1 when the bit count leaves int64 or the block count leaves the grid
+int64_t bits_words(int64_t count, int index_bits) {
+  if (count < 0 || count > (INT64_MAX - 8192) / 32) return -1;
+  const int64_t words = (count * index_bits + 31) / 32;
+  return (words + 255) / 256 > 0x3fffffff ? -1 : words;
+}
+PackBitsParams pack_bits_params(const int64_t *idx, int32_t *words, int64_t count, int64_t n_words, int index_bits, int64_t n_codes) {
+  PackBitsParams k{};
+  k.idx = idx; k.words = words; k.n_idx = (long)count; k.n_words = (long)n_words; k.n_codes = n_codes; k.w = index_bits;
+  return k;
+}
+// the records argument of the unpack / histogram entry points: n_records fields of `count` indices at records + r stride + offset
+bool packed_fields_ok(const void *records, int64_t n_records, int64_t stride_words, int64_t offset_words, int64_t count,
+                      int index_bits) {
+  if (!records || n_records < 0 || count < 0 || index_bits < 1 || index_bits > 32 || offset_words < 0) return false;
+  const int64_t words = bits_words(count, index_bits);
+  if (words < 0 || stride_words < 0 || stride_words - offset_words < words) return false;
+  return n_records == 0 || count == 0 || n_records <= INT64_MAX / count;
+}
+}  // namespace
+
+int gq_indices_pack_bits(const int64_t *idx, int32_t *words, int64_t count, int index_bits, int64_t n_codes,
+                         int32_t *violations_or_null, void *stream) {
+  const int64_t n_words = bits_words(count, index_bits);
+  if (!bits_args_ok(index_bits, n_codes) || n_words < 0 || (count > 0 && (!idx || !words))) return GQHIP_ERR_INVALID_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (violations_or_null && hipMemsetAsync(violations_or_null, 0, sizeof(int32_t), st) != hipSuccess) return check_launch();
+  if (count == 0) return GQHIP_OK;
+  return launch(pack_bits_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st,
+                pack_bits_params(idx, words, count, n_words, index_bits, n_codes), violations_or_null);
+}
+
+int gq_indices_unpack_bits(const int32_t *records, int64_t *idx, int64_t n_records, int64_t stride_words, int64_t offset_words,
+                           int64_t count, int index_bits, void *stream) {
+  if (!packed_fields_ok(records, n_records, stride_words, offset_words, count, index_bits) || !idx) return GQHIP_ERR_INVALID_ARG;
+  const int64_t total = n_records * count;
+  if (total == 0) return GQHIP_OK;
+  const int64_t blocks = (total + 255) / 256;
+  return launch(unpack_bits_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                records, idx, (long)n_records, (long)stride_words, (long)offset_words, (long)count, index_bits);
+}
+
+int gq_index_histogram_packed(const int32_t *records, int64_t n_records, int64_t stride_words, int64_t offset_words, int64_t count,
+                              int index_bits, int64_t n, int64_t *hist, void *stream) {
+  if (!packed_fields_ok(records, n_records, stride_words, offset_words, count, index_bits) || !hist || n < 1)
+    return GQHIP_ERR_INVALID_ARG;
+  const int64_t total = n_records * count;
+  if (total == 0) return GQHIP_OK;
+  const int64_t blocks = (total + 255) / 256;
+  return launch(hist_packed_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                records, (long)n_records, (long)stride_words, (long)offset_words, (long)count, index_bits, n,
+                reinterpret_cast<unsigned long long *>(hist));
+}
+
+int64_t gq_step_record_bits_workspace_bytes(int64_t B, int64_t per_image) {
+  const int64_t psnr = gq_step_record_workspace_bytes(B, per_image);
+  return psnr < 0 ? -1 : psnr + 8;          // + one 64-bit word: violations count | ticket
+}
+
+static int step_record_bits_launch(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                                   int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int stride, hipStream_t st) {
+  const int64_t n_words = bits_words(n_idx, index_bits);
+  if (n_words < 0) return GQHIP_ERR_INVALID_ARG;
+  StepRecordBitsParams p{};
+  p.r.x = x; p.r.x_rec = x_rec; p.r.idx = idx; p.r.rec = rec;
+  p.r.per_image = (long)per_image; p.r.n_idx = (long)n_idx; p.r.B = (int)B; p.r.stride = stride;
+  p.r.chunks = (int)((per_image + kPsnrChunk - 1) / kPsnrChunk);
+  if ((int64_t)p.r.chunks * B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  p.r.psnr_blocks = p.r.chunks * (int)B;
+  p.r.partial = static_cast<double *>(workspace_zeroed);
+  p.r.ticket = reinterpret_cast<int *>(static_cast<char *>(workspace_zeroed) + B * p.r.chunks * 8);
+  p.viol = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace_zeroed) + gq_step_record_workspace_bytes(B, per_image));
+  p.k = pack_bits_params(idx, rec + B * stride, n_idx, n_words, index_bits, n_codes);
+  p.pack_blocks = n_words > 0 ? (int)((n_words + 255) / 256) : 1;
+  const int64_t blocks = (int64_t)p.pack_blocks + p.r.psnr_blocks;
+  if (n_words > ((int64_t)1 << 31) || blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;      // the ticket field: pack_blocks < 2^24
+  return launch(step_record_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+}
+
+int gq_step_record_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                            int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int64_t workspace_bytes,
+                            void *stream) {
+  if (B < 0 || per_image < 1 || n_idx < 0 || B > 0x3fffffff || !bits_args_ok(index_bits, n_codes)) return GQHIP_ERR_INVALID_ARG;
+  if (!rec || (B > 0 && (!x || !x_rec)) || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
+  if (!workspace_zeroed || workspace_bytes < gq_step_record_bits_workspace_bytes(B, per_image)) return GQHIP_ERR_WORKSPACE;
+  return step_record_bits_launch(x, x_rec, idx, rec, B, per_image, n_idx, index_bits, n_codes, workspace_zeroed, 1,
+                                 static_cast<hipStream_t>(stream));
+}
+
 // ---- SSIM / MS-SSIM (csrc/gq_ssim.h) ---------------------------------------------------------------------------------------------
 namespace {
 constexpr int64_t kSsimMsMin = 256;          // pit/evaluations/ssim.py:31-34: MS-SSIM only when both sides are >= 256
@@ -1359,6 +1454,29 @@ int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *i
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t head = ((gq_step_record_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
   int rc = step_record_launch(x, x_rec, idx, rec, B, C * H * W, n_idx, workspace_zeroed, 3, st);    // PSNR words + indices
+  if (rc != GQHIP_OK) return rc;
+  return ssim_launch(x, x_rec, B, C, layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3, pl,
+                     static_cast<char *>(workspace_zeroed) + head, st);
+}
+
+int64_t gq_step_record_ssim_bits_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
+  SsimPlan pl;
+  if (!ssim_plan(B, C, H, W, pl)) return -1;
+  const int64_t head = ((gq_step_record_bits_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
+  return head + pl.bytes;
+}
+
+int gq_step_record_ssim_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
+                                 int64_t W, int layout, int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed,
+                                 int64_t workspace_bytes, void *stream) {
+  SsimPlan pl;
+  if (!ssim_plan(B, C, H, W, pl) || (layout != 0 && layout != 1) || n_idx < 0 || !bits_args_ok(index_bits, n_codes))
+    return GQHIP_ERR_INVALID_ARG;
+  if (!x || !x_rec || !rec || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
+  if (!workspace_zeroed || workspace_bytes < gq_step_record_ssim_bits_workspace_bytes(B, C, H, W)) return GQHIP_ERR_WORKSPACE;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t head = ((gq_step_record_bits_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
+  int rc = step_record_bits_launch(x, x_rec, idx, rec, B, C * H * W, n_idx, index_bits, n_codes, workspace_zeroed, 3, st);
   if (rc != GQHIP_OK) return rc;
   return ssim_launch(x, x_rec, B, C, layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3, pl,
                      static_cast<char *>(workspace_zeroed) + head, st);

@@ -129,6 +129,14 @@ _SIGNATURES = {
     "gq_ssim_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp]),
     "gq_step_record_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gq_step_record_ssim_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
+    "gq_indices_pack_bits": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, _i64, _vp, _vp]),
+    "gq_indices_unpack_bits": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp]),
+    "gq_index_histogram_packed": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _vp]),
+    "gq_step_record_bits_workspace_bytes": (_i64, [_i64, _i64]),
+    "gq_step_record_bits_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
+    "gq_step_record_ssim_bits_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
+    "gq_step_record_ssim_bits_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, _i64,
+                                                     _vp, _i64, _vp]),
     "gq_mha_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
     "gq_mha_fwd_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "gq_mha_fwd_lse_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -1441,6 +1449,84 @@ def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
         _check(lib().gq_step_record_ssim_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
                                              image_layout(x), idx.numel(), ws.data_ptr(), ws.numel(), _stream()),
                "gq_step_record_ssim_f32")
+    return rec
+
+
+def _words_out(t, n_words: int, what: str):
+    """A caller's int32 output of ``n_words`` contiguous words on a HIP device (a slice of a record, say)."""
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n_words):
+        raise GqHipError(f"{what} must be {n_words} contiguous int32 words on a HIP device")
+    return t
+
+
+def indices_pack_bits(idx, index_bits: int, n_codes: int, out=None, violations=None):
+    """The bit-packed index stream of ``idx`` (int64, any shape, logical order): int32 [ceil(count index_bits / 32)] (gqhip.h:
+    gq_indices_pack_bits).  ``out``: write the words there; ``violations``: a one-element int32 tensor that receives the number of
+    indices outside [0, n_codes).  No host read."""
+    idx = _dev(idx, torch.int64, "indices")
+    n_words = (idx.numel() * index_bits + 31) // 32
+    out = torch.empty(n_words, dtype=torch.int32, device=idx.device) if out is None else _words_out(out, n_words, "out")
+    if violations is not None:
+        _words_out(violations, 1, "violations")
+    with torch.cuda.device(idx.device):
+        _check(lib().gq_indices_pack_bits(idx.data_ptr(), out.data_ptr(), idx.numel(), index_bits, n_codes, _ptr(violations),
+                                          _stream()), "gq_indices_pack_bits")
+    return out
+
+
+def _packed_records(records, what: str):
+    if not (records.is_cuda and records.dtype == torch.int32 and records.dim() == 2):
+        raise GqHipError(f"{what}: records must be an int32 [n_records, words] tensor on a HIP device")
+    return records if records.is_contiguous() else records.contiguous()
+
+
+def indices_unpack_bits(records, offset_words: int, count: int, index_bits: int):
+    """int64 [n_records, count]: the ``count`` indices of ``index_bits`` bits that start ``offset_words`` into each row of the
+    int32 [n_records, words] tensor ``records`` (gqhip.h: gq_indices_unpack_bits)."""
+    records = _packed_records(records, "indices_unpack_bits")
+    out = torch.empty((records.shape[0], count), dtype=torch.int64, device=records.device)
+    with torch.cuda.device(records.device):
+        _check(lib().gq_indices_unpack_bits(records.data_ptr(), out.data_ptr(), records.shape[0], records.shape[1], offset_words,
+                                            count, index_bits, _stream()), "gq_indices_unpack_bits")
+    return out
+
+
+def index_histogram_packed(records, offset_words: int, count: int, index_bits: int, hist):
+    """hist (int64 [n], HIP) += the counts of the packed indices of ``records`` (as in indices_unpack_bits); values >= n are skipped
+    (gqhip.h: gq_index_histogram_packed).  The int64 indices are never formed."""
+    records = _packed_records(records, "index_histogram_packed")
+    if not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.dim() == 1 and hist.device == records.device):
+        raise GqHipError("index_histogram_packed: hist must be a contiguous int64 [n] tensor on the records' device")
+    with torch.cuda.device(records.device):
+        _check(lib().gq_index_histogram_packed(records.data_ptr(), records.shape[0], records.shape[1], offset_words, count,
+                                               index_bits, hist.numel(), hist.data_ptr(), _stream()), "gq_index_histogram_packed")
+    return hist
+
+
+def step_record_bits(x, x_rec, idx, rec, index_bits: int, n_codes: int, ws_cache: dict):
+    """step_record with the bit-packed index words and the violations word behind the same PSNR words (gqhip.h:
+    gq_step_record_bits_f32)."""
+    B = x.shape[0]
+    per = x[0].numel()
+    idx = idx.contiguous()
+    ws = _zeroed_ws(ws_cache, ("bits", x.device, B, per), lib().gq_step_record_bits_workspace_bytes(B, per), x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().gq_step_record_bits_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, per, idx.numel(),
+                                             index_bits, n_codes, ws.data_ptr(), ws.numel(), _stream()), "gq_step_record_bits_f32")
+    return rec
+
+
+def step_record_ssim_bits(x, x_rec, idx, rec, index_bits: int, n_codes: int, ws_cache: dict):
+    """step_record_ssim with the bit-packed index words and the violations word behind the same metric words (gqhip.h:
+    gq_step_record_ssim_bits_f32)."""
+    B, C, H, W = x.shape
+    idx = idx.contiguous()
+    ws = _zeroed_ws(ws_cache, ("rec3bits", x.device, B, C, H, W), lib().gq_step_record_ssim_bits_workspace_bytes(B, C, H, W),
+                    x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().gq_step_record_ssim_bits_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
+                                                  image_layout(x), idx.numel(), index_bits, n_codes, ws.data_ptr(), ws.numel(),
+                                                  _stream()), "gq_step_record_ssim_bits_f32")
     return rec
 
 

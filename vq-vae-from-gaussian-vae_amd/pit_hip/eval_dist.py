@@ -10,6 +10,10 @@ metric -> all_gather, :207-257 rank-0 re-interleave).  What changes:
   batch -- the code indices as uint16 (2^16-entry codebook) bit-cast into the
   same buffer as the fp32 per-image metrics -- into ONE int32 record and the
   step does ONE ``all_gather_into_tensor``.
+  A codebook of any other size (``n_codes``, up to 2^32) takes the bit-packed
+  record instead: bit_length(n_codes - 1) bits per index, a violations word in
+  place of the per-step host range check, and a whole-set usage histogram
+  accumulated on rank 0 from the gathered words.
 * records stay on the device; nothing is copied to the host until the end.
 * no data-path collective besides that gather: images are independent, the
   4 MiB codebook and the weights are replicated (regenerated from the seed).
@@ -80,25 +84,112 @@ def init_from_env(backend: Optional[str] = None) -> Dict[str, int]:
 
 
 # ----------------------------------------------------------------------------- packed record
+def index_bits_for(n_codes: int) -> int:
+    """Bits per index of the bit-packed wire format for a codebook of ``n_codes`` entries: the width of n_codes - 1, at least 1."""
+    if not 1 <= n_codes <= 1 << 32:
+        raise ValueError(f"the bit-packed wire format takes 1 <= n_codes <= 2^32, got {n_codes}")
+    return max(1, (n_codes - 1).bit_length())
+
+
+def _wrap_i32(words: torch.Tensor) -> torch.Tensor:
+    """int64 values in [0, 2^32) as the int32 words of the same 32 bits."""
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+
+
+def pack_index_bits(flat: torch.Tensor, index_bits: int) -> torch.Tensor:
+    """The bit-packed index stream in torch expressions (any device; no host read): index k of the int64 vector ``flat`` -- its
+    low ``index_bits`` bits, the value taken as unsigned 32-bit -- occupies bits [k w, (k + 1) w) of a little-endian bit stream
+    over int32 words (stream bit p = bit p mod 32 of word p div 32), zero-padded to a whole word.  w = 16 is the "low half
+    first" uint16 pair format.  The words gq_indices_pack_bits writes, bit for bit."""
+    w = index_bits
+    if not 1 <= w <= 32:
+        raise ValueError(f"index_bits is in 1..32, got {w}")
+    count = flat.numel()
+    n_words = (count * w + 31) // 32
+    v = flat.reshape(-1).to(torch.int64) & ((1 << w) - 1)
+    p = torch.arange(count, dtype=torch.int64, device=flat.device) * w
+    word, off = p >> 5, p & 31
+    c = v << off                                   # < 2^63: at most 32 value bits shifted by at most 31
+    acc = torch.zeros(n_words + 1, dtype=torch.int64, device=flat.device)
+    acc.index_add_(0, word, c & 0xFFFFFFFF)        # the fields are disjoint bit ranges: the sum is their OR
+    acc.index_add_(0, word + 1, c >> 32)
+    return _wrap_i32(acc[:n_words])
+
+
+def unpack_index_bits(words: torch.Tensor, count: int, index_bits: int) -> torch.Tensor:
+    """Inverse of pack_index_bits along the last dimension: int32 [..., >= ceil(count w / 32)] -> int64 [..., count], each value
+    in [0, 2^w)."""
+    w = index_bits
+    if not 1 <= w <= 32:
+        raise ValueError(f"index_bits is in 1..32, got {w}")
+    n_words = (count * w + 31) // 32
+    u = words[..., :n_words].to(torch.int64) & 0xFFFFFFFF
+    u = torch.cat([u, u.new_zeros(u.shape[:-1] + (1,))], dim=-1)
+    p = torch.arange(count, dtype=torch.int64, device=words.device) * w
+    word, off = p >> 5, p & 31
+    lo, hi = u.index_select(-1, word), u.index_select(-1, word + 1)
+    hi = hi & ((torch.ones_like(off) << off) - 1)  # a straddling index takes fewer than `off` bits of the next word
+    return ((lo >> off) | (hi << (32 - off))) & ((1 << w) - 1)
+
+
+def count_index_violations(flat: torch.Tensor, n_codes: int) -> torch.Tensor:
+    """The record's violations word: how many indices lie outside [0, n_codes), saturated at 2^31 - 1; a 0-d int32 tensor."""
+    bad = ((flat < 0) | (flat >= n_codes)).sum()
+    return bad.clamp(max=(1 << 31) - 1).to(torch.int32)
+
+
 class StepRecord:
     """Layout of one rank's per-step record: int32 words =
-    [ per-image metrics as fp32 bits (bs * n_metrics) | indices as uint16 pairs ]."""
+    [ per-image metrics as fp32 bits (bs * n_metrics) | indices as uint16 pairs ]
+    or, with ``n_codes`` (any codebook size up to 2^32), the bit-packed record
+    [ per-image metrics as fp32 bits | ceil(bs tokens w / 32) index words (pack_index_bits) | 1 violations word ]
+    with w = index_bits_for(n_codes).  The violations word counts this record's indices outside [0, n_codes) (such an index is
+    packed as its low w bits); nothing is read on the host while packing."""
 
-    def __init__(self, bs: int, tokens_per_image: int, n_metrics: int, check_range: bool = False) -> None:
+    def __init__(self, bs: int, tokens_per_image: int, n_metrics: int, check_range: bool = False,
+                 n_codes: Optional[int] = None) -> None:
         """``check_range``: validate 0 <= index < 2^16 on every pack (a device->host sync: eval drivers set it, the
-        benchmark's timed loop does not -- its codebook has exactly 2^16 entries)."""
+        benchmark's timed loop does not -- its codebook has exactly 2^16 entries).  ``n_codes``: None keeps that uint16 format;
+        an integer selects the bit-packed record, whose range check is the violations word (``check_range`` is not used)."""
         self.bs, self.tokens, self.n_metrics = bs, tokens_per_image, n_metrics
         self.check_range = check_range
+        self.n_codes = n_codes
         self.metric_words = bs * n_metrics
-        self.index_words = (bs * tokens_per_image + 1) // 2
-        self.words = self.metric_words + self.index_words
+        if n_codes is None:
+            self.index_bits = 16
+            self.index_words = (bs * tokens_per_image + 1) // 2
+            self.words = self.metric_words + self.index_words
+        else:
+            self.index_bits = index_bits_for(n_codes)
+            self.index_words = (bs * tokens_per_image * self.index_bits + 31) // 32
+            self.words = self.metric_words + self.index_words + 1
+
+    def _pack_bits(self, indices: torch.Tensor, metrics: torch.Tensor) -> torch.Tensor:
+        """pack() of the bit-packed record: the index and violations words from gq_indices_pack_bits on a HIP device, from the
+        torch expressions elsewhere."""
+        flat = indices.reshape(-1)
+        rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
+        rec[: self.metric_words] = metrics.reshape(-1).to(torch.float32).view(torch.int32)
+        if flat.is_cuda and flat.dtype == torch.int64:
+            from . import _lib
+
+            _lib.indices_pack_bits(flat, self.index_bits, self.n_codes, rec[self.metric_words: -1], rec[-1:])
+        else:
+            rec[self.metric_words: -1] = pack_index_bits(flat, self.index_bits)
+            rec[-1] = count_index_violations(flat, self.n_codes)
+        return rec
 
     def pack(self, indices: torch.Tensor, metrics: torch.Tensor) -> torch.Tensor:
-        """indices: int64 [bs, ...] with values < 2^16; metrics: fp32 [bs, n_metrics]."""
+        """indices: int64 [bs, ...] with values < 2^16 (< n_codes in the bit-packed record); metrics: fp32 [bs, n_metrics]."""
         dev = indices.device
+        flat = indices.reshape(-1)
+        if self.n_codes is not None:
+            if flat.numel() != self.bs * self.tokens or metrics.numel() != self.metric_words:
+                raise ValueError(f"StepRecord.pack: got {flat.numel()} indices / {metrics.numel()} metrics, layout is "
+                                 f"{self.bs} x {self.tokens} / {self.metric_words}")
+            return self._pack_bits(indices, metrics)
         rec = torch.empty(self.words, dtype=torch.int32, device=dev)
         rec[: self.metric_words] = metrics.reshape(-1).to(torch.float32).view(torch.int32)
-        flat = indices.reshape(-1)
         if flat.numel() != self.bs * self.tokens or metrics.numel() != self.metric_words:
             raise ValueError(f"StepRecord.pack: got {flat.numel()} indices / {metrics.numel()} metrics, layout is "
                              f"{self.bs} x {self.tokens} / {self.metric_words}")
@@ -114,7 +205,7 @@ class StepRecord:
         """pack(indices, psnr_zero_mean(x, x_rec)) for the one-metric layout.  On a HIP device: ONE launch of libgqhip
         (gq_step_record_f32: the PSNR reduction and the uint16 packing in the same kernel) instead of the ~13 elementwise /
         reduction kernels of the torch expressions; elsewhere exactly those expressions."""
-        if self.n_metrics == 1 and not self.check_range and indices.is_cuda:
+        if self.n_metrics == 1 and (self.n_codes is not None or not self.check_range) and indices.is_cuda:
             from . import _lib
 
             flat_n = indices.numel()
@@ -123,6 +214,9 @@ class StepRecord:
                                  f"{self.bs} x {self.tokens}")
             if _lib.step_record_ok(x, x_rec, indices):
                 rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
+                if self.n_codes is not None:     # gq_step_record_bits_f32: the same PSNR words, the bit-packed indices, the violations word
+                    return _lib.step_record_bits(x, x_rec, indices, rec, self.index_bits, self.n_codes,
+                                                 self.__dict__.setdefault("_ws", {}))
                 return _lib.step_record(x, x_rec, indices, rec, self.__dict__.setdefault("_ws", {}))
         return self.pack(indices, psnr_zero_mean(x, x_rec)[:, None])
 
@@ -143,6 +237,10 @@ class StepRecord:
                                  f"is {self.bs} x {self.tokens}")
             x, x_rec = _dense_pair(x, x_rec)
             if _lib.step_record_ok(x, x_rec, indices) and _lib.ssim_ok(x, x_rec):
+                if self.n_codes is not None:     # gq_step_record_ssim_bits_f32: no host read
+                    rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
+                    return _lib.step_record_ssim_bits(x, x_rec, indices, rec, self.index_bits, self.n_codes,
+                                                      self.__dict__.setdefault("_ws", {}))
                 if self.check_range:
                     _check_index_range(indices.reshape(-1))
                 rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
@@ -154,10 +252,41 @@ class StepRecord:
         """rec: int32 [..., words] -> (indices int64 [..., bs, tokens], metrics fp32 [..., bs, n_metrics])."""
         lead = rec.shape[:-1]
         metrics = rec[..., : self.metric_words].contiguous().view(torch.float32).reshape(*lead, self.bs, self.n_metrics)
+        if self.n_codes is not None:
+            count = self.bs * self.tokens
+            if rec.is_cuda:
+                from . import _lib
+
+                flat = _lib.indices_unpack_bits(rec.reshape(-1, self.words), self.metric_words, count, self.index_bits)
+            else:
+                flat = unpack_index_bits(rec[..., self.metric_words: -1], count, self.index_bits)
+            return flat.reshape(*lead, self.bs, self.tokens), metrics
         words = rec[..., self.metric_words:].to(torch.int64) & 0xFFFFFFFF
         lo, hi = words & 0xFFFF, (words >> 16) & 0xFFFF
         flat = torch.stack([lo, hi], dim=-1).reshape(*lead, -1)[..., : self.bs * self.tokens]
         return flat.reshape(*lead, self.bs, self.tokens), metrics
+
+    def violations(self, rec: torch.Tensor) -> torch.Tensor:
+        """rec: int32 [..., words] of the bit-packed record -> its violations words, int32 [...]."""
+        if self.n_codes is None:
+            raise ValueError("StepRecord.violations: the uint16 record has no violations word")
+        return rec[..., -1]
+
+    def add_to_histogram(self, rec: torch.Tensor, hist: torch.Tensor) -> torch.Tensor:
+        """hist (int64 [n_codes]) += the index counts of the bit-packed records rec (int32 [..., words]); a packed value >= n_codes
+        is skipped.  On a HIP device the kernel reads the packed words (gq_index_histogram_packed: no int64 indices are formed);
+        elsewhere torch expressions.  No host read."""
+        if self.n_codes is None:
+            raise ValueError("StepRecord.add_to_histogram: needs the bit-packed record (n_codes)")
+        if rec.is_cuda:
+            from . import _lib
+
+            return _lib.index_histogram_packed(rec.reshape(-1, self.words), self.metric_words, self.bs * self.tokens,
+                                               self.index_bits, hist)
+        flat = unpack_index_bits(rec[..., self.metric_words: -1], self.bs * self.tokens, self.index_bits).reshape(-1)
+        ok = (flat < self.n_codes).to(torch.int64)
+        hist.index_add_(0, flat.clamp(max=self.n_codes - 1), ok)
+        return hist
 
 
 def _check_index_range(flat: torch.Tensor) -> None:
@@ -335,12 +464,41 @@ def codebook_usage(indices: torch.Tensor, n_codes: int):
 
 
 @torch.no_grad()
+def sharded_eval_steps(model, images_for, batches, layout: StepRecord, world: int, device,
+                       hist: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+    """The per-step loop of evaluate_sharded: encode / decode / pack / ONE gather per batch of ``batches``; returns the gathered
+    [world, words] records, one per step.  ``hist`` (int64 [n_codes], bit-packed records only): each gathered record's indices are
+    added to it as they arrive.  With a bit-packed ``layout`` nothing in the loop reads the device from the host."""
+    gathered = []
+    for ids in batches:
+        x = images_for(ids).to(device, non_blocking=True)
+        zhat, info = model.encode(x, return_reg_log=True)
+        rec_img = model.decode(zhat)
+        if layout.n_metrics == 1:
+            rec = layout.pack_with_psnr(info["indices"], x, rec_img)
+        else:
+            rec = layout.pack_with_metrics(info["indices"], x, rec_img)
+        gathered.append(gather_step(rec, world))
+        if hist is not None:
+            layout.add_to_histogram(gathered[-1], hist)
+    return gathered
+
+
+@torch.no_grad()
 def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world: int, device,
-                     tokens_per_image: int, metrics: Sequence[str] = ("psnr",)) -> Optional[Dict[str, torch.Tensor]]:
+                     tokens_per_image: int, metrics: Sequence[str] = ("psnr",),
+                     n_codes: Optional[int] = None) -> Optional[Dict[str, torch.Tensor]]:
     """The reference eval loop for this path: each rank encodes/decodes its shard, one gather per
     step, rank 0 returns indices + PSNR in dataset order.  ``images_for(ids) -> [len(ids),3,H,W]``.
     ``metrics``: ("psnr",) or ("psnr", "ssim", "ms_ssim") (eval.py:165-178; any order): the three-metric record, still ONE
-    gather per step, and "ssim" / "ms_ssim" in the result too."""
+    gather per step, and "ssim" / "ms_ssim" in the result too.
+    ``n_codes``: None keeps the uint16 record and its per-step range check (a host read per step; indices < 2^16).  An integer
+    (1 .. 2^32) selects the bit-packed record of StepRecord(n_codes=...): max(1, bit_length(n_codes - 1)) bits per index on the
+    wire, no host read inside the loop; every rank checks the gathered violations words once after the loop and raises
+    ValueError naming the first (rank, step) whose indices left [0, n_codes).  Rank 0 also accumulates the whole evaluated
+    set's usage histogram from the gathered records (eval.py:127,152-154's all_hist; the items the sampler wraps around to pad
+    the last batch count, as they do in "indices") and the result gains "hist" (int64 [n_codes]), "usage" and "entropy"
+    (cal_ent: eval.py:137-141)."""
     names = set(metrics)
     if names == {"psnr"}:
         n_metrics = 1
@@ -349,26 +507,35 @@ def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world
     else:
         raise ValueError(f"evaluate_sharded: metrics are ('psnr',) or ('psnr', 'ssim', 'ms_ssim'), got {tuple(metrics)}")
     batches = shard_batches(n_images, world, rank, bs)
-    layout = StepRecord(bs, tokens_per_image, n_metrics=n_metrics, check_range=True)
-    gathered = []
-    for ids in batches:
-        x = images_for(ids).to(device, non_blocking=True)
-        zhat, info = model.encode(x, return_reg_log=True)
-        rec_img = model.decode(zhat)
-        if n_metrics == 1:
-            rec = layout.pack_with_psnr(info["indices"], x, rec_img)
-        else:
-            rec = layout.pack_with_metrics(info["indices"], x, rec_img)
-        gathered.append(gather_step(rec, world))
-    if rank != 0 or not gathered:
+    hist = None
+    if n_codes is None:
+        layout = StepRecord(bs, tokens_per_image, n_metrics=n_metrics, check_range=True)
+    else:
+        layout = StepRecord(bs, tokens_per_image, n_metrics=n_metrics, n_codes=n_codes)
+        if rank == 0:
+            hist = torch.zeros(n_codes, dtype=torch.int64, device=device)
+    gathered = sharded_eval_steps(model, images_for, batches, layout, world, device, hist)
+    if not gathered or (rank != 0 and n_codes is None):
+        return None
+    if n_codes is not None:
+        viol = torch.stack([layout.violations(g) for g in gathered], dim=1).cpu()   # [W, steps]: the ONE host read of the range check
+        bad = torch.nonzero(viol)
+        if bad.numel():
+            r, s = (int(v) for v in bad[0])
+            raise ValueError(f"evaluate_sharded: rank {r}, step {s}: {int(viol[r, s])} indices outside [0, {n_codes}) "
+                             f"({bad.shape[0]} rank-steps in all)")
+    if rank != 0:
         return None
     allrec = torch.stack(gathered, dim=1)  # [W, steps, words]
     idx, met = layout.unpack(allrec)       # [W, steps, bs, tokens], [W, steps, bs, n_metrics]
     per_rank_idx = [idx[r].reshape(-1, tokens_per_image) for r in range(world)]
-    if n_metrics == 1:
-        per_rank_psnr = [met[r].reshape(-1) for r in range(world)]
-        return {"indices": reinterleave(per_rank_idx), "psnr": reinterleave(per_rank_psnr)}
     out = {"indices": reinterleave(per_rank_idx)}
-    for k, name in enumerate(("psnr", "ssim", "ms_ssim")):
-        out[name] = reinterleave([met[r][..., k].reshape(-1) for r in range(world)])
+    if n_metrics == 1:
+        out["psnr"] = reinterleave([met[r].reshape(-1) for r in range(world)])
+    else:
+        for k, name in enumerate(("psnr", "ssim", "ms_ssim")):
+            out[name] = reinterleave([met[r][..., k].reshape(-1) for r in range(world)])
+    if n_codes is not None:
+        out["hist"] = hist
+        out["usage"], out["entropy"] = cal_ent(hist)
     return out
