@@ -31,7 +31,9 @@
  *   lfq_pack_f32     pit/quantization/lfq.py:147-158.
  *   lfq_train_f32 / lfq_backward_f32  pit/quantization/lfq.py:56-76, 160-208 (LFQQuantizer.forward in train()) and its autograd backward.
  *   lfq_unpack_f32   pit/quantization/lfq.py:210-228 (also BSQ: pit/quantization/bsq.py:85-156).
+ *   bsq_train_f32 / bsq_backward_f32  pit/quantization/bsq.py:14-37, 64-133 (BSQQuantizer.forward in train()) and its autograd backward.
  *   fsq_quantize_f32 / fsq_dequant_f32  pit/quantization/fsq.py:29-89.
+ *   fsq_train_f32 / fsq_backward_f32  pit/quantization/fsq.py:6-9, 29-68 (FSQQuantizer.forward with round_ste's value) and its autograd backward.
  *   gn_silu_f32      pit/modules/unet.py:49-57 (Normalize + nonlinearity pairs).
  *   gq_index_histogram eval.py:127,137-141,152-154 (stubbed-out histogram).
  *   gq_ssim_f32      pit/evaluations/ssim.py:5-63 (get_ssim / get_ssim_and_msssim via pytorch_msssim), eval.py:170-178.
@@ -62,7 +64,9 @@ extern "C" {
                                *    (vq_backward_f32, vq_backward_workspace_bytes), LFQQuantizer's train step
                                *    (lfq_train_f32, lfq_backward_f32, lfq_train_workspace_bytes), the bit-packed index wire format for any
                                *    codebook size (gq_indices_pack_bits, gq_indices_unpack_bits, gq_index_histogram_packed,
-                               *    gq_step_record_bits_f32, gq_step_record_ssim_bits_f32 and their two _workspace_bytes functions) */
+                               *    gq_step_record_bits_f32, gq_step_record_ssim_bits_f32 and their two _workspace_bytes functions), the train steps of
+                               *    BSQQuantizer (bsq_train_f32, bsq_backward_f32, bsq_train_workspace_bytes) and FSQQuantizer (fsq_train_f32,
+                               *    fsq_backward_f32) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -357,6 +361,45 @@ int fsq_quantize_f32(const float *z, const int32_t *levels_host, int64_t nlev, f
                      int32_t *idx, int64_t rows, void *stream);
 int fsq_dequant_f32(const int32_t *idx, const int32_t *levels_host, int64_t nlev, float *zhat,
                     int64_t rows, void *stream);
+
+/* ---- BSQQuantizer's train step (bsq.py:14-37, 64-133) in ONE forward and ONE backward call.
+ *   x: [B, C, L] (layout 0, BCHW) or [B, L, C] (layout 1, BLC; also channels_last memory; there x, quantized, g_q and grad_x are
+ *   16-byte aligned), C = 16 d, d = log2(codebook_size) in 1..16 (the reference packs exactly 16 codebooks); channel i d + j is
+ *   codebook i, bit plane j.  Per position: n = ||x||_2 summed in fp64, u = fl32(x / max(n, 1e-12)), q = u > 0 ? 1 : -1 (the sign
+ *   of the fp32 quotient), q_scale = fl32(1 / sqrt(C)), s = -400 u / sqrt(C), p = sigma(s) with e = exp(-|s|): the larger of
+ *   (p, 1 - p) is 1 / (1 + e), the smaller e / (1 + e); eps = 1e-5; M = B L 16.
+ * bsq_train_f32 writes
+ *   quantized (layout of x) = fl(fl(u + fl(q - u)) q_scale);
+ *   idx int64 [B, L, d] (BLC) / [B, d, L] (BCHW): idx[j] = sum_i bit(i, j) << (15 - i);
+ *   avg [d][2] floats = the reference's avg_probs: (mean of p, mean of 1 - p) over the M entries of bit plane j, each summed on its
+ *     own in fp64 and rounded once; kept by the caller for the backward;
+ *   scalars [3] floats ON THE DEVICE = {entropy_aux_loss = w_s per_sample_entropy - w_b codebook_entropy, per_sample_entropy =
+ *     (1 / M) sum (-p log(p + eps) - (1 - p) log(1 - p + eps)), codebook_entropy = -sum over avg of a log(a + eps)}.
+ * bsq_backward_f32, with the gradients arriving at quantized (g_q, layout of x) and at entropy_aux_loss (ONE float ON THE DEVICE),
+ * NULL = zero, writes grad_x (layout of x) from x and avg alone, in one launch:
+ *     g_u = q_scale g_q + g_aux (-400 / sqrt(C)) p (1 - p) ((w_s / M) h'(p) - (w_b / M) A'_j),
+ *     h'(p) = -log(p + eps) - p / (p + eps) + log(1 - p + eps) + (1 - p) / (1 - p + eps), A'_j the same at avg[j];
+ *     grad_x = (g_u - u (u . g_u)) / n when n >= 1e-12, g_u / 1e-12 otherwise; fp64, rounded once.
+ * The forward is two launches (per-block fp64 partial sums, one finishing block); no float atomics, every sum's order depends on the
+ * shape alone: bit-identical from run to run.  Neither call reads the host or synchronises; both are ordered on `stream`.
+ * workspace: bsq_train_workspace_bytes(B L, d) bytes (-1: rows < 0 or too many, d outside 1..16), 16-byte aligned, contents
+ * don't-care on entry, nothing in it is kept between calls; NULL, misaligned or short -> GQHIP_ERR_WORKSPACE.  B L = 0: GQHIP_OK. */
+int64_t bsq_train_workspace_bytes(int64_t rows, int64_t d);
+int bsq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, float *scalars, int64_t B, int64_t L, int64_t C,
+                  int64_t d, int layout, float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream);
+int bsq_backward_f32(const float *x, const float *avg, const float *g_q_or_null, const float *g_aux_or_null, float *grad_x,
+                     int64_t B, int64_t L, int64_t C, int64_t d, int layout, float w_s, float w_b, void *workspace,
+                     int64_t workspace_bytes, void *stream);
+
+/* ---- FSQQuantizer's train step (fsq.py:6-9, 29-68) on a module layout in place: z, zhat, g_zhat, grad_z are [B, nlev, L] (layout 0)
+ * or [B, L, nlev] (layout 1); idx int32 [B L] (one packed index per position).  levels_host as in fsq_quantize_f32 (every level >= 2).
+ * fsq_train_f32: b as in fsq_quantize_f32, r = rint(b), zhat = fl(fl(b + fl(r - b)) / half_width) (round_ste's value), idx = the
+ * pack of r + half_width.  fsq_backward_f32: grad_z = g_zhat (half_l / half_width) sech^2(z + shift), sech^2 t = 4 e / (1 + e)^2 with
+ * e = exp(-2 |t|), in fp64, rounded once.  One launch each, no workspace.  B L = 0: GQHIP_OK. */
+int fsq_train_f32(const float *z, const int32_t *levels_host, int64_t nlev, float *zhat, int32_t *idx, int64_t B, int64_t L,
+                  int layout, void *stream);
+int fsq_backward_f32(const float *z, const float *g_zhat, const int32_t *levels_host, int64_t nlev, float *grad_z, int64_t B,
+                     int64_t L, int layout, void *stream);
 
 /* ---- fused GroupNorm (+ SiLU) for the conv stack -----------------------------------
  * y = act( (x - mean_g) * rstd_g * gamma_c + beta_c ), act = SiLU when apply_silu != 0.

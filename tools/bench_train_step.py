@@ -15,6 +15,10 @@ z = [16, 16, 32, 32] ~ 0.02 N(0, 1) (entropies not saturated), NCHW and channels
     q, info = m(z);  ((q * w).sum() + 0.37 * info["entropy_aux_loss"] + 1.3 * info["commit_loss"]).backward()
 (the op-by-op path of the 65 536-code case builds the [16 384, 65 536] logits: several GB and tens of ms per step, so time it with a
 small `--iters`).
+With `--only bsq`: BSQQuantizer("bchw", 2, 16) (sd3unet_bsq_16) in train() on z = [16, 16, 32, 32] ~ N(0, 1); with `--only fsq`:
+FSQQuantizer([8, 8, 8, 5, 5, 5], "bchw") (sd3unet_fsq_16) in train() on z = [16, 6, 32, 32] ~ N(0, 1); NCHW and channels_last; a step is
+    q, info = m(z);  ((q * w).sum() + 0.37 * info["entropy_aux_loss"]).backward()        (FSQ: without the loss term)
+Their fused routes are opt-in (GQHIP_BSQ_TRAIN_FUSED=1 / GQHIP_FSQ_TRAIN_FUSED=1); the JSON line says which route ran ("opt_in").
 `--iters` timed steps after `--warmup`, in 10 batches, each between two device events (the time between the events includes whatever
 the host makes the device wait for, which is the point: the op-by-op path stops the host three times per step).  Prints one JSON line
 per (module, shape, layout): median / min / max over the batches of the per-step time in microseconds.
@@ -35,7 +39,7 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--label", default="")
-    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'; 'vq' / 'lfq' run the VQ / LFQ cases instead")
+    ap.add_argument("--only", default="", help="substring filter on 'gq1' / 'gq2'; 'vq' / 'lfq' / 'bsq' / 'fsq' run those cases instead")
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(a.root, "vq-vae-from-gaussian-vae_amd"))
     import torch
@@ -112,6 +116,33 @@ def main() -> int:
                                   "us_min": round(min(times), 2), "us_max": round(max(times), 2),
                                   "peak_mb": round(torch.cuda.max_memory_allocated() / 1e6, 1),
                                   "fused": os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"}), flush=True)
+        return 0
+    if a.only in ("bsq", "fsq"):
+        from pit_hip.quantization.bsq import BSQQuantizer
+        from pit_hip.quantization.fsq import FSQQuantizer
+
+        c = 16 if a.only == "bsq" else 6
+        var = f"GQHIP_{a.only.upper()}_TRAIN_FUSED"
+        for channels_last in (False, True):
+            g = torch.Generator().manual_seed(c)
+            z, w = torch.randn(16, c, 32, 32, generator=g).to(dev), torch.randn(16, c, 32, 32, generator=g).to(dev)
+            if channels_last:
+                z, w = z.contiguous(memory_format=torch.channels_last), w.contiguous(memory_format=torch.channels_last)
+            z.requires_grad_(True)
+            m = (BSQQuantizer("bchw", 2, 16) if a.only == "bsq" else FSQQuantizer([8, 8, 8, 5, 5, 5], "bchw")).to(dev).train()
+
+            def step():
+                z.grad = None
+                q, info = m(z)
+                loss = (q * w).sum()
+                (loss + 0.37 * info["entropy_aux_loss"] if a.only == "bsq" else loss).backward()
+
+            times = timed(step)
+            fused = os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
+            print(json.dumps({"label": a.label, "module": a.only, "z": [16, c, 32, 32], "channels_last": channels_last,
+                              "steps": per * batches, "us_median": round(statistics.median(times), 2),
+                              "us_min": round(min(times), 2), "us_max": round(max(times), 2), "fused": fused,
+                              "opt_in": fused and os.environ.get(var, "0") == "1"}), flush=True)
         return 0
     for kind in ("gq1", "gq2"):
         if a.only and a.only not in kind:

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Print a sha256 of every output and gradient of one seeded forward (and backward) of each quantiser module, at tiny shapes.
 
-    python tools/module_output_hashes.py [--root TREE] > listing.txt
+    python tools/module_output_hashes.py [--root TREE] [--bsq-fsq] > listing.txt
 
 For a change that must not move a bit at module level (a refactor of the Python layer between the modules and libgqhip.so): run it
 against the parent tree and against the branch (`--root TREE` imports pit_hip from another checkout, whose libgqhip.so must be
 built) and compare the two listings line for line.  Cases: GaussianQuantRegularizer in eval() and train(); GaussianQuantRegularizer2
 with use_ste on and off, dim_idx 1 and -1, 4-d and 5-d inputs, under autograd and without; VQQuantizer with 1 and 2 sub-codebooks in
 train() and eval(); LFQQuantizer with 8 and 16 bits in train(); dequant(indices) after every forward without autograd.  Each on a contiguous, a channels_last (4-d inputs) and a "blc"
-tensor.  A line is `case | name | dtype shape stride | sha256 of the values in logical order`; scalars print their repr."""
+tensor.  `--bsq-fsq` appends BSQQuantizer (1 and 2 bits per codebook) and FSQQuantizer in train() and eval() (their fused train steps are
+opt-in: unset, the listing must equal the parent's).  A line is `case | name | dtype shape stride | sha256 of the values in logical order`; scalars print their repr."""
 import argparse
 import hashlib
 import os
@@ -18,6 +19,7 @@ import sys
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--bsq-fsq", action="store_true", help="append the BSQQuantizer / FSQQuantizer cases")
     a = ap.parse_args()
     sys.path.insert(0, os.path.join(a.root, "vq-vae-from-gaussian-vae_amd"))
     import torch
@@ -126,6 +128,23 @@ def main() -> int:
             m = LFQQuantizer(fmt, 1 << d, 1).to(dev).train()
             run(f"lfq d={d} train {lay}", m, x.clone(), w, 1 if fmt == "bchw" else 2,
                 (("entropy_aux_loss", 0.37), ("commit_loss", 1.3)))
+    # ---- BSQ (1 and 2 bits per codebook) and FSQ, on request ----------------------------------------------------------------
+    if a.bsq_fsq:
+        from pit_hip.quantization.bsq import BSQQuantizer
+        from pit_hip.quantization.fsq import FSQQuantizer
+
+        for d in (1, 2):
+            for lay, (fmt, x, w) in layouts((2, 16 * d, 6, 6), 40 + d).items():
+                for mode in ("train", "eval"):
+                    m = BSQQuantizer(fmt, 1 << d, 16).to(dev)
+                    m = m.train() if mode == "train" else m.eval()
+                    run(f"bsq d={d} {mode} {lay}", m, x.clone(), w, 1 if fmt == "bchw" else 2,
+                        (("entropy_aux_loss", 0.37),) if mode == "train" else (), grad=mode == "train")
+        for lay, (fmt, x, w) in layouts((2, 6, 6, 6), 50, scale=2.0).items():
+            for mode in ("train", "eval"):
+                m = FSQQuantizer([8, 8, 8, 5, 5, 5], fmt).to(dev)
+                m = m.train() if mode == "train" else m.eval()
+                run(f"fsq {mode} {lay}", m, x.clone(), w, 1 if fmt == "bchw" else 2, (), grad=mode == "train")
     torch.cuda.synchronize()
     return 0
 

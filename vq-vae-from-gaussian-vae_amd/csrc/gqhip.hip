@@ -26,6 +26,7 @@
 #include "gq_ssim.h"
 #include "vq_train.h"
 #include "lfq_train.h"
+#include "bsq_fsq_train.h"
 
 using namespace gqhip;
 
@@ -1112,6 +1113,83 @@ int lfq_backward_f32(const float *x, const float *avg, const float *g_q_or_null,
   return launch(lfq_bwd_choice(g.dh), dim3((unsigned)blocks), dim3(64 * kLfqBwdWaves), 0, st, p);
 }
 
+// ---- BSQQuantizer's train step (bsq_fsq_train.h) ----
+namespace {
+static int64_t bsq_part_blocks(int64_t rows) {                     // an upper bound of the forward's blocks for either layout
+  const int64_t b = (rows + 15) / 16;
+  return b < 1 ? 1 : (b > kBsqMaxBlocks ? kBsqMaxBlocks : b);
+}
+static bool bsq_geometry(int64_t B, int64_t L, int64_t C, int64_t d, int layout, BsqGeom *g) {
+  if (B < 0 || L < 0 || d < 1 || d > kBsqMaxD || C != 16 * d) return false;
+  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return false;
+  if (B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff) return false;
+  g->P = (long)(B * L); g->L = (long)L; g->d = (int)d; g->C = (int)C;
+  g->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  const int64_t rpb = g->mode == 1 ? kBsqBchwThreads : (d == 1 ? 64 : d == 2 ? 32 : 16);      // positions a block covers per step
+  const int64_t tiles = (g->P + rpb - 1) / rpb;
+  g->iters = (int)((tiles + kBsqMaxBlocks - 1) / kBsqMaxBlocks);
+  if (g->iters < 1) g->iters = 1;
+  g->blocks = (int)((tiles + g->iters - 1) / g->iters);
+  g->q_scale = (float)(1.0 / sqrt((double)C));
+  g->cs = -400.0 / sqrt((double)C);
+  g->M = (double)g->P * 16.0;
+  return true;
+}
+using BsqFwdKernel = void (*)(const BsqFwdParams);
+using BsqBwdKernel = void (*)(const BsqBwdParams);
+// "blc": lanes per row and 16-byte chunks per lane for C = 16 d floats
+static int bsq_blc_slot(int d) { return d == 1 ? 0 : d == 2 ? 1 : d <= 4 ? 2 : d <= 8 ? 3 : d <= 12 ? 4 : 5; }
+static BsqFwdKernel bsq_fwd_choice(const BsqGeom &g) {
+  static const BsqFwdKernel blc[6] = {bsq_fwd_blc_kernel<4, 1>,  bsq_fwd_blc_kernel<8, 1>,  bsq_fwd_blc_kernel<16, 1>,
+                                      bsq_fwd_blc_kernel<16, 2>, bsq_fwd_blc_kernel<16, 3>, bsq_fwd_blc_kernel<16, 4>};
+  return g.mode == 1 ? bsq_fwd_bchw_kernel : blc[bsq_blc_slot(g.d)];
+}
+static BsqBwdKernel bsq_bwd_choice(const BsqGeom &g) {
+  static const BsqBwdKernel blc[6] = {bsq_bwd_blc_kernel<4, 1>,  bsq_bwd_blc_kernel<8, 1>,  bsq_bwd_blc_kernel<16, 1>,
+                                      bsq_bwd_blc_kernel<16, 2>, bsq_bwd_blc_kernel<16, 3>, bsq_bwd_blc_kernel<16, 4>};
+  return g.mode == 1 ? bsq_bwd_bchw_kernel : blc[bsq_blc_slot(g.d)];
+}
+}  // namespace
+
+int64_t bsq_train_workspace_bytes(int64_t rows, int64_t d) {
+  if (rows < 0 || rows > 0x3fffffff || d < 1 || d > kBsqMaxD) return -1;
+  return align256(bsq_part_blocks(rows) * (2 * d + 1) * 8);
+}
+
+int bsq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, float *scalars, int64_t B, int64_t L, int64_t C,
+                  int64_t d, int layout, float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream) {
+  BsqGeom g;
+  if (!x || !quantized || !idx || !avg || !scalars || !bsq_geometry(B, L, C, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
+  const unsigned amask = g.mode == 2 ? 15u : 3u;                   // "blc" rows are read and written 16 bytes at a time
+  if (((bits(x) | bits(quantized)) & amask) || ((bits(avg) | bits(scalars)) & 3u) || (bits(idx) & 7u)) return GQHIP_ERR_INVALID_ARG;
+  if (g.P == 0) return GQHIP_OK;
+  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < bsq_train_workspace_bytes(g.P, d)) return GQHIP_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  BsqFwdParams p{};
+  p.x = x; p.quant = quantized; p.idx = idx; p.avg = avg; p.scalars = scalars; p.part = static_cast<double *>(workspace);
+  p.g = g; p.ws = w_s; p.wb = w_b;
+  const int rc = launch(bsq_fwd_choice(g), dim3((unsigned)g.blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, st, p);
+  if (rc != GQHIP_OK) return rc;
+  return launch(bsq_finish_kernel, dim3(1), dim3(256), 0, st, p);
+}
+
+int bsq_backward_f32(const float *x, const float *avg, const float *g_q_or_null, const float *g_aux_or_null, float *grad_x,
+                     int64_t B, int64_t L, int64_t C, int64_t d, int layout, float w_s, float w_b, void *workspace,
+                     int64_t workspace_bytes, void *stream) {
+  BsqGeom g;
+  if (!x || !avg || !grad_x || !bsq_geometry(B, L, C, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
+  const unsigned amask = g.mode == 2 ? 15u : 3u;
+  if (((bits(x) | bits(grad_x) | bits(g_q_or_null)) & amask) || ((bits(avg) | bits(g_aux_or_null)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (g.P == 0) return GQHIP_OK;
+  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < bsq_train_workspace_bytes(g.P, d)) return GQHIP_ERR_WORKSPACE;
+  BsqBwdParams p{};
+  p.x = x; p.avg = avg; p.g_q = g_q_or_null; p.g_aux = g_aux_or_null; p.grad_x = grad_x;
+  p.g = g; p.ws = w_s; p.wb = w_b;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t blocks = g.mode == 1 ? (g.P + kBsqBchwThreads - 1) / kBsqBchwThreads : g.blocks;
+  return launch(bsq_bwd_choice(g), dim3((unsigned)blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, st, p);
+}
+
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,
                    int64_t dim, int64_t n, int layout, int grouping, void *stream) {
   ZGeom g;
@@ -1177,6 +1255,36 @@ int fsq_dequant_f32(const int32_t *idx, const int32_t *levels_host, int64_t nlev
   if (rows == 0) return GQHIP_OK;
   return launch(fsq_dequant_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
                 static_cast<hipStream_t>(stream), idx, L, zhat, (long)rows);
+}
+
+// ---- FSQQuantizer's train step (bsq_fsq_train.h) ----
+static int fsq_train_args(const int32_t *levels_host, int64_t nlev, int64_t B, int64_t L, int layout, FsqTrainParams *p) {
+  if (B < 0 || L < 0 || B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
+  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return GQHIP_ERR_INVALID_ARG;
+  p->P = (long)(B * L); p->L = (long)L; p->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  return fsq_levels(levels_host, nlev, &p->lv);
+}
+
+int fsq_train_f32(const float *z, const int32_t *levels_host, int64_t nlev, float *zhat, int32_t *idx, int64_t B, int64_t L,
+                  int layout, void *stream) {
+  FsqTrainParams p{};
+  if (!z || !zhat || !idx || ((bits(z) | bits(zhat) | bits(idx)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (fsq_train_args(levels_host, nlev, B, L, layout, &p) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
+  if (p.P == 0) return GQHIP_OK;
+  p.z = z; p.out = zhat; p.idx = idx;
+  return launch(fsq_train_kernel, dim3((unsigned)((p.P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+}
+
+int fsq_backward_f32(const float *z, const float *g_zhat, const int32_t *levels_host, int64_t nlev, float *grad_z, int64_t B,
+                     int64_t L, int layout, void *stream) {
+  FsqTrainParams p{};
+  if (!z || !g_zhat || !grad_z || ((bits(z) | bits(g_zhat) | bits(grad_z)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (fsq_train_args(levels_host, nlev, B, L, layout, &p) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
+  if (p.P == 0) return GQHIP_OK;
+  p.z = z; p.g_zhat = g_zhat; p.out = grad_z;
+  const int64_t blocks = (p.P * p.lv.n + 255) / 256;
+  if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
+  return launch(fsq_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 int gq_index_histogram(const int64_t *idx, int64_t count, int64_t n, int32_t *hist, void *stream) {

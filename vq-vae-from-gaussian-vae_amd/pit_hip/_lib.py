@@ -67,6 +67,11 @@ _SIGNATURES = {
                                      ctypes.c_float, _vp, _i64, _vp]),
     "lfq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
                                         ctypes.c_float, _vp, _i64, _vp]),
+    "bsq_train_workspace_bytes": (_i64, [_i64, _i64]),
+    "bsq_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                     _vp, _i64, _vp]),
+    "bsq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
+                                        ctypes.c_float, _vp, _i64, _vp]),
     "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                       ctypes.c_int, _vp]),
     "vq_argmin_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -74,6 +79,8 @@ _SIGNATURES = {
     "lfq_unpack_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "fsq_quantize_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _vp, _i64, _vp]),
     "fsq_dequant_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _i64, _vp]),
+    "fsq_train_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _vp, _i64, _i64, ctypes.c_int, _vp]),
+    "fsq_backward_f32": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _i64, _i64, ctypes.c_int, _vp]),
     "gn_silu_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int,
                                    ctypes.c_int, _vp, _vp]),
     "add_bias_stats_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
@@ -639,6 +646,70 @@ def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float =
     return grad_x
 
 
+class BsqTrainWorkspace(_Scratch):
+    """Scratch of bsq_train / bsq_backward (gqhip.h: bsq_train_workspace_bytes), grown on demand and reused across calls; its
+    contents never matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
+
+    _what = "the BSQ train step's workspace"
+
+    def get(self, rows: int, d: int, device) -> Tuple[int, int]:
+        return self._take(lib().bsq_train_workspace_bytes(rows, d), device, f"rows={rows} d={d}")
+
+
+def _bsq_geometry(x, dim: int, layout: str):
+    """(B, L, C) of x in a module layout with C = 16 * dim channels (16 codebooks of ``dim`` bits)."""
+    if not 1 <= dim <= 16:
+        raise GqHipError(f"a BSQ codebook holds 1..16 bits, got {dim}")
+    B, L, C = _z_geometry(x, 1, layout, holds="z")[:3]
+    if C != 16 * dim:
+        raise GqHipError(f"{C} channels do not hold 16 codebooks of {dim} bits")
+    return B, L, C
+
+
+def _aligned16(t):
+    """The "blc" kernels move rows 16 bytes at a time: a view at an odd storage offset is copied."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
+def bsq_train(x, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0, ws: Optional[BsqTrainWorkspace] = None):
+    """BSQQuantizer's train-mode forward in one call (gqhip.h: bsq_train_f32): x [B, 16 dim, ...] ("bchw") or [B, L, 16 dim]
+    ("blc") -> (quantized in the layout of x, indices int64 [B, dim, ...] / [B, L, dim], avg float32 [dim, 2] (for bsq_backward),
+    scalars float32 [3] on the device = {entropy_aux_loss, per_sample_entropy, codebook_entropy})."""
+    x = _aligned16(_dev(x, torch.float32, "x"))
+    B, L, C = _bsq_geometry(x, dim, layout)
+    ws = ws or BsqTrainWorkspace()
+    dev = x.device
+    quantized = torch.empty_like(x)
+    idx = torch.empty(((B, dim) + tuple(x.shape[2:])) if layout == "bchw" else (B, L, dim), dtype=torch.int64, device=dev)
+    avg = torch.empty(dim, 2, dtype=torch.float32, device=dev)
+    scalars = torch.empty(3, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(B * L, dim, dev)
+        _check(lib().bsq_train_f32(x.data_ptr(), quantized.data_ptr(), idx.data_ptr(), avg.data_ptr(), scalars.data_ptr(), B, L, C,
+                                   dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()), "bsq_train_f32")
+    return quantized, idx, avg, scalars
+
+
+def bsq_backward(x, avg, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0, g_q=None, g_aux=None,
+                 ws: Optional[BsqTrainWorkspace] = None):
+    """The backward of BSQQuantizer's train step in one call (gqhip.h: bsq_backward_f32).  x, avg: the forward's operand and its
+    ``avg``; ``g_q`` (shape of x; made contiguous in x's layout when it is not) and ``g_aux`` (one float32 on the device) are the
+    gradients arriving at quantized and entropy_aux_loss, None = zero.  Returns grad_x."""
+    x, avg = _aligned16(_dev(x, torch.float32, "x")), _dev(avg, torch.float32, "avg")
+    B, L, C = _bsq_geometry(x, dim, layout)
+    if avg.numel() != 2 * dim:
+        raise GqHipError(f"avg must hold [{dim}, 2] floats, got {avg.numel()}")
+    g_q, g_aux = _aligned16(_grad_of(g_q, x.shape, "g_q", "x")), _grad_scalar(g_aux, "g_aux")
+    ws = ws or BsqTrainWorkspace()
+    dev = x.device
+    grad_x = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(B * L, dim, dev)
+        _check(lib().bsq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(g_aux), grad_x.data_ptr(), B, L, C, dim,
+                                      GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()), "bsq_backward_f32")
+    return grad_x
+
+
 def lfq_unpack(idx, nbits: int):
     idx = _dev(idx, torch.int64, "indices")
     rows = idx.numel()
@@ -665,6 +736,43 @@ def fsq_quantize(z, levels):
         _check(lib().fsq_quantize_f32(z.data_ptr(), arr, n, zhat.data_ptr(), idx.data_ptr(), rows, _stream()),
                "fsq_quantize_f32")
     return zhat, idx
+
+
+def _fsq_geometry(z, levels, layout: str):
+    B, L, C = _z_geometry(z, 1, layout, holds="z")[:3]
+    if C != len(levels):
+        raise GqHipError(f"{C} channels do not hold {len(levels)} levels")
+    return B, L
+
+
+def fsq_train(z, levels, layout: str):
+    """FSQQuantizer's forward with round_ste's value in one call (gqhip.h: fsq_train_f32): z [B, nlev, ...] ("bchw") or
+    [B, L, nlev] ("blc") -> (zhat in the layout of z, packed indices int32 [B, 1, ...] / [B, L, 1])."""
+    z = _dev(z, torch.float32, "z")
+    B, L = _fsq_geometry(z, levels, layout)
+    arr, n = _levels(levels)
+    zhat = torch.empty_like(z)
+    idx = torch.empty(((B, 1) + tuple(z.shape[2:])) if layout == "bchw" else (B, L, 1), dtype=torch.int32, device=z.device)
+    with torch.cuda.device(z.device):
+        _check(lib().fsq_train_f32(z.data_ptr(), arr, n, zhat.data_ptr(), idx.data_ptr(), B, L, GQHIP_LAYOUT[layout], _stream()),
+               "fsq_train_f32")
+    return zhat, idx
+
+
+def fsq_backward(z, g_zhat, levels, layout: str):
+    """The backward of fsq_train in one call (gqhip.h: fsq_backward_f32): ``g_zhat`` has the shape of z (made contiguous in z's
+    layout when it is not).  Returns grad_z."""
+    z = _dev(z, torch.float32, "z")
+    B, L = _fsq_geometry(z, levels, layout)
+    g_zhat = _grad_of(g_zhat, z.shape, "g_zhat", "z")
+    if g_zhat is None:
+        raise GqHipError("g_zhat is required")
+    arr, n = _levels(levels)
+    grad_z = torch.empty_like(z)
+    with torch.cuda.device(z.device):
+        _check(lib().fsq_backward_f32(z.data_ptr(), g_zhat.data_ptr(), arr, n, grad_z.data_ptr(), B, L, GQHIP_LAYOUT[layout],
+                                      _stream()), "fsq_backward_f32")
+    return grad_z
 
 
 def fsq_dequant(idx, levels):

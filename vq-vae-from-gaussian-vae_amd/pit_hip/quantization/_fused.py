@@ -17,6 +17,15 @@ def train_fused() -> bool:
     return os.environ.get("GQHIP_TRAIN_FUSED", "1") != "0"
 
 
+_OPT_IN = {"bsq": "GQHIP_BSQ_TRAIN_FUSED", "fsq": "GQHIP_FSQ_TRAIN_FUSED"}
+
+
+def train_fused_opt_in(family: str) -> bool:
+    """True when the fused train step of ``family`` ("bsq", "fsq") is asked for: ``train_fused()`` and the family's own variable
+    (GQHIP_BSQ_TRAIN_FUSED / GQHIP_FSQ_TRAIN_FUSED) set to 1.  Read per call; unset, these modules keep their torch routes."""
+    return train_fused() and os.environ.get(_OPT_IN[family], "0") == "1"
+
+
 def _same(t):
     return t
 

@@ -2,13 +2,16 @@
 
 Binary spherical quantisation: L2-normalise the channel vector, take signs, scale by
 1/sqrt(embed_dim); the index packs the 16 sign bits big-endian (bsq.py:95-99 hard-codes 16).
-Eval losses are zeros like the reference (bsq.py:113-118)."""
+Eval losses are zeros like the reference (bsq.py:113-118).  With GQHIP_BSQ_TRAIN_FUSED=1 in the environment (read per
+call: ``_fused.train_fused_opt_in``) a HIP tensor in ``train()`` takes ONE forward library call (``bsq_train_f32``) and,
+under autograd, ONE backward call (``bsq_backward_f32``); unset, or with GQHIP_TRAIN_FUSED=0, the torch route below runs."""
 from __future__ import annotations
 
 import torch
 import torch.nn.functional as F
 
 from .. import _lib
+from ._fused import format_view, train_fused_opt_in
 from .lfq import LFQQuantizer
 
 
@@ -25,6 +28,32 @@ def bsq_entropy_loss(x, embed_dim, temperature=0.01, sample_minimization_weight=
     return sample_entropy, avg_entropy, loss
 
 
+class _BSQTrainFn(torch.autograd.Function):
+    """One forward library call and one backward library call for BSQQuantizer's train step under autograd.
+
+    ``xv`` is x in a library layout; ``cfg`` = (codebook_dim, layout, w_s, w_b, workspace).  Differentiable outputs: quantized
+    and entropy_aux_loss; the indices and the two entropies are not.  Saved: x and ``avg`` ([d, 2] floats) -- the backward
+    rebuilds u, p and q from x."""
+
+    @staticmethod
+    def forward(ctx, xv, cfg):
+        d, layout, w_s, w_b, ws = cfg
+        quantized, ind, avg, scal = _lib.bsq_train(xv, d, layout, w_s, w_b, ws)
+        aux, sample, batch = scal.unbind(0)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xv, avg)
+        ctx.mark_non_differentiable(ind, sample, batch)
+        return quantized, ind, aux, sample, batch
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_q, _g_ind, g_aux, _g_sample, _g_batch):
+        xv, avg = ctx.saved_tensors
+        d, layout, w_s, w_b, ws = ctx.cfg
+        return _lib.bsq_backward(xv, avg, d, layout, w_s, w_b, g_q=g_q, g_aux=g_aux, ws=ws), None
+
+
 class BSQQuantizer(LFQQuantizer):
     def __init__(self, format, codebook_size, num_codebooks=1, sample_minimization_weight=1.0,
                  batch_maximization_weight=1.0):
@@ -32,8 +61,26 @@ class BSQQuantizer(LFQQuantizer):
                          sample_minimization_weight=sample_minimization_weight,
                          batch_maximization_weight=batch_maximization_weight)
         self.embed_dim = self.codebook_dim * num_codebooks
+        self._bws = _lib.BsqTrainWorkspace()
+
+    def _forward_fused(self, x):
+        """bsq.py:64-133 in train() as one call.  A channels_last x is read, and quantized / indices are written, in that memory
+        (_fused.format_view); nothing is copied in either direction."""
+        assert self.num_codebooks == 16, "the reference packs exactly 16 codebook bits (bsq.py:97)"
+        xv, layout, as_module = format_view(x.float(), self.format)
+        cfg = (self.codebook_dim, layout, self.sample_minimization_weight, self.batch_maximization_weight, self._bws)
+        if torch.is_grad_enabled() and xv.requires_grad:
+            quantized, ind, aux, sample, batch = _BSQTrainFn.apply(xv, cfg)
+        else:
+            quantized, ind, _, scal = _lib.bsq_train(xv, *cfg)
+            aux, sample, batch = scal.unbind(0)
+        info = {"indices": as_module(ind), "entropy_aux_loss": aux, "per_sample_entropy": sample.detach(),
+                "codebook_entropy": batch.detach()}
+        return as_module(quantized).to(x.dtype), info
 
     def forward(self, x):
+        if x.is_cuda and self.training and train_fused_opt_in("bsq"):
+            return self._forward_fused(x)
         if self.format == "bchw":
             b, c, h, w = x.shape
             xf = x.reshape(b, c, h * w).transpose(1, 2)

@@ -2,13 +2,38 @@
 
 Finite scalar quantisation (FSQ paper, appendix A.1): per channel, bound with a shifted tanh,
 round to the nearest of `levels[l]` values, mixed-radix pack (channel 0 most significant).
-Indices are int32 like the reference."""
+Indices are int32 like the reference.  With GQHIP_FSQ_TRAIN_FUSED=1 in the environment (read per call:
+``_fused.train_fused_opt_in``) a HIP tensor in ``train()`` takes ONE forward library call (``fsq_train_f32``: round_ste's
+value, the reference's op order) and, under autograd, ONE backward call (``fsq_backward_f32``)."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
 from .. import _lib
+from ._fused import format_view, train_fused_opt_in
+
+
+class _FSQTrainFn(torch.autograd.Function):
+    """One forward library call and one backward library call for FSQQuantizer under autograd.  ``zv`` is z in a library layout;
+    ``cfg`` = (levels, layout).  The indices are not differentiable.  Saved: z."""
+
+    @staticmethod
+    def forward(ctx, zv, cfg):
+        zhat, ind = _lib.fsq_train(zv, *cfg)
+        ctx.cfg = cfg
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(zv)
+        ctx.mark_non_differentiable(ind)
+        return zhat, ind
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_zhat, _g_ind):
+        if g_zhat is None:
+            return None, None
+        (zv,) = ctx.saved_tensors
+        return _lib.fsq_backward(zv, g_zhat, *ctx.cfg), None
 
 
 class FSQQuantizer(nn.Module):
@@ -20,8 +45,22 @@ class FSQQuantizer(nn.Module):
         self.format = format
         assert self.format in ["bchw", "blc"]
 
+    def _forward_fused(self, z):
+        """fsq.py:29-68 as one call; a channels_last z is read, and zhat / indices are written, in that memory."""
+        zv, layout, as_module = format_view(z, self.format)
+        cfg = (self._levels, layout)
+        if torch.is_grad_enabled() and zv.requires_grad:
+            zhat, ind = _FSQTrainFn.apply(zv, cfg)
+        else:
+            zhat, ind = _lib.fsq_train(zv, *cfg)
+        ndim = z[0].numel()
+        info = {"indices": as_module(ind), "bits": torch.sum(torch.log2(self.levels)) * ndim}
+        return as_module(zhat), info
+
     def forward(self, z):
         z = z.float()
+        if z.is_cuda and self.training and train_fused_opt_in("fsq"):
+            return self._forward_fused(z)
         if self.format == "bchw":
             b, c, h, w = z.shape
             zf = z.reshape(b, c, h * w).transpose(1, 2)
