@@ -210,6 +210,73 @@ def test_record_violations_word_counts_injected_indices_exactly():
     assert torch.equal(lay.pack(bad.reshape(B, T).to(DEV), torch.zeros(B, 1, device=DEV))[B:], rec[B:])
 
 
+@pytest.mark.parametrize("bs,tokens,n_metrics", [(3, 5, 1), (3, 5, 3), (1, 1, 1)])
+def test_uint16_records_unpack_on_the_device_as_in_torch(bs, tokens, n_metrics):
+    """The uint16 record takes the unpack kernel too (w = 16): a [2, words] stack, odd counts, the index field at word 3 / 9 / 1."""
+    from pit_hip.eval_dist import StepRecord, unpack_index_bits
+
+    lay = StepRecord(bs, tokens, n_metrics)
+    g = torch.Generator().manual_seed(bs * 10 + n_metrics)
+    idx = torch.randint(0, 65536, (2, bs, tokens), generator=g)
+    idx[0, 0, 0], idx[1, -1, -1] = 65535, 32768
+    met = torch.randn(2, bs, n_metrics, generator=g)
+    stack = torch.stack([lay.pack(idx[r], met[r]) for r in range(2)])
+    assert stack.shape == (2, lay.words)
+    got_idx, got_met = lay.unpack(stack.to(DEV))
+    want_idx, want_met = lay.unpack(stack)
+    assert torch.equal(want_idx, idx) and torch.equal(want_idx.reshape(2, -1), unpack_index_bits(stack[:, lay.metric_words:], bs * tokens, 16))
+    assert got_idx.dtype == torch.int64 and torch.equal(got_idx.cpu(), want_idx)
+    assert torch.equal(got_met.cpu(), want_met)
+
+
+@pytest.mark.parametrize("cl", [False, True])
+@pytest.mark.parametrize("B,C,H,W,T", [(3, 3, 5, 7, 5), (2, 3, 64, 48, 3), (1, 3, 256, 256, 4)])
+def test_one_step_record_wrapper_serves_every_format_and_metric_count(B, C, H, W, T, cl):
+    """_lib.step_record through uint16 / bits x one / three metrics on ONE ws_cache: per_image not a multiple of 4 with one chunk and
+    an odd index count; two PSNR chunks with a NaN MS-SSIM; five SSIM levels behind the record's head.  Index and violations
+    words: the torch packers, exactly.  PSNR: the torch expression within 2e-6 (fp64 sum of the reference's fp32 terms vs torch's
+    fp32 mean; test_step_record_one_launch_matches_the_torch_expressions) and the same bits from all four; SSIM / MS-SSIM: the bits
+    of get_ssim_and_msssim (test_three_metric_record), NaN included.  Every workspace is all zero behind the calls, and serves a
+    smaller B."""
+    from pit_hip.eval_dist import (count_index_violations, get_ssim_and_msssim, index_bits_for, pack_index_bits,
+                                   psnr_zero_mean)
+
+    L = _L()
+    x, xr = _images(B, C, H, W, cl, B * 100 + H)
+    want_psnr = psnr_zero_mean(x, xr)
+    ssim, ms = get_ssim_and_msssim(x, xr, zero_mean=True)
+    assert bool(torch.isnan(ms).all()) == (H < 256)
+    idx = torch.randint(0, 65536, (B, T), generator=torch.Generator().manual_seed(T)).to(DEV)
+    idx[0, 0], idx[-1, -1] = 65535, 65536 + 3                        # the last one: out of range for n_codes = 65536 only
+    flat = idx.reshape(-1).cpu()
+    ws_cache, psnr_words = {}, []
+    for n_metrics in (1, 3):
+        for n_codes in (None, 65536, 1 << 18):
+            w = 16 if n_codes is None else index_bits_for(n_codes)
+            n_words = (B * T * w + 31) // 32
+            rec = torch.full((B * n_metrics + n_words + (n_codes is not None) + 4,), GUARD, dtype=torch.int32, device=DEV)
+            for _ in range(2):                                        # the second call runs in the workspace the first left
+                out = L.step_record(x, xr, idx, rec[:-4], ws_cache, n_metrics, None if n_codes is None else w, n_codes)
+            assert out.data_ptr() == rec.data_ptr() and bool((rec[-4:] == GUARD).all())
+            m = B * n_metrics
+            assert torch.equal(rec[m: m + n_words].cpu(), pack_index_bits(flat, w)), (n_metrics, n_codes)
+            if n_codes is not None:
+                assert int(rec[m + n_words]) == int(count_index_violations(flat, n_codes)) == (n_codes == 65536)
+            psnr_words.append(rec[0:m:n_metrics].clone())
+            if n_metrics == 3:
+                assert torch.equal(rec[1:m:3], ssim.view(torch.int32)) and torch.equal(rec[2:m:3], ms.view(torch.int32))
+    assert all(torch.equal(p, psnr_words[0]) for p in psnr_words)
+    torch.testing.assert_close(psnr_words[0].view(torch.float32), want_psnr, rtol=2e-6, atol=0)
+    assert len(ws_cache) == 4 and all(int(t.count_nonzero()) == 0 for t in ws_cache.values())
+    if B > 1:                                                         # a smaller B: its own entries of the same cache
+        short = torch.empty(3 * (B - 1) + ((B - 1) * T * 18 + 31) // 32 + 1, dtype=torch.int32, device=DEV)
+        L.step_record(x[:B - 1], xr[:B - 1], idx[:B - 1], short, ws_cache, 3, 18, 1 << 18)
+        assert torch.equal(short[0:3 * (B - 1):3], psnr_words[0][:B - 1])
+        assert torch.equal(short[1:3 * (B - 1):3], ssim[:B - 1].view(torch.int32))
+        assert torch.equal(short[3 * (B - 1): -1].cpu(), pack_index_bits(flat[:(B - 1) * T], 18)) and int(short[-1]) == 0
+        assert len(ws_cache) == 5 and all(int(t.count_nonzero()) == 0 for t in ws_cache.values())
+
+
 def test_packed_histogram_equals_bincount():
     """n = 2^18, two records, w = 18, the field 3 words into rows wider than the field; it ADDS to hist; with a smaller n the values
     >= n are skipped."""

@@ -289,6 +289,99 @@ def test_conv_stack_cabi_status_table():
     assert ["conv1x1_f16x3", "one/fake/HW=384", 3] in got
 
 
+_RECORD_ENTRIES = {          # entry point: (argument names, its size function, that function's arguments)
+    "gq_step_record_f32": ("x x_rec idx rec B per_image n_idx ws ws_bytes stream", "gq_step_record_workspace_bytes", "B per_image"),
+    "gq_step_record_bits_f32": ("x x_rec idx rec B per_image n_idx index_bits n_codes ws ws_bytes stream",
+                                "gq_step_record_bits_workspace_bytes", "B per_image"),
+    "gq_step_record_ssim_f32": ("x x_rec idx rec B C H W layout n_idx ws ws_bytes stream", "gq_step_record_ssim_workspace_bytes",
+                                "B C H W"),
+    "gq_step_record_ssim_bits_f32": ("x x_rec idx rec B C H W layout n_idx index_bits n_codes ws ws_bytes stream",
+                                     "gq_step_record_ssim_bits_workspace_bytes", "B C H W"),
+}
+_RECORD_SHAPES = ((1, 3, 5, 7), (2, 3, 64, 48), (16, 3, 256, 256), (3, 3, 257, 263))
+_RECORD_REFUSED = ((-1, 3, 64, 48), (0, 3, 64, 48), ((1 << 30) + 1, 3, 64, 48), (2, 0, 64, 48), (2, 3, 0, 48), (2, 3, 64, 0))
+
+
+def _record_cabi_table(lib):
+    """[entry or size function, case id, status or byte count] over the families of test_record_cabi_status_table; ``lib``: a
+    loaded libgqhip with the signatures set."""
+    fake, ample = 0x10000, 1 << 62          # the pointer is never dereferenced: see the test's docstring
+    rows = []
+    for entry, (names, size_name, size_args) in _RECORD_ENTRIES.items():
+        names, size_args = names.split(), size_args.split()
+        fn, size = getattr(lib, entry), getattr(lib, size_name)
+        bits, image = "index_bits" in names, "C" in names
+        ptrs = ("x", "x_rec", "idx", "rec", "ws")
+        base = dict(B=2, per_image=3 * 64 * 48, C=3, H=64, W=48, layout=0, n_idx=5, index_bits=18, n_codes=1 << 18, stream=None)
+
+        def case(cid, nulls=(), ws_bytes=ample, **scalars):
+            vals = dict(base, **{p: (None if p in nulls else fake) for p in ptrs}, ws_bytes=ws_bytes)
+            assert set(scalars) <= set(vals), scalars
+            vals.update(scalars)
+            rows.append([entry, cid, fn(*[vals[n] for n in names])])
+
+        need = size(*[base[n] for n in size_args])
+        case("base")
+        case("nothing/null", ptrs, 0, B=0, n_idx=0)
+        case("nothing/fake", B=0, n_idx=0)
+        case("all/null", ptrs)
+        for p in ptrs[:4]:
+            case("null:" + p, (p,))
+        case("ws/null", ("ws",), need)
+        case("ws/short", (), need - 1)
+        case("ws/exact", (), need)
+        for B in (-1, 0, 1, (1 << 30) + 1):
+            case("B=%d" % B, B=B)
+        case("B=0/ws/null", ("ws",), 0, B=0)
+        case("B=0/images/null", ("x", "x_rec"), B=0)
+        for n in ("C", "H", "W") if image else ("per_image",):
+            case(n + "=0", **{n: 0})
+        if image:
+            case("layout=2", layout=2)
+            case("layout=1", layout=1)
+        for n_idx in (-1, 0, 1):
+            case("n_idx=%d" % n_idx, n_idx=n_idx)
+        case("n_idx=0/idx/null", ("idx",), n_idx=0)
+        case("n_idx=2^62", n_idx=1 << 62)
+        if bits:
+            for w in (0, 1, 16, 32, 33):
+                for n_codes in (0, 1, 1 << w, (1 << w) + 1):
+                    case("index_bits=%d,n_codes=%d" % (w, n_codes), index_bits=w, n_codes=n_codes)
+            case("n_idx=2^33,index_bits=32", n_idx=1 << 33, index_bits=32, n_codes=1)      # the ticket field of the violations word
+            case("n_idx=2^33,index_bits=32/ws/short", (), 0, n_idx=1 << 33, index_bits=32, n_codes=1)
+        # B x chunks beyond 2^30: refused, but only behind the workspace check
+        big = dict(B=1 << 20, C=1, H=4096, W=4096) if image else dict(B=1 << 20, per_image=1 << 24)
+        case("B*chunks=2^31", **big)
+        case("B*chunks=2^31/ws/short", (), 0, **big)
+        for B, C, H, W in _RECORD_SHAPES + _RECORD_REFUSED:
+            args = (B, C, H, W) if image else (B, C * H * W)
+            rows.append([size_name, "x".join(map(str, args)), size(*args)])
+    return rows
+
+
+def test_record_cabi_status_table():
+    """The four step-record entry points of csrc/gqhip.hip return the status, and their four size functions the byte count, that
+    tests/golden/record_cabi_status.json records (recorded with this generator from the library as it was before the record's
+    checks and workspace layout were brought together in one plan): nothing to do with all pointers NULL or set, each pointer NULL
+    in turn, the workspace NULL / one byte short / exact, and each shape, count and index-format argument out of its range in
+    turn.  Without a device an entry point that gets past its checks returns 3 ("kernel launch failed": no device) and launches
+    nothing, so 0 / 1 / 2 / 3 tell "empty", "refused", "workspace" and "would launch" apart -- the ORDER of the checks included.
+    SAFETY: the pointers passed are made up.  They are never dereferenced only because nothing can launch, so this test must
+    never run where a HIP device is present: it skips there, whatever else is asked of it."""
+    if torch.cuda.is_available():
+        pytest.skip("passes made-up pointers: safe only where no kernel can launch")
+    got = _record_cabi_table(_lib().lib())
+    want = json.load(open(os.path.join(G, "record_cabi_status.json")))
+    assert len(got) == len(want) > 150 and {e for e, _, _ in got} == set(_RECORD_ENTRIES) | {v[1] for v in _RECORD_ENTRIES.values()}
+    assert {s for e, _, s in got if e in _RECORD_ENTRIES} == {0, 1, 2, 3}
+    diff = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not diff, diff[:20]
+    # a few of the rules, spelled out: only gq_step_record_f32 has "nothing to do"; the bit-packed records always want the workspace
+    assert ["gq_step_record_f32", "nothing/null", 0] in got and ["gq_step_record_bits_f32", "nothing/null", 1] in got
+    assert ["gq_step_record_f32", "B=0/ws/null", 3] in got and ["gq_step_record_bits_f32", "B=0/ws/null", 2] in got
+    assert ["gq_step_record_ssim_f32", "B=0", 1] in got and ["gq_step_record_f32", "B*chunks=2^31/ws/short", 2] in got
+
+
 def test_no_cpu_fallback():
     L = _lib()
     mu = torch.zeros(4, 16)

@@ -78,6 +78,28 @@ def test_sixteen_bits_are_the_legacy_pair_words():
         assert torch.equal(old.unpack(r_old)[0], new.unpack(r_new)[0])
 
 
+@pytest.mark.parametrize("bs,tokens", [(3, 5), (1, 1), (2, 8)])
+def test_uint16_record_masks_indices_outside_its_domain(bs, tokens):
+    """Outside the documented domain (values < 2^16) a uint16 record packed without the range check carries each index's low 16
+    bits -- the words of pack_index_bits(., 16), which are the kernel's -- and no index spills into its neighbour's half-word."""
+    from pit_hip.eval_dist import StepRecord, pack_index_bits
+
+    flat = torch.randint(0, 65536, (bs * tokens,), generator=torch.Generator().manual_seed(bs * 100 + tokens))
+    flat[0] = 65536 + 7
+    if flat.numel() > 1:
+        flat[-1], flat[1], flat[-2] = -1, -1, 65536 + 7       # an even and an odd position each
+    lay = StepRecord(bs, tokens, 2, check_range=False)
+    met = torch.randn(bs, 2, generator=torch.Generator().manual_seed(1))
+    rec = lay.pack(flat.reshape(bs, tokens), met)
+    assert rec.numel() == lay.words and torch.equal(rec[lay.metric_words:], pack_index_bits(flat, 16))
+    idx, m2 = lay.unpack(rec)
+    assert torch.equal(idx.reshape(-1), flat & 0xFFFF) and torch.equal(m2, met)
+    if flat.numel() == 1:                                     # (1, 1) holds one index: the other value in a record of its own
+        rec = lay.pack(torch.tensor([[-1]]), met)
+        assert torch.equal(rec[lay.metric_words:], pack_index_bits(torch.tensor([-1]), 16))
+        assert lay.unpack(rec)[0].tolist() == [[0xFFFF]]
+
+
 def test_record_layout_words_and_violations_word():
     from pit_hip.eval_dist import StepRecord, index_bits_for
 

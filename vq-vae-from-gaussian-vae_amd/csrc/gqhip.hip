@@ -1311,36 +1311,6 @@ int gq_indices_from_u16(const uint16_t *in, int64_t *idx, int64_t count, void *s
                 static_cast<hipStream_t>(stream), in, idx, (long)count);
 }
 
-int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image) {
-  if (B < 0 || per_image < 1) return -1;
-  const int64_t chunks = (per_image + kPsnrChunk - 1) / kPsnrChunk;
-  return B * chunks * 8 + ((B * 4 + 7) / 8) * 8;
-}
-
-static int step_record_launch(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
-                              int64_t n_idx, void *workspace_zeroed, int stride, hipStream_t st) {
-  StepRecordParams p{};
-  p.x = x; p.x_rec = x_rec; p.idx = idx; p.rec = rec;
-  p.per_image = (long)per_image; p.n_idx = (long)n_idx; p.B = (int)B; p.stride = stride;
-  p.chunks = (int)((per_image + kPsnrChunk - 1) / kPsnrChunk);
-  if ((int64_t)p.chunks * B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
-  p.psnr_blocks = p.chunks * (int)B;
-  p.partial = static_cast<double *>(workspace_zeroed);
-  p.ticket = reinterpret_cast<int *>(static_cast<char *>(workspace_zeroed) + B * p.chunks * 8);
-  const int64_t words = (n_idx + 1) / 2;
-  const int64_t blocks = p.psnr_blocks + (words + 255) / 256;
-  return launch(step_record_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-}
-
-int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
-                       int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
-  if (B < 0 || per_image < 1 || n_idx < 0 || B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
-  if (B == 0 && n_idx == 0) return GQHIP_OK;
-  if (!rec || (B > 0 && (!x || !x_rec)) || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
-  if (B > 0 && (!workspace_zeroed || workspace_bytes < gq_step_record_workspace_bytes(B, per_image))) return GQHIP_ERR_WORKSPACE;
-  return step_record_launch(x, x_rec, idx, rec, B, per_image, n_idx, workspace_zeroed, 1, static_cast<hipStream_t>(stream));
-}
-
 // ---- the bit-packed index wire format (csrc/gq_aux.h) ----------------------------------------------------------------------------
 namespace {
 // 1 <= index_bits <= 32 and 1 <= n_codes <= 2^index_bits: every in-range index survives the packing
@@ -1399,41 +1369,6 @@ int gq_index_histogram_packed(const int32_t *records, int64_t n_records, int64_t
   return launch(hist_packed_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
                 records, (long)n_records, (long)stride_words, (long)offset_words, (long)count, index_bits, n,
                 reinterpret_cast<unsigned long long *>(hist));
-}
-
-int64_t gq_step_record_bits_workspace_bytes(int64_t B, int64_t per_image) {
-  const int64_t psnr = gq_step_record_workspace_bytes(B, per_image);
-  return psnr < 0 ? -1 : psnr + 8;          // + one 64-bit word: violations count | ticket
-}
-
-static int step_record_bits_launch(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
-                                   int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int stride, hipStream_t st) {
-  const int64_t n_words = bits_words(n_idx, index_bits);
-  if (n_words < 0) return GQHIP_ERR_INVALID_ARG;
-  StepRecordBitsParams p{};
-  p.r.x = x; p.r.x_rec = x_rec; p.r.idx = idx; p.r.rec = rec;
-  p.r.per_image = (long)per_image; p.r.n_idx = (long)n_idx; p.r.B = (int)B; p.r.stride = stride;
-  p.r.chunks = (int)((per_image + kPsnrChunk - 1) / kPsnrChunk);
-  if ((int64_t)p.r.chunks * B > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
-  p.r.psnr_blocks = p.r.chunks * (int)B;
-  p.r.partial = static_cast<double *>(workspace_zeroed);
-  p.r.ticket = reinterpret_cast<int *>(static_cast<char *>(workspace_zeroed) + B * p.r.chunks * 8);
-  p.viol = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace_zeroed) + gq_step_record_workspace_bytes(B, per_image));
-  p.k = pack_bits_params(idx, rec + B * stride, n_idx, n_words, index_bits, n_codes);
-  p.pack_blocks = n_words > 0 ? (int)((n_words + 255) / 256) : 1;
-  const int64_t blocks = (int64_t)p.pack_blocks + p.r.psnr_blocks;
-  if (n_words > ((int64_t)1 << 31) || blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;      // the ticket field: pack_blocks < 2^24
-  return launch(step_record_bits_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-}
-
-int gq_step_record_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
-                            int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int64_t workspace_bytes,
-                            void *stream) {
-  if (B < 0 || per_image < 1 || n_idx < 0 || B > 0x3fffffff || !bits_args_ok(index_bits, n_codes)) return GQHIP_ERR_INVALID_ARG;
-  if (!rec || (B > 0 && (!x || !x_rec)) || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
-  if (!workspace_zeroed || workspace_bytes < gq_step_record_bits_workspace_bytes(B, per_image)) return GQHIP_ERR_WORKSPACE;
-  return step_record_bits_launch(x, x_rec, idx, rec, B, per_image, n_idx, index_bits, n_codes, workspace_zeroed, 1,
-                                 static_cast<hipStream_t>(stream));
 }
 
 // ---- SSIM / MS-SSIM (csrc/gq_ssim.h) ---------------------------------------------------------------------------------------------
@@ -1546,48 +1481,108 @@ int gq_ssim_f32(const float *x, const float *x_rec, int64_t B, int64_t C, int64_
                      static_cast<hipStream_t>(stream));
 }
 
-int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
-  SsimPlan pl;
-  if (!ssim_plan(B, C, H, W, pl)) return -1;
-  const int64_t head = ((gq_step_record_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
-  return head + pl.bytes;
+// ---- one rank's per-step record (csrc/gq_aux.h: step_record_kernel / step_record_bits_kernel; csrc/gq_ssim.h) -------------------
+namespace {
+// One description of a record call.  rec = [ B x stride metric words | index words | bits: 1 violations word ]: stride 1 (PSNR) or 3
+// (PSNR, SSIM, MS-SSIM), the index words uint16 pairs or (`bits`) the index_bits-wide stream.
+struct RecordPlan {
+  int status;                 // of the checks that come before the pointers are looked at
+  bool nothing;               // the call returns OK before it looks at a pointer
+  bool need_ws;               // the call wants `bytes` of zeroed workspace
+  bool grid_ok;               // the block counts fit the kernels' fields (checked after the workspace, as it always was)
+  bool bits;
+  int stride, index_bits, layout, chunks, psnr_blocks, pack_blocks;
+  int64_t B, C, per_image, n_idx, n_codes, n_words;
+  // the workspace, all zero between calls: B x chunks fp64 PSNR partials at 0, B int32 tickets (padded to 8 bytes) at off_ticket,
+  // bits only: the 64-bit violations count | ticket at off_viol, stride 3 only: the SSIM workspace at off_ssim (a multiple of 256)
+  int64_t off_ticket, off_viol, off_ssim, bytes;          // bytes: -1 for a shape the size functions refuse
+  SsimPlan ssim;              // stride 3
+};
+
+// Stride 1 takes the image as (C, H, W) = (per_image, 1, 1).  The size functions pass n_idx = 0 and any valid index format: `bytes`
+// depends on neither, nor on anything checked after it is set.
+RecordPlan record_plan(int stride, bool bits, int64_t B, int64_t C, int64_t H, int64_t W, int layout, int64_t n_idx, int index_bits,
+                       int64_t n_codes) {
+  RecordPlan pl{};
+  pl.status = GQHIP_ERR_INVALID_ARG; pl.bytes = -1;
+  pl.stride = stride; pl.bits = bits; pl.index_bits = index_bits; pl.layout = layout;
+  pl.B = B; pl.C = C; pl.n_idx = n_idx; pl.n_codes = n_codes;
+  // the shape; three metrics refuse B < 1 (and sides or block counts beyond 2^30) through ssim_plan
+  if (stride == 3 ? !ssim_plan(B, C, H, W, pl.ssim) : (B < 0 || C < 1)) return pl;
+  pl.per_image = C * H * W;
+  const int64_t chunks = (pl.per_image + kPsnrChunk - 1) / kPsnrChunk;
+  pl.off_ticket = B * chunks * 8;
+  pl.off_viol = pl.off_ticket + ((B * 4 + 7) / 8) * 8;
+  pl.off_ssim = ((pl.off_viol + (bits ? 8 : 0) + 255) / 256) * 256;
+  pl.bytes = stride == 3 ? pl.off_ssim + pl.ssim.bytes : pl.off_viol + (bits ? 8 : 0);
+  // the arguments
+  if (B > 0x3fffffff || n_idx < 0 || (stride == 3 && layout != 0 && layout != 1) || (bits && !bits_args_ok(index_bits, n_codes))) return pl;
+  pl.status = GQHIP_OK;
+  pl.nothing = !bits && stride == 1 && B == 0 && n_idx == 0;     // the bit-packed record still writes its violations word ...
+  pl.need_ws = bits || B > 0;                                    // ... through the workspace; the uint16 one needs it for PSNR only
+  // the grid: B x chunks PSNR blocks and the packing blocks of 256 words; bits_words bounds the stream (-1)
+  pl.n_words = bits ? bits_words(n_idx, index_bits) : (n_idx + 1) / 2;
+  if (B * chunks > 0x3fffffff || pl.n_words < 0) return pl;
+  pl.chunks = (int)chunks; pl.psnr_blocks = (int)(B * chunks);
+  pl.pack_blocks = bits && pl.n_words == 0 ? 1 : (int)((pl.n_words + 255) / 256);
+  // the ticket field of the violations word: pack_blocks < 2^24
+  pl.grid_ok = !bits || (pl.n_words <= ((int64_t)1 << 31) && (int64_t)pl.pack_blocks + pl.psnr_blocks <= 0x7fffffff);
+  return pl;
+}
+
+// The pointer and workspace checks of every record entry point, then step_record_kernel or step_record_bits_kernel and, for three
+// metrics, the SSIM launches into rec + 1 / rec + 2 at stride 3.
+int record_launch(const RecordPlan &pl, const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, void *ws, int64_t ws_bytes,
+                  void *stream) {
+  if (pl.status != GQHIP_OK || pl.nothing) return pl.status;
+  if (!rec || (pl.B > 0 && (!x || !x_rec)) || (pl.n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
+  if (pl.need_ws && (!ws || ws_bytes < pl.bytes)) return GQHIP_ERR_WORKSPACE;
+  if (!pl.grid_ok) return GQHIP_ERR_INVALID_ARG;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  char *base = static_cast<char *>(ws);
+  StepRecordBitsParams p{};
+  StepRecordParams &r = p.r;
+  r.x = x; r.x_rec = x_rec; r.idx = idx; r.rec = rec;
+  r.per_image = (long)pl.per_image; r.n_idx = (long)pl.n_idx; r.B = (int)pl.B; r.stride = pl.stride;
+  r.chunks = pl.chunks; r.psnr_blocks = pl.psnr_blocks;
+  r.partial = reinterpret_cast<double *>(base);
+  r.ticket = reinterpret_cast<int *>(base + pl.off_ticket);
+  p.viol = reinterpret_cast<unsigned long long *>(base + pl.off_viol);         // p.viol, p.k, p.pack_blocks: the bit-packed kernel's
+  p.k = pack_bits_params(idx, rec + pl.B * pl.stride, pl.n_idx, pl.n_words, pl.index_bits, pl.n_codes);
+  p.pack_blocks = pl.pack_blocks;
+  const dim3 grid((unsigned)((int64_t)pl.psnr_blocks + pl.pack_blocks));
+  const int rc = pl.bits ? launch(step_record_bits_kernel, grid, dim3(256), 0, st, p) : launch(step_record_kernel, grid, dim3(256), 0, st, r);
+  if (rc != GQHIP_OK || pl.stride != 3) return rc;
+  return ssim_launch(x, x_rec, pl.B, pl.C, pl.layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3,
+                     pl.ssim, base + pl.off_ssim, st);
+}
+}  // namespace
+
+int64_t gq_step_record_workspace_bytes(int64_t B, int64_t per_image) { return record_plan(1, false, B, per_image, 1, 1, 0, 0, 0, 0).bytes; }
+int64_t gq_step_record_bits_workspace_bytes(int64_t B, int64_t per_image) { return record_plan(1, true, B, per_image, 1, 1, 0, 0, 1, 1).bytes; }
+int64_t gq_step_record_ssim_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) { return record_plan(3, false, B, C, H, W, 0, 0, 0, 0).bytes; }
+int64_t gq_step_record_ssim_bits_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) { return record_plan(3, true, B, C, H, W, 0, 0, 1, 1).bytes; }
+
+int gq_step_record_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                       int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
+  return record_launch(record_plan(1, false, B, per_image, 1, 1, 0, n_idx, 0, 0), x, x_rec, idx, rec, workspace_zeroed, workspace_bytes, stream);
+}
+
+int gq_step_record_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t per_image,
+                            int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed, int64_t workspace_bytes,
+                            void *stream) {
+  return record_launch(record_plan(1, true, B, per_image, 1, 1, 0, n_idx, index_bits, n_codes), x, x_rec, idx, rec, workspace_zeroed, workspace_bytes, stream);
 }
 
 int gq_step_record_ssim_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
                             int64_t W, int layout, int64_t n_idx, void *workspace_zeroed, int64_t workspace_bytes, void *stream) {
-  SsimPlan pl;
-  if (!ssim_plan(B, C, H, W, pl) || (layout != 0 && layout != 1) || n_idx < 0) return GQHIP_ERR_INVALID_ARG;
-  if (!x || !x_rec || !rec || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
-  if (!workspace_zeroed || workspace_bytes < gq_step_record_ssim_workspace_bytes(B, C, H, W)) return GQHIP_ERR_WORKSPACE;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t head = ((gq_step_record_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
-  int rc = step_record_launch(x, x_rec, idx, rec, B, C * H * W, n_idx, workspace_zeroed, 3, st);    // PSNR words + indices
-  if (rc != GQHIP_OK) return rc;
-  return ssim_launch(x, x_rec, B, C, layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3, pl,
-                     static_cast<char *>(workspace_zeroed) + head, st);
-}
-
-int64_t gq_step_record_ssim_bits_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W) {
-  SsimPlan pl;
-  if (!ssim_plan(B, C, H, W, pl)) return -1;
-  const int64_t head = ((gq_step_record_bits_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
-  return head + pl.bytes;
+  return record_launch(record_plan(3, false, B, C, H, W, layout, n_idx, 0, 0), x, x_rec, idx, rec, workspace_zeroed, workspace_bytes, stream);
 }
 
 int gq_step_record_ssim_bits_f32(const float *x, const float *x_rec, const int64_t *idx, int32_t *rec, int64_t B, int64_t C, int64_t H,
                                  int64_t W, int layout, int64_t n_idx, int index_bits, int64_t n_codes, void *workspace_zeroed,
                                  int64_t workspace_bytes, void *stream) {
-  SsimPlan pl;
-  if (!ssim_plan(B, C, H, W, pl) || (layout != 0 && layout != 1) || n_idx < 0 || !bits_args_ok(index_bits, n_codes))
-    return GQHIP_ERR_INVALID_ARG;
-  if (!x || !x_rec || !rec || (n_idx > 0 && !idx)) return GQHIP_ERR_INVALID_ARG;
-  if (!workspace_zeroed || workspace_bytes < gq_step_record_ssim_bits_workspace_bytes(B, C, H, W)) return GQHIP_ERR_WORKSPACE;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int64_t head = ((gq_step_record_bits_workspace_bytes(B, C * H * W) + 255) / 256) * 256;
-  int rc = step_record_bits_launch(x, x_rec, idx, rec, B, C * H * W, n_idx, index_bits, n_codes, workspace_zeroed, 3, st);
-  if (rc != GQHIP_OK) return rc;
-  return ssim_launch(x, x_rec, B, C, layout, 1, reinterpret_cast<float *>(rec + 1), reinterpret_cast<float *>(rec + 2), 3, pl,
-                     static_cast<char *>(workspace_zeroed) + head, st);
+  return record_launch(record_plan(3, true, B, C, H, W, layout, n_idx, index_bits, n_codes), x, x_rec, idx, rec, workspace_zeroed, workspace_bytes, stream);
 }
 
 int gqhip_profile_enable(int on) {

@@ -1501,36 +1501,54 @@ def _zeroed_ws(ws_cache: dict, key, need: int, device):
     return ws
 
 
-def step_record_ok(x, x_rec, idx) -> bool:
-    """gq_step_record_f32 applies: fp32 HIP images of one dense layout (NCHW or channels_last), int64 indices on the same device."""
-    if not (x.is_cuda and x_rec.is_cuda and idx.is_cuda and x.dtype == torch.float32 and x_rec.dtype == torch.float32
-            and idx.dtype == torch.int64 and x.shape == x_rec.shape and x.dim() == 4):
+def _image_pair_ok(x, x_rec, need_items: bool) -> bool:
+    """fp32 HIP images [B, C, H, W] of one shape, one device and one dense layout (NCHW or channels_last); ``need_items``: B >= 1
+    and a non-empty image as well."""
+    if not (x.is_cuda and x_rec.is_cuda and x.device == x_rec.device and x.dtype == torch.float32 and x_rec.dtype == torch.float32
+            and x.dim() == 4 and x.shape == x_rec.shape and (not need_items or (x.shape[0] > 0 and x[0].numel() > 0))):
         return False
     la, lb = image_layout(x), image_layout(x_rec)
     return la is not None and la == lb
 
 
-def step_record(x, x_rec, idx, rec, ws_cache: dict):
-    """rec[:] = [ per-image PSNR(x, x_rec; zero_mean) as fp32 bits | idx as uint16 pairs ] in ONE launch (gqhip.h:
-    gq_step_record_f32; eval.py:152-154,165-169).  ``ws_cache``: the caller's dict that keeps the (zeroed, self-resetting)
-    workspace between calls."""
-    B = x.shape[0]
-    per = x[0].numel()
-    idx = idx.contiguous()      # (any memory order of the SAME logical [B, K, h, w] order is fine for the caller; contiguous = logical order)
-    ws = _zeroed_ws(ws_cache, (x.device, B, per), lib().gq_step_record_workspace_bytes(B, per), x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gq_step_record_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, per, idx.numel(),
-                                        ws.data_ptr(), ws.numel(), _stream()), "gq_step_record_f32")
-    return rec
+def step_record_ok(x, x_rec, idx) -> bool:
+    """The record kernels apply: _image_pair_ok images, int64 indices on a HIP device.  (Images on two devices are refused like
+    everything else the kernels do not take; this predicate used to pass them on.)"""
+    return idx.is_cuda and idx.dtype == torch.int64 and _image_pair_ok(x, x_rec, False)
 
 
 def ssim_ok(x, x_rec) -> bool:
-    """gq_ssim_f32 applies: fp32 HIP images [B, C, H, W] of one dense layout (NCHW or channels_last), B >= 1."""
-    if not (x.is_cuda and x_rec.is_cuda and x.device == x_rec.device and x.dtype == torch.float32
-            and x_rec.dtype == torch.float32 and x.dim() == 4 and x.shape == x_rec.shape and x.shape[0] > 0 and x[0].numel() > 0):
-        return False
-    la, lb = image_layout(x), image_layout(x_rec)
-    return la is not None and la == lb
+    """gq_ssim_f32 applies: _image_pair_ok images, B >= 1."""
+    return _image_pair_ok(x, x_rec, True)
+
+
+def step_record(x, x_rec, idx, rec, ws_cache: dict, n_metrics: int = 1, index_bits: Optional[int] = None,
+                n_codes: Optional[int] = None):
+    """rec[:] = [ B x n_metrics metric words | index words ] of one rank's step (gqhip.h: gq_step_record*_f32; eval.py:152-154,
+    165-178).  n_metrics 1: per-image PSNR(x, x_rec; zero_mean) as fp32 bits, ONE launch; 3: (PSNR, SSIM, MS-SSIM), the PSNR words
+    those of n_metrics 1 bit for bit.  ``index_bits`` None: idx as uint16 pairs; else the bit-packed stream of that width and the
+    violations word (indices outside [0, n_codes)) behind it.  ``ws_cache``: the caller's dict that keeps the (zeroed, self-
+    resetting) workspace between calls."""
+    L = lib()
+    B, C, H, W = x.shape
+    bits = index_bits is not None
+    if n_metrics == 1:
+        size, call = (L.gq_step_record_bits_workspace_bytes, L.gq_step_record_bits_f32) if bits else \
+            (L.gq_step_record_workspace_bytes, L.gq_step_record_f32)
+        shape = image = (B, C * H * W)
+    elif n_metrics == 3:
+        size, call = (L.gq_step_record_ssim_bits_workspace_bytes, L.gq_step_record_ssim_bits_f32) if bits else \
+            (L.gq_step_record_ssim_workspace_bytes, L.gq_step_record_ssim_f32)
+        shape, image = (B, C, H, W), (B, C, H, W, image_layout(x))
+    else:
+        raise GqHipError(f"step_record: n_metrics is 1 or 3, not {n_metrics}")
+    wire = (index_bits, n_codes) if bits else ()
+    idx = idx.contiguous()      # (any memory order of the SAME logical [B, K, h, w] order is fine for the caller; contiguous = logical order)
+    ws = _zeroed_ws(ws_cache, ("bits" if bits else "u16", n_metrics, x.device, B, C, H, W), size(*shape), x.device)
+    with torch.cuda.device(x.device):
+        _check(call(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), *image, idx.numel(), *wire, ws.data_ptr(),
+                    ws.numel(), _stream()), call.__name__)
+    return rec
 
 
 def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
@@ -1545,19 +1563,6 @@ def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
         _check(lib().gq_ssim_f32(x.data_ptr(), x_rec.data_ptr(), B, C, H, W, layout, 1 if zero_mean else 0, ssim.data_ptr(),
                                  ms.data_ptr() if ms is not None else None, ws.data_ptr(), ws.numel(), _stream()), "gq_ssim_f32")
     return ssim, ms
-
-
-def step_record_ssim(x, x_rec, idx, rec, ws_cache: dict):
-    """rec[:] = [ B x (PSNR, SSIM, MS-SSIM) of (x, x_rec; zero_mean) as fp32 bits | idx as uint16 pairs ] (gqhip.h:
-    gq_step_record_ssim_f32; eval.py:152-154,165-178): the PSNR and index words are those of step_record bit for bit."""
-    B, C, H, W = x.shape
-    idx = idx.contiguous()
-    ws = _zeroed_ws(ws_cache, ("rec3", x.device, B, C, H, W), lib().gq_step_record_ssim_workspace_bytes(B, C, H, W), x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gq_step_record_ssim_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
-                                             image_layout(x), idx.numel(), ws.data_ptr(), ws.numel(), _stream()),
-               "gq_step_record_ssim_f32")
-    return rec
 
 
 def _words_out(t, n_words: int, what: str):
@@ -1609,33 +1614,6 @@ def index_histogram_packed(records, offset_words: int, count: int, index_bits: i
         _check(lib().gq_index_histogram_packed(records.data_ptr(), records.shape[0], records.shape[1], offset_words, count,
                                                index_bits, hist.numel(), hist.data_ptr(), _stream()), "gq_index_histogram_packed")
     return hist
-
-
-def step_record_bits(x, x_rec, idx, rec, index_bits: int, n_codes: int, ws_cache: dict):
-    """step_record with the bit-packed index words and the violations word behind the same PSNR words (gqhip.h:
-    gq_step_record_bits_f32)."""
-    B = x.shape[0]
-    per = x[0].numel()
-    idx = idx.contiguous()
-    ws = _zeroed_ws(ws_cache, ("bits", x.device, B, per), lib().gq_step_record_bits_workspace_bytes(B, per), x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gq_step_record_bits_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, per, idx.numel(),
-                                             index_bits, n_codes, ws.data_ptr(), ws.numel(), _stream()), "gq_step_record_bits_f32")
-    return rec
-
-
-def step_record_ssim_bits(x, x_rec, idx, rec, index_bits: int, n_codes: int, ws_cache: dict):
-    """step_record_ssim with the bit-packed index words and the violations word behind the same metric words (gqhip.h:
-    gq_step_record_ssim_bits_f32)."""
-    B, C, H, W = x.shape
-    idx = idx.contiguous()
-    ws = _zeroed_ws(ws_cache, ("rec3bits", x.device, B, C, H, W), lib().gq_step_record_ssim_bits_workspace_bytes(B, C, H, W),
-                    x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gq_step_record_ssim_bits_f32(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), B, C, H, W,
-                                                  image_layout(x), idx.numel(), index_bits, n_codes, ws.data_ptr(), ws.numel(),
-                                                  _stream()), "gq_step_record_ssim_bits_f32")
-    return rec
 
 
 MHA_HEAD_DIMS = (64,)    # head dims gq_mha_fwd_f32 is built for

@@ -155,115 +155,96 @@ class StepRecord:
         self.check_range = check_range
         self.n_codes = n_codes
         self.metric_words = bs * n_metrics
-        if n_codes is None:
-            self.index_bits = 16
-            self.index_words = (bs * tokens_per_image + 1) // 2
-            self.words = self.metric_words + self.index_words
-        else:
-            self.index_bits = index_bits_for(n_codes)
-            self.index_words = (bs * tokens_per_image * self.index_bits + 31) // 32
-            self.words = self.metric_words + self.index_words + 1
+        self.index_bits = 16 if n_codes is None else index_bits_for(n_codes)
+        self.index_words = (bs * tokens_per_image * self.index_bits + 31) // 32
+        self.words = self.metric_words + self.index_words + (n_codes is not None)
+        self._ws = {}        # the library's zeroed, self-resetting workspaces (_lib.step_record)
 
-    def _pack_bits(self, indices: torch.Tensor, metrics: torch.Tensor) -> torch.Tensor:
-        """pack() of the bit-packed record: the index and violations words from gq_indices_pack_bits on a HIP device, from the
-        torch expressions elsewhere."""
+    def _check_counts(self, who: str, indices: torch.Tensor, n_items: int, items: str, want_items: int) -> None:
+        if indices.numel() != self.bs * self.tokens or n_items != want_items:
+            raise ValueError(f"StepRecord.{who}: got {indices.numel()} indices / {n_items} {items}, layout is "
+                             f"{self.bs} x {self.tokens} / {want_items}")
+
+    def pack(self, indices: torch.Tensor, metrics: torch.Tensor) -> torch.Tensor:
+        """indices: int64 [bs, ...] with values < 2^16 (< n_codes in the bit-packed record); metrics: fp32 [bs, n_metrics].  The
+        index words are the stream of pack_index_bits in both formats (w = 16: the uint16 pairs), so an index outside the stated
+        range is packed as its low w bits; gq_indices_pack_bits writes them on a HIP device, the torch expressions elsewhere."""
         flat = indices.reshape(-1)
+        self._check_counts("pack", flat, metrics.numel(), "metrics", self.metric_words)
+        if self.n_codes is None and self.check_range:
+            _check_index_range(flat)
         rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
         rec[: self.metric_words] = metrics.reshape(-1).to(torch.float32).view(torch.int32)
+        end = self.metric_words + self.index_words
+        viol = rec[end:] if self.n_codes is not None else None
         if flat.is_cuda and flat.dtype == torch.int64:
             from . import _lib
 
-            _lib.indices_pack_bits(flat, self.index_bits, self.n_codes, rec[self.metric_words: -1], rec[-1:])
+            _lib.indices_pack_bits(flat, self.index_bits, self.n_codes or 1 << 16, rec[self.metric_words: end], viol)
         else:
-            rec[self.metric_words: -1] = pack_index_bits(flat, self.index_bits)
-            rec[-1] = count_index_violations(flat, self.n_codes)
+            rec[self.metric_words: end] = pack_index_bits(flat, self.index_bits)
+            if viol is not None:
+                viol[0] = count_index_violations(flat, self.n_codes)
         return rec
 
-    def pack(self, indices: torch.Tensor, metrics: torch.Tensor) -> torch.Tensor:
-        """indices: int64 [bs, ...] with values < 2^16 (< n_codes in the bit-packed record); metrics: fp32 [bs, n_metrics]."""
-        dev = indices.device
-        flat = indices.reshape(-1)
-        if self.n_codes is not None:
-            if flat.numel() != self.bs * self.tokens or metrics.numel() != self.metric_words:
-                raise ValueError(f"StepRecord.pack: got {flat.numel()} indices / {metrics.numel()} metrics, layout is "
-                                 f"{self.bs} x {self.tokens} / {self.metric_words}")
-            return self._pack_bits(indices, metrics)
-        rec = torch.empty(self.words, dtype=torch.int32, device=dev)
-        rec[: self.metric_words] = metrics.reshape(-1).to(torch.float32).view(torch.int32)
-        if flat.numel() != self.bs * self.tokens or metrics.numel() != self.metric_words:
-            raise ValueError(f"StepRecord.pack: got {flat.numel()} indices / {metrics.numel()} metrics, layout is "
-                             f"{self.bs} x {self.tokens} / {self.metric_words}")
-        if self.check_range:
-            _check_index_range(flat)
-        if flat.numel() % 2:
-            flat = torch.cat([flat, flat.new_zeros(1)])
-        u16 = flat.to(torch.int32)  # values < 65536
-        rec[self.metric_words:] = u16[0::2] | (u16[1::2] << 16)
-        return rec
+    def _pack_on_device(self, indices: torch.Tensor, x: torch.Tensor, x_rec: torch.Tensor) -> Optional[torch.Tensor]:
+        """The finished record from ONE library call (_lib.step_record: the metrics of (x, x_rec; zero_mean), the index words and
+        the violations word), or None where the kernels do not apply: off a HIP device, or for images / indices they do not take
+        (_lib.step_record_ok; three metrics: images brought to one dense layout first, and _lib.ssim_ok).
+        Which PSNR a record carries is observable -- the kernel sums in fp64, torch's mean in fp32 -- and ``check_range`` (the
+        uint16 record's host read of the indices' range; the bit-packed record has its violations word instead) decides it by one
+        rule: a uint16 record with ``check_range`` and ONE metric is not packed here but by the torch expressions (pack() checks
+        the range); with THREE metrics the range is checked on the host here and the kernels run."""
+        host_check = self.n_codes is None and self.check_range
+        if not indices.is_cuda or (host_check and self.n_metrics == 1):
+            return None
+        from . import _lib
+
+        self._check_counts("pack_with_psnr" if self.n_metrics == 1 else "pack_with_metrics", indices, x.shape[0], "images", self.bs)
+        if self.n_metrics == 3:
+            x, x_rec = _dense_pair(x, x_rec)
+        if not _lib.step_record_ok(x, x_rec, indices) or (self.n_metrics == 3 and not _lib.ssim_ok(x, x_rec)):
+            return None
+        if host_check:
+            _check_index_range(indices.reshape(-1))
+        rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
+        return _lib.step_record(x, x_rec, indices, rec, self._ws, self.n_metrics,
+                                None if self.n_codes is None else self.index_bits, self.n_codes)
 
     def pack_with_psnr(self, indices: torch.Tensor, x: torch.Tensor, x_rec: torch.Tensor) -> torch.Tensor:
         """pack(indices, psnr_zero_mean(x, x_rec)) for the one-metric layout.  On a HIP device: ONE launch of libgqhip
-        (gq_step_record_f32: the PSNR reduction and the uint16 packing in the same kernel) instead of the ~13 elementwise /
-        reduction kernels of the torch expressions; elsewhere exactly those expressions."""
-        if self.n_metrics == 1 and (self.n_codes is not None or not self.check_range) and indices.is_cuda:
-            from . import _lib
-
-            flat_n = indices.numel()
-            if flat_n != self.bs * self.tokens or x.shape[0] != self.bs:
-                raise ValueError(f"StepRecord.pack_with_psnr: got {flat_n} indices / {x.shape[0]} images, layout is "
-                                 f"{self.bs} x {self.tokens}")
-            if _lib.step_record_ok(x, x_rec, indices):
-                rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
-                if self.n_codes is not None:     # gq_step_record_bits_f32: the same PSNR words, the bit-packed indices, the violations word
-                    return _lib.step_record_bits(x, x_rec, indices, rec, self.index_bits, self.n_codes,
-                                                 self.__dict__.setdefault("_ws", {}))
-                return _lib.step_record(x, x_rec, indices, rec, self.__dict__.setdefault("_ws", {}))
-        return self.pack(indices, psnr_zero_mean(x, x_rec)[:, None])
+        (gq_step_record_f32 / gq_step_record_bits_f32: the PSNR reduction and the index packing in the same kernel) instead of
+        the ~13 elementwise / reduction kernels of the torch expressions; elsewhere exactly those expressions."""
+        rec = self._pack_on_device(indices, x, x_rec) if self.n_metrics == 1 else None
+        return rec if rec is not None else self.pack(indices, psnr_zero_mean(x, x_rec)[:, None])
 
     def pack_with_metrics(self, indices: torch.Tensor, x: torch.Tensor, x_rec: torch.Tensor) -> torch.Tensor:
         """pack(indices, metrics of (x, x_rec) with zero_mean) for the one-metric layout (PSNR: pack_with_psnr) or the
         three-metric one (PSNR, SSIM, MS-SSIM per image: eval.py:165-178).  Three metrics on a HIP device: ONE library call
-        (gq_step_record_ssim_f32, whose PSNR and index words are those of pack_with_psnr bit for bit); elsewhere, or for a
-        layout the kernels do not take, the torch expressions."""
+        (gq_step_record_ssim_f32 / gq_step_record_ssim_bits_f32, whose PSNR and index words are those of pack_with_psnr bit for
+        bit); elsewhere, or for a layout the kernels do not take, the torch expressions."""
         if self.n_metrics == 1:
             return self.pack_with_psnr(indices, x, x_rec)
         if self.n_metrics != 3:
             raise ValueError(f"StepRecord.pack_with_metrics: n_metrics is 1 (psnr) or 3 (psnr, ssim, ms_ssim), not {self.n_metrics}")
-        if indices.is_cuda:
-            from . import _lib
-
-            if indices.numel() != self.bs * self.tokens or x.shape[0] != self.bs:
-                raise ValueError(f"StepRecord.pack_with_metrics: got {indices.numel()} indices / {x.shape[0]} images, layout "
-                                 f"is {self.bs} x {self.tokens}")
-            x, x_rec = _dense_pair(x, x_rec)
-            if _lib.step_record_ok(x, x_rec, indices) and _lib.ssim_ok(x, x_rec):
-                if self.n_codes is not None:     # gq_step_record_ssim_bits_f32: no host read
-                    rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
-                    return _lib.step_record_ssim_bits(x, x_rec, indices, rec, self.index_bits, self.n_codes,
-                                                      self.__dict__.setdefault("_ws", {}))
-                if self.check_range:
-                    _check_index_range(indices.reshape(-1))
-                rec = torch.empty(self.words, dtype=torch.int32, device=indices.device)
-                return _lib.step_record_ssim(x, x_rec, indices, rec, self.__dict__.setdefault("_ws", {}))
+        rec = self._pack_on_device(indices, x, x_rec)
+        if rec is not None:
+            return rec
         ssim, ms = get_ssim_and_msssim(x, x_rec, zero_mean=True)
         return self.pack(indices, torch.stack([psnr_zero_mean(x, x_rec), ssim.to(torch.float32), ms.to(torch.float32)], 1))
 
     def unpack(self, rec: torch.Tensor):
-        """rec: int32 [..., words] -> (indices int64 [..., bs, tokens], metrics fp32 [..., bs, n_metrics])."""
+        """rec: int32 [..., words] -> (indices int64 [..., bs, tokens], metrics fp32 [..., bs, n_metrics]); gq_indices_unpack_bits
+        on a HIP device, unpack_index_bits elsewhere, both formats."""
         lead = rec.shape[:-1]
         metrics = rec[..., : self.metric_words].contiguous().view(torch.float32).reshape(*lead, self.bs, self.n_metrics)
-        if self.n_codes is not None:
-            count = self.bs * self.tokens
-            if rec.is_cuda:
-                from . import _lib
+        count = self.bs * self.tokens
+        if rec.is_cuda:
+            from . import _lib
 
-                flat = _lib.indices_unpack_bits(rec.reshape(-1, self.words), self.metric_words, count, self.index_bits)
-            else:
-                flat = unpack_index_bits(rec[..., self.metric_words: -1], count, self.index_bits)
-            return flat.reshape(*lead, self.bs, self.tokens), metrics
-        words = rec[..., self.metric_words:].to(torch.int64) & 0xFFFFFFFF
-        lo, hi = words & 0xFFFF, (words >> 16) & 0xFFFF
-        flat = torch.stack([lo, hi], dim=-1).reshape(*lead, -1)[..., : self.bs * self.tokens]
+            flat = _lib.indices_unpack_bits(rec.reshape(-1, self.words), self.metric_words, count, self.index_bits)
+        else:
+            flat = unpack_index_bits(rec[..., self.metric_words: self.metric_words + self.index_words], count, self.index_bits)
         return flat.reshape(*lead, self.bs, self.tokens), metrics
 
     def violations(self, rec: torch.Tensor) -> torch.Tensor:
