@@ -72,6 +72,84 @@ int main() {
                                    nullptr, buf, (double *)buf, 1, 16, 16, 16, 1024, 0, 1, -30.0, 20.0, 1.0, 1, 10.0, 0.5, 1.01, 1e-7, 1e7, 0,
                                    nullptr, 0, nullptr, 0, nullptr) != GQHIP_ERR_WORKSPACE;       // valid arguments, no workspace
   }
+  {
+    // the train steps: nothing to do with every pointer NULL, then refused shapes / alignments / workspaces behind non-NULL host
+    // addresses -- each must stop at a status before anything is launched or read
+    alignas(16) char buf[64];
+    float *f = (float *)buf, *f4 = (float *)(buf + 4);
+    int64_t *i8 = (int64_t *)buf;
+    const int32_t lev[17] = {8, 8, 8, 5, 5, 5, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2}, lev1[3] = {8, 1, 8}, lev4[16] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4};
+    const int64_t big = ((int64_t)1 << 30) + 1, many = (int64_t)1 << 40;
+    bad += gq_gauss_train_f32(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 16, 8, 0, 0, -30.0, 20.0, 12.0, 0.5, 1.01, 1e-7, 1e7,
+                              0, 144.0, nullptr) == GQHIP_OK;                                  // the pointers are checked before "nothing to do"
+    bad += gq_gauss_train_f32(f, f, f, nullptr, f, buf, (double *)buf, 0, 36, 16, 8, 0, 0, -30.0, 20.0, 12.0, 0.5, 1.01, 1e-7, 1e7, 0, 0.0,
+                              nullptr) != GQHIP_OK;                                            // empty batch
+    bad += gq_gauss_train_f32(f, f, f, nullptr, f, buf + 4, (double *)buf, 2, 36, 16, 8, 0, 0, -30.0, 20.0, 12.0, 0.5, 1.01, 1e-7, 1e7, 0, 144.0,
+                              nullptr) != GQHIP_ERR_INVALID_ARG;                               // scalars_out not 8-byte aligned
+    bad += gq_gauss_train_f32(f, f, f, nullptr, f, buf, (double *)buf, 2, 36, 16, 8, 0, 0, -30.0, 20.0, 12.0, 0.5, 1.01, 1e-7, 1e7, 0, 0.0,
+                              nullptr) != GQHIP_ERR_INVALID_ARG;                               // loss_divisor 0
+    bad += gq_gauss_train_f32(f, f, f, nullptr, f, buf, (double *)buf, big, big, 16, 8, 0, 0, -30.0, 20.0, 12.0, 0.5, 1.01, 1e-7, 1e7, 0, 1.0,
+                              nullptr) != GQHIP_ERR_INVALID_ARG;                               // rows beyond 2^30
+    bad += gq_gauss_backward_f32(f, f, nullptr, nullptr, nullptr, (const double *)buf, f, 0, 36, 16, 8, 1, 1, -30.0, 20.0, 12.0, 0.5, 144.0,
+                                 nullptr) != GQHIP_OK;
+    bad += gq_gauss_backward_f32(f, f, nullptr, nullptr, (const float *)(buf + 2), (const double *)buf, f, 2, 36, 16, 8, 1, 1, -30.0, 20.0, 12.0, 0.5,
+                                 144.0, nullptr) != GQHIP_ERR_INVALID_ARG;                     // g_kl not 4-byte aligned
+    bad += gq_gauss_backward_f32(f, f, nullptr, nullptr, nullptr, (const double *)buf, f, 2, 0, 16, 8, 1, 1, -30.0, 20.0, 12.0, 0.5, 144.0,
+                                 nullptr) != GQHIP_ERR_INVALID_ARG;                            // L = 0
+    bad += vq_backward_workspace_bytes(0x3fffffff, 0x7fffffff, 64) <= 0 || vq_backward_workspace_bytes(many, 1024, 8) != -1 ||
+           vq_backward_workspace_bytes(4096, 1024, 65) != -1;
+    bad += vq_backward_f32(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 16, 8, 1024, 0, 0.25, 1, nullptr, 0, nullptr) == GQHIP_OK;
+    bad += vq_backward_f32(f, f, i8, nullptr, nullptr, nullptr, nullptr, 0, 36, 16, 8, 1024, 0, 0.25, 1, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += vq_backward_f32(f, f, i8, nullptr, nullptr, f, nullptr, 2, 36, 16, 8, 1024, 0, 0.25, 1, nullptr, 0, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += vq_backward_f32(f, f, i8, nullptr, nullptr, f, nullptr, 2, 36, 16, 8, 1024, 0, 0.25, 1, buf + 8, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += vq_backward_f32(f, f, i8, nullptr, nullptr, f, nullptr, 2, 36, 16, 8, (int64_t)1 << 31, 0, 0.25, 1, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += vq_backward_f32(f, f, i8, nullptr, nullptr, f, nullptr, big, big, 16, 8, 1024, 0, 0.25, 1, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += lfq_train_workspace_bytes(0x3fffffff, 16) <= 0 || lfq_train_workspace_bytes(many, 8) != -1 || lfq_train_workspace_bytes(4096, 17) != -1;
+    bad += lfq_train_f32(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, 0, nullptr) == GQHIP_OK;
+    bad += lfq_train_f32(f, f, i8, f, f, 0, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 0, 16, 2, 8, 1, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, many, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, buf + 8, many, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, buf, 0, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += lfq_train_f32(f, f, i8, (float *)(buf + 2), f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 36, 63, 9, 7, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;   // 63 bits
+    bad += lfq_train_f32(f, f, i8, f, f, 2, 36, 17, 1, 17, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;  // d past its limit
+    bad += lfq_train_f32(f, f, i8, f, f, 1 << 15, 1 << 14, 3, 3, 1, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;   // B L nc beyond 2^30
+    bad += lfq_train_f32(f, f, i8, f, f, big, big, 16, 2, 8, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += lfq_backward_f32(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, 0, nullptr) == GQHIP_OK;
+    bad += lfq_backward_f32(f, f, nullptr, nullptr, nullptr, f, 0, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += lfq_backward_f32(f, f, nullptr, nullptr, nullptr, f, 2, 36, 16, 2, 8, 2, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;  // layout
+    bad += lfq_backward_f32(f, f, nullptr, nullptr, (const float *)(buf + 2), f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += lfq_backward_f32(f, f, nullptr, nullptr, nullptr, f, 2, 36, 16, 2, 8, 0, 1.f, 1.f, nullptr, many, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += bsq_train_workspace_bytes(0x3fffffff, 16) <= 0 || bsq_train_workspace_bytes(many, 2) != -1 || bsq_train_workspace_bytes(4096, 17) != -1;
+    bad += bsq_train_f32(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 32, 2, 0, 1.f, 1.f, nullptr, 0, nullptr) == GQHIP_OK;
+    bad += bsq_train_f32(f, f, i8, f, f, 0, 36, 32, 2, 0, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += bsq_train_f32(f4, f, i8, f, f, 2, 36, 32, 2, 0, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_ERR_WORKSPACE;       // "bchw": 4-byte rows will do
+    bad += bsq_train_f32(f4, f, i8, f, f, 2, 36, 32, 2, 1, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;      // "blc": 16-byte rows
+    bad += bsq_train_f32(f, f, (int64_t *)(buf + 4), f, f, 2, 36, 32, 2, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += bsq_train_f32(f, f, i8, f, f, 2, 36, 31, 2, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += bsq_train_f32(f, f, i8, f, f, 2, 36, 272, 17, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += bsq_train_f32(f, f, i8, f, f, big, big, 32, 2, 0, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += bsq_backward_f32(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 36, 32, 2, 0, 1.f, 1.f, nullptr, 0, nullptr) == GQHIP_OK;
+    bad += bsq_backward_f32(f, f, nullptr, nullptr, f, 2, 0, 32, 2, 1, 1.f, 1.f, nullptr, 0, nullptr) != GQHIP_OK;
+    bad += bsq_backward_f32(f, f, f4, nullptr, f, 2, 36, 32, 2, 1, 1.f, 1.f, buf, many, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += bsq_backward_f32(f, f, nullptr, nullptr, f, 2, 36, 32, 2, 0, 1.f, 1.f, buf + 8, many, nullptr) != GQHIP_ERR_WORKSPACE;
+    bad += fsq_train_f32(nullptr, nullptr, 6, nullptr, nullptr, 0, 36, 0, nullptr) == GQHIP_OK;
+    bad += fsq_train_f32(f, lev, 6, f, (int32_t *)buf, 0, 36, 0, nullptr) != GQHIP_OK;
+    bad += fsq_train_f32(f, lev, 6, f, (int32_t *)buf, 2, 0, 1, nullptr) != GQHIP_OK;
+    bad += fsq_train_f32(f, nullptr, 6, f, (int32_t *)buf, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_train_f32(f, lev, 0, f, (int32_t *)buf, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_train_f32(f, lev, 17, f, (int32_t *)buf, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_train_f32(f, lev1, 3, f, (int32_t *)buf, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;                    // a level of 1
+    bad += fsq_train_f32(f, lev4, 16, f, (int32_t *)buf, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;                   // 2^32 codes
+    bad += fsq_train_f32(f, lev, 6, f, (int32_t *)(buf + 2), 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_train_f32(f, lev, 6, f, (int32_t *)buf, big, big, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_backward_f32(nullptr, nullptr, nullptr, 6, nullptr, 0, 36, 0, nullptr) == GQHIP_OK;
+    bad += fsq_backward_f32(f, f, lev, 6, f, 0, 36, 0, nullptr) != GQHIP_OK;
+    bad += fsq_backward_f32(f, f, lev, 6, f, 2, 36, 2, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_backward_f32(f, f, lev4, 16, f, 2, 36, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+    bad += fsq_backward_f32(f, f, lev, 6, f, 1 << 15, 1 << 15, 0, nullptr) != GQHIP_ERR_INVALID_ARG;
+  }
   bad += gqhip_cb_cache_degenerate(nullptr, 65536, 4) != -1;
   bad += lfq_pack_f32(nullptr, nullptr, nullptr, 4, 16, nullptr) == GQHIP_OK;
   bad += lfq_pack_f32(nullptr, nullptr, nullptr, 4, 63, nullptr) == GQHIP_OK;

@@ -382,6 +382,182 @@ def test_record_cabi_status_table():
     assert ["gq_step_record_ssim_f32", "B=0", 1] in got and ["gq_step_record_f32", "B*chunks=2^31/ws/short", 2] in got
 
 
+_NC_D = [dict(C=15), dict(nc=9, d=7, C=63), dict(nc=31, d=2, C=62), dict(nc=0, C=0)]
+_VQ_N = [dict(n=0), dict(n=1), dict(n=1 << 31)]
+_TRAIN_ENTRIES = {       # entry point: (argument names, valid scalars, its size function as (name, arguments) or None, perturbations)
+    "gq_gauss_train_f32": ("z noise zhat sd_out kl2row scalars_out lam_state B L c dim layout grouping lv_min lv_max log2n tolerance "
+                           "lam_factor lam_lo lam_hi lam_max_decreases loss_divisor stream",
+                           dict(B=2, L=36, c=16, dim=8, layout=0, grouping=0, lv_min=-30.0, lv_max=20.0, log2n=12.0, tolerance=0.5,
+                                lam_factor=1.01, lam_lo=1e-7, lam_hi=1e7, lam_max_decreases=0, loss_divisor=144.0), None, []),
+    "gq_gauss_backward_f32": ("z noise g_zhat g_sd g_kl lam_before grad_z B L c dim layout grouping lv_min lv_max log2n tolerance "
+                              "loss_divisor stream",
+                              dict(B=2, L=36, c=16, dim=8, layout=0, grouping=0, lv_min=-30.0, lv_max=20.0, log2n=12.0, tolerance=0.5,
+                                   loss_divisor=144.0), None, []),
+    "vq_quantize_z_f32": ("z emb idx zq loss2 B L c dim n layout beta legacy workspace workspace_bytes cb_cache cb_cache_bytes stream",
+                          dict(B=2, L=36, c=16, dim=8, n=1024, layout=0, beta=0.25, legacy=1, cb_cache_bytes=0),
+                          ("gqhip_workspace_bytes", "rows n dim"), _VQ_N + [dict(n=1 << 30), dict(legacy=0)]),
+    "vq_backward_f32": ("z emb idx g_zq g_loss grad_z grad_emb B L c dim n layout beta legacy workspace workspace_bytes stream",
+                        dict(B=2, L=36, c=16, dim=8, n=1024, layout=0, beta=0.25, legacy=1),
+                        ("vq_backward_workspace_bytes", "rows n dim"),
+                        _VQ_N + [dict(legacy=0), dict(grad_z=None, grad_emb=None), dict(g_loss=None, grad_emb=None),
+                                 dict(B=0, grad_emb=None), dict(L=0, grad_emb=None)]),
+    "lfq_train_f32": ("x quantized idx avg scalars B L C nc d layout w_s w_b workspace workspace_bytes stream",
+                      dict(B=2, L=36, C=16, nc=2, d=8, layout=0, w_s=1.0, w_b=1.0), ("lfq_train_workspace_bytes", "rows d"),
+                      _NC_D + [dict(B=1 << 15, L=1 << 14, nc=2, d=1, C=2), dict(B=1 << 15, L=1 << 14, nc=3, d=1, C=3)]),
+    "lfq_backward_f32": ("x avg g_q g_aux g_commit grad_x B L C nc d layout w_s w_b workspace workspace_bytes stream",
+                         dict(B=2, L=36, C=16, nc=2, d=8, layout=0, w_s=1.0, w_b=1.0), ("lfq_train_workspace_bytes", "rows d"),
+                         _NC_D + [dict(B=1 << 15, L=1 << 14, nc=2, d=1, C=2), dict(B=1 << 15, L=1 << 14, nc=3, d=1, C=3),
+                                  dict(d=16, nc=1, C=16), dict(d=5, nc=1, C=5), dict(d=12, nc=1, C=12)]),
+    "bsq_train_f32": ("x quantized idx avg scalars B L C d layout w_s w_b workspace workspace_bytes stream",
+                      dict(B=2, L=36, C=32, d=2, layout=0, w_s=1.0, w_b=1.0), ("bsq_train_workspace_bytes", "rows d"),
+                      [dict(C=31), dict(C=16), dict(C=2)]),
+    "bsq_backward_f32": ("x avg g_q g_aux grad_x B L C d layout w_s w_b workspace workspace_bytes stream",
+                         dict(B=2, L=36, C=32, d=2, layout=0, w_s=1.0, w_b=1.0), ("bsq_train_workspace_bytes", "rows d"),
+                         [dict(C=31), dict(C=16), dict(C=2)]),
+    "fsq_train_f32": ("z levels_host nlev zhat idx B L layout stream", dict(B=2, L=36, layout=0), None, []),
+    "fsq_backward_f32": ("z g_zhat levels_host nlev grad_z B L layout stream", dict(B=2, L=36, layout=0), None,
+                         [dict(B=1 << 14, L=1 << 14, levels=[2] * 16), dict(B=1 << 15, L=1 << 14, levels=[2] * 16)]),
+}
+_TRAIN_SIZES = {         # size function: four valid shapes, then refused ones
+    "vq_backward_workspace_bytes": ((1, 1, 1), (4096, 1024, 8), (0, 65536, 64), (0x3fffffff, 0x7fffffff, 64),
+                                    (-1, 1024, 8), (1 << 30, 1024, 8), (4096, 0, 8), (4096, 1 << 31, 8), (4096, 1024, 0), (4096, 1024, 65)),
+    "lfq_train_workspace_bytes": ((1, 1), (4096, 8), (0, 16), (0x3fffffff, 16), (-1, 8), (1 << 30, 8), (4096, 0), (4096, 17)),
+    "bsq_train_workspace_bytes": ((1, 1), (4096, 2), (0, 16), (0x3fffffff, 16), (-1, 2), (1 << 30, 2), (4096, 0), (4096, 17)),
+}
+
+
+def _train_cabi_table(lib, signatures):
+    """[entry or size function, case id, status or byte count] over the families of test_train_cabi_status_table; ``lib``: a
+    loaded libgqhip with the ``signatures`` (pit_hip._lib._SIGNATURES) set."""
+    fake, ample = 0x10000, 1 << 62          # the pointers are never dereferenced: see the test's docstring
+    rows = []
+    for entry, (names, base, size, perturbations) in _TRAIN_ENTRIES.items():
+        names = names.split()
+        argtypes = signatures[entry][1]
+        assert len(names) == len(argtypes), entry
+        ptrs = [n for n, t in zip(names, argtypes) if t is ctypes.c_void_p and n != "stream"]
+        has_ws, fsq = "workspace" in ptrs, "levels_host" in names
+        fn = getattr(lib, entry)
+
+        def need_of(v):
+            """the workspace the call of these scalars wants, by the entry point's own size function"""
+            if not size:
+                return 0
+            K = v["c"] // v["dim"] if "c" in v and v["dim"] > 0 else v.get("nc", 1)
+            shape = dict(v, rows=v["B"] * v["L"] * K)
+            return getattr(lib, size[0])(*[shape[a] for a in size[1].split()])
+
+        def case(cid, nulls=(), off=None, ws_bytes=ample, levels=(8, 8, 8, 5, 5, 5), nlev=None, **scalars):
+            vals = dict(base, **{p: (None if p in nulls else fake + (off or {}).get(p, 0)) for p in ptrs}, stream=None)
+            if "cb_cache" in vals:
+                vals["cb_cache"] = None
+            assert set(scalars) <= set(vals), scalars
+            vals.update(scalars)
+            if has_ws:
+                vals["workspace_bytes"] = ws_bytes(need_of(vals)) if callable(ws_bytes) else ws_bytes
+            if fsq:                         # read on the host: a real array (17 elements, so that every nlev asked for is backed)
+                vals["levels_host"] = None if levels is None else (ctypes.c_int32 * 17)(*(list(levels) + [2] * (17 - len(levels))))
+                vals["nlev"] = len(levels or ()) if nlev is None else nlev
+            rows.append([entry, cid, fn(*[vals[n] for n in names])])
+
+        def ident(p):
+            return ",".join("%s=%r" % kv for kv in p.items())
+
+        case("base")
+        case("nothing/null", ptrs, None, 0, B=0)
+        case("nothing/fake", B=0)
+        case("all/null", ptrs)
+        for p in ptrs:
+            if p not in ("workspace", "cb_cache"):
+                case("null:" + p, (p,))
+        for layout in (0, 1):               # the masks 3 / 7 / 15, per layout (BSQ's "blc" rows move 16 bytes at a time)
+            for p in ptrs:
+                if p not in ("workspace", "cb_cache"):
+                    for off in (2, 4, 8):
+                        case("layout=%d/%s+%d" % (layout, p, off), (), {p: off}, layout=layout)
+        if has_ws:
+            case("ws/null", ("workspace",), None, lambda need: need)
+            case("ws/short", (), None, lambda need: need - 1)
+            case("ws/exact", (), None, lambda need: need)
+            case("ws/+8", (), {"workspace": 8})
+            case("ws/+8/short", (), {"workspace": 8}, lambda need: need - 1)
+            case("ws/null/+pointer", ("workspace",), {ptrs[0]: 2}, lambda need: need)
+            case("B=0/ws/null", ("workspace",), None, 0, B=0)
+            case("L=0/ws/null", ("workspace",), None, 0, L=0)
+        for B in (-1, 0, 1, (1 << 30) + 1):
+            case("B=%d" % B, B=B)
+        for L in (-1, 0, 1, (1 << 30) + 1):
+            case("L=%d" % L, L=L)
+        case("B=0/L=2^30+1", B=0, L=(1 << 30) + 1)      # refused, or nothing to do: the Gaussian and VQ steps bound the rows later
+        case("B=2^30+1/L=0", B=(1 << 30) + 1, L=0)
+        case("B*L=2^30", B=1 << 15, L=1 << 15)
+        case("B*L=2^30-2^15", B=(1 << 15) - 1, L=1 << 15)
+        case("B*L=2^30/ws/short", (), None, 0, B=1 << 15, L=1 << 15)
+        for layout in (0, 1, 2, -1):
+            case("layout=%d" % layout, layout=layout)
+        if "grouping" in names:
+            for grouping in (0, 1, 2, -1):
+                case("grouping=%d" % grouping, grouping=grouping)
+                case("layout=1/grouping=%d" % grouping, layout=1, grouping=grouping)
+        if "dim" in names:
+            for dim in (0, 1, 64, 65):
+                case("dim=%d" % dim, dim=dim, c=2 * max(dim, 1))
+            for c in (0, 12, 17):
+                case("c=%d" % c, c=c)
+        if "d" in names:
+            for d in (0, 1, 16, 17):
+                case("d=%d" % d, d=d, C=d * (1 if "nc" in names else 16), **({"nc": 1} if "nc" in names else {}))
+        if "loss_divisor" in names:
+            for v in (0.0, -1.0, _NAN):
+                case("loss_divisor=%r" % v, loss_divisor=v)
+            case("B=0/loss_divisor=0.0", B=0, loss_divisor=0.0)
+        if fsq:
+            case("levels/null", levels=None, nlev=6)
+            for nlev in (0, 1, 16, 17):
+                case("nlev=%d" % nlev, levels=[2] * 16, nlev=nlev)
+            case("level=1", levels=[8, 1, 8])
+            case("product=2^31-2^16", levels=[65536, 32767])
+            case("product=2^31", levels=[65536, 32768])
+            case("product=2^32", levels=[4] * 16)
+            case("B=0/levels/null", levels=None, nlev=6, B=0)
+        for p in perturbations:
+            p = dict(p)
+            nulls = tuple(k for k in ptrs if k in p and p.pop(k, 0) is None)
+            case(ident(dict(p, **{k: None for k in nulls})), nulls, **p)
+    for size_name, shapes in _TRAIN_SIZES.items():
+        for args in shapes:
+            rows.append([size_name, "x".join(map(str, args)), getattr(lib, size_name)(*args)])
+    return rows
+
+
+def test_train_cabi_status_table():
+    """The nine train-step entry points of csrc/gqhip.hip and vq_quantize_z_f32 return the status, and the three train workspace
+    size functions the byte count, that tests/golden/train_cabi_status.json records (recorded with this generator from the library
+    as it was before the train steps' host checks, workspace rule and launch chain were brought together): nothing to do with all
+    pointers NULL or set, each pointer NULL in turn (the optional ones too), each pointer off its alignment by 2, 4 and 8 bytes in
+    either layout (the masks 3, 7 and 15), the workspace NULL / one byte short / exact / misaligned, and each shape, layout,
+    grouping, width, codebook-size, divisor and level argument at and past its limits in turn.  Without a device an entry point that
+    gets past its checks returns 3 ("kernel launch failed": no device) and launches nothing, so 0 / 1 / 2 / 3 tell "empty",
+    "refused", "workspace" and "would launch" apart -- the ORDER of the checks included.
+    SAFETY: the pointers passed are made up (all but FSQ's levels, which the host reads: a real array).  They are never
+    dereferenced only because nothing can launch, so this test must never run where a HIP device is present: it skips there,
+    whatever else is asked of it."""
+    if torch.cuda.is_available():
+        pytest.skip("passes made-up pointers: safe only where no kernel can launch")
+    L = _lib()
+    got = _train_cabi_table(L.lib(), L._SIGNATURES)
+    want = json.load(open(os.path.join(G, "train_cabi_status.json")))
+    assert len(got) == len(want) > 300 and {e for e, _, _ in got} == set(_TRAIN_ENTRIES) | set(_TRAIN_SIZES)
+    assert len(_TRAIN_ENTRIES) == 10 and {s for e, _, s in got if e in _TRAIN_ENTRIES} == {0, 1, 2, 3}
+    diff = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not diff, diff[:20]
+    # a few of the rules, spelled out: vq_backward_f32 alone calls a misaligned workspace an invalid argument, before it looks at its
+    # size; "blc" BSQ rows want 16-byte pointers; an empty batch asks for no workspace
+    assert ["vq_backward_f32", "ws/+8/short", 1] in got and ["lfq_train_f32", "ws/+8/short", 2] in got
+    assert ["bsq_train_f32", "layout=1/x+8", 1] in got and ["bsq_train_f32", "layout=0/x+8", 3] in got
+    assert ["lfq_train_f32", "B=0/ws/null", 0] in got and ["gq_gauss_train_f32", "L=0", 1] in got and ["fsq_train_f32", "L=0", 0] in got
+
+
 def test_no_cpu_fallback():
     L = _lib()
     mu = torch.zeros(4, 16)

@@ -643,7 +643,40 @@ bool z_geometry(int64_t B, int64_t L, int64_t c, int64_t dim, int layout, int gr
   g->om.K = (int)g->K; g->om.L = (int)L; g->om.c = (int)c; g->om.grouping = grouping;
   return true;
 }
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+// ---- the host vocabulary of the train steps: alignment, geometry, workspace rule, workspace carving, launch chain ----
+// every pointer given is NULL or aligned to `mask` + 1 bytes
+template <class... P>
+bool aligned(unsigned mask, const P *...p) { return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & mask) == 0; }
+// g->P positions, g->L of them per image, g->mode 1 = "bchw" / 2 = "blc"; false: a negative size, an unknown layout, or B, L, B L or B L
+// `per_position` beyond 2^30 - 1.  (Not under z_geometry: that wants L >= 1 and leaves the bound to its callers, behind their "nothing to do".)
+template <class G>
+bool train_geometry(int64_t B, int64_t L, int layout, int64_t per_position, G *g) {
+  const int64_t lim = 0x3fffffff;
+  if (B < 0 || L < 0 || B > lim || L > lim || B * L > lim || B * L * per_position > lim) return false;
+  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return false;
+  g->P = (long)(B * L); g->L = (long)L; g->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  return true;
+}
+// the one workspace rule: there, 16-byte aligned, and of at least `need` bytes
+int workspace_status(const void *ws, int64_t bytes, int64_t need) {
+  return ws && aligned(15u, ws) && bytes >= need ? GQHIP_OK : GQHIP_ERR_WORKSPACE;
+}
+struct Carve {   // a workspace handed out front to back in 256-byte steps: take() is where the next block starts, `off` the bytes taken so far
+  int64_t off = 0;
+  int64_t take(int64_t bytes) { const int64_t at = off; off += align256(bytes); return at; }
+};
+template <class T>
+T *at(void *workspace, int64_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }   // ... and the block taken at `off`
+struct Chain {   // launches on one stream, in order, through launch() (gqhip_internal.h): `rc` is the first failing status, nothing is launched after it
+  hipStream_t st;
+  int rc = GQHIP_OK;
+  explicit Chain(void *stream) : st(static_cast<hipStream_t>(stream)) {}
+  template <class... P, class... A>
+  Chain &run(void (*kernel)(P...), dim3 grid, dim3 block, A &&...args) {
+    if (rc == GQHIP_OK) rc = launch(kernel, grid, block, 0, st, static_cast<A &&>(args)...);
+    return *this;
+  }
+};
 
 // the statistics block's parameters (gq_gauss.h); `kl2row` may be filled in later
 GaussStatsParams gauss_stats_params(const float *kl2row, int64_t rows, double *lam_state, void *scalars, double log2n, double tolerance,
@@ -815,7 +848,7 @@ int gq_quantize_z_gauss_f32(const float *z, const float *noise, const float *cb,
   if (!z || !noise || !cb || !idx || !zhat || !zhat_noquant || !scalars_out || !lam_state ||
       !z_geometry(B, L, c, dim, layout, grouping, &g))
     return GQHIP_ERR_INVALID_ARG;
-  if (!aligned8(scalars_out) || !aligned8(lam_state)) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned(7u, scalars_out, lam_state)) return GQHIP_ERR_INVALID_ARG;
   if (g.rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
   if (g.rows > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -863,12 +896,11 @@ int gq_gauss_train_f32(const float *z, const float *noise, float *zhat, float *s
                        double lv_max, double log2n, double tolerance, double lam_factor, double lam_lo, double lam_hi,
                        int lam_max_decreases, double loss_divisor, void *stream) {
   ZGeom g;
-  if (!z || !noise || !zhat || !kl2row || !scalars_out || !lam_state || !z_geometry(B, L, c, dim, layout, grouping, &g))
+  if (!z || !noise || !zhat || !kl2row || !scalars_out || !lam_state || !aligned(7u, scalars_out, lam_state) ||
+      !z_geometry(B, L, c, dim, layout, grouping, &g))
     return GQHIP_ERR_INVALID_ARG;
-  if (!aligned8(scalars_out) || !aligned8(lam_state)) return GQHIP_ERR_INVALID_ARG;
   if (g.rows == 0) return GQHIP_OK;      // (the reference's means of an empty tensor are NaN; nothing is written here)
   if (g.rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   GaussTrainParams p{};
   p.z = z; p.noise = noise; p.zhat = zhat; p.sd_out = sd_out_or_null; p.kl2row = kl2row;
   p.lv_min = (float)lv_min; p.lv_max = (float)lv_max;
@@ -877,11 +909,9 @@ int gq_gauss_train_f32(const float *z, const float *noise, float *zhat, float *s
   const int variant = train_variant(layout, grouping, dim, g.K, L, bits(z) | bits(noise) | bits(zhat) | bits(sd_out_or_null),
                                     (long)g.rows, &p.items);
   const auto fwd = variant == 1 ? gauss_train_fwd_kernel<4, false> : variant == 2 ? gauss_train_fwd_kernel<4, true> : gauss_train_fwd_kernel<1, false>;
-  const int rc = launch(fwd, dim3(train_grid(p.items)), dim3(256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
-  return launch(gauss_stats_finalize_kernel, dim3(1), dim3(256), 0, st,      // the second launch: same stream, in order
-                gauss_stats_params(kl2row, g.rows, lam_state, scalars_out, log2n, tolerance, lam_factor, lam_lo, lam_hi,
-                                   lam_max_decreases, loss_divisor));
+  return Chain(stream).run(fwd, dim3(train_grid(p.items)), dim3(256), p)       // then, on the same stream, the statistics block
+      .run(gauss_stats_finalize_kernel, dim3(1), dim3(256), gauss_stats_params(kl2row, g.rows, lam_state, scalars_out, log2n, tolerance,
+                                                                              lam_factor, lam_lo, lam_hi, lam_max_decreases, loss_divisor)).rc;
 }
 
 int gq_gauss_backward_f32(const float *z, const float *noise, const float *g_zhat_or_null, const float *g_sd_or_null,
@@ -889,8 +919,9 @@ int gq_gauss_backward_f32(const float *z, const float *noise, const float *g_zha
                           int64_t dim, int layout, int grouping, double lv_min, double lv_max, double log2n, double tolerance,
                           double loss_divisor, void *stream) {
   ZGeom g;
-  if (!z || !noise || !lam_before || !grad_z || !z_geometry(B, L, c, dim, layout, grouping, &g)) return GQHIP_ERR_INVALID_ARG;
-  if (!aligned8(lam_before) || (bits(g_kl_or_null) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (!z || !noise || !lam_before || !grad_z || !aligned(7u, lam_before) || !aligned(3u, g_kl_or_null) ||
+      !z_geometry(B, L, c, dim, layout, grouping, &g))
+    return GQHIP_ERR_INVALID_ARG;
   if (g.rows == 0) return GQHIP_OK;
   if (g.rows > 0x3fffffff || !(loss_divisor > 0.0)) return GQHIP_ERR_INVALID_ARG;
   GaussTrainParams p{};
@@ -943,15 +974,15 @@ static bool vq_backward_layout(int64_t items, int64_t n, int64_t dim, VqBwdLayou
   while (((int64_t)1 << bits) < n) ++bits;
   w->passes = bits <= 8 ? 1 : (bits + 7) / 8;
   w->tiles = (int)((items + kVqSortTile - 1) / kVqSortTile);
-  int64_t off = 0;
+  Carve ws;
   for (int i = 0; i < 2; ++i) {
-    w->keys[i] = off; off += align256(items * 4);
-    w->vals[i] = off; off += align256(items * 4);
+    w->keys[i] = ws.take(items * 4);
+    w->vals[i] = ws.take(items * 4);
   }
-  w->table = off;   off += align256((int64_t)256 * w->tiles * 4);
-  w->partial = off; off += align256(2 * ((items + kVqChunk - 1) / kVqChunk) * dim * 8);
-  w->flag = off;    off += 256;
-  w->total = off;
+  w->table = ws.take((int64_t)256 * w->tiles * 4);
+  w->partial = ws.take(2 * ((items + kVqChunk - 1) / kVqChunk) * dim * 8);
+  w->flag = ws.take(256);
+  w->total = ws.off;
   return true;
 }
 }  // namespace
@@ -967,45 +998,40 @@ int vq_backward_f32(const float *z, const float *emb, const int64_t *idx, const 
   ZGeom g;
   VqBwdLayout w;
   if (!z || !emb || !idx || !z_geometry(B, L, c, dim, layout, GQHIP_GROUP_STRIDED, &g)) return GQHIP_ERR_INVALID_ARG;
-  if (!vq_backward_layout(g.rows, n, dim, &w) || (bits(g_loss_or_null) & 3u) || (bits(workspace) & 15u)) return GQHIP_ERR_INVALID_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (g.rows > 0 && (!workspace || workspace_bytes < w.total)) return GQHIP_ERR_WORKSPACE;
-  if (grad_emb_or_null && hipMemsetAsync(grad_emb_or_null, 0, sizeof(float) * n * dim, st) != hipSuccess) return check_launch();
+  // the odd one among the train steps: a misaligned workspace is an invalid argument here, and is looked at before the workspace's size
+  if (!vq_backward_layout(g.rows, n, dim, &w) || !aligned(3u, g_loss_or_null) || !aligned(15u, workspace)) return GQHIP_ERR_INVALID_ARG;
+  Chain ch(stream);
+  if (g.rows > 0 && workspace_status(workspace, workspace_bytes, w.total) != GQHIP_OK) return GQHIP_ERR_WORKSPACE;
+  if (grad_emb_or_null && hipMemsetAsync(grad_emb_or_null, 0, sizeof(float) * n * dim, ch.st) != hipSuccess) return check_launch();
   if (g.rows == 0) return GQHIP_OK;
-  char *ws = static_cast<char *>(workspace);
   const int last = (w.passes - 1) & 1;                           // pass i writes buffer pair i & 1
   VqBwdParams p{};
   p.z = z; p.emb = emb; p.idx = idx; p.g_zq = g_zq_or_null; p.g_loss = g_loss_or_null;
   p.grad_z = grad_z_or_null; p.grad_emb = grad_emb_or_null;
-  p.keys = reinterpret_cast<const unsigned *>(ws + w.keys[last]); p.vals = reinterpret_cast<const unsigned *>(ws + w.vals[last]);
-  p.partial = reinterpret_cast<double *>(ws + w.partial); p.flag = reinterpret_cast<int *>(ws + w.flag);
+  p.keys = at<const unsigned>(workspace, w.keys[last]); p.vals = at<const unsigned>(workspace, w.vals[last]);
+  p.partial = at<double>(workspace, w.partial); p.flag = at<int>(workspace, w.flag);
   p.items = (long)g.rows; p.total = (long)(B * L * c);
   p.cz = (legacy ? 1.0 : beta) * 2.0 / (double)p.total; p.ce = (legacy ? beta : 1.0) * 2.0 / (double)p.total;
   p.dim = (int)dim; p.n = (int)n; p.omap = g.om;
   if (grad_z_or_null) {
     const bool wide = ((bits(z) | bits(g_zq_or_null) | bits(grad_z_or_null)) & 15u) == 0 && (layout == GQHIP_LAYOUT_BCHW ? L : c) % 4 == 0;
     const long threads = wide ? p.total / 4 : p.total;
-    const int rc = launch(wide ? vq_grad_z_kernel<4> : vq_grad_z_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p);
-    if (rc != GQHIP_OK) return rc;
+    ch.run(wide ? vq_grad_z_kernel<4> : vq_grad_z_kernel<1>, dim3((unsigned)((threads + 255) / 256)), dim3(256), p);
   }
-  if (!grad_emb_or_null || !g_loss_or_null) return GQHIP_OK;    // no gradient arrives at the loss: grad_emb stays the zeros above
+  if (!grad_emb_or_null || !g_loss_or_null) return ch.rc;       // no gradient arrives at the loss: grad_emb stays the zeros above
   VqSortParams sp{};
-  sp.idx = idx; sp.table = reinterpret_cast<int *>(ws + w.table); sp.flag = p.flag;
+  sp.idx = idx; sp.table = at<int>(workspace, w.table); sp.flag = p.flag;
   sp.items = p.items; sp.tiles = w.tiles; sp.n = p.n; sp.omap = g.om;
   for (int pass = 0; pass < w.passes; ++pass) {
     sp.first = pass == 0; sp.shift = 8 * pass;
-    sp.keys_in = reinterpret_cast<const unsigned *>(ws + w.keys[(pass + 1) & 1]); sp.vals_in = reinterpret_cast<const unsigned *>(ws + w.vals[(pass + 1) & 1]);
-    sp.keys_out = reinterpret_cast<unsigned *>(ws + w.keys[pass & 1]); sp.vals_out = reinterpret_cast<unsigned *>(ws + w.vals[pass & 1]);
-    int rc = launch(vq_sort_count_kernel, dim3((unsigned)w.tiles), dim3(64), 0, st, sp);
-    if (rc == GQHIP_OK) rc = launch(vq_sort_scan_kernel, dim3(1), dim3(1024), 0, st, sp.table, (long)256 * w.tiles);
-    if (rc == GQHIP_OK) rc = launch(vq_sort_place_kernel, dim3((unsigned)w.tiles), dim3(64), 0, st, sp);
-    if (rc != GQHIP_OK) return rc;
+    sp.keys_in = at<const unsigned>(workspace, w.keys[(pass + 1) & 1]); sp.vals_in = at<const unsigned>(workspace, w.vals[(pass + 1) & 1]);
+    sp.keys_out = at<unsigned>(workspace, w.keys[pass & 1]); sp.vals_out = at<unsigned>(workspace, w.vals[pass & 1]);
+    ch.run(vq_sort_count_kernel, dim3((unsigned)w.tiles), dim3(64), sp)
+        .run(vq_sort_scan_kernel, dim3(1), dim3(1024), sp.table, (long)256 * w.tiles)
+        .run(vq_sort_place_kernel, dim3((unsigned)w.tiles), dim3(64), sp);
   }
-  const int64_t blocks = (g.rows * dim + 255) / 256;
-  if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
-  const int rc = launch(vq_emb_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
-  return launch(vq_emb_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
+  const dim3 blocks((unsigned)((g.rows * dim + 255) / 256));      // rows < 2^30 and dim <= 64: at most 2^28
+  return ch.run(vq_emb_sum_kernel, blocks, dim3(256), p).run(vq_emb_combine_kernel, blocks, dim3(256), p).rc;
 }
 
 // ---- LFQQuantizer's train step (lfq_train.h) ----
@@ -1024,23 +1050,20 @@ static bool lfq_layout(int64_t rows, int64_t d, LfqLayout *w) {
   w->chunks = (int)((rows + kLfqChunk - 1) / kLfqChunk);
   w->elem_blocks = (int)((rows + 255) / 256);                    // positions <= rows
   w->avg_blocks = (int)((((int64_t)1 << d) + 255) / 256);
-  int64_t off = 0;
-  w->elem_part = off; off += align256((int64_t)w->elem_blocks * 16);
-  w->part = off;      off += align256((int64_t)w->chunks * w->Mpad * w->Npad * 4);
-  w->ent_part = off;  off += align256((int64_t)w->avg_blocks * 8);
-  w->G = off;         off += align256(((int64_t)4) << d);
-  w->GT = off;        off += align256(((int64_t)4) << d);
-  w->total = off;
+  Carve ws;
+  w->elem_part = ws.take((int64_t)w->elem_blocks * 16);
+  w->part = ws.take((int64_t)w->chunks * w->Mpad * w->Npad * 4);
+  w->ent_part = ws.take((int64_t)w->avg_blocks * 8);
+  w->G = ws.take(((int64_t)4) << d);
+  w->GT = ws.take(((int64_t)4) << d);
+  w->total = ws.off;
   return true;
 }
-static bool lfq_geometry(int64_t B, int64_t L, int64_t C, int64_t nc, int64_t d, int layout, LfqGeom *g) {
-  if (B < 0 || L < 0 || nc < 1 || d < 1 || d > kLfqMaxD || nc * d > 62 || C != nc * d) return false;
-  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return false;
-  if (B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff || B * L * nc > 0x3fffffff) return false;
-  g->P = (long)(B * L); g->R = (long)(B * L * nc); g->L = (long)L;
+static bool lfq_geometry(int64_t B, int64_t L, int64_t C, int64_t nc, int64_t d, int layout, LfqGeom *g, LfqLayout *w) {
+  if (nc < 1 || d < 1 || d > kLfqMaxD || nc * d > 62 || C != nc * d || !train_geometry(B, L, layout, nc, g)) return false;
+  g->R = g->P * (long)nc;
   g->nc = (int)nc; g->d = (int)d; g->dl = (int)d / 2; g->dh = (int)d - g->dl; g->C = (int)C;
-  g->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  return true;
+  return lfq_layout(g->R, d, w);
 }
 }  // namespace
 
@@ -1053,28 +1076,22 @@ int lfq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, fl
                   int64_t nc, int64_t d, int layout, float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream) {
   LfqGeom g;
   LfqLayout w;
-  if (!x || !quantized || !idx || !avg || !scalars || !lfq_geometry(B, L, C, nc, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
-  if (!lfq_layout(g.R, d, &w) || ((bits(avg) | bits(scalars)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (!x || !quantized || !idx || !avg || !scalars || !lfq_geometry(B, L, C, nc, d, layout, &g, &w) || !aligned(3u, avg, scalars))
+    return GQHIP_ERR_INVALID_ARG;
   if (g.R == 0) return GQHIP_OK;
-  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char *ws = static_cast<char *>(workspace);
+  if (const int rc = workspace_status(workspace, workspace_bytes, w.total)) return rc;
   LfqFwdParams p{};
   p.x = x; p.quant = quantized; p.idx = idx; p.avg = avg; p.scalars = scalars;
-  p.elem_part = reinterpret_cast<double *>(ws + w.elem_part); p.part = reinterpret_cast<float *>(ws + w.part);
-  p.ent_part = reinterpret_cast<double *>(ws + w.ent_part);
+  p.elem_part = at<double>(workspace, w.elem_part); p.part = at<float>(workspace, w.part); p.ent_part = at<double>(workspace, w.ent_part);
   p.g = g; p.ws = w_s; p.wb = w_b;
   p.chunks = w.chunks; p.Mpad = w.Mpad; p.Npad = w.Npad; p.avg_blocks = w.avg_blocks;
   p.elem_blocks = (int)((g.P + 255) / 256);
-  int rc = launch(lfq_elem_kernel, dim3((unsigned)p.elem_blocks), dim3(256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
   const int T = w.wide ? 128 : 64;
   const dim3 grid((unsigned)w.chunks, (unsigned)((w.Mpad / T) * (w.Npad / T)));
-  rc = launch(w.wide ? lfq_avg_gemm_kernel<2> : lfq_avg_gemm_kernel<1>, grid, dim3(256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
-  rc = launch(lfq_avg_reduce_kernel, dim3((unsigned)w.avg_blocks), dim3(256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
-  return launch(lfq_finish_kernel, dim3(1), dim3(256), 0, st, p);
+  return Chain(stream).run(lfq_elem_kernel, dim3((unsigned)p.elem_blocks), dim3(256), p)
+      .run(w.wide ? lfq_avg_gemm_kernel<2> : lfq_avg_gemm_kernel<1>, grid, dim3(256), p)
+      .run(lfq_avg_reduce_kernel, dim3((unsigned)w.avg_blocks), dim3(256), p)
+      .run(lfq_finish_kernel, dim3(1), dim3(256), p).rc;
 }
 
 namespace {
@@ -1095,22 +1112,18 @@ int lfq_backward_f32(const float *x, const float *avg, const float *g_q_or_null,
                      float w_s, float w_b, void *workspace, int64_t workspace_bytes, void *stream) {
   LfqGeom g;
   LfqLayout w;
-  if (!x || !avg || !grad_x || !lfq_geometry(B, L, C, nc, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
-  if (!lfq_layout(g.R, d, &w) || ((bits(avg) | bits(g_aux_or_null) | bits(g_commit_or_null)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (!x || !avg || !grad_x || !lfq_geometry(B, L, C, nc, d, layout, &g, &w) || !aligned(3u, avg, g_aux_or_null, g_commit_or_null))
+    return GQHIP_ERR_INVALID_ARG;
   if (g.R == 0) return GQHIP_OK;
-  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < w.total) return GQHIP_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  char *ws = static_cast<char *>(workspace);
+  if (const int rc = workspace_status(workspace, workspace_bytes, w.total)) return rc;
   LfqBwdParams p{};
   p.x = x; p.avg = avg; p.g_q = g_q_or_null; p.g_aux = g_aux_or_null; p.g_commit = g_commit_or_null; p.grad_x = grad_x;
-  p.G = reinterpret_cast<float *>(ws + w.G); p.GT = reinterpret_cast<float *>(ws + w.GT);
+  p.G = at<float>(workspace, w.G); p.GT = at<float>(workspace, w.GT);
   p.g = g; p.ws = w_s; p.wb = w_b;
-  if (g_aux_or_null) {
-    const int rc = launch(lfq_g_kernel, dim3((unsigned)w.avg_blocks), dim3(256), 0, st, p);
-    if (rc != GQHIP_OK) return rc;
-  }
+  Chain ch(stream);
+  if (g_aux_or_null) ch.run(lfq_g_kernel, dim3((unsigned)w.avg_blocks), dim3(256), p);
   const int64_t blocks = (g.R + 32 * kLfqBwdWaves - 1) / (32 * kLfqBwdWaves);
-  return launch(lfq_bwd_choice(g.dh), dim3((unsigned)blocks), dim3(64 * kLfqBwdWaves), 0, st, p);
+  return ch.run(lfq_bwd_choice(g.dh), dim3((unsigned)blocks), dim3(64 * kLfqBwdWaves), p).rc;
 }
 
 // ---- BSQQuantizer's train step (bsq_fsq_train.h) ----
@@ -1120,11 +1133,8 @@ static int64_t bsq_part_blocks(int64_t rows) {                     // an upper b
   return b < 1 ? 1 : (b > kBsqMaxBlocks ? kBsqMaxBlocks : b);
 }
 static bool bsq_geometry(int64_t B, int64_t L, int64_t C, int64_t d, int layout, BsqGeom *g) {
-  if (B < 0 || L < 0 || d < 1 || d > kBsqMaxD || C != 16 * d) return false;
-  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return false;
-  if (B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff) return false;
-  g->P = (long)(B * L); g->L = (long)L; g->d = (int)d; g->C = (int)C;
-  g->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
+  if (d < 1 || d > kBsqMaxD || C != 16 * d || !train_geometry(B, L, layout, 1, g)) return false;
+  g->d = (int)d; g->C = (int)C;
   const int64_t rpb = g->mode == 1 ? kBsqBchwThreads : (d == 1 ? 64 : d == 2 ? 32 : 16);      // positions a block covers per step
   const int64_t tiles = (g->P + rpb - 1) / rpb;
   g->iters = (int)((tiles + kBsqMaxBlocks - 1) / kBsqMaxBlocks);
@@ -1153,7 +1163,7 @@ static BsqBwdKernel bsq_bwd_choice(const BsqGeom &g) {
 
 int64_t bsq_train_workspace_bytes(int64_t rows, int64_t d) {
   if (rows < 0 || rows > 0x3fffffff || d < 1 || d > kBsqMaxD) return -1;
-  return align256(bsq_part_blocks(rows) * (2 * d + 1) * 8);
+  return align256(bsq_part_blocks(rows) * (2 * d + 1) * 8);       // one block (BsqFwdParams::part): nothing to carve
 }
 
 int bsq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, float *scalars, int64_t B, int64_t L, int64_t C,
@@ -1161,16 +1171,14 @@ int bsq_train_f32(const float *x, float *quantized, int64_t *idx, float *avg, fl
   BsqGeom g;
   if (!x || !quantized || !idx || !avg || !scalars || !bsq_geometry(B, L, C, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
   const unsigned amask = g.mode == 2 ? 15u : 3u;                   // "blc" rows are read and written 16 bytes at a time
-  if (((bits(x) | bits(quantized)) & amask) || ((bits(avg) | bits(scalars)) & 3u) || (bits(idx) & 7u)) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned(amask, x, quantized) || !aligned(3u, avg, scalars) || !aligned(7u, idx)) return GQHIP_ERR_INVALID_ARG;
   if (g.P == 0) return GQHIP_OK;
-  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < bsq_train_workspace_bytes(g.P, d)) return GQHIP_ERR_WORKSPACE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (const int rc = workspace_status(workspace, workspace_bytes, bsq_train_workspace_bytes(g.P, d))) return rc;
   BsqFwdParams p{};
   p.x = x; p.quant = quantized; p.idx = idx; p.avg = avg; p.scalars = scalars; p.part = static_cast<double *>(workspace);
   p.g = g; p.ws = w_s; p.wb = w_b;
-  const int rc = launch(bsq_fwd_choice(g), dim3((unsigned)g.blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, st, p);
-  if (rc != GQHIP_OK) return rc;
-  return launch(bsq_finish_kernel, dim3(1), dim3(256), 0, st, p);
+  return Chain(stream).run(bsq_fwd_choice(g), dim3((unsigned)g.blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), p)
+      .run(bsq_finish_kernel, dim3(1), dim3(256), p).rc;
 }
 
 int bsq_backward_f32(const float *x, const float *avg, const float *g_q_or_null, const float *g_aux_or_null, float *grad_x,
@@ -1179,15 +1187,14 @@ int bsq_backward_f32(const float *x, const float *avg, const float *g_q_or_null,
   BsqGeom g;
   if (!x || !avg || !grad_x || !bsq_geometry(B, L, C, d, layout, &g)) return GQHIP_ERR_INVALID_ARG;
   const unsigned amask = g.mode == 2 ? 15u : 3u;
-  if (((bits(x) | bits(grad_x) | bits(g_q_or_null)) & amask) || ((bits(avg) | bits(g_aux_or_null)) & 3u)) return GQHIP_ERR_INVALID_ARG;
+  if (!aligned(amask, x, grad_x, g_q_or_null) || !aligned(3u, avg, g_aux_or_null)) return GQHIP_ERR_INVALID_ARG;
   if (g.P == 0) return GQHIP_OK;
-  if (!workspace || (bits(workspace) & 15u) || workspace_bytes < bsq_train_workspace_bytes(g.P, d)) return GQHIP_ERR_WORKSPACE;
+  if (const int rc = workspace_status(workspace, workspace_bytes, bsq_train_workspace_bytes(g.P, d))) return rc;
   BsqBwdParams p{};
   p.x = x; p.avg = avg; p.g_q = g_q_or_null; p.g_aux = g_aux_or_null; p.grad_x = grad_x;
   p.g = g; p.ws = w_s; p.wb = w_b;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t blocks = g.mode == 1 ? (g.P + kBsqBchwThreads - 1) / kBsqBchwThreads : g.blocks;
-  return launch(bsq_bwd_choice(g), dim3((unsigned)blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, st, p);
+  return launch(bsq_bwd_choice(g), dim3((unsigned)blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,
@@ -1258,18 +1265,11 @@ int fsq_dequant_f32(const int32_t *idx, const int32_t *levels_host, int64_t nlev
 }
 
 // ---- FSQQuantizer's train step (bsq_fsq_train.h) ----
-static int fsq_train_args(const int32_t *levels_host, int64_t nlev, int64_t B, int64_t L, int layout, FsqTrainParams *p) {
-  if (B < 0 || L < 0 || B > 0x3fffffff || L > 0x3fffffff || B * L > 0x3fffffff) return GQHIP_ERR_INVALID_ARG;
-  if (layout != GQHIP_LAYOUT_BCHW && layout != GQHIP_LAYOUT_BLC) return GQHIP_ERR_INVALID_ARG;
-  p->P = (long)(B * L); p->L = (long)L; p->mode = layout == GQHIP_LAYOUT_BCHW ? 1 : 2;
-  return fsq_levels(levels_host, nlev, &p->lv);
-}
-
 int fsq_train_f32(const float *z, const int32_t *levels_host, int64_t nlev, float *zhat, int32_t *idx, int64_t B, int64_t L,
                   int layout, void *stream) {
   FsqTrainParams p{};
-  if (!z || !zhat || !idx || ((bits(z) | bits(zhat) | bits(idx)) & 3u)) return GQHIP_ERR_INVALID_ARG;
-  if (fsq_train_args(levels_host, nlev, B, L, layout, &p) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
+  if (!z || !zhat || !idx || !aligned(3u, z, zhat, idx) || !train_geometry(B, L, layout, 1, &p) || fsq_levels(levels_host, nlev, &p.lv) != GQHIP_OK)
+    return GQHIP_ERR_INVALID_ARG;
   if (p.P == 0) return GQHIP_OK;
   p.z = z; p.out = zhat; p.idx = idx;
   return launch(fsq_train_kernel, dim3((unsigned)((p.P + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
@@ -1278,12 +1278,11 @@ int fsq_train_f32(const float *z, const int32_t *levels_host, int64_t nlev, floa
 int fsq_backward_f32(const float *z, const float *g_zhat, const int32_t *levels_host, int64_t nlev, float *grad_z, int64_t B,
                      int64_t L, int layout, void *stream) {
   FsqTrainParams p{};
-  if (!z || !g_zhat || !grad_z || ((bits(z) | bits(g_zhat) | bits(grad_z)) & 3u)) return GQHIP_ERR_INVALID_ARG;
-  if (fsq_train_args(levels_host, nlev, B, L, layout, &p) != GQHIP_OK) return GQHIP_ERR_INVALID_ARG;
+  if (!z || !g_zhat || !grad_z || !aligned(3u, z, g_zhat, grad_z) || !train_geometry(B, L, layout, 1, &p) || fsq_levels(levels_host, nlev, &p.lv) != GQHIP_OK)
+    return GQHIP_ERR_INVALID_ARG;
   if (p.P == 0) return GQHIP_OK;
   p.z = z; p.g_zhat = g_zhat; p.out = grad_z;
-  const int64_t blocks = (p.P * p.lv.n + 255) / 256;
-  if (blocks > 0x7fffffff) return GQHIP_ERR_INVALID_ARG;
+  const int64_t blocks = (p.P * p.lv.n + 255) / 256;              // P < 2^30 and at most 16 levels: at most 2^26
   return launch(fsq_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 

@@ -402,21 +402,31 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
     return idx, zhat, (pure if use_ste else zhat), noquant, std, scalars
 
 
-def _z_geometry(t, dim: int, layout: str, holds: str = "mu|logvar"):
-    """(B, L, c, K, rows, shape of zhat, shape of the indices) of a tensor in a module layout (gqhip.h) whose channel axis holds
-    [mu | logvar] (an encoder output: 2 c channels), "z" (c channels) or "idx" (the indices themselves: K = c / dim channels)."""
+def _channel_geometry(t, layout: str, channels: Optional[int] = None, holds: str = ""):
+    """(B, L, C, shape) of a tensor in a module layout (gqhip.h): [B, C, ...] ("bchw", L = the positions of one image) or
+    [B, L, C] ("blc"); ``shape(k)`` is the shape of an output with k channels in that layout.  ``channels``: what C must be,
+    ``holds`` naming it in the error."""
     if layout not in GQHIP_LAYOUT or t.dim() < 3 or (layout == "blc" and t.dim() != 3):
         raise GqHipError(f"expected [B, C, ...] (bchw) or [B, L, C] (blc), got {tuple(t.shape)} as {layout!r}")
     if layout == "bchw":
-        B, ch, L = t.shape[0], t.shape[1], int(t[0, 0].numel())
+        B, C, L = t.shape[0], t.shape[1], int(t[0, 0].numel())
     else:
-        B, L, ch = t.shape
+        B, L, C = t.shape
+    if channels is not None and C != channels:
+        raise GqHipError(f"{C} channels do not hold {holds}")
+
+    def shape(k):
+        return ((B, k) + tuple(t.shape[2:])) if layout == "bchw" else (B, L, k)
+
+    return B, L, C, shape
+
+
+def _z_geometry(t, dim: int, layout: str, holds: str = "mu|logvar"):
+    """(B, L, c, K, rows, shape of zhat, shape of the indices) of a tensor in a module layout whose channel axis holds
+    [mu | logvar] (an encoder output: 2 c channels), "z" (c channels) or "idx" (the indices themselves: K = c / dim channels)."""
+    B, L, ch, shape = _channel_geometry(t, layout)
     c = {"mu|logvar": ch // 2, "z": ch, "idx": ch * dim}[holds]
     K = c // dim
-
-    def shape(channels):
-        return ((B, channels) + tuple(t.shape[2:])) if layout == "bchw" else (B, L, channels)
-
     return B, L, c, K, B * L * K, shape(c), shape(K)
 
 
@@ -516,14 +526,28 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     return idx, zq, loss
 
 
-class VqBackwardWorkspace(_Scratch):
-    """Scratch of vq_backward (gqhip.h: vq_backward_workspace_bytes), grown on demand and reused across calls; its contents never
-    matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
+class _TrainWorkspace(_Scratch):
+    """Scratch of one family's train step, grown on demand and reused across calls; its contents never matter on entry.  One per
+    stream at a time.  Graph captures: the rule of ``_Scratch``.  A family names its size function (gqhip.h) and that function's
+    arguments; ``get(*arguments, device)`` -> (pointer, bytes)."""
 
-    _what = "vq_backward's workspace"
+    _size, _shape = "", ()
 
-    def get(self, items: int, n: int, dim: int, device) -> Tuple[int, int]:
-        return self._take(lib().vq_backward_workspace_bytes(items, n, dim), device, f"items={items} n={n} dim={dim}")
+    def get(self, *shape_and_device) -> Tuple[int, int]:
+        *shape, device = shape_and_device
+        return self._take(getattr(lib(), self._size)(*shape), device, " ".join(f"{k}={v}" for k, v in zip(self._shape, shape)))
+
+
+class VqBackwardWorkspace(_TrainWorkspace):     # of vq_backward
+    _what, _size, _shape = "vq_backward's workspace", "vq_backward_workspace_bytes", ("items", "n", "dim")
+
+
+class LfqTrainWorkspace(_TrainWorkspace):       # of lfq_train / lfq_backward
+    _what, _size, _shape = "the LFQ train step's workspace", "lfq_train_workspace_bytes", ("rows", "d")
+
+
+class BsqTrainWorkspace(_TrainWorkspace):       # of bsq_train / bsq_backward
+    _what, _size, _shape = "the BSQ train step's workspace", "bsq_train_workspace_bytes", ("rows", "d")
 
 
 def vq_backward(z, emb, idx, dim: int, layout: str, beta: float, legacy: bool, g_zq=None, g_loss=None, want_grad_z: bool = True,
@@ -586,22 +610,9 @@ def lfq_pack(x):
     return idx, q
 
 
-class LfqTrainWorkspace(_Scratch):
-    """Scratch of lfq_train / lfq_backward (gqhip.h: lfq_train_workspace_bytes), grown on demand and reused across calls; its
-    contents never matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
-
-    _what = "the LFQ train step's workspace"
-
-    def get(self, rows: int, d: int, device) -> Tuple[int, int]:
-        return self._take(lib().lfq_train_workspace_bytes(rows, d), device, f"rows={rows} d={d}")
-
-
-def _lfq_geometry(x, num_codebooks: int, dim: int, layout: str):
-    """(B, L, C) of x in a module layout: [B, C, ...] ("bchw") or [B, L, C] ("blc"), C = num_codebooks * dim."""
-    B, L, C = _z_geometry(x, 1, layout, holds="z")[:3]
-    if C != num_codebooks * dim:
-        raise GqHipError(f"{C} channels do not hold {num_codebooks} codebooks of {dim} bits")
-    return B, L, C
+def _lfq_avg_numel(dim: int) -> int:
+    """floats in lfq_train's ``avg`` (a width the library refuses still gets a buffer: the refusal is the library's)"""
+    return 1 << dim if 1 <= dim <= 16 else 1
 
 
 def lfq_train(x, num_codebooks: int, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0,
@@ -610,12 +621,12 @@ def lfq_train(x, num_codebooks: int, dim: int, layout: str, w_s: float = 1.0, w_
     (quantized in the layout of x, indices int64 [B, 1, ...] / [B, L, 1], avg float32 [2^dim] (for lfq_backward), scalars
     float32 [4] on the device = {entropy_aux_loss, per_sample_entropy, codebook_entropy, commit_loss})."""
     x = _dev(x, torch.float32, "x")
-    B, L, C = _lfq_geometry(x, num_codebooks, dim, layout)
+    B, L, C, shape = _channel_geometry(x, layout, num_codebooks * dim, f"{num_codebooks} codebooks of {dim} bits")
     ws = ws or LfqTrainWorkspace()
     dev = x.device
     quantized = torch.empty_like(x)
-    idx = torch.empty(((B, 1) + tuple(x.shape[2:])) if layout == "bchw" else (B, L, 1), dtype=torch.int64, device=dev)
-    avg = torch.empty(1 << dim if 1 <= dim <= 16 else 1, dtype=torch.float32, device=dev)
+    idx = torch.empty(shape(1), dtype=torch.int64, device=dev)
+    avg = torch.empty(_lfq_avg_numel(dim), dtype=torch.float32, device=dev)
     scalars = torch.empty(4, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
@@ -631,8 +642,8 @@ def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float =
     ``avg``; ``g_q`` (shape of x; made contiguous in x's layout when it is not), ``g_aux`` and ``g_commit`` (one float32 on the
     device each) are the gradients arriving at quantized, entropy_aux_loss and commit_loss, None = zero.  Returns grad_x."""
     x, avg = _dev(x, torch.float32, "x"), _dev(avg, torch.float32, "avg")
-    B, L, C = _lfq_geometry(x, num_codebooks, dim, layout)
-    if avg.numel() != (1 << dim if 1 <= dim <= 16 else 1):
+    B, L, C, _ = _channel_geometry(x, layout, num_codebooks * dim, f"{num_codebooks} codebooks of {dim} bits")
+    if avg.numel() != _lfq_avg_numel(dim):
         raise GqHipError(f"avg must hold 2^{dim} floats, got {avg.numel()}")
     g_q, g_aux, g_commit = _grad_of(g_q, x.shape, "g_q", "x"), _grad_scalar(g_aux, "g_aux"), _grad_scalar(g_commit, "g_commit")
     ws = ws or LfqTrainWorkspace()
@@ -646,24 +657,11 @@ def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float =
     return grad_x
 
 
-class BsqTrainWorkspace(_Scratch):
-    """Scratch of bsq_train / bsq_backward (gqhip.h: bsq_train_workspace_bytes), grown on demand and reused across calls; its
-    contents never matter on entry.  One per stream at a time.  Graph captures: the rule of ``_Scratch``."""
-
-    _what = "the BSQ train step's workspace"
-
-    def get(self, rows: int, d: int, device) -> Tuple[int, int]:
-        return self._take(lib().bsq_train_workspace_bytes(rows, d), device, f"rows={rows} d={d}")
-
-
-def _bsq_geometry(x, dim: int, layout: str):
-    """(B, L, C) of x in a module layout with C = 16 * dim channels (16 codebooks of ``dim`` bits)."""
+def _bsq_avg_shape(dim: int):
+    """shape of bsq_train's ``avg``: per bit of the 1..16 a BSQ codebook holds, the mean probabilities of its two values"""
     if not 1 <= dim <= 16:
         raise GqHipError(f"a BSQ codebook holds 1..16 bits, got {dim}")
-    B, L, C = _z_geometry(x, 1, layout, holds="z")[:3]
-    if C != 16 * dim:
-        raise GqHipError(f"{C} channels do not hold 16 codebooks of {dim} bits")
-    return B, L, C
+    return dim, 2
 
 
 def _aligned16(t):
@@ -676,12 +674,13 @@ def bsq_train(x, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0, ws: 
     ("blc") -> (quantized in the layout of x, indices int64 [B, dim, ...] / [B, L, dim], avg float32 [dim, 2] (for bsq_backward),
     scalars float32 [3] on the device = {entropy_aux_loss, per_sample_entropy, codebook_entropy})."""
     x = _aligned16(_dev(x, torch.float32, "x"))
-    B, L, C = _bsq_geometry(x, dim, layout)
+    avg_shape = _bsq_avg_shape(dim)
+    B, L, C, shape = _channel_geometry(x, layout, 16 * dim, f"16 codebooks of {dim} bits")
     ws = ws or BsqTrainWorkspace()
     dev = x.device
     quantized = torch.empty_like(x)
-    idx = torch.empty(((B, dim) + tuple(x.shape[2:])) if layout == "bchw" else (B, L, dim), dtype=torch.int64, device=dev)
-    avg = torch.empty(dim, 2, dtype=torch.float32, device=dev)
+    idx = torch.empty(shape(dim), dtype=torch.int64, device=dev)
+    avg = torch.empty(avg_shape, dtype=torch.float32, device=dev)
     scalars = torch.empty(3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L, dim, dev)
@@ -696,8 +695,9 @@ def bsq_backward(x, avg, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1
     ``avg``; ``g_q`` (shape of x; made contiguous in x's layout when it is not) and ``g_aux`` (one float32 on the device) are the
     gradients arriving at quantized and entropy_aux_loss, None = zero.  Returns grad_x."""
     x, avg = _aligned16(_dev(x, torch.float32, "x")), _dev(avg, torch.float32, "avg")
-    B, L, C = _bsq_geometry(x, dim, layout)
-    if avg.numel() != 2 * dim:
+    avg_shape = _bsq_avg_shape(dim)
+    B, L, C, _ = _channel_geometry(x, layout, 16 * dim, f"16 codebooks of {dim} bits")
+    if avg.numel() != math.prod(avg_shape):
         raise GqHipError(f"avg must hold [{dim}, 2] floats, got {avg.numel()}")
     g_q, g_aux = _aligned16(_grad_of(g_q, x.shape, "g_q", "x")), _grad_scalar(g_aux, "g_aux")
     ws = ws or BsqTrainWorkspace()
@@ -738,21 +738,14 @@ def fsq_quantize(z, levels):
     return zhat, idx
 
 
-def _fsq_geometry(z, levels, layout: str):
-    B, L, C = _z_geometry(z, 1, layout, holds="z")[:3]
-    if C != len(levels):
-        raise GqHipError(f"{C} channels do not hold {len(levels)} levels")
-    return B, L
-
-
 def fsq_train(z, levels, layout: str):
     """FSQQuantizer's forward with round_ste's value in one call (gqhip.h: fsq_train_f32): z [B, nlev, ...] ("bchw") or
     [B, L, nlev] ("blc") -> (zhat in the layout of z, packed indices int32 [B, 1, ...] / [B, L, 1])."""
     z = _dev(z, torch.float32, "z")
-    B, L = _fsq_geometry(z, levels, layout)
+    B, L, _, shape = _channel_geometry(z, layout, len(levels), f"{len(levels)} levels")
     arr, n = _levels(levels)
     zhat = torch.empty_like(z)
-    idx = torch.empty(((B, 1) + tuple(z.shape[2:])) if layout == "bchw" else (B, L, 1), dtype=torch.int32, device=z.device)
+    idx = torch.empty(shape(1), dtype=torch.int32, device=z.device)
     with torch.cuda.device(z.device):
         _check(lib().fsq_train_f32(z.data_ptr(), arr, n, zhat.data_ptr(), idx.data_ptr(), B, L, GQHIP_LAYOUT[layout], _stream()),
                "fsq_train_f32")
@@ -763,7 +756,7 @@ def fsq_backward(z, g_zhat, levels, layout: str):
     """The backward of fsq_train in one call (gqhip.h: fsq_backward_f32): ``g_zhat`` has the shape of z (made contiguous in z's
     layout when it is not).  Returns grad_z."""
     z = _dev(z, torch.float32, "z")
-    B, L = _fsq_geometry(z, levels, layout)
+    B, L, _, _ = _channel_geometry(z, layout, len(levels), f"{len(levels)} levels")
     g_zhat = _grad_of(g_zhat, z.shape, "g_zhat", "z")
     if g_zhat is None:
         raise GqHipError("g_zhat is required")
