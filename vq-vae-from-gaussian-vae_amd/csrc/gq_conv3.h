@@ -169,7 +169,8 @@ __device__ __forceinline__ void conv3_epilogue(const Conv3Params &p, const Conv3
 //      LDS (no Xs: saves writing and re-reading 4 bytes per element and a launch).  A chunk is 16 channels = 64 bytes of
 //      a pixel's fp32 row; thread -> 4 channels of up to 6 patch pixels (the same channel quad for all of them), the
 //      folded scale / shift of the image's channels sit in LDS.  The conversions of chunk k + 1 are spread over taps 3..8
-//      of chunk k (one piece per tap: in the MFMAs' shadow, and late enough for the loads issued at tap 0 to have landed).
+//      of chunk k (one piece per tap, late enough for the loads issued at tap 0 to have landed), and within a tap over its
+//      MFMAs: three VALU instructions behind each of the 24 (run_chunk below).
 struct Conv3GnParams {
   Conv3Params c;
   const float *x;          // [B][H][W][cin]
@@ -180,6 +181,9 @@ struct Conv3GnParams {
   float scale;
 };
 
+#ifndef GQHIP_C3_VALU_PER_MFMA
+#define GQHIP_C3_VALU_PER_MFMA 3   // conversion VALU placed after each MFMA of taps 3..8 (0: left to the compiler)
+#endif
 #ifdef GQHIP_CLOCK_STAMPS
 __device__ unsigned long long g_c3_stamps[4 * 8192];   // diagnostic build: per-block timeline (tools/c3_timeline.py)
 #endif
@@ -229,8 +233,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
   f32x4 st[3];
   auto issue = [&](int i, int chunk) { st[i % 3] = *reinterpret_cast<const f32x4 *>(xb + goff[i] + chunk * 16); };
   auto convert = [&](int i, int chunk, int buf) {    // piece i of the chunk (in st[i % 3]) -> activated, scaled, split, into LDS
-    const int q = qs + 64 * i;
-    if (q >= kC3Pix) return;
+    // No branch for the lanes past the patch (piece 5, q >= 340): they take pixel 339 again, as goff[] and inb do.  Same
+    // source address, same inb bit, same channel quad: the same bytes go to the same LDS address twice, which is benign --
+    // and the tap's MFMAs and this conversion stay one basic block (see the main loop).
+    const int q = qs + 64 * i < kC3Pix ? qs + 64 * i : kC3Pix - 1;
     const f32x4 a4 = *reinterpret_cast<const f32x4 *>(&sAff[0][chunk * 16 + 4 * w]);
     const f32x4 sh4 = *reinterpret_cast<const f32x4 *>(&sAff[1][chunk * 16 + 4 * w]);
     const f32x4 v = gn_act<SILU>(st[i % 3], a4, sh4) * (((inb >> i) & 1) ? pp.scale : 0.f);
@@ -279,8 +285,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
 #ifdef GQHIP_CLOCK_STAMPS
   const unsigned long long st_r1 = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int chunk = 0; chunk < p.nch; ++chunk) {
-    const bool more = chunk + 1 < p.nch;
+  // One chunk = nine taps in ONE basic block: `more` is a compile-time constant (the last chunk is peeled) and convert() has
+  // no branch, so the ~50 VALU instructions of a piece's conversion sit in the same scheduling region as the tap's 24 MFMAs
+  // and the group barriers below can place them between the MFMAs (1 MFMA : GQHIP_C3_VALU_PER_MFMA VALU) instead of behind them.
+  auto run_chunk = [&](int chunk, auto more_tag) {
+    constexpr bool more = decltype(more_tag)::value;
     const unsigned char *A = sA + (chunk & 1) * kC3Buf;
     const int nbuf = (chunk + 1) & 1;
 #pragma unroll
@@ -291,15 +300,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
 #endif
       conv3_tap(A + aoff[tap % 3], tap / 3, bs[tap % 3], acc);
 #if !(defined(GQHIP_ABL) && (GQHIP_ABL & 64))      // diagnostic build: no staging of the next chunk
-      if (more) {
+      if constexpr (more) {
         if (tap >= 3) convert(tap - 3, chunk + 1, nbuf);
         if (tap < kC3Loads) issue(tap, chunk + 1);
+#if GQHIP_C3_VALU_PER_MFMA > 0
+        if (tap >= 3) {
+#pragma unroll
+          for (int m = 0; m < 24; ++m) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, GQHIP_C3_VALU_PER_MFMA, 0);   // then VALU of the conversion
+          }
+        }
+#endif
       }
 #endif
       __builtin_amdgcn_sched_barrier(0);   // keeps hipcc from hoisting the LDS reads of later taps (spills otherwise)
     }
     __syncthreads();
-  }
+  };
+  for (int chunk = 0; chunk + 1 < p.nch; ++chunk) run_chunk(chunk, std::true_type{});
+  run_chunk(p.nch - 1, std::false_type{});
 #ifdef GQHIP_CLOCK_STAMPS
   const unsigned long long st_r2 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -324,12 +344,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_gn_f16x3_kernel(const Conv3GnP
 // without the epilogue 1.37 M, one A operand per tap instead of eight 1.79 M (LDS reads cost nothing), all off 0.98 M cycles
 // (pipes 90 % busy at 1.88 GHz).  Tried and measured within 2 %: delaying the second block of every CU by 10-80 us (the two
 // blocks' phases are already spread: both are inside their main loop 50 % of the time, one 46 %), one block per CU (1124 vs
-// 1019 us: a wave alone on its SIMD runs its main loop almost twice as fast), weight loads pinned to the top of the tap and the
-// conversion's ~60 VALU instructions spread between the MFMAs with sched_group_barrier (hipcc keeps them in one block; 8 spills),
+// 1019 us: a wave alone on its SIMD runs its main loop almost twice as fast), weight loads pinned to the top of the tap,
 // a wave owning 8 rows x 32 channels (two weight operands per tap instead of four, none loaded twice per block, 16 A reads:
 // bit-identical, no spills, 1045 vs 1031-1052 us), s_setprio 1 / 3 around the tap's MFMAs or around the conversion instead
 // (1068-1080 us), __builtin_amdgcn_iglp_opt(0) per tap (-1 %, at the noise level).  The texture addresser is busy 26 % of the cycles, L2 read latency averages
 // 317 cycles, 67 % of the L2 requests hit: no unit of the memory pipeline is saturated -- the waves' in-order waits are.
+//
+// The conversion between the MFMAs (profiles/r26).  Round 3 noted "the conversion's ~60 VALU instructions spread between the
+// MFMAs with sched_group_barrier (hipcc keeps them in one block; 8 spills)".  The cause was a branch, not hipcc: `if (more)`
+// and convert()'s early return for q >= 340 made every tap a basic block of its own (24 MFMAs, s_cbranch, then ~50 VALU in
+// one run: 4 v_exp, 4 v_rcp, the Newton step, cvt / sub, one ds_write2st64_b64), and no scheduling directive crosses a
+// branch: a wave issued no MFMA while it converted.  With the last chunk peeled (`more` a compile-time constant) and the
+// clamp instead of the return the nine taps are ONE block of 216 MFMAs, and 24 x {1 MFMA, 3 VALU} per tap leaves 3-8 VALU
+// behind each MFMA of taps 3..8: 252 VGPRs, no scratch, two waves per SIMD (before: 254).  Peeling alone leaves the VALU
+// in one run behind the MFMAs and spills (16 bytes per lane).  Measured in bench.py, six profiled runs a side: <1, 128>
+// 892 -> 842 us (-5.6 %), <1, 256> 692 -> 657 us (-5.1 %), at batch 1 72 -> 63 and 88 -> 73 us; matrix pipes 66 -> 75 % busy
+// at 16 x 256^2 x 128 -> 128 (same MFMA count, 14 % more VALU instructions issued -- waves 2 and 3 used to skip the sixth piece --,
+// 14 % fewer wave-cycles waiting).  1 MFMA : 2 VALU (-DGQHIP_C3_VALU_PER_MFMA=2) measured 983-985 us against 964-976 for 1 : 3
+// and 1017-1022 for the branchy loop (tools/convstack/conv3_bench.py, residual + statistics); singling out the
+// transcendentals (mask 0x400: one v_exp / v_rcp + one VALU behind MFMAs 2..9) clumps the rest (runs of 22) and measured
+// 980-991.  No A-operand read-ahead across the tap boundary: a (h, l) pair is 8 registers and 4 are free.
 
 // Measured alternative (round 2, removed): a wave-specialised persistent variant -- one block of 8 waves per CU, waves 0-3
 // only multiplying (every operand from LDS, next tap's operands read under the current tap's MFMAs), waves 4-7 only
@@ -472,23 +506,57 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f16x3_kernel(const Conv1Params
 #pragma unroll
   for (int i = 0; i < NI; ++i) convert(i, 0);
   __syncthreads();
-  for (int s = 0; s < nst; ++s) {
-    const bool more = s + 1 < nst;
-    const unsigned char *A = sA + (s & 1) * kStage;
-    const int nbuf = (s + 1) & 1;
-    load_b(2 * s + 1, b1);
-    if (more) issue(s + 1);
-    kstep(A, b0);
-    __builtin_amdgcn_sched_barrier(0);
-    load_b(2 * s + 2 < nks ? 2 * s + 2 : nks - 1, b0);
-    kstep(A + kChunk, b1);
-    if (more) {
-      affine(s + 1);
+  // One stage = two k-steps.  128-pixel tiles (RR = 2): the last stage is peeled, so `more` is a compile-time constant, and the
+  // next stage's constants are fetched before the second k-step (affine() branches on the pending bias): that k-step's MFMAs
+  // and the NI conversions are then one basic block and the conversions are spread between the MFMAs (profiles/r26:
+  // <0, 2, 1, 1> 104.4 -> 99.3 us, <512, 2, 0, 0> 46.7 -> 44.3 us per call in bench.py).  256-pixel tiles keep the loop with
+  // a run-time `more` and the conversions behind the MFMAs: the same treatment measured -1.3 % / +1.5 % / +1.6 % on the three
+  // instantiations the benchmark launches, none of them clearly below the parent.
+  if constexpr (RR == 2) {
+    auto run_stage = [&](int s, auto more_tag) {
+      constexpr bool more = decltype(more_tag)::value;
+      const unsigned char *A = sA + (s & 1) * kStage;
+      const int nbuf = (s + 1) & 1;
+      load_b(2 * s + 1, b1);
+      if constexpr (more) issue(s + 1);
+      kstep(A, b0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (more) affine(s + 1);
+      load_b(2 * s + 2 < nks ? 2 * s + 2 : nks - 1, b0);
+      kstep(A + kChunk, b1);
+      if constexpr (more) {
 #pragma unroll
-      for (int i = 0; i < NI; ++i) convert(i, nbuf);
+        for (int i = 0; i < NI; ++i) convert(i, nbuf);
+#pragma unroll
+        for (int m = 0; m < 6 * RR; ++m) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
+          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);   // then VALU of the conversions (NI x ~25 over 6 RR MFMAs)
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();
+    };
+    for (int s = 0; s + 1 < nst; ++s) run_stage(s, std::true_type{});
+    run_stage(nst - 1, std::false_type{});
+  } else {
+    for (int s = 0; s < nst; ++s) {
+      const bool more = s + 1 < nst;
+      const unsigned char *A = sA + (s & 1) * kStage;
+      const int nbuf = (s + 1) & 1;
+      load_b(2 * s + 1, b1);
+      if (more) issue(s + 1);
+      kstep(A, b0);
+      __builtin_amdgcn_sched_barrier(0);
+      load_b(2 * s + 2 < nks ? 2 * s + 2 : nks - 1, b0);
+      kstep(A + kChunk, b1);
+      if (more) {
+        affine(s + 1);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) convert(i, nbuf);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();
     }
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();
   }
   if constexpr (SPLIT != 0) {
     // lane l of wave (wm, wn): channels wn * 64 + 4 (l & 15) .. + 3 of the block's 128, tokens 32 (y0 + RR wm + rr) + (l >> 4) + 4 i
@@ -688,7 +756,9 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
     const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
     const int cy = gy < 0 ? 0 : (gy >= H ? H - 1 : gy), cx = gx < 0 ? 0 : (gx >= W ? W - 1 : gx);
     goff[i] = (cy * W + cx) * cin;
-    loff[i] = q < PR * PC ? conv3_lds_off(R, X, w >> 1) + 8 * (w & 1) : -1;
+    // lanes past the patch (q >= 297, last piece) take pixel 296 again -- source address, inb bit, channel quad and LDS address
+    // are those of the lane that owns it, so the same bytes land twice: benign, and commit_piece() needs no branch
+    loff[i] = conv3_lds_off(R, X, w >> 1) + 8 * (w & 1);
     inb |= (unsigned)(in ? 1 : 0) << i;
   }
   f32x4 st[NP];
@@ -696,21 +766,17 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
 #pragma unroll
     for (int i = 0; i < NP; ++i) st[i] = *reinterpret_cast<const f32x4 *>(xb + goff[i] + chunk * 16);
   };
-  auto commit = [&](int buf) {
+  auto commit_piece = [&](int i, int buf) {
+    const f32x4 v = st[i] * (((inb >> i) & 1) ? scale : 0.f);
+    f16x4 hi, lo;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      if (loff[i] < 0) continue;
-      const f32x4 v = st[i] * (((inb >> i) & 1) ? scale : 0.f);
-      f16x4 hi, lo;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hi[e] = (_Float16)v[e];
-        lo[e] = (_Float16)(v[e] - (float)hi[e]);
-      }
-      unsigned char *d = sA + buf * kC3Buf + loff[i];
-      *reinterpret_cast<f16x4 *>(d) = hi;
-      *reinterpret_cast<f16x4 *>(d + kC3Plane) = lo;
+    for (int e = 0; e < 4; ++e) {
+      hi[e] = (_Float16)v[e];
+      lo[e] = (_Float16)(v[e] - (float)hi[e]);
     }
+    unsigned char *d = sA + buf * kC3Buf + loff[i];
+    *reinterpret_cast<f16x4 *>(d) = hi;
+    *reinterpret_cast<f16x4 *>(d + kC3Plane) = lo;
   };
   f32x16 acc[4][2];
   GQ_C3_ZERO_ACC(acc);
@@ -733,13 +799,19 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
   load_b(0, b0);
   load_b(1, b1);
   issue(0);
-  commit(0);
+#pragma unroll
+  for (int i = 0; i < NP; ++i) commit_piece(i, 0);
   __syncthreads();
   int ks = 0;
-  for (int chunk = 0; chunk < nch; ++chunk) {
-    const bool more = chunk + 1 < nch;
-    if (more) issue(chunk + 1);
+  // One chunk = four taps; `more` is a compile-time constant (the last chunk is peeled), so the next chunk's commit -- pieces
+  // 0, 1 in tap 2, pieces 2..4 in tap 3 -- sits in the block of that tap's MFMAs and is spread between them (it used to be
+  // a block of ~125 VALU instructions behind the chunk's last MFMA, in front of the barrier).  profiles/r26: <256> 1378 ->
+  // 1306 us, <512> 825 -> 781 us per call in bench.py.
+  auto run_chunk = [&](int chunk, auto more_tag) {
+    constexpr bool more = decltype(more_tag)::value;
+    if constexpr (more) issue(chunk + 1);
     const unsigned char *A = sA + (chunk & 1) * kC3Buf;
+    const int nbuf = (chunk + 1) & 1;
 #pragma unroll
     for (int ti = 0; ti < 4; ++ti) {           // tap (u, v) = (ti >> 1, ti & 1)
       load_b(ks + 2, b2);
@@ -750,11 +822,30 @@ __global__ __launch_bounds__(256, 2) void upconv2x_f16x3_kernel(const Upconv2Par
         b1[k] = b2[k];
       }
       ++ks;
+      if constexpr (more) {
+        if (ti == 2) {
+          commit_piece(0, nbuf);
+          commit_piece(1, nbuf);
+        }
+        if (ti == 3) {
+          commit_piece(2, nbuf);
+          commit_piece(3, nbuf);
+          commit_piece(4, nbuf);
+        }
+        if (ti >= 2) {
+#pragma unroll
+          for (int m = 0; m < 24; ++m) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);            // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);            // then VALU of the commit
+          }
+        }
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (more) commit((chunk + 1) & 1);
     __syncthreads();
-  }
+  };
+  for (int chunk = 0; chunk + 1 < nch; ++chunk) run_chunk(chunk, std::true_type{});
+  run_chunk(nch - 1, std::false_type{});
   // ---- epilogue (gq_epilogue.h): lane l of wave (wm, wn) -> channels wn * 64 + 4 (l & 15) .. + 3 of the low-resolution positions
   // (y0 + 4 wm + rr, x0 + (l >> 4) + 4 i), i.e. of output pixels (2 y + pa, 2 x + pb): a pixel's 256 bytes are still one run ----
   constexpr int cout = COUT;
