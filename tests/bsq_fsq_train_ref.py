@@ -1,6 +1,7 @@
 """fp64 restatement of one train step of BSQQuantizer (reference pit/quantization/bsq.py:14-37, 64-133) and of FSQQuantizer
 (pit/quantization/fsq.py:6-9, 29-68) with their gradients -- the checker of tests/test_gpu_bsq_fsq_train_step.py, proven on the
-CPU by tests/test_bsq_fsq_train_host.py and used by tests/golden/make_golden_bsq_fsq_train.py to fill g26 / g27.  numpy only.
+CPU by tests/test_bsq_fsq_train_host.py and used by tests/golden/make_golden_bsq_fsq_train.py to fill g26 / g27 (and by
+make_golden_train_variants.py to fill g29).  numpy only.
 
 BSQ.  A position holds C = 16 d channels, channel i d + j = codebook i, bit plane j; M = B L 16.  The scalar loss differentiated:
     loss = sum(quantized * w) + g_aux * entropy_aux_loss
@@ -160,6 +161,23 @@ BSQ_CASES = {
     "blc_d3_special": dict(format="blc", d=3, shape=(2, 19, 48), kind="special", scale=1.0),                 # C no power of two; the clamp
     "bchw_d1_saturated": dict(format="bchw", d=1, shape=(2, 16, 8, 8), kind="positive", scale=1.0),          # every p ~ 1.4e-11
     "bchw_d1_cl": dict(format="bchw", d=1, shape=(2, 16, 8, 8), kind="randn", scale=1.0, channels_last=True),
+}
+# The "blc" kernel pairs BSQ_CASES never launches (fixture g29, tests/golden/make_golden_train_variants.py).  A row of C = 16 d
+# floats is C4 = 4 d chunks of 16 bytes on 16 lanes, NS = ceil(d / 4) chunks per lane; 37 rows = two whole 16-row groups and 5 rows.
+BSQ_VARIANT_CASES = {
+    "blc_d5": dict(format="blc", d=5, shape=(1, 37, 80), kind="randn", scale=1.0),        # <16, 2>: 4 of 16 lanes live in chunk 2
+    "blc_d6": dict(format="blc", d=6, shape=(1, 37, 96), kind="randn", scale=1.0),        # <16, 2>: 8 live
+    "blc_d8": dict(format="blc", d=8, shape=(1, 37, 128), kind="randn", scale=1.0),       # <16, 2>: no idle lane
+    "blc_d9": dict(format="blc", d=9, shape=(1, 37, 144), kind="randn", scale=1.0),       # <16, 3>: 4 live in chunk 3
+    "blc_d10": dict(format="blc", d=10, shape=(1, 37, 160), kind="randn", scale=1.0),     # <16, 3>: 8 live
+    "blc_d11": dict(format="blc", d=11, shape=(1, 37, 176), kind="randn", scale=1.0),     # <16, 3>: 12 live
+    "blc_d12": dict(format="blc", d=12, shape=(1, 37, 192), kind="randn", scale=1.0),     # <16, 3>: no idle lane
+    "blc_d13": dict(format="blc", d=13, shape=(1, 37, 208), kind="randn", scale=1.0),     # <16, 4>: 4 live in chunk 4
+    "blc_d14": dict(format="blc", d=14, shape=(1, 37, 224), kind="randn", scale=1.0),     # <16, 4>: 8 live
+    "blc_d15": dict(format="blc", d=15, shape=(1, 37, 240), kind="randn", scale=1.0),     # <16, 4>: 12 live
+    "bchw_d9": dict(format="bchw", d=9, shape=(1, 144, 7, 11), kind="randn", scale=1.0),  # bchw at a d no power of two: 64 + 13 positions
+    "bchw_d15": dict(format="bchw", d=15, shape=(2, 240, 3, 3), kind="randn", scale=1.0),       # two images in one block of 18 positions
+    "bchw_d10_cl": dict(format="bchw", d=10, shape=(1, 160, 5, 7), kind="randn", scale=1.0, channels_last=True),   # <16, 3> from NHWC
 }
 BSQ_UNDERFLOW = dict(format="blc", d=1, shape=(1, 3, 16))       # forward only, stored fp32: row 1 holds 1e18, 1e-30, -1e-30 and zeros
 FSQ_CASES = {

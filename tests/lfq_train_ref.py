@@ -1,6 +1,6 @@
 """fp64 restatement of one train step of LFQQuantizer (reference pit/quantization/lfq.py:56-76, 127-206) and of its gradient -- the
 checker of tests/test_gpu_lfq_train_step.py, proven on the CPU by tests/test_lfq_train_host.py and used by
-tests/golden/make_golden_lfq_train.py to fill g25_lfq_train_step.npz.  numpy only.
+tests/golden/make_golden_lfq_train.py to fill g25_lfq_train_step.npz (make_golden_train_variants.py: g28).  numpy only.
 
 Row r = (b L + l) nc + ci holds the d channels ci d + i of position (b, l); R rows, N = 2^d codes, T = 0.01, eps = 1e-5.  The scalar
 loss that is differentiated:
@@ -152,3 +152,31 @@ CASES = {
     "bchw_4096x1_cl": dict(format="bchw", d=12, nc=1, shape=(1, 12, 5, 5), scale=0.02, channels_last=True),
 }
 G_AUX, G_COMMIT = 0.37, 1.3
+
+# The kernel variants CASES never launches (fixture g28, tests/golden/make_golden_train_variants.py).  With dl = d // 2 and
+# dh = d - dl the host picks lfq_bwd_kernel<MT>, MT = max(1, 2^dh / 32), and 64 x 64 forward tiles below d = 14, 128 x 128 from there.
+# Rows: 70 = a partial 256-row chunk of the forward, one 64-row block of the backward and 6 rows; 300 = a whole chunk and 44 rows
+# (a partial 32-row step), four whole backward blocks and one whose second wave is partly dead.
+VARIANT_CASES = {
+    "blc_d2": dict(format="blc", d=2, nc=1, shape=(1, 70, 2), scale=0.02),           # dh = dl = 1: two live entries per table, the rest padding
+    "blc_d3x2": dict(format="blc", d=3, nc=2, shape=(1, 35, 6), scale=0.02),         # odd d below 5 with nc > 1: row -> (position, ci)
+    "blc_d4": dict(format="blc", d=4, nc=1, shape=(1, 70, 4), scale=0.02),           # 4 x 4 entries in a 64 x 64 tile
+    "blc_d6": dict(format="blc", d=6, nc=1, shape=(1, 70, 6), scale=0.02),           # k-table of 8: slots 3 and 4 of ck are padding
+    "blc_d7": dict(format="blc", d=7, nc=1, shape=(1, 70, 7), scale=0.02),           # dh 4, dl 3: MT = 1, both passes generic
+    "blc_d9": dict(format="blc", d=9, nc=1, shape=(1, 300, 9), scale=0.02),          # dh 5, dl 4: MT = 1 with kdim = 16, slot 4 of ck padded
+    "blc_d10": dict(format="blc", d=10, nc=1, shape=(1, 300, 10), scale=0.02),       # dh = dl = 5: the 16-byte slab copy at MT = 1
+    "blc_d11x2": dict(format="blc", d=11, nc=2, shape=(1, 150, 22), scale=0.02),     # lfq_bwd_kernel<2>, generic second pass, nc > 1
+    "blc_d13": dict(format="blc", d=13, nc=1, shape=(1, 300, 13), scale=0.02),       # lfq_bwd_kernel<4>; forward grid 2 x 1 of 64 x 64
+    "blc_d13x4": dict(format="blc", d=13, nc=4, shape=(1, 75, 52), scale=0.02, same_as="blc_d13"),    # the same memory, rows of 4
+    "blc_d14": dict(format="blc", d=14, nc=1, shape=(1, 300, 14), scale=0.02),       # lfq_bwd_kernel<4>, both passes slab copies; 1 x 1 wide
+    "blc_d15": dict(format="blc", d=15, nc=1, shape=(1, 300, 15), scale=0.02),       # lfq_bwd_kernel<8>, generic second pass; 2 x 1 wide
+    "bchw_d13x4_cl": dict(format="bchw", d=13, nc=4, shape=(1, 52, 5, 5), scale=0.02, channels_last=True),     # the module's NHWC route
+}
+
+
+def variant(fix, tag, key):
+    """Array ``key`` of a VARIANT_CASES case in g28.  A case with ``same_as`` views the other case's x, w and grad_x64."""
+    cfg = VARIANT_CASES[tag]
+    if "same_as" in cfg and key in ("x", "w", "grad_x64"):
+        return fix[f"{cfg['same_as']}_{key}"].reshape(cfg["shape"])
+    return fix[f"{tag}_{key}"]

@@ -1,7 +1,7 @@
 """CPU: the host half of the fused BSQ / FSQ train steps -- the new entry points exist, are bound and validate their arguments
 before any HIP call, the opt-in switch is off by default, the fixtures g26 / g27 load, the fp64 checker the GPU tests rely on
 (tests/bsq_fsq_train_ref.py) agrees with a central difference, and a CPU BSQQuantizer / FSQQuantizer step (the torch branch, which
-CPU tensors keep) lands on the fixtures."""
+CPU tensors keep) lands on the fixtures, g29 (the "blc" kernel pairs g26 leaves out) among them."""
 import ctypes
 import inspect
 import os
@@ -250,11 +250,8 @@ def _as_input(a, cfg):
     return t.requires_grad_(True)
 
 
-@pytest.mark.parametrize("tag", list(R.BSQ_CASES))
-def test_cpu_bsq_train_step_lands_on_the_fixture(tag, monkeypatch):
-    """A CPU tensor keeps the torch branch.  That branch asks the library for the sign pack, which has no CPU implementation: numpy
-    answers in its place, so what is checked is the differentiable glue -- the indices bit for bit, quantized within its three
-    roundings, the scalars and grad_x within twice the reference's own fp32 error."""
+def _cpu_bsq_step(cfg, x, w, g_aux, monkeypatch):
+    """One train step of the CPU module under autograd: (quantized, info, x.grad)."""
     from pit_hip import _lib as L
     from pit_hip.quantization.bsq import BSQQuantizer
 
@@ -267,22 +264,84 @@ def test_cpu_bsq_train_step_lands_on_the_fixture(tag, monkeypatch):
 
     monkeypatch.setattr(L, "lfq_pack", cpu_pack)
     monkeypatch.setenv("GQHIP_BSQ_TRAIN_FUSED", "1")                                 # a CPU tensor does not take the fused route
-    d, cfg = _bsq(), R.BSQ_CASES[tag]
-    x, w = _inputs(d, tag)
     m = BSQQuantizer(cfg["format"], 1 << cfg["d"], 16, sample_minimization_weight=cfg.get("w_s", 1.0),
                      batch_maximization_weight=cfg.get("w_b", 1.0)).train()
     xt = _as_input(x, cfg)
     quantized, info = m(xt)
     assert set(info) == {"indices", "entropy_aux_loss", "per_sample_entropy", "codebook_entropy"}
     assert "BSQTrainFn" not in type(info["entropy_aux_loss"].grad_fn).__name__
-    ((quantized * torch.from_numpy(w)).sum() + float(d[f"{tag}_g_aux"]) * info["entropy_aux_loss"]).backward()
+    ((quantized * torch.from_numpy(w)).sum() + g_aux * info["entropy_aux_loss"]).backward()
+    return quantized.detach().numpy(), info, xt.grad.numpy()
+
+
+@pytest.mark.parametrize("tag", list(R.BSQ_CASES))
+def test_cpu_bsq_train_step_lands_on_the_fixture(tag, monkeypatch):
+    """A CPU tensor keeps the torch branch.  That branch asks the library for the sign pack, which has no CPU implementation: numpy
+    answers in its place, so what is checked is the differentiable glue -- the indices bit for bit, quantized within its three
+    roundings, the scalars and grad_x within twice the reference's own fp32 error."""
+    d, cfg = _bsq(), R.BSQ_CASES[tag]
+    x, w = _inputs(d, tag)
+    quantized, info, grad = _cpu_bsq_step(cfg, x, w, float(d[f"{tag}_g_aux"]), monkeypatch)
     assert np.array_equal(info["indices"].numpy(), d[f"{tag}_indices"])
     qs = 1.0 / np.sqrt(16 * cfg["d"])
-    assert np.all(np.abs(quantized.detach().numpy() - d[f"{tag}_quantized"]) <= 6 * R.U * qs)
+    assert np.all(np.abs(quantized - d[f"{tag}_quantized"]) <= 6 * R.U * qs)
     for name in R.SCALARS:
         got = R.err_units(float(info[name].detach()), float(d[f"{tag}_{name}64"]), float(d[f"{tag}_{name}_abs"]))
         assert got <= 2.0 * float(d[f"{tag}_{name}_ref_err"]) + 2.0, (name, got)
-    got = R.err_units(xt.grad.numpy(), d[f"{tag}_grad_x64"], d[f"{tag}_grad_x_abs"])
+    got = R.err_units(grad, d[f"{tag}_grad_x64"], d[f"{tag}_grad_x_abs"])
+    assert got <= 2.0 * float(d[f"{tag}_grad_x_ref_err"]) + 2.0, got
+
+
+# ---- g29: the "blc" kernel pairs the cases above never launch (R.BSQ_VARIANT_CASES) ------------------------------------------------
+G29 = os.path.join(G, "g29_bsq_train_variants.npz")
+
+
+def test_bsq_variant_fixture_loads_and_is_complete():
+    d = np.load(G29)
+    for tag, cfg in R.BSQ_VARIANT_CASES.items():
+        x, w = _inputs(d, tag)
+        assert x.shape == cfg["shape"] == w.shape and x.shape[1 if cfg["format"] == "bchw" else 2] == 16 * cfg["d"]
+        assert d[f"{tag}_x"].dtype == np.float16 and d[f"{tag}_indices"].dtype == np.int64 and np.isfinite(x).all()
+        assert d[f"{tag}_indices"].size * 16 == x.size and float(d[f"{tag}_g_aux"]) == R.G_AUX
+        for name in R.SCALARS:
+            assert float(d[f"{tag}_{name}_ref_err"]) >= 0.0 and float(d[f"{tag}_{name}_abs"]) > 0.0
+            assert np.isfinite(float(d[f"{tag}_{name}64"])) and d[f"{tag}_{name}"].dtype == np.float32
+        assert float(d[f"{tag}_grad_x_ref_err"]) > 0.0
+    blc = {c["d"] for c in list(R.BSQ_VARIANT_CASES.values()) + list(R.BSQ_CASES.values()) if c["format"] == "blc" or c.get("channels_last")}
+    assert set(range(5, 16)) - {7} <= blc                                             # (d = 7 and 16 run in the GPU test's MULTI)
+    assert os.path.getsize(G29) < (400 << 10)
+
+
+@pytest.mark.parametrize("tag", list(R.BSQ_VARIANT_CASES))
+def test_bsq_checker_reproduces_the_variant_fixture(tag):
+    """The checker equals the reference's fp64 scalars to 1e-12 and lies within ref_err of its fp32 run; g29 holds no grad_x64 (the
+    generator asserted the checker's against the reference's fp64 autograd to 1e-12 of the sum of |terms|)."""
+    d, cfg = np.load(G29), R.BSQ_VARIANT_CASES[tag]
+    x, w = _inputs(d, tag)
+    s = R.bsq64(x, cfg, w, float(d[f"{tag}_g_aux"]))
+    for name in R.SCALARS:
+        v64 = float(d[f"{tag}_{name}64"])
+        assert abs(s[name] - v64) <= 1e-12 * max(abs(v64), s[name + "_abs"])
+        assert abs(s[name + "_abs"] - float(d[f"{tag}_{name}_abs"])) <= 1e-12 * s[name + "_abs"]
+        assert R.err_units(d[f"{tag}_{name}"], s[name], s[name + "_abs"]) <= float(d[f"{tag}_{name}_ref_err"]) * (1 + 1e-6) + 1e-6
+    assert np.array_equal(s["indices"], d[f"{tag}_indices"])
+    assert np.isfinite(s["grad_x"]).all() and (s["grad_x_abs"] > 0).all()
+
+
+@pytest.mark.parametrize("tag", list(R.BSQ_VARIANT_CASES))
+def test_cpu_bsq_train_step_lands_on_the_variant_fixture(tag, monkeypatch):
+    """The three checks of test_cpu_bsq_train_step_lands_on_the_fixture at the new widths; quantized against +-q_scale."""
+    d, cfg = np.load(G29), R.BSQ_VARIANT_CASES[tag]
+    x, w = _inputs(d, tag)
+    quantized, info, grad = _cpu_bsq_step(cfg, x, w, float(d[f"{tag}_g_aux"]), monkeypatch)
+    s = R.bsq64(x, cfg, w, float(d[f"{tag}_g_aux"]))
+    assert np.array_equal(info["indices"].numpy(), d[f"{tag}_indices"])
+    qs = float(np.float32(1.0 / np.sqrt(16 * cfg["d"])))
+    assert np.all(np.abs(quantized - np.where(s["u"] > 0, qs, -qs)) <= 3 * R.U * qs)
+    for name in R.SCALARS:
+        got = R.err_units(float(info[name].detach()), float(d[f"{tag}_{name}64"]), float(d[f"{tag}_{name}_abs"]))
+        assert got <= 2.0 * float(d[f"{tag}_{name}_ref_err"]) + 2.0, (name, got)
+    got = R.err_units(grad, s["grad_x"], s["grad_x_abs"])
     assert got <= 2.0 * float(d[f"{tag}_grad_x_ref_err"]) + 2.0, got
 
 

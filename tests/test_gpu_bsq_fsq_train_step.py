@@ -5,7 +5,13 @@ tests/bsq_fsq_train_ref.py (proven on the CPU by tests/test_bsq_fsq_train_host.p
 
 Bounds: per case and per output, 2 x max(the error the reference's own fp32 run shows against its fp64 run -- {name}_ref_err in the
 fixture, in units of 2^-24 x sum of |terms| --, 1 unit); the factor 2 covers a different summation order over rows, the 1-unit floor
-the one rounding of u to fp32 that the fp64 run does not have.  Every case prints its figures before asserting."""
+the one rounding of u to fp32 that the fp64 run does not have.  Every case prints its figures before asserting.
+
+Section 12 launches the "blc" kernel pairs g26's widths leave out (<16, 3> at d = 9 .. 12, the partly idle last chunk of <16, 2> and
+<16, 4>) and "bchw" at d = 9 and 15, from g29 (R.BSQ_VARIANT_CASES; tests/golden/make_golden_train_variants.py), under the same rule
+``_bound``: the reference's own error there is 2.2 .. 5.7 units on grad_x and 0.03 .. 3.6 on the scalars, a gate of 4.4 .. 11.5 and
+2 .. 7.1 units.  Measured (profiles/r27/gpu_new_tests.txt): grad_x 0.60 .. 0.84 units, with g_aux alone 0.37 .. 0.77, scalars 0.00 ..
+0.78."""
 import itertools
 import os
 
@@ -317,3 +323,87 @@ def test_channels_last_input_gets_its_gradient_in_channels_last_memory(family, b
     assert g0.is_contiguous() and g1.is_contiguous(memory_format=torch.channels_last) and not g1.is_contiguous()
     assert q1.is_contiguous(memory_format=torch.channels_last) and xc.data_ptr() == ptr
     assert torch.equal(g0, g1) and torch.equal(q0, q1) and torch.equal(i0["indices"], i1["indices"])
+
+
+# ------------------------------------------------------------------------------------------ 12. every "blc" kernel pair (g29)
+@pytest.fixture(scope="module")
+def g29():
+    return dict(np.load(os.path.join(G, "g29_bsq_train_variants.npz")))
+
+
+@pytest.mark.parametrize("tag", list(R.BSQ_VARIANT_CASES))
+def test_bsq_variant_against_fp64(tag, g29):
+    """indices bit for bit, quantized within its three roundings, avg rounded once, the scalars and grad_x (with both gradients,
+    and with g_aux alone) within _bound of the case's own reference error.  g29 holds no grad_x64: it is the checker's, which its
+    generator held against the reference's fp64 autograd."""
+    from pit_hip import _lib
+
+    d, cfg = g29, R.BSQ_VARIANT_CASES[tag]
+    x, w = _in(d[f"{tag}_x"], cfg), _in(d[f"{tag}_w"], cfg)
+    xv, layout = _lib_view(x, cfg)
+    wv = _lib_view(w, cfg)[0]
+    x_np, w_np = d[f"{tag}_x"].astype(np.float32), d[f"{tag}_w"].astype(np.float32)
+    full, aux = R.bsq64(x_np, cfg, w_np, R.G_AUX), R.bsq64(x_np, cfg, None, R.G_AUX)
+    ws = _lib.BsqTrainWorkspace()
+    q, ind, avg, scal = _lib.bsq_train(xv, cfg["d"], layout, 1.0, 1.0, ws)
+    g_full = _lib.bsq_backward(xv, avg, cfg["d"], layout, 1.0, 1.0, g_q=wv, g_aux=_scalar(R.G_AUX), ws=ws)
+    g_aux = _lib.bsq_backward(xv, avg, cfg["d"], layout, 1.0, 1.0, g_aux=_scalar(R.G_AUX), ws=ws)
+    scal = scal.cpu().numpy()
+    errs = {name: R.err_units(scal[i], float(d[f"{tag}_{name}64"]), float(d[f"{tag}_{name}_abs"])) for i, name in enumerate(R.SCALARS)}
+    bounds = {name: _bound(d[f"{tag}_{name}_ref_err"]) for name in R.SCALARS}
+    errs["grad_x"] = R.err_units(_home(g_full, x, cfg), full["grad_x"], full["grad_x_abs"])
+    errs["grad_x_aux_only"] = R.err_units(_home(g_aux, x, cfg), aux["grad_x"], aux["grad_x_abs"])
+    bounds["grad_x"] = bounds["grad_x_aux_only"] = _bound(d[f"{tag}_grad_x_ref_err"])
+    for name, e in errs.items():
+        print(f"{tag}: {name} {e:.2f} units (bound {bounds[name]:.2f})")
+    assert layout == ("bchw" if tag in ("bchw_d9", "bchw_d15") else "blc")
+    assert np.array_equal(_home(ind, x, cfg), d[f"{tag}_indices"])
+    qs = float(np.float32(1.0 / np.sqrt(16 * cfg["d"])))
+    assert np.all(np.abs(_home(q, x, cfg) - np.where(full["u"] > 0, qs, -qs)) <= 3.0 * R.U * qs)
+    assert np.all(np.abs(avg.cpu().numpy() - full["avg"]) <= R.U * full["avg"] + 1e-45)          # each entry rounded once
+    for name, e in errs.items():
+        assert e <= bounds[name], (name, e)
+
+
+@pytest.mark.parametrize("tag", ["blc_d10", "blc_d14"])
+def test_bsq_variant_runs_are_bitwise_equal_whatever_the_workspace_holds(tag, g29):
+    from pit_hip import _lib
+
+    cfg = R.BSQ_VARIANT_CASES[tag]
+    x, w = _in(g29[f"{tag}_x"], cfg), _in(g29[f"{tag}_w"], cfg)
+    runs = []
+    for fill in (None, 0xFF, 0):                                          # the workspace's contents are don't-care on entry
+        ws = _lib.BsqTrainWorkspace()
+        if fill is not None:
+            ws.get(x.shape[0] * x.shape[1], cfg["d"], torch.device(DEV))
+            ws.buf.fill_(fill)
+        q, _, avg, scal = _lib.bsq_train(x, cfg["d"], "blc", 1.0, 1.0, ws)
+        gx = _lib.bsq_backward(x, avg, cfg["d"], "blc", 1.0, 1.0, g_q=w, g_aux=_scalar(R.G_AUX), ws=ws)
+        runs.append((avg.clone(), scal.clone(), q.clone(), gx.clone()))
+    print(tag, "scalars", runs[0][1].tolist())
+    assert all(torch.equal(a, b) and torch.equal(a, c) for a, b, c in zip(*runs))
+    assert all(bool(torch.isfinite(t).all()) for t in runs[0])
+
+
+def test_bsq_module_route_at_d10_channels_last(g29, opt_in):
+    """BSQQuantizer("bchw", 2^10, 16) on an NHWC tensor takes the <16, 3> "blc" pair through the autograd function; x.grad has x's
+    strides and equals the direct library call bit for bit."""
+    from pit_hip import _lib
+
+    tag = "bchw_d10_cl"
+    cfg = R.BSQ_VARIANT_CASES[tag]
+    m = _bsq_module(cfg).train()
+    x, w = _in(g29[f"{tag}_x"], cfg).requires_grad_(True), _in(g29[f"{tag}_w"], cfg)
+    q, info = m(x)
+    assert _made_by(q, "BSQTrainFn") and "BSQTrainFn" in type(info["entropy_aux_loss"].grad_fn).__name__
+    ((q * w).sum() + R.G_AUX * info["entropy_aux_loss"]).backward()
+    xv, layout = _lib_view(x.detach(), cfg)
+    ws = _lib.BsqTrainWorkspace()
+    ql, il, avg, scal = _lib.bsq_train(xv, 10, layout, 1.0, 1.0, ws)
+    gl = _lib.bsq_backward(xv, avg, 10, layout, 1.0, 1.0, g_q=_lib_view(w, cfg)[0], g_aux=_scalar(R.G_AUX), ws=ws)
+    print(f"{tag}: x strides {x.stride()} grad strides {x.grad.stride()} max |grad| {float(x.grad.abs().max()):.4f}")
+    assert layout == "blc" and not x.is_contiguous() and x.grad.shape == x.shape and x.grad.stride() == x.stride()
+    assert np.array_equal(x.grad.cpu().numpy().view(np.int32), _home(gl, x.detach(), cfg).view(np.int32))
+    assert np.array_equal(q.detach().cpu().numpy(), _home(ql, x.detach(), cfg))
+    assert np.array_equal(info["indices"].cpu().numpy(), _home(il, x.detach(), cfg))
+    assert [float(info[k].detach()) for k in R.SCALARS] == scal.tolist()

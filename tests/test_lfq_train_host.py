@@ -1,7 +1,7 @@
 """CPU: the host half of LFQQuantizer's fused train step -- the three entry points exist, are bound and validate their arguments
 before any HIP call, the fixture g25 loads, the fp64 checker the GPU tests rely on (tests/lfq_train_ref.py) agrees with the dense
 [R, N] formula, with the reference's fp64 autograd and with a central difference, and a CPU LFQQuantizer step (the torch branch,
-which CPU tensors keep) equals the fixture."""
+which CPU tensors keep) equals the fixture.  The same for g28, the fixture of the kernel variants g25 leaves out."""
 import ctypes
 import inspect
 import os
@@ -167,11 +167,8 @@ def test_checker_against_a_central_difference():
         assert abs(num - s["grad_x"][i]) <= 1e-5 * max(s["grad_x_abs"][i], 1e-3), (i, num, s["grad_x"][i])
 
 
-@pytest.mark.parametrize("tag", list(R.CASES))
-def test_cpu_module_train_step_equals_the_fixture(tag, monkeypatch):
-    """A CPU tensor keeps the torch branch.  That branch asks the library for the sign pack, which has no CPU implementation: numpy
-    answers in its place, so what is checked is the differentiable glue -- quantized and the indices bit for bit, the scalars and
-    grad_x within twice the reference's own fp32 error (torch's CPU softmax is the reference's)."""
+def _cpu_module_step(cfg, x, w, g_aux, g_commit, monkeypatch):
+    """One train step of the CPU module under autograd: (quantized, info, x.grad)."""
     from pit_hip import _lib as L
     from pit_hip.quantization.lfq import LFQQuantizer
 
@@ -183,8 +180,6 @@ def test_cpu_module_train_step_equals_the_fixture(tag, monkeypatch):
         return idx, torch.where(bits, 1.0, -1.0)
 
     monkeypatch.setattr(L, "lfq_pack", cpu_pack)
-    d, cfg = _fixture(), R.CASES[tag]
-    x, w = _inputs(d, tag)
     m = LFQQuantizer(cfg["format"], 1 << cfg["d"], cfg["nc"], sample_minimization_weight=cfg.get("w_s", 1.0),
                      batch_maximization_weight=cfg.get("w_b", 1.0)).train()
     xt = torch.from_numpy(x)
@@ -194,12 +189,95 @@ def test_cpu_module_train_step_equals_the_fixture(tag, monkeypatch):
     quantized, info = m(xt)
     assert set(info) == {"indices", "entropy_aux_loss", "per_sample_entropy", "codebook_entropy", "commit_loss"}
     assert "LFQTrainFn" not in type(info["entropy_aux_loss"].grad_fn).__name__
-    ((quantized * torch.from_numpy(w)).sum() + float(d[f"{tag}_g_aux"]) * info["entropy_aux_loss"]
-     + float(d[f"{tag}_g_commit"]) * info["commit_loss"]).backward()
+    ((quantized * torch.from_numpy(w)).sum() + g_aux * info["entropy_aux_loss"] + g_commit * info["commit_loss"]).backward()
+    return quantized.detach().numpy(), info, xt.grad.numpy()
+
+
+@pytest.mark.parametrize("tag", list(R.CASES))
+def test_cpu_module_train_step_equals_the_fixture(tag, monkeypatch):
+    """A CPU tensor keeps the torch branch.  That branch asks the library for the sign pack, which has no CPU implementation: numpy
+    answers in its place, so what is checked is the differentiable glue -- quantized and the indices bit for bit, the scalars and
+    grad_x within twice the reference's own fp32 error (torch's CPU softmax is the reference's)."""
+    d, cfg = _fixture(), R.CASES[tag]
+    x, w = _inputs(d, tag)
+    quantized, info, grad = _cpu_module_step(cfg, x, w, float(d[f"{tag}_g_aux"]), float(d[f"{tag}_g_commit"]), monkeypatch)
     assert np.array_equal(info["indices"].numpy(), d[f"{tag}_indices"])
-    assert np.array_equal(quantized.detach().numpy(), d[f"{tag}_quantized"])
+    assert np.array_equal(quantized, d[f"{tag}_quantized"])
     for name in R.SCALARS:
         got = R.err_units(float(info[name].detach()), float(d[f"{tag}_{name}64"]), float(d[f"{tag}_{name}_abs"]))
         assert got <= 2.0 * float(d[f"{tag}_{name}_ref_err"]) + 2.0, (name, got)
-    got = R.err_units(xt.grad.numpy(), d[f"{tag}_grad_x64"], d[f"{tag}_grad_x_abs"])
+    got = R.err_units(grad, d[f"{tag}_grad_x64"], d[f"{tag}_grad_x_abs"])
+    assert got <= 2.0 * float(d[f"{tag}_grad_x_ref_err"]) + 2.0, got
+
+
+# ---- g28: the kernel variants the cases above never launch (R.VARIANT_CASES) -------------------------------------------------------
+G28 = os.path.join(G, "g28_lfq_train_variants.npz")
+
+
+def _vinputs(d, tag):
+    return R.variant(d, tag, "x").astype(np.float32), R.variant(d, tag, "w").astype(np.float32)
+
+
+def _indices(x, cfg):
+    """The big-endian pack of a position's nc d sign bits, in the module's shape."""
+    bits = (R.to_rows(x, cfg)[0] > 0).reshape(-1, cfg["d"] * cfg["nc"])
+    want = np.zeros(bits.shape[0], np.int64)
+    for i in range(bits.shape[1]):
+        want = want * 2 + bits[:, i]
+    return want
+
+
+def test_variant_fixture_loads_and_is_complete():
+    d = np.load(G28)
+    widths = set()
+    for tag, cfg in R.VARIANT_CASES.items():
+        x, w = _vinputs(d, tag)
+        assert x.shape == cfg["shape"] == w.shape == R.variant(d, tag, "grad_x64").shape
+        assert R.variant(d, tag, "x").dtype == np.float16 and d[f"{tag}_indices"].dtype == np.int64 and np.isfinite(x).all()
+        assert R.variant(d, tag, "grad_x64").dtype == np.float64
+        assert d[f"{tag}_indices"].size * cfg["d"] * cfg["nc"] == x.size
+        assert float(d[f"{tag}_g_aux"]) == R.G_AUX and float(d[f"{tag}_g_commit"]) == R.G_COMMIT
+        for name in R.SCALARS:
+            assert float(d[f"{tag}_{name}_ref_err"]) >= 0.0 and float(d[f"{tag}_{name}_abs"]) > 0.0
+            assert np.isfinite(float(d[f"{tag}_{name}64"])) and d[f"{tag}_{name}"].dtype == np.float32
+        assert float(d[f"{tag}_grad_x_ref_err"]) > 0.0
+        widths.add(cfg["d"])
+    assert widths | {c["d"] for c in R.CASES.values()} == set(range(1, 17))          # every code width has a fixture case
+    assert np.array_equal(_vinputs(d, "blc_d13x4")[0].reshape(-1), _vinputs(d, "blc_d13")[0].reshape(-1))
+    assert os.path.getsize(G28) < (400 << 10)
+
+
+@pytest.mark.parametrize("tag", list(R.VARIANT_CASES))
+def test_checker_reproduces_the_variant_fixture(tag):
+    """As test_checker_reproduces_the_fixture; g28 stores neither quantized nor grad_x_abs, the rules state them."""
+    d, cfg = np.load(G28), R.VARIANT_CASES[tag]
+    x, w = _vinputs(d, tag)
+    s = R.factorised64(x, cfg, w, float(d[f"{tag}_g_aux"]), float(d[f"{tag}_g_commit"]))
+    for name in R.SCALARS:
+        v64 = float(d[f"{tag}_{name}64"])
+        assert abs(s[name] - v64) <= 1e-12 * max(abs(v64), s[name + "_abs"])
+        assert abs(s[name + "_abs"] - float(d[f"{tag}_{name}_abs"])) <= 1e-12 * s[name + "_abs"]
+        assert R.err_units(d[f"{tag}_{name}"], s[name], s[name + "_abs"]) <= float(d[f"{tag}_{name}_ref_err"]) * (1 + 1e-6) + 1e-6
+    assert np.all(np.abs(s["grad_x"] - R.variant(d, tag, "grad_x64")) <= 1e-7 * s["grad_x_abs"])
+    if cfg["d"] <= 12:
+        dn = R.dense64(x, cfg)
+        for name in R.SCALARS:
+            assert abs(s[name] - dn[name]) <= 1e-12 * max(abs(dn[name]), dn[name + "_abs"]), name
+    assert np.array_equal(d[f"{tag}_indices"].reshape(-1), _indices(x, cfg))
+
+
+@pytest.mark.parametrize("tag", list(R.VARIANT_CASES))
+def test_cpu_module_train_step_equals_the_variant_fixture(tag, monkeypatch):
+    """The three checks of test_cpu_module_train_step_equals_the_fixture at the new widths; quantized is x + (q - x) in fp32, which
+    the generator asserted of the reference's."""
+    d, cfg = np.load(G28), R.VARIANT_CASES[tag]
+    x, w = _vinputs(d, tag)
+    quantized, info, grad = _cpu_module_step(cfg, x, w, float(d[f"{tag}_g_aux"]), float(d[f"{tag}_g_commit"]), monkeypatch)
+    assert np.array_equal(info["indices"].numpy(), d[f"{tag}_indices"])
+    assert np.array_equal(quantized, x + (np.where(x > 0, 1.0, -1.0).astype(np.float32) - x))
+    for name in R.SCALARS:
+        got = R.err_units(float(info[name].detach()), float(d[f"{tag}_{name}64"]), float(d[f"{tag}_{name}_abs"]))
+        assert got <= 2.0 * float(d[f"{tag}_{name}_ref_err"]) + 2.0, (name, got)
+    s = R.factorised64(x, cfg, w, float(d[f"{tag}_g_aux"]), float(d[f"{tag}_g_commit"]))
+    got = R.err_units(grad, R.variant(d, tag, "grad_x64"), s["grad_x_abs"])
     assert got <= 2.0 * float(d[f"{tag}_grad_x_ref_err"]) + 2.0, got
