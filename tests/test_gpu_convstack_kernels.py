@@ -142,7 +142,7 @@ def test_gn_act_bound_is_a_bound_and_unet_agrees_with_fp32_gemms():
     x[0, 5, 3, 3] = 1e4                                  # one outlier: the worst case of the bound
     with torch.no_grad():
         y = U._norm_act(norm, x.contiguous(memory_format=torch.channels_last))
-    assert float(y.abs().max()) <= U._gn_act_bound(norm, x) and y._act_bound == U._gn_act_bound(norm, x)
+    assert float(y.abs().max()) <= U._gn_act_bound(norm, x) and U._left_bound(y) == U._gn_act_bound(norm, x)
     cfg = dict(ch=128, out_ch=3, in_channels=3, resolution=64, z_channels=16, double_z=True, ch_mult=[1, 2, 4, 4],
                num_res_blocks=2, attn_resolutions=[8], dropout=0.0)
     dec = U.Decoder(**cfg).eval().to(DEV).to(memory_format=torch.channels_last)
@@ -180,7 +180,7 @@ def test_fused_groupnorm_transforms_bit_identical_on_the_f16_routes():
         with torch.no_grad():
             for f4 in (False, True):
                 Uw = U._wino_weights(conv, f4)
-                f16 = U._f16_args_gn(conv, norm, x, f4)
+                f16 = U._f16_args(conv, x, f4, norm)
                 for pre in (None, pb):
                     stats = _lib.gn_stats(x, 32, pre)
                     gn = (norm.weight, norm.bias, 32, 1e-6, True, stats, pre)
@@ -472,7 +472,7 @@ def test_upconv2x_direct_matches_fp64():
         if outlier:
             x[1, 7, 3, 5] = outlier     # the device-side scale comes from a rigorous bound: no overflow, same accuracy elsewhere
         x = x.contiguous(memory_format=torch.channels_last)
-        x._gn_stats = (_lib.gn_stats(x, 32), 32)
+        U._leave_stats(x, _lib.gn_stats(x, 32), 32)
         with torch.no_grad():
             ref = F.conv2d(F.interpolate(x.double(), scale_factor=2.0, mode="nearest"), up.conv.weight.double(),
                            up.conv.bias.double(), 1, 1)
@@ -493,7 +493,7 @@ def test_upconv2x_direct_matches_fp64():
         # three products of 22-bit splits over 4 x 4 Cin terms (measured 5.6-8.0e-6); with the 3e4 outlier both routes carry its
         # rounding (the error is quoted against mean |y|, the outlier's own products are ~1e4 times that)
         assert e_dir <= (1.2e-5 if not outlier else 3.0 * e_lib + 1e-6), (e_dir, e_lib)
-        st, groups = y_dir._gn_stats
+        st, groups = U._left_stats(y_dir, 32), 32
         assert groups == 32 and torch.allclose(_lib.gn_stats_values(st), _lib.gn_stats_values(_lib.gn_stats(y_dir.contiguous(memory_format=torch.channels_last), 32)), rtol=1e-6, atol=1e-3)
     # shapes the kernel does not tile are refused by the binding (the module then upsamples and convolves)
     wf, us = _lib.upconv_weights_f16(torch.randn(4 * 128, 4 * 128, device=DEV), 128, 128)

@@ -48,12 +48,14 @@ def _stv(stats):
 def _stats_follow_output(y, what):
     """The GroupNorm statistics a kernel leaves with its output are sums over THAT output (shifted fp64 partial sums per thread,
     exact integer accumulation across threads): relative 2e-6 of the sum of magnitudes."""
-    st = getattr(y, "_gn_stats", None)
+    from pit_hip.modules import unet as U
+
+    st = U._left_stats(y, U.GN_GROUPS)
     assert st is not None, what
     y64 = R.d64(y)
-    got = _stv(st[0]).double()
-    want = R.stats_of(y64, st[1])
-    mag = R.stats_of(y64.abs(), st[1])
+    got = _stv(st).double()
+    want = R.stats_of(y64, U.GN_GROUPS)
+    mag = R.stats_of(y64.abs(), U.GN_GROUPS)
     assert float(((got - want).abs() / (mag + 1e-30)).max()) <= 2e-6, what
 
 
@@ -256,7 +258,7 @@ def test_shortcut_and_attention_pointwise_routes_each_match_fp64():
                 ref, bound = R.attn_ref_and_bound(ta, R.d64(xa), c_proj=cs)
                 ya = att(xa)
                 R.bound_gate(ya, ref, bound, f"AttnBlock 512 at 16 x 16, 1x1 {'own' if own else 'library'}")
-                if getattr(ya, "_gn_stats", None) is not None:
+                if U._left_stats(ya, U.GN_GROUPS) is not None:
                     _stats_follow_output(ya, "AttnBlock statistics")
 
 
@@ -418,7 +420,7 @@ def test_winograd_fused_tail_and_unfused_each_match_fp64():
                 y0, stats0 = _lib.add_bias_stats(res, _lib.wino_conv3x3(x, Uw), bias, 32)
                 for name, yy, st in (("fused tail", y, stats), ("plain + add_bias_stats", y0, stats0)):
                     R.lin_gate(yy, ref, mag, c, f"Winograd F({4 if f4 else 2},3) {cin}->{cout}, {name}")
-                    yy._gn_stats = (st, 32)
+                    U._leave_stats(yy, st, 32)
                     _stats_follow_output(yy, name)
 
 

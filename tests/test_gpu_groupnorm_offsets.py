@@ -292,11 +292,11 @@ def test_direct_conv_epilogue_statistics_on_offset_groups():
             up.conv.weight.mul_(0.2)
             up.conv.bias.copy_(_conv_out_offsets(ch, ch + 3).to(DEV))
         x = _cl(torch.randn(B, ch, H, W, device=DEV))
-        x._gn_stats = (_lib.gn_stats(x, 32), 32)
+        U._leave_stats(x, _lib.gn_stats(x, 32), 32)
         with torch.no_grad(), switch(DIRECT_UPCONV=True):
             y, pb = up(x)
         assert pb is None
-        st, groups = y._gn_stats
+        st, groups = U._left_stats(y, 32), 32
         check_record(st, y, groups, f"upconv2x_direct {ch} ch {H}x{W}")
 
 

@@ -33,7 +33,7 @@ for cin in (128, 256):
         sc = torch.nn.functional.conv2d(xn.double().abs(), conv.weight.double().abs(), None, 1, 1)
         err = float(((y.double() - ref).abs() / sc).max())
         yw, _ = _lib.wino_conv3x3(x, U._wino_weights(conv, False), gn=gn, residual=res, bias=conv.bias, stats_groups=32,
-                                  f16=U._f16_args_gn(conv, norm, x, False))
+                                  f16=U._f16_args(conv, x, False, norm))
         errw = float(((yw.double() - ref).abs() / sc).max())
         st_ref = torch.stack([ref.reshape(2, 32, 4, -1).sum((2, 3)), (ref ** 2).reshape(2, 32, 4, -1).sum((2, 3))], -1).flatten()
         print(f"Cin {cin}: direct max err {err:.2e} of sum|x||w| (Winograd F2 route {errw:.2e}); max abs diff {float((y.double()-ref).abs().max()):.2e}; "

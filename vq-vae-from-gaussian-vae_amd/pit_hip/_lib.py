@@ -12,7 +12,7 @@ import threading
 import math
 import os
 import subprocess
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -917,6 +917,32 @@ def _split_f16(w):
     return hi, (ws - hi.float()).half(), u_scale
 
 
+class GnFold(NamedTuple):
+    """The ``gn`` argument of the conv-stack wrappers: the GroupNorm (+ SiLU) a kernel applies to x + pre_bias while it stages
+    it.  ``stats``: the statistics records of x + pre_bias (gn_stats, or what the producer of x left).  A plain 7-tuple in
+    this order is taken as one."""
+    gamma: Optional[torch.Tensor]
+    beta: Optional[torch.Tensor]
+    groups: int
+    eps: float
+    silu: bool
+    stats: Optional[torch.Tensor]
+    pre_bias: Optional[torch.Tensor]
+
+
+_NO_GN = GnFold(None, None, 1, 0.0, False, None, None)    # what the kernels with an optional GroupNorm get without one
+
+
+class F16Gemm(NamedTuple):
+    """The ``f16`` argument of wino_conv3x3: U3 [T, 3 Cin, Cout] fp16 = [U_h; U_l; U_h] of U * u_scale, ``bound`` >= max|tensor
+    the input transform sees|, ``wf2``: (U_h, U_l) in wino_gemm_f16x2's operand order (wino_weights_operand_order) or None.
+    A plain 3- or 4-tuple in this order is taken as one."""
+    U3: torch.Tensor
+    u_scale: float
+    bound: float
+    wf2: Optional[torch.Tensor] = None
+
+
 def gn_silu(x, gamma, beta, groups: int, eps: float, silu: bool = True, pre_bias=None):
     """Fused GroupNorm(+SiLU) on an NCHW or channels_last fp32 HIP tensor (see gqhip.h:gn_silu_f32)."""
     layout = image_layout(x)
@@ -1004,13 +1030,13 @@ def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0,
     """3x3 stride-1 padding-1 convolution of a channels_last fp32 HIP tensor by Winograd F(2x2, 3x3) in three stages (input
     transform, GEMMs, output transform):
     U [16, Cin, Cout] = G g G^T (see unet._wino_weights).  Returns [B, Cout, H, W] channels_last, no bias.
-    ``gn`` = (gamma, beta, groups, eps, silu, stats, pre_bias): the convolution's input is SiLU(GroupNorm(x + pre_bias)),
+    ``gn`` (a GnFold): the convolution's input is SiLU(GroupNorm(x + pre_bias)),
     applied inside the input transform (the normalised tensor is never materialised).
     ``stats_groups`` > 0: the output transform also adds bias[c] (+ ``residual``) and returns
     (y, GroupNorm statistics of y) -- the tail of a ResnetBlock, or conv1 + the statistics norm2 needs, in one pass.
-    ``f16`` = (U3, u_scale, x_bound): run the 16 / 36 GEMMs as ONE fp16 batched GEMM with fp32 accumulation over a K axis
+    ``f16`` (an F16Gemm: U3, u_scale, bound[, wf2]): run the 16 / 36 GEMMs as ONE fp16 batched GEMM with fp32 accumulation over a K axis
     that carries the three products of two-term fp16 splits (see gqhip.h:wino_in_nhwc_f16x3): U3 [T, 3 Cin, Cout] fp16 =
-    [U_h; U_l; U_h] of U * u_scale, x_bound >= max|x| (guarantees the scaled transform stays inside fp16's range)."""
+    [U_h; U_l; U_h] of U * u_scale, bound >= max|x| (guarantees the scaled transform stays inside fp16's range)."""
     _need_nhwc("wino_conv3x3", x, c=4, h=2, w=2)
     B, C, H, W = x.shape
     T, cout = U.shape[0], U.shape[2]
@@ -1024,12 +1050,12 @@ def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0,
     # as the three planes the library's K-concatenated GEMM wants (3 C wide)
     planes, v_scale, mscale = 0, 1.0, 1.0
     if f16 is not None:
-        U3, u_scale, x_bound = f16[:3]
-        # |B^T d B| <= amp * max|d| (amp = squared max abs row sum of B^T: 100 for F(4x4,3x3), 4 for F(2x2,3x3)); with gn, x_bound
-        # bounds SiLU(GroupNorm(x)), the tensor the transform actually sees
-        v_scale = _pow2_scale(x_bound, 100.0 if f4 else 4.0)
-        use_own = len(f16) > 3 and f16[3] is not None and tiles % 256 == 0 and own_gemm_fits(T, tiles, cout, C)
-        planes, mscale = 2 if use_own else 3, 1.0 / (v_scale * u_scale)
+        f16 = F16Gemm(*f16)
+        # |B^T d B| <= amp * max|d| (amp = squared max abs row sum of B^T: 100 for F(4x4,3x3), 4 for F(2x2,3x3)); with gn, the
+        # bound is that of SiLU(GroupNorm(x)), the tensor the transform actually sees
+        v_scale = _pow2_scale(f16.bound, 100.0 if f4 else 4.0)
+        use_own = f16.wf2 is not None and tiles % 256 == 0 and own_gemm_fits(T, tiles, cout, C)
+        planes, mscale = 2 if use_own else 3, 1.0 / (v_scale * f16.u_scale)
     L = lib()
     with torch.cuda.device(x.device):
         # 1. input transform (with the GroupNorm + SiLU of gn applied on the way)
@@ -1038,10 +1064,10 @@ def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0,
         # 2. the 16 / 36 GEMMs [tiles, Cin] x [Cin, Cout], fp32 accumulation
         if planes == 2:
             M = torch.empty((T, tiles, cout), dtype=torch.float32, device=x.device)
-            _check(L.wino_gemm_f16x2(V.data_ptr(), f16[3].data_ptr(), M.data_ptr(), T, tiles, C, cout, _stream()), "wino_gemm_f16x2")
+            _check(L.wino_gemm_f16x2(V.data_ptr(), f16.wf2.data_ptr(), M.data_ptr(), T, tiles, C, cout, _stream()), "wino_gemm_f16x2")
             del V                                             # (this route has always freed its operand before y is taken)
         elif planes == 3:
-            M = torch.bmm(V, U3, out_dtype=torch.float32)     # ONE fp16 GEMM per tile position
+            M = torch.bmm(V, f16.U3, out_dtype=torch.float32)     # ONE fp16 GEMM per tile position
         else:
             M = torch.bmm(V, U)                               # hipBLASLt
         # 3. output transform (with bias, residual and the statistics of the result when asked for)
@@ -1070,9 +1096,9 @@ def _wino_in(L, x, V, gn, t: int, planes: int, v_scale: float) -> None:
     else:
         name = {0: "wino4_in_gn_nhwc_f32" if t == 4 else "wino_in_gn_nhwc_f32", 2: "wino_in_gn_nhwc_f16x2",
                 3: "wino_in_gn_nhwc_f16x3"}[planes]
-        gamma, beta, groups, eps, silu, stats, pre_bias = gn
-        rc = getattr(L, name)(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(), V.data_ptr(), B, H, W,
-                              C, groups, float(eps), 1 if silu else 0, *f16_args, _stream())
+        gn = GnFold(*gn)
+        rc = getattr(L, name)(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
+                              V.data_ptr(), B, H, W, C, gn.groups, float(gn.eps), 1 if gn.silu else 0, *f16_args, _stream())
     _check(rc, name)
 
 
@@ -1196,25 +1222,26 @@ def conv3x3_direct(x, wf, u_scale: float, x_bound: float, gn, residual=None, bia
     _need_residual("conv3x3_direct", residual, (B, cout, H, W))
     v_scale = _pow2_scale(x_bound)
     mscale = 1.0 / (v_scale * u_scale)
-    gamma, beta, groups, eps, silu, stats, pre_bias = gn
+    gn = GnFold(*gn)
     with torch.cuda.device(x.device):
         y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
-        _check(lib().conv3x3_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(),
-                                      groups, float(eps), 1 if silu else 0, float(v_scale), wf.data_ptr(), _ptr(bias),
+        _check(lib().conv3x3_gn_f16x3(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
+                                      gn.groups, float(gn.eps), 1 if gn.silu else 0, float(v_scale), wf.data_ptr(), _ptr(bias),
                                       _ptr(residual), y.data_ptr(), _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1),
                                       mscale, _stream()), "conv3x3_gn_f16x3")
     return _y_or_both(y, ostats)
 
 
 def _conv1_args(x, wf, u_scale: float, scale, gn, post_scale: float, what: str, pre_bias=None):
-    """Shared checks of the 1x1 routes; returns _operand_scales' (device scales pointer or None, v_scale, mscale).
+    """Shared checks of the 1x1 routes (``gn``: a GnFold or None); returns _operand_scales' (device scales pointer or None,
+    v_scale, mscale).
     post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)."""
     _need_nhwc(what, x, c=32, hw=128)
     if wf.shape[0] * 16 != x.shape[1] or wf.shape[1] != 1:
         raise GqHipError(what + ": weights do not match (need conv3_weights_f16 of a [Cout, %d, 1, 1] kernel)" % x.shape[1])
-    if gn is not None and pre_bias is not None and pre_bias is not gn[6]:
-        raise GqHipError(what + ": with gn the pending bias is gn[6] (the one its statistics include); pre_bias differs from it")
-    if gn is not None and (torch.is_tensor(scale) or gn[4] or x.shape[1] > 512 or (x.shape[1] // gn[2]) % 4):
+    if gn is not None and pre_bias is not None and pre_bias is not gn.pre_bias:
+        raise GqHipError(what + ": with gn the pending bias is gn.pre_bias (the one its statistics include); pre_bias differs from it")
+    if gn is not None and (torch.is_tensor(scale) or gn.silu or x.shape[1] > 512 or (x.shape[1] // gn.groups) % 4):
         raise GqHipError(what + ": the GroupNorm variant needs a host-side bound, no SiLU, C <= 512 and 4 | channels per group")
     if torch.is_tensor(scale) and post_scale != 1.0:
         raise GqHipError(what + ": post_scale needs a host-side scale bound")
@@ -1227,9 +1254,10 @@ def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats
     with the split of x inside the kernel (gqhip.h:conv1x1_f16x3).  ``wf, u_scale`` from conv3_weights_f16 of the [Cout, Cin, 1, 1]
     kernel; ``pre_bias``: per-channel bias still pending on x (added before the split); ``scale``: a float bound >=
     max|x + pre_bias|, or the device float[2] of f16_scales(statistics of x + pre_bias, 1.0, u_scale).
-    ``gn`` = (gamma, beta, groups, eps, False, statistics of x + pre_bias, pre_bias) as for conv3x3_direct: the convolution's
+    ``gn`` (a GnFold with silu False and the statistics of x + pre_bias) as for conv3x3_direct: the convolution's
     input is GroupNorm(x + pre_bias), normalised while it is staged (gqhip.h:conv1x1_gn_f16x3); ``scale`` then bounds the
     normalised tensor."""
+    gn = None if gn is None else GnFold(*gn)
     sdev, v_scale, mscale = _conv1_args(x, wf, u_scale, scale, gn, post_scale, "conv1x1_direct", pre_bias)
     B, C, H, W = x.shape
     cout = wf.shape[2] * 32
@@ -1237,11 +1265,10 @@ def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats
     with torch.cuda.device(x.device):
         y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
         if gn is not None:
-            gamma, beta, groups, eps, _, stats, gn_pb = gn
-            _check(lib().conv1x1_gn_f16x3(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(gn_pb), stats.data_ptr(), groups,
-                                          float(eps), wf.data_ptr(), float(v_scale), float(mscale), _ptr(bias), _ptr(residual),
-                                          y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1), _stream()),
-                   "conv1x1_gn_f16x3")
+            _check(lib().conv1x1_gn_f16x3(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias),
+                                          gn.stats.data_ptr(), gn.groups, float(gn.eps), wf.data_ptr(), float(v_scale),
+                                          float(mscale), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout,
+                                          max(stats_groups, 1), _stream()), "conv1x1_gn_f16x3")
         else:
             _check(lib().conv1x1_f16x3(x.data_ptr(), _ptr(pre_bias), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias),
                                        _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1),
@@ -1254,18 +1281,19 @@ def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, 
     of attention_from_operands itself (gqhip.h:conv1x1_qkv_split_f16x3): (Q3, K3, V3), byte for byte those
     attn_split_qkv_f16x3(sq, sv) makes of the fp32 projection, which is never stored.  C % 128 == 0.  ``out``: the three
     operand tensors to fill (attention_operands' shapes, dense fp16) instead of fresh ones."""
+    gn = None if gn is None else GnFold(*gn)
     _, v_scale, mscale = _conv1_args(x, wf, u_scale, float(scale), gn, 1.0, "qkv_split_direct", pre_bias)
     B, C, H, W = x.shape
     if wf.shape[2] * 32 != 3 * C or C % 128:
         raise GqHipError("qkv_split_direct: needs the [3C, C, 1, 1] projection, C % 128 == 0")
-    gamma, beta, groups, eps, _, stats, gn_pb = gn if gn is not None else (None, None, 1, 0.0, False, None, pre_bias)
+    gn = gn if gn is not None else _NO_GN._replace(pre_bias=pre_bias)
     with torch.cuda.device(x.device):
         Q3, K3, V3 = attention_operands(B, H * W, C, x.device) if out is None else out
         for t, shape in zip((Q3, K3, V3), ((B, H * W, 3 * C), (B, H * W, 3 * C), (B, 3 * H * W, C))):
             if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape and t.is_contiguous()):
                 raise GqHipError("qkv_split_direct: out must be dense fp16 [B, L, 3C], [B, L, 3C], [B, 3L, C]")
-        _check(lib().conv1x1_qkv_split_f16x3(x.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(gn_pb), _ptr(stats), groups, float(eps),
-                                             wf.data_ptr(), float(v_scale), mscale, _ptr(bias), Q3.data_ptr(),
+        _check(lib().conv1x1_qkv_split_f16x3(x.data_ptr(), _ptr(gn.gamma), _ptr(gn.beta), _ptr(gn.pre_bias), _ptr(gn.stats),
+                                             gn.groups, float(gn.eps), wf.data_ptr(), float(v_scale), mscale, _ptr(bias), Q3.data_ptr(),
                                              K3.data_ptr(), V3.data_ptr(), float(sq), float(sv), B, H * W, C, _stream()),
                "conv1x1_qkv_split_f16x3")
     return Q3, K3, V3
@@ -1338,17 +1366,17 @@ def upconv2x_direct(x, wf, u_scale: float, scale, bias=None, stats_groups: int =
 
 def conv3x3_gn_small(x, w_ohwi, bias, gn):
     """conv3x3(SiLU(GroupNorm(x))) into 1..4 channels (gqhip.h:conv3x3_gn_small_f32): x channels_last fp32 [B, Cin, H, W],
-    w_ohwi [Cout, 3, 3, Cin] fp32 contiguous, ``gn`` = (gamma, beta, groups, eps, silu, stats, pre_bias)."""
+    w_ohwi [Cout, 3, 3, Cin] fp32 contiguous, ``gn``: a GnFold."""
     _need_nhwc("conv3x3_gn_small", x, c=32, h=16, w=16)
     B, C, H, W = x.shape
     cout = w_ohwi.shape[0]
     if tuple(w_ohwi.shape) != (cout, 3, 3, C) or not w_ohwi.is_contiguous() or w_ohwi.dtype != torch.float32:
         raise GqHipError("conv3x3_gn_small: weights must be fp32 [Cout, 3, 3, Cin] contiguous")
-    gamma, beta, groups, eps, silu, stats, pre_bias = gn
+    gn = GnFold(*gn)
     y = _out_nhwc(x, cout, H, W)
     with torch.cuda.device(x.device):
-        _check(lib().conv3x3_gn_small_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), stats.data_ptr(),
-                                          groups, float(eps), 1 if silu else 0, w_ohwi.data_ptr(), _ptr(bias), y.data_ptr(),
+        _check(lib().conv3x3_gn_small_f32(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
+                                          gn.groups, float(gn.eps), 1 if gn.silu else 0, w_ohwi.data_ptr(), _ptr(bias), y.data_ptr(),
                                           B, H, W, C, cout, _stream()), "conv3x3_gn_small_f32")
     return y
 
@@ -1391,20 +1419,17 @@ def conv_f32_weights(weight):
 
 def conv3x3_f32(x, wk, cout: int, bias=None, gn=None):
     """3x3 convolution (stride 1, padding 1) of a channels_last fp32 HIP tensor on the fp32 matrix cores with a fixed summation
-    order (gqhip.h:conv3x3_f32: bit-reproducible).  ``wk`` from conv_f32_weights; ``gn`` = (gamma, beta, groups, eps, silu, stats,
-    pre_bias): the input is act(GroupNorm(x + pre_bias)), applied while the patch is staged."""
+    order (gqhip.h:conv3x3_f32: bit-reproducible).  ``wk`` from conv_f32_weights; ``gn`` (a GnFold): the input is
+    act(GroupNorm(x + pre_bias)), applied while the patch is staged."""
     _need_nhwc("conv3x3_f32", x)
     B, C, H, W = x.shape
     if not conv_f32_ok(C, cout, H, W, gn is not None) or wk.numel() != ((cout + 31) // 32) * 9 * (C // 8) * 256:
         raise GqHipError(f"conv3x3_f32: shape {tuple(x.shape)} -> {cout} channels is not tiled by the kernel")
     y = _out_nhwc(x, cout, H, W)
-    gamma = beta = stats = pre_bias = None
-    groups, eps, silu = 1, 0.0, False
-    if gn is not None:
-        gamma, beta, groups, eps, silu, stats, pre_bias = gn
+    gn = _NO_GN if gn is None else GnFold(*gn)
     with torch.cuda.device(x.device):
-        _check(lib().conv3x3_f32(x.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(pre_bias), _ptr(stats), groups, float(eps),
-                                 1 if silu else 0, wk.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W, C, cout, _stream()),
+        _check(lib().conv3x3_f32(x.data_ptr(), _ptr(gn.gamma), _ptr(gn.beta), _ptr(gn.pre_bias), _ptr(gn.stats), gn.groups, float(gn.eps),
+                                 1 if gn.silu else 0, wk.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W, C, cout, _stream()),
                "conv3x3_f32")
     return y
 

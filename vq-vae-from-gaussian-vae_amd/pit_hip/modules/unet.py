@@ -32,25 +32,137 @@ import torch.nn.functional as F
 from .. import _lib
 
 
+# ---- switches: module-level, read at call time (tests, tools/convstack/route_trace.py and A/B timing turn them off one at a
+# time).  Which library calls each setting leaves: tests/golden/convstack_routes.json.
+GN_GROUPS = 32             # unet.py:54-57: every Normalize is GroupNorm(32, C, eps=1e-6); the groups of every statistics record left
+# libgqhip's GroupNorm(+ swish) (gn_silu / gn_apply, either layout) and, on channels_last tensors, every own convolution below
+# (_own_ok); off: ATen ops, except in the residual adds (_add) and the q | k | v projection (AttnBlock._own_qkv_ok)
+FUSED_GN = True
+DEFER_BIAS = True          # convolutions run bias-free; the consumer (next GroupNorm, residual add, kernel epilogue) folds the bias in
+FUSED_ADD_STATS = True     # residual add (and attention proj_out tail) also leaves the next GroupNorm's statistics (channels_last)
+STATS_ARENA = True         # the statistics records of a forward from one arena zeroed by one fill (not ~60 memset launches per step)
+_MAX_STATS_ARENAS = 8      # ... one arena per (thread, stream) that ran the module, the least recently used one goes
+# every inference forward of Encoder / Decoder on a HIP device checks its weight-derived caches against a content hash of the
+# parameters (catches ``param.data`` writes, which bump no version counter); see _WeightGuard
+WEIGHT_GUARD = os.environ.get("GQHIP_WEIGHT_GUARD", "1") != "0"   # (the env switch: A/B timing)
+# marked 3x3 convolutions (mark_winograd: decoder and, with WINOGRAD_ENCODER, encoder) of >= WINOGRAD_MIN_CH channels that the
+# direct kernel does not take: libgqhip's Winograd transforms around 16 (F(2x2,3x3)) or 36 (F(4x4,3x3)) GEMMs
+WINOGRAD = True
+WINOGRAD_MIN_CH = 128
+WINOGRAD_F4 = True         # convolutions marked f4 (the decoder's), H % 4 == W % 4 == 0: F(4x4,3x3) on 6x6 tiles instead of F(2x2,3x3)
+# in the encoder too (read when an Encoder is built): measured perturbation of z 4.2e-6 vs the CPU reference (direct MIOpen convs:
+# 3.4e-6), no index change on the CPU golden nor on 16 384 rows against the direct-conv encoder (tools/encoder_winograd_check.py)
+WINOGRAD_ENCODER = True
+FUSED_WINO_TAIL = True     # Winograd output transform / direct-kernel epilogue + bias + residual + next GroupNorm's statistics: one pass
+# The 16 / 36 Winograd GEMMs as ONE fp16 batched GEMM with fp32 accumulation whose K axis carries the three products of
+# two-term fp16 splits of both operands (22-bit significands): measured error 2.5-2.9e-7 of sum|a||b| against 2.6-3.5e-7
+# for hipBLASLt's fp32 GEMM (itself a split-bf16 emulation on gfx950), at 1.2x (128 channels) to 2.5x (512) its speed
+# (tools/bmm_bf16x3.py).  False: the library's fp32 GEMM.
+WINOGRAD_F16X3 = True
+# the 256- / 512-channel Winograd GEMMs through libgqhip's wino_gemm_f16x2 on the [h | l] operand (weights in MFMA
+# operand order, three products in the kernel) where its grid fills the chip (_lib.own_gemm_fits: everything but the
+# 32 x 32 levels' 36 x 1024-tile GEMMs); else the library GEMM over [h | h | l]
+WINOGRAD_OWN_GEMM = True
+# GroupNorm+SiLU applied inside the Winograd input transforms (F(2x2,3x3) / F(4x4,3x3)): the normalised tensor is never written or
+# re-read.  Bit-identical V to gn_apply + plain transform (same folded scale / shift, same silu_f32): 53.4 -> 50.8 ms / step.
+FUSED_WINO_GN = True
+FUSED_WINO_GN_F4 = True
+# 3x3 convolutions into 128 channels (256 x 256 level) -- and, where the alternative is F(2x2,3x3) (the encoder), into 256
+# channels (128 x 128 level) -- as a direct fp16 x 3 implicit GEMM instead of Winograd: reads the activation once and
+# writes the result once where Winograd moves 6.4 / 10.7 GB of transformed tensors per convolution at 256 x 256
+DIRECT_CONV = True
+DIRECT_CONV_S2 = True      # Downsample (pad + 3x3 stride 2) as an fp16 x 3 convolution on the four phase images of x
+DIRECT_CONV_1X1 = True     # 1x1 shortcut / proj_out / q | k | v convolutions as an fp16 x 3 GEMM, the split of x inside the kernel
+# Upsample: nearest x2 + conv3x3 as four 2x2 phase convolutions of the low-resolution input (2.25x fewer flops), computed directly by
+# libgqhip's upconv2x_f16x3 (one kernel); shapes it does not tile: NHWC upsample copy + the ordinary convolution routes
+DIRECT_UPCONV = True
+CONV_IN_SMALL = True       # the encoder's conv_in (3 -> 128) on libgqhip's fixed-order fp32 kernel (+ bias + statistics), not MIOpen
+FUSED_CONV_OUT = True      # decoder conv_out (128 -> 3) with norm_out + swish fused in: one VALU kernel
+# encoder conv_out (512 -> 2 z, norm_out + swish fused in) and decoder conv_in (z -> 512) on the fp32 matrix cores with a fixed
+# summation order (bit-reproducible; MIOpen's pick for the former combines split-K partial sums with atomics)
+CONV_F32 = True
+FUSED_QKV = True           # q, k, v as one GEMM with fused biases (channels_last): libgqhip's 1x1 kernel at 512 channels, else addmm
+ATTN_FUSED_PROJ = True     # GroupNorm inside the q | k | v projection's staging, the GEMM operands written by its epilogue
+ATTN_F16X3 = True          # both attention GEMMs as fp16 x 3 library GEMMs (split of q, k, v and softmax + split: libgqhip kernels)
+ATTN_MATH = "auto"         # explicit matmul/softmax/matmul instead of the fused SDPA kernel: "auto" = on HIP devices
+
+
 def _gn(ch: int) -> nn.GroupNorm:
     # unet.py:54-57
     return nn.GroupNorm(32, ch, eps=1e-6, affine=True)
 
 
-def _silu(x: torch.Tensor) -> torch.Tensor:
-    # unet.py:49-51 (x * sigmoid(x)); F.silu is the same function, one kernel.
-    return F.silu(x)
-
-
 def _infer_ok(x: torch.Tensor) -> bool:
-    """Inference on a HIP device, fp32, 4-D: what every libgqhip route asks of its input.  (FUSED_GN is not part of it: the
-    sites that consult that switch name it themselves.)"""
+    """Inference on a HIP device, fp32, 4-D: what every libgqhip route asks of its input.  (Whatever FUSED_GN says: _own_ok
+    adds that switch and the layout; _add and AttnBlock._own_qkv_ok deliberately ask this much only.)"""
     return x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and x.dim() == 4
 
 
 def _nhwc(x: torch.Tensor) -> bool:
     """Dense channels_last (and not NCHW-contiguous as well)."""
     return _lib.image_layout(x) == 1
+
+
+def _own_ok(x: torch.Tensor) -> bool:
+    """libgqhip's own convolutions apply: FUSED_GN, inference on a HIP device, fp32, 4-D, dense channels_last."""
+    return FUSED_GN and _infer_ok(x) and _nhwc(x)
+
+
+def _plain3x3(conv: nn.Module) -> bool:
+    """A Conv2d with kernel 3x3, stride 1, padding 1, dilation 1, groups 1 and zero padding."""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
+
+
+# ---- what a producer leaves on its output for the consumer: tensor attributes (ResnetBlock / AttnBlock return plain tensors; an
+# attribute does not follow a view or a copy, so its carrier is the very tensor the producer wrote).  Only these four touch them.
+def _leave_stats(y: torch.Tensor, records, groups: int, pre_bias=None, memo: bool = False) -> torch.Tensor:
+    """Tag y with the GroupNorm statistics records (``groups`` groups) its producer computed with it; returns y.  ``memo``: the
+    records were computed afterwards, for y + ``pre_bias`` (this very object, or None) -- kept apart from the producer's."""
+    if memo:
+        y._gn_stats_pb = (records, groups, pre_bias)
+    else:
+        y._gn_stats = (records, groups)
+    return y
+
+
+def _left_stats(x: torch.Tensor, groups: int, pre_bias=None, memo: bool = False):
+    """The statistics records the producer of x left, or None.  They serve only a GroupNorm of the same ``groups``, with no bias
+    pending on x, and x dense channels_last (the only layout the records' consumers take).  ``memo``: failing that, the
+    records memoised for x + this very ``pre_bias`` object."""
+    st = getattr(x, "_gn_stats", None)
+    if st is not None and pre_bias is None and st[1] == groups and _nhwc(x):
+        return st[0]
+    st = getattr(x, "_gn_stats_pb", None) if memo else None
+    return st[0] if st is not None and st[1] == groups and st[2] is pre_bias else None
+
+
+def _leave_bound(y: torch.Tensor, bound: float) -> None:
+    y._act_bound = bound   # a rigorous bound on |y| for y = swish(GroupNorm(.)) (_gn_act_bound); _left_bound: that, or None
+
+
+def _left_bound(x: torch.Tensor):
+    return getattr(x, "_act_bound", None)
+
+
+def _tagged(out):
+    """A library call's (y, statistics records of y in GN_GROUPS groups) as the modules' (y, pending_bias): y tagged, no bias."""
+    return _leave_stats(*out, GN_GROUPS), None
+
+
+def _stats_of(x: torch.Tensor, pre_bias, groups: int):
+    """GroupNorm statistics of x + pre_bias: left by the producer of x, computed earlier for the same pending bias, or
+    computed (and remembered on x) here."""
+    stats = _left_stats(x, groups, pre_bias, memo=True)
+    if stats is None:
+        stats = _lib.gn_stats(x, groups, pre_bias)
+        _leave_stats(x, stats, groups, pre_bias, memo=True)
+    return stats
+
+
+def _gn_tuple(norm: nn.GroupNorm, x: torch.Tensor, pre_bias, silu: bool = True) -> _lib.GnFold:
+    """The ``gn`` argument of the kernels that apply ``norm`` (+ swish) while they stage x + pre_bias (statistics: _stats_of)."""
+    return _lib.GnFold(norm.weight, norm.bias, norm.num_groups, norm.eps, silu, _stats_of(x, pre_bias, norm.num_groups), pre_bias)
 
 
 def _use_fused(x: torch.Tensor, norm: nn.GroupNorm) -> bool:
@@ -72,18 +184,16 @@ def _norm_act(norm: nn.GroupNorm, x: torch.Tensor, act: bool = True, pre_bias=No
     """GroupNorm followed by swish (unet.py:140-141, :146-147, :432-433) -- one fused HIP pass pair.
     ``pre_bias``: per-channel bias still pending on ``x`` (see ``_conv3x3``)."""
     if _use_fused(x, norm):
-        st = getattr(x, "_gn_stats", None)   # left behind by the residual add that produced x (see _add)
-        # producer statistics serve only channels_last, matching groups and no pending bias; gn_silu recomputes them otherwise
-        # (_gn_stats_pb, the memo of _stats_of, is never read here)
-        if st is not None and pre_bias is None and st[1] == norm.num_groups and _nhwc(x):
-            y = _lib.gn_apply(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act, st[0])
+        stats = _left_stats(x, norm.num_groups, pre_bias)   # of the producer (e.g. _add); never the memo of _stats_of
+        if stats is not None:
+            y = _lib.gn_apply(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act, stats)
         else:
             y = _lib.gn_silu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=act, pre_bias=pre_bias)
         if WINOGRAD_F16X3:
-            y._act_bound = _gn_act_bound(norm, x)   # lets the Winograd GEMMs that consume y run as fp16 x 3 (see _f16_args)
+            _leave_bound(y, _gn_act_bound(norm, x))   # lets the Winograd GEMMs that consume y run as fp16 x 3 (see _f16_args)
         return y
     y = norm(_materialize(x, pre_bias))
-    return _silu(y) if act else y
+    return F.silu(y) if act else y   # unet.py:49-51 (x * sigmoid(x)): the same function, one kernel
 
 
 def _defer_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
@@ -91,28 +201,15 @@ def _defer_ok(x: torch.Tensor, conv: nn.Conv2d) -> bool:
     return FUSED_GN and DEFER_BIAS and _infer_ok(x) and conv.bias is not None and conv.padding_mode == "zeros"
 
 
-def _f16_gemm_ok(x: torch.Tensor) -> bool:
-    """The library-GEMM half of the fp16 x 3 routes needs bmm(out_dtype=fp32) (recent PyTorch-ROCm): probed once."""
-    return _lib.bmm_out_dtype_ok(x.device)
-
-
-def _f16_args(conv: nn.Conv2d, x: torch.Tensor, f4: bool):
-    """(U3, u_scale, bound) for _lib.wino_conv3x3's fp16 x 3 route, or None: needs a rigorous bound on |x| (left on the
-    tensor by _norm_act: every Winograd convolution of this UNet is fed by GroupNorm + swish)."""
-    bound = getattr(x, "_act_bound", None)   # there only when _norm_act ran with WINOGRAD_F16X3 set
-    if not WINOGRAD_F16X3 or bound is None or not _f16_gemm_ok(x):
+def _f16_args(conv: nn.Conv2d, x: torch.Tensor, f4: bool, norm=None):
+    """The ``f16`` argument of _lib.wino_conv3x3's fp16 x 3 route, or None.  The route needs a rigorous bound on the tensor the
+    input transform sees: with ``norm`` (GroupNorm + swish run inside the transform, the activated tensor is never materialised)
+    it is computed here, else it is the one _norm_act left on x (there only when it ran with WINOGRAD_F16X3 set)."""
+    bound = None if not WINOGRAD_F16X3 else _left_bound(x) if norm is None else _gn_act_bound(norm, x)
+    if bound is None or not _lib.bmm_out_dtype_ok(x.device):   # (bmm(out_dtype=fp32): recent PyTorch-ROCm, probed once)
         return None
     u3, u_scale, wf2 = _wino_weights_f16(conv, f4)
-    return u3, u_scale, bound, (wf2 if WINOGRAD_OWN_GEMM else None)
-
-
-def _f16_args_gn(conv: nn.Conv2d, norm: nn.GroupNorm, x: torch.Tensor, f4: bool):
-    """_f16_args for a convolution whose GroupNorm + swish runs inside the input transform: the bound is that of the
-    activated tensor, which is never materialised, so it is computed here."""
-    if not WINOGRAD_F16X3 or not _f16_gemm_ok(x):
-        return None
-    u3, u_scale, wf2 = _wino_weights_f16(conv, f4)
-    return u3, u_scale, _gn_act_bound(norm, x), (wf2 if WINOGRAD_OWN_GEMM else None)
+    return _lib.F16Gemm(u3, u_scale, bound, wf2 if WINOGRAD_OWN_GEMM else None)
 
 
 def _conv3x3(conv: nn.Conv2d, x: torch.Tensor, norm=None, pre_bias=None, residual=None, residual_bias=None,
@@ -156,17 +253,8 @@ def _conv3x3(conv: nn.Conv2d, x: torch.Tensor, norm=None, pre_bias=None, residua
         out = _lib.conv3x3_direct(x, wf, us, _gn_act_bound(norm, x), gn=_gn_tuple(norm, x, pre_bias), **epilogue)
     else:
         gn = None if norm is None else _gn_tuple(norm, x, pre_bias)
-        f16 = _f16_args(conv, x, f4) if norm is None else _f16_args_gn(conv, norm, x, f4)
-        out = _lib.wino_conv3x3(x, _wino_weights(conv, f4), gn=gn, f16=f16, **epilogue)
-    if not tail:
-        return out, conv.bias
-    out[0]._gn_stats = (out[1], GN_GROUPS)
-    return out[0], None
-
-
-def _conv(conv: nn.Conv2d, x: torch.Tensor):
-    """Run ``conv`` (any kernel size and stride) and return (y, pending_bias): ``_conv3x3`` without a GroupNorm."""
-    return _conv3x3(conv, x)
+        out = _lib.wino_conv3x3(x, _wino_weights(conv, f4), gn=gn, f16=_f16_args(conv, x, f4, norm), **epilogue)
+    return _tagged(out) if tail else (out, conv.bias)
 
 
 def _match_layout(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
@@ -177,10 +265,12 @@ def _match_layout(x: torch.Tensor, conv: nn.Conv2d) -> torch.Tensor:
     return x
 
 
+# ---- route predicates, one per libgqhip route: the switch, what the module layer adds (markers, biases, layouts) and exactly the
+# divisibility the route's _lib wrapper enforces (_pointwise_ok excepted: see there); _wino_ok / _direct_ok are combined in _conv3x3
 def _wino_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
-    return (WINOGRAD and getattr(conv, "_gq_wino", False) and conv.in_channels >= WINOGRAD_MIN_CH
-            and conv.out_channels >= WINOGRAD_MIN_CH and conv.out_channels % 4 == 0 and x.shape[2] % 2 == 0
-            and x.shape[3] % 2 == 0 and _nhwc(x))
+    """_lib.wino_conv3x3: a marked convolution of >= WINOGRAD_MIN_CH channels, Cout % 4, even H and W, channels_last."""
+    return (WINOGRAD and getattr(conv, "_gq_wino", False) and min(conv.in_channels, conv.out_channels) >= WINOGRAD_MIN_CH
+            and conv.out_channels % 4 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and _nhwc(x))
 
 
 def _direct_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
@@ -196,46 +286,53 @@ def _direct_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     return conv.out_channels == 256 and not (WINOGRAD_F4 and getattr(conv, "_gq_wino4", False))
 
 
-def _direct_weights(conv: nn.Conv2d):
-    """(Wf, u_scale) of conv3x3_direct / conv1x1_direct, cached until the weight changes."""
-    return _cached(conv, "direct_wf", _wkey(conv.weight), lambda: _lib.conv3_weights_f16(conv.weight))
-
-
-def _stats_of(x: torch.Tensor, pre_bias, groups: int):
-    """GroupNorm statistics of x + pre_bias: left by the producer of x, computed earlier for the same pending bias, or
-    computed (and remembered on x) here."""
-    st = getattr(x, "_gn_stats", None)
-    if st is not None and pre_bias is None and st[1] == groups:
-        return st[0]
-    sp = getattr(x, "_gn_stats_pb", None)
-    if sp is not None and sp[1] == groups and sp[2] is pre_bias:
-        return sp[0]
-    stats = _lib.gn_stats(x, groups, pre_bias)
-    x._gn_stats_pb = (stats, groups, pre_bias)
-    return stats
-
-
-def _gn_tuple(norm: nn.GroupNorm, x: torch.Tensor, pre_bias):
-    """The ``gn`` argument of wino_conv3x3 / conv3x3_direct: statistics left by the producer of x, or computed here."""
-    return (norm.weight, norm.bias, norm.num_groups, norm.eps, True, _stats_of(x, pre_bias, norm.num_groups), pre_bias)
-
-
 def _pointwise_ok(conv: nn.Conv2d, x: torch.Tensor) -> bool:
     """1x1 convolutions into 128 / 256 / 512 channels (ResnetBlock shortcuts, attention proj_out) as libgqhip's fp16 x 3
     GEMM over the pixels (gq_conv3.h: conv1x1_f16x3) instead of MIOpen's fp32 implicit GEMM (~100 TFLOP/s)."""
     # (HW % 256 and Cin % 128 are asked here although the library takes HW % 128 and Cin % 32)
-    return (DIRECT_CONV_1X1 and FUSED_GN and _infer_ok(x) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+    return (DIRECT_CONV_1X1 and _own_ok(x) and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.padding == (0, 0) and conv.groups == 1 and conv.out_channels in (128, 256, 512)
-            and conv.in_channels % 128 == 0 and (x.shape[2] * x.shape[3]) % 256 == 0 and _nhwc(x))
+            and conv.in_channels % 128 == 0 and (x.shape[2] * x.shape[3]) % 256 == 0)
+
+
+def _proj_tail_ok(conv: nn.Conv2d, x: torch.Tensor, a: torch.Tensor) -> bool:
+    """_lib.conv1x1_direct with its tail for the attention block: x + conv(a) + bias and the next GroupNorm's statistics."""
+    return (_pointwise_ok(conv, a) and FUSED_ADD_STATS and _nhwc(x) and conv.bias is not None
+            and _lib.gn_nhwc_ok(x.shape[1], GN_GROUPS))
+
+
+def _stride2_ok(conv: nn.Conv2d, x: torch.Tensor, mode: str) -> bool:
+    """_lib.conv3x3s2_direct for Downsample's convolution (always 3x3, stride 2, padding 0) behind a zero pad; needs the bias."""
+    return (DIRECT_CONV_S2 and mode == "constant" and _own_ok(x) and conv.out_channels in (128, 256, 512)
+            and conv.in_channels % 16 == 0 and conv.bias is not None and x.shape[2] % 16 == 0 and x.shape[3] % 64 == 0
+            and _lib.gn_nhwc_ok(x.shape[1], GN_GROUPS) and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS))
+
+
+def _upconv_ok(up: "Upsample", x: torch.Tensor) -> bool:
+    """_lib.upconv2x_direct for Upsample with a deferrable bias (the caller adds: statistics left by the producer of x)."""
+    return (DIRECT_UPCONV and DEFER_BIAS and up.with_conv and _own_ok(x) and _plain3x3(up.conv) and up.conv.bias is not None
+            and up.conv.out_channels in (128, 256, 512) and x.shape[1] % 16 == 0 and x.shape[2] % 8 == 0
+            and x.shape[3] % 32 == 0 and _lib.gn_nhwc_ok(up.conv.out_channels, GN_GROUPS))
+
+
+def _conv_f32_ok(conv: nn.Conv2d, x: torch.Tensor, gn: bool) -> bool:
+    """_lib.conv3x3_f32 for the narrow ends of the stack (encoder conv_out with ``gn``, decoder conv_in without): a fixed
+    summation order, hence bit-reproducible -- MIOpen's pick for 512 -> 32 channels is a split-K kernel with atomics."""
+    return (CONV_F32 and _own_ok(x) and _plain3x3(conv)
+            and _lib.conv_f32_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], gn))
+
+
+def _direct_weights(conv: nn.Conv2d):
+    """(Wf, u_scale) of conv3x3_direct / conv1x1_direct, cached until the weight changes."""
+    return _cached(conv, "direct_wf", _wkey(conv.weight), lambda: _lib.conv3_weights_f16(conv.weight))
 
 
 def _norm_act_conv_small(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, pre_bias=None) -> torch.Tensor:
     """conv(swish(norm(x + pre_bias))) for a 3x3 convolution into <= 4 channels (the decoder's conv_out, unet.py:585-587):
     one libgqhip kernel -- GroupNorm + swish applied while staging, fp32 FMAs -- instead of a normalisation pass and
     MIOpen's implicit GEMM (0.2 + 0.96 ms at 16 x 256 x 256 x 128)."""
-    if (FUSED_CONV_OUT and _use_fused(x, norm) and conv.out_channels <= 4 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
-            and x.shape[1] % 32 == 0 and x.shape[1] <= 512 and x.shape[2] % 16 == 0 and x.shape[3] % 16 == 0 and _nhwc(x)):
+    if (FUSED_CONV_OUT and _own_ok(x) and _use_fused(x, norm) and _plain3x3(conv) and conv.out_channels <= 4
+            and x.shape[1] % 32 == 0 and x.shape[1] <= 512 and x.shape[2] % 16 == 0 and x.shape[3] % 16 == 0):
         ohwi = _cached(conv, "ohwi", _wkey(conv.weight), lambda: conv.weight.detach().permute(0, 2, 3, 1).contiguous())
         return _lib.conv3x3_gn_small(x, ohwi, conv.bias, _gn_tuple(norm, x, pre_bias))
     return conv(_norm_act(norm, x, pre_bias=pre_bias))
@@ -256,16 +353,6 @@ def _cached(module: nn.Module, name: str, key, build):
     return ent[1]
 
 
-def _conv_f32_ok(conv: nn.Conv2d, x: torch.Tensor, gn: bool) -> bool:
-    """The narrow ends of the stack (encoder conv_out, decoder conv_in) on libgqhip's fp32 matrix-core convolution: a fixed
-    summation order, hence bit-reproducible -- MIOpen's pick for 512 -> 32 channels is a split-K kernel with atomics."""
-    if not (CONV_F32 and FUSED_GN and _infer_ok(x) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
-            and _nhwc(x)):
-        return False
-    return _lib.conv_f32_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3], gn)
-
-
 def _conv_f32(conv: nn.Conv2d, x: torch.Tensor, gn=None) -> torch.Tensor:
     wk = _cached(conv, "f32_wk", _wkey(conv.weight), lambda: _lib.conv_f32_weights(conv.weight))
     return _lib.conv3x3_f32(x, wk, conv.out_channels, bias=conv.bias, gn=gn)
@@ -273,18 +360,13 @@ def _conv_f32(conv: nn.Conv2d, x: torch.Tensor, gn=None) -> torch.Tensor:
 
 def _conv_in_small(conv: nn.Conv2d, x: torch.Tensor):
     """The encoder's conv_in (unet.py:411-413, 3 -> 128 channels) -> (y, pending_bias).  On the channels_last path: libgqhip's
-    fixed-order fp32 kernel with the bias and the first GroupNorm's statistics in its epilogue (round 4; it was the last MIOpen
-    convolution of the bench shapes: 0.24 ms per call once MIOpen's CK solver runs, 4 ms for each of a process's first eight
-    calls).  Other shapes / layouts: ``_conv``."""
-    if (CONV_IN_SMALL and FUSED_GN and _infer_ok(x) and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"
-            and GN_GROUPS == 32 and _nhwc(x)
+    fixed-order fp32 kernel with the bias and the first GroupNorm's statistics in its epilogue (MIOpen: 0.24 ms per call once
+    its CK solver runs, 4 ms for each of a process's first eight calls).  Other shapes / layouts: ``_conv3x3``."""
+    if (CONV_IN_SMALL and _own_ok(x) and _plain3x3(conv) and GN_GROUPS == 32   # (the kernel's statistics epilogue: 32 groups)
             and _lib.conv_cin_small_ok(conv.in_channels, conv.out_channels, x.shape[2], x.shape[3])):
         wk = _cached(conv, "cin_small_wk", _wkey(conv.weight), lambda: _lib.conv_cin_small_weights(conv.weight))
-        y, st = _lib.conv3x3_cin_small(x, wk, conv.bias, stats_groups=GN_GROUPS)
-        y._gn_stats = (st, GN_GROUPS)
-        return y, None
-    return _conv(conv, x)
+        return _tagged(_lib.conv3x3_cin_small(x, wk, conv.bias, stats_groups=GN_GROUPS))
+    return _conv3x3(conv, x)
 
 
 def _norm_act_conv_f32(norm: nn.GroupNorm, conv: nn.Conv2d, x: torch.Tensor, pre_bias=None) -> torch.Tensor:
@@ -318,16 +400,9 @@ def _wino_weights_f16(conv: nn.Conv2d, f4: bool = False):
     wino_in_nhwc_f16x3) -- and, where libgqhip's own GEMM applies (Cin % 32 == 0, Cout % 128 == 0), (U_h, U_l) in MFMA operand
     order for wino_gemm_f16x2 (the [h | l] route).  Cached like (and keyed like) the fp32 U."""
     def build():
-        U = _wino_weights(conv, f4)
-        amax = float(U.abs().max())
-        u_scale = 2.0 ** math.floor(math.log2(16384.0 / max(amax, 1e-30))) if amax > 0 else 1.0
-        us = U * u_scale
-        h = us.half()
-        l = (us - h.float()).half()
-        wf2 = None
-        if WINOGRAD_OWN_GEMM and U.shape[1] % 32 == 0 and U.shape[2] % 128 == 0:
-            wf2 = _lib.wino_weights_operand_order(h, l)
-        return torch.cat([h, l, h], 1).contiguous(), u_scale, wf2
+        h, l, u_scale = _lib._split_f16(_wino_weights(conv, f4))
+        own = WINOGRAD_OWN_GEMM and h.shape[1] % 32 == 0 and h.shape[2] % 128 == 0
+        return torch.cat([h, l, h], 1).contiguous(), u_scale, (_lib.wino_weights_operand_order(h, l) if own else None)
 
     return _cached(conv, "wino_u3", _wkey(conv.weight) + (f4, WINOGRAD_OWN_GEMM), build)
 
@@ -416,9 +491,6 @@ def _with_stats_arena(module: nn.Module, run, x: torch.Tensor):
         return run(x)
 
 
-_MAX_STATS_ARENAS = 8
-
-
 def _guarded(module: nn.Module, run0, x: torch.Tensor):
     """run(x) with the module's weight caches verified against the parameters' bytes (see _WeightGuard).  Costs one host wait per
     forward (for a copy queued at the forward's start: the host stays at most one module ahead of the device).  A caller that
@@ -459,8 +531,7 @@ def mark_winograd(module: nn.Module, f4: bool = False) -> None:
     """Flag the stride-1, padding-1 3x3 convolutions of ``module`` for the Winograd path (see ``_conv3x3``);
     ``f4``: F(4x4,3x3) where the spatial size allows it (decoder only: larger rounding error)."""
     for m in module.modules():
-        if (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride == (1, 1) and m.padding == (1, 1)
-                and m.dilation == (1, 1) and m.groups == 1 and m.padding_mode == "zeros"):
+        if _plain3x3(m):
             m._gq_wino = True
             m._gq_wino4 = f4
 
@@ -472,62 +543,11 @@ def _add(a: torch.Tensor, b: torch.Tensor, bias=None) -> torch.Tensor:
         if FUSED_ADD_STATS and la == 1 and lb == 1 and _lib.gn_nhwc_ok(a.shape[1], GN_GROUPS):
             # every residual add of this UNet feeds a GroupNorm(32): leave its statistics with the sum, the
             # consumer (_norm_act) then skips its own statistics pass over the tensor
-            y, stats = _lib.add_bias_stats(a, b, bias, GN_GROUPS)
-            y._gn_stats = (stats, GN_GROUPS)
-            return y
+            return _leave_stats(*_lib.add_bias_stats(a, b, bias, GN_GROUPS), GN_GROUPS)
         if la is not None and la == lb and ((la == 0 and (a.shape[2] * a.shape[3]) % 4 == 0) or
                                             (la == 1 and a.shape[1] % 4 == 0)):
             return _lib.add_bias(a, b, bias)
     return _materialize(a + b, bias)
-
-
-FUSED_GN = True    # module-level switches (tests / A-B timing)
-WINOGRAD = True          # decoder 3x3 convs with >= WINOGRAD_MIN_CH channels: Winograd F(2x2,3x3) + 16 hipBLASLt GEMMs
-WINOGRAD_MIN_CH = 128
-FUSED_WINO_TAIL = True   # Winograd output transform + bias + residual add + next GroupNorm's statistics in one pass
-WINOGRAD_F4 = True       # decoder: F(4x4,3x3) (36 GEMMs on 6x6 tiles) instead of F(2x2,3x3)
-# The 16 / 36 Winograd GEMMs as ONE fp16 batched GEMM with fp32 accumulation whose K axis carries the three products of
-# two-term fp16 splits of both operands (22-bit significands): measured error 2.5-2.9e-7 of sum|a||b| against 2.6-3.5e-7
-# for hipBLASLt's fp32 GEMM (itself a split-bf16 emulation on gfx950), at 1.2x (128 channels) to 2.5x (512) its speed
-# (tools/bmm_bf16x3.py).  False: the library's fp32 GEMM.
-WINOGRAD_F16X3 = True
-# the 256- / 512-channel Winograd GEMMs through libgqhip's wino_gemm_f16x2 on the [h | l] operand (weights in MFMA
-# operand order, three products in the kernel) where its grid fills the chip (_lib.own_gemm_fits: everything but the
-# 32 x 32 levels' 36 x 1024-tile GEMMs); else the library GEMM over [h | h | l]
-WINOGRAD_OWN_GEMM = True
-# 3x3 convolutions into 128 channels (256 x 256 level) -- and, where the alternative is F(2x2,3x3) (the encoder), into 256
-# channels (128 x 128 level) -- as a direct fp16 x 3 implicit GEMM instead of Winograd: reads the activation once and
-# writes the result once where Winograd moves 6.4 / 10.7 GB of transformed tensors per convolution at 256 x 256
-DIRECT_CONV = True
-DIRECT_CONV_S2 = True      # Downsample (pad + 3x3 stride 2) as an fp16 x 3 convolution on the four phase images of x
-DIRECT_CONV_1X1 = True     # 1x1 shortcut / proj_out convolutions as an fp16 x 3 GEMM with the split of x inside the kernel
-FUSED_CONV_OUT = True      # decoder conv_out (128 -> 3) with norm_out + swish fused in: one VALU kernel
-# encoder conv_out (512 -> 2 z, norm_out + swish fused in) and decoder conv_in (z -> 512) on the fp32 matrix cores with a fixed
-# summation order (bit-reproducible; MIOpen's pick for the former combines split-K partial sums with atomics)
-CONV_F32 = True
-# every inference forward of Encoder / Decoder on a HIP device checks its weight-derived caches against a content hash of the
-# parameters (catches ``param.data`` writes, which bump no version counter); see _WeightGuard
-WEIGHT_GUARD = os.environ.get("GQHIP_WEIGHT_GUARD", "1") != "0"   # (the env switch: A/B timing)
-# GroupNorm+SiLU applied inside the Winograd input transforms (F(2x2,3x3) / F(4x4,3x3)): the normalised tensor is never
-# written or re-read.  Bit-identical V to gn_apply + plain transform (same folded scale / shift, same silu_f32); pays
-# since the loads of a tile are issued ahead of the activations (branch-free borders): 53.4 -> 50.8 ms / step.
-FUSED_WINO_GN = True
-FUSED_WINO_GN_F4 = True
-# also in the encoder: measured perturbation of z 4.2e-6 vs the CPU reference (direct MIOpen convs: 3.4e-6), no index
-# change on the CPU golden nor on 16 384 rows against the direct-conv encoder (tools/encoder_winograd_check.py)
-WINOGRAD_ENCODER = True
-# Upsample: nearest x2 + conv3x3 as four 2x2 phase convolutions of the low-resolution input (2.25x fewer flops), computed directly by
-# libgqhip's upconv2x_f16x3 (one kernel); shapes it does not tile: NHWC upsample copy + the ordinary convolution routes
-DIRECT_UPCONV = True
-FUSED_QKV = True         # attention: q, k, v as one GEMM with fused biases (channels_last)
-FUSED_ADD_STATS = True   # residual add also produces the next GroupNorm's statistics (channels_last only)
-STATS_ARENA = True       # the statistics records of a forward from one arena zeroed by one fill (not ~60 memset launches per step)
-CONV_IN_SMALL = True     # the encoder's conv_in (3 -> 128) on libgqhip's fixed-order fp32 kernel (+ bias + statistics), not MIOpen
-GN_GROUPS = 32     # unet.py:54-57: every Normalize is GroupNorm(32, C, eps=1e-6)
-DEFER_BIAS = True
-ATTN_FUSED_PROJ = True   # attention: GroupNorm inside the q | k | v projection's staging, the GEMM operands written by its epilogue
-ATTN_F16X3 = True   # both attention GEMMs as fp16 x 3 library GEMMs (split of q, k, v and softmax + split in libgqhip kernels)
-ATTN_MATH = "auto"  # explicit matmul/softmax/matmul instead of the fused SDPA kernel: "auto" = on HIP devices
 
 
 def _sdpa(q, k, v):
@@ -578,7 +598,7 @@ class ResnetBlock(nn.Module):
             scales = _lib.f16_scales(_stats_of(x, pre_bias, GN_GROUPS), 1.0, us)
             return _lib.conv1x1_direct(x, wf, us, scales, pre_bias=pre_bias), nin.bias
         # nin(x + pb) = nin_nobias(x) + W.pb + nin.bias : every constant goes into the fused add
-        xs, bs = _conv(nin, x)
+        xs, bs = _conv3x3(nin, x)
         if pre_bias is not None:
             wpb = nin.weight.reshape(self.out_channels, self.in_channels) @ pre_bias
             bs = wpb if bs is None else bs + wpb
@@ -665,20 +685,16 @@ class AttnBlock(nn.Module):
 
     def _proj_out(self, x: torch.Tensor, a: torch.Tensor, a_scale: float) -> torch.Tensor:
         """x + proj_out(a * a_scale)."""
-        c = x.shape[1]
-        if _pointwise_ok(self.proj_out, a) and FUSED_ADD_STATS and _nhwc(x) and self.proj_out.bias is not None:
+        if _proj_tail_ok(self.proj_out, x, a):
             # proj_out + bias + residual add + the next GroupNorm's statistics in one fp16 x 3 GEMM over the pixels.  Scale:
             # the attention output is a convex combination of the rows of v, so |a| <= max|v| <= max|y| max_j ||W_v[j]||_1 +
             # max|b_v|, with |y| bounded by the GroupNorm bound
-            if _lib.gn_nhwc_ok(c, GN_GROUPS):   # (_pointwise_ok: a is channels_last)
-                wf, us = _direct_weights(self.proj_out)
-                out, st = _lib.conv1x1_direct(a, wf, us, self._v_bound(_gn_act_bound(self.norm, x)) / a_scale, residual=x,
-                                              bias=self.proj_out.bias, stats_groups=GN_GROUPS, post_scale=a_scale)
-                out._gn_stats = (st, GN_GROUPS)
-                return out
+            wf, us = _direct_weights(self.proj_out)
+            return _tagged(_lib.conv1x1_direct(a, wf, us, self._v_bound(_gn_act_bound(self.norm, x)) / a_scale, residual=x,
+                                               bias=self.proj_out.bias, stats_groups=GN_GROUPS, post_scale=a_scale))[0]
         if a_scale != 1.0:
             a = a * a_scale
-        p, pb = _conv(self.proj_out, a)
+        p, pb = _conv3x3(self.proj_out, a)
         return _add(x, p, pb)
 
     @staticmethod
@@ -691,7 +707,7 @@ class AttnBlock(nn.Module):
     @staticmethod
     def _f16x3_attention_ok(y: torch.Tensor) -> bool:
         """Both attention GEMMs as fp16 x 3 library GEMMs (_lib.attention_f16x3 / attention_from_operands)."""
-        return ATTN_F16X3 and y.shape[1] % 4 == 0 and _f16_gemm_ok(y) and (y.shape[2] * y.shape[3]) in _lib.ATTN_L_OK
+        return ATTN_F16X3 and y.shape[1] % 4 == 0 and _lib.bmm_out_dtype_ok(y.device) and (y.shape[2] * y.shape[3]) in _lib.ATTN_L_OK
 
     def _fused_proj_attention(self, x: torch.Tensor):
         """The fp16 x 3 attention route below with its two reformatting passes folded into the q | k | v projection
@@ -710,8 +726,7 @@ class AttnBlock(nn.Module):
         qkv_wf, qkv_us = self._qkv_weights_f16()
         yb = _gn_act_bound(self.norm, x)
         sq, sv = _lib.attention_scales(self._qk_bound(yb), self._v_bound(yb))
-        gn = (self.norm.weight, self.norm.bias, self.norm.num_groups, self.norm.eps, False,
-              _stats_of(x, None, self.norm.num_groups), None)
+        gn = _gn_tuple(self.norm, x, None, silu=False)
         q3, k3, v3 = _lib.qkv_split_direct(x, qkv_wf, qkv_us, yb, sq, sv, bias=bqkv, gn=gn)
         return _lib.attention_from_operands(q3, k3, v3, sq, sv)
 
@@ -749,27 +764,22 @@ class Downsample(nn.Module):
             self.conv = _conv3(ch, ch, stride=2, padding=0)
 
     def forward(self, x: torch.Tensor):
-        """Returns (y, pending_bias) -- see ``_conv``."""
+        """Returns (y, pending_bias) -- see ``_conv3x3``."""
         if not self.with_conv:
             return F.avg_pool2d(x, 2, 2), None
         conv = self.conv
-        if (DIRECT_CONV_S2 and self.mode == "constant" and FUSED_GN and _infer_ok(x) and conv.out_channels in (128, 256, 512)
-                and conv.in_channels % 16 == 0 and conv.bias is not None and x.shape[2] % 16 == 0 and x.shape[3] % 64 == 0
-                and _nhwc(x)):
+        if _stride2_ok(conv, x, self.mode):
             # pad + stride-2 convolution + bias + the next GroupNorm's statistics as ONE fp16 x 3 kernel on the four phase
             # images of x (MIOpen: a padding pass + an fp32 implicit GEMM, 0.7-1.0 ms); the scale of x comes, on the device,
-            # from the statistics its producer left behind: |x| <= sqrt(group sum of squares)
-            if _lib.gn_nhwc_ok(x.shape[1], GN_GROUPS) and _lib.gn_nhwc_ok(conv.out_channels, GN_GROUPS):
-                s2_wf, s2_us = _cached(conv, "s2_wf", _wkey(conv.weight), lambda: _lib.conv3s2_weights_f16(conv.weight))
-                scales = _lib.f16_scales(_stats_of(x, None, GN_GROUPS), 1.0, s2_us)
-                y, st = _lib.conv3x3s2_direct(x, s2_wf, s2_us, scales, bias=conv.bias, stats_groups=GN_GROUPS)
-                y._gn_stats = (st, GN_GROUPS)
-                return y, None
+            # from the statistics its producer left behind (or computed here): |x| <= sqrt(group sum of squares)
+            s2_wf, s2_us = _cached(conv, "s2_wf", _wkey(conv.weight), lambda: _lib.conv3s2_weights_f16(conv.weight))
+            scales = _lib.f16_scales(_stats_of(x, None, GN_GROUPS), 1.0, s2_us)
+            return _tagged(_lib.conv3x3s2_direct(x, s2_wf, s2_us, scales, bias=conv.bias, stats_groups=GN_GROUPS))
         if self.mode == "constant":
             x = F.pad(x, (0, 1, 0, 1), mode="constant", value=0)
         else:
             x = F.pad(x, (0, 1, 0, 1), mode=self.mode)
-        return _conv(self.conv, x)
+        return _conv3x3(self.conv, x)
 
 
 class Upsample(nn.Module):
@@ -802,31 +812,23 @@ class Upsample(nn.Module):
         return _cached(self, "phase_w", _wkey(self.conv.weight), build)
 
     def forward(self, x: torch.Tensor):
-        """Returns (y, pending_bias) -- see ``_conv``."""
-        fast = FUSED_GN and _infer_ok(x) and x.shape[1] % 4 == 0 and _nhwc(x)
-        if (fast and DIRECT_UPCONV and self.with_conv and _defer_ok(x, self.conv) and self.conv.kernel_size == (3, 3)
-                and self.conv.stride == (1, 1) and self.conv.padding == (1, 1)):
-            # nearest x2 then conv3x3 == four 2x2 convolutions of the low-resolution input (one per output phase): 16 instead
-            # of 36 tap evaluations per source pixel, no upsampled tensor -- computed directly by libgqhip's upconv2x_f16x3 (one
-            # kernel per Upsample), with the bias added and the statistics of the next ResnetBlock's norm1 left behind; the
-            # scale of x comes, on the device, from the statistics its producer left (sqrt of a group's sum of squares bounds
-            # its largest element)
-            b, c, h, w = x.shape
-            st = getattr(x, "_gn_stats", None)
-            cout = self.conv.out_channels
-            if (st is not None and cout in (128, 256, 512) and c % 16 == 0 and h % 8 == 0 and w % 32 == 0
-                    and self.conv.bias is not None and _lib.gn_nhwc_ok(cout, GN_GROUPS)):
-                wf, wf_us = _cached(self, "phase_wf", _wkey(self.conv.weight),
-                                    lambda: _lib.upconv_weights_f16(self._phase_weights(), c, cout))
-                scales = _lib.f16_scales(st[0], 1.0, wf_us)
-                y, ostats = _lib.upconv2x_direct(x, wf, wf_us, scales, bias=self.conv.bias, stats_groups=GN_GROUPS)
-                y._gn_stats = (ostats, GN_GROUPS)
-                return y, None
-        if fast:   # shapes the direct kernel does not tile: upsample (a plain NHWC copy kernel), then the convolution
+        """Returns (y, pending_bias) -- see ``_conv3x3``."""
+        # nearest x2 then conv3x3 == four 2x2 convolutions of the low-resolution input (one per output phase): 16 instead of 36
+        # tap evaluations per source pixel, no upsampled tensor -- one libgqhip kernel, with the bias added and the statistics of
+        # the next ResnetBlock's norm1 left behind.  The scale of x comes, on the device, from the statistics its producer left (sqrt
+        # of a group's sum of squares bounds its largest element): without those (a memo of _stats_of does not count), not taken
+        stats = _left_stats(x, GN_GROUPS) if _upconv_ok(self, x) else None
+        if stats is not None:
+            c, cout = x.shape[1], self.conv.out_channels
+            wf, wf_us = _cached(self, "phase_wf", _wkey(self.conv.weight),
+                                lambda: _lib.upconv_weights_f16(self._phase_weights(), c, cout))
+            scales = _lib.f16_scales(stats, 1.0, wf_us)
+            return _tagged(_lib.upconv2x_direct(x, wf, wf_us, scales, bias=self.conv.bias, stats_groups=GN_GROUPS))
+        if _own_ok(x) and x.shape[1] % 4 == 0:   # what the direct kernel does not take: a plain NHWC copy kernel, then the convolution
             x = _lib.upsample2x_nhwc(x)   # ATen's NHWC nearest kernel runs at ~1.6 TB/s; this one is a plain copy
         else:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
-        return _conv(self.conv, x) if self.with_conv else (x, None)
+        return _conv3x3(self.conv, x) if self.with_conv else (x, None)
 
 
 def _make_attn(ch: int, attn_type: str) -> nn.Module:
@@ -965,10 +967,7 @@ class Decoder(nn.Module):
 
     def _forward(self, z: torch.Tensor) -> torch.Tensor:
         z = _match_layout(z, self.conv_in)
-        if _conv_f32_ok(self.conv_in, z, False):
-            h, pb = _conv_f32(self.conv_in, z), None
-        else:
-            h, pb = _conv(self.conv_in, z)
+        h, pb = (_conv_f32(self.conv_in, z), None) if _conv_f32_ok(self.conv_in, z, False) else _conv3x3(self.conv_in, z)
         h, pb = self.mid(h, pb), None
         for lvl in reversed(range(self.num_resolutions)):
             h, pb = self.up[lvl].run(h, pb), None
