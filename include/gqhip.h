@@ -34,6 +34,7 @@
  *   bsq_train_f32 / bsq_backward_f32  pit/quantization/bsq.py:14-37, 64-133 (BSQQuantizer.forward in train()) and its autograd backward.
  *   fsq_quantize_f32 / fsq_dequant_f32  pit/quantization/fsq.py:29-89.
  *   fsq_train_f32 / fsq_backward_f32  pit/quantization/fsq.py:6-9, 29-68 (FSQQuantizer.forward with round_ste's value) and its autograd backward.
+ *   lpips_head_f32 / lpips_head_backward_f32  pit/modules/lpips/loss/lpips.py:46-66, 136-148 (the five comparison heads of LPIPS.forward) and their autograd backward.
  *   gn_silu_f32      pit/modules/unet.py:49-57 (Normalize + nonlinearity pairs).
  *   gq_index_histogram eval.py:127,137-141,152-154 (stubbed-out histogram).
  *   gq_ssim_f32      pit/evaluations/ssim.py:5-63 (get_ssim / get_ssim_and_msssim via pytorch_msssim), eval.py:170-178.
@@ -66,7 +67,8 @@ extern "C" {
                                *    codebook size (gq_indices_pack_bits, gq_indices_unpack_bits, gq_index_histogram_packed,
                                *    gq_step_record_bits_f32, gq_step_record_ssim_bits_f32 and their two _workspace_bytes functions), the train steps of
                                *    BSQQuantizer (bsq_train_f32, bsq_backward_f32, bsq_train_workspace_bytes) and FSQQuantizer (fsq_train_f32,
-                               *    fsq_backward_f32) */
+                               *    fsq_backward_f32), the LPIPS comparison head (lpips_head_f32, lpips_head_backward_f32,
+                               *    lpips_head_workspace_bytes) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -400,6 +402,26 @@ int fsq_train_f32(const float *z, const int32_t *levels_host, int64_t nlev, floa
                   int layout, void *stream);
 int fsq_backward_f32(const float *z, const float *g_zhat, const int32_t *levels_host, int64_t nlev, float *grad_z, int64_t B,
                      int64_t L, int layout, void *stream);
+
+/* ---- the LPIPS comparison head (pit/modules/lpips/loss/lpips.py:46-66: normalize_tensor, squared difference, the `lin` layer's
+ * dropout and 1x1 convolution, spatial_average) of one VGG level, forward and backward, on a module layout in place (csrc/lpips_head.h).
+ *   f0, f1, grad_f1: [B, C, HW] (layout 0, BCHW) or [B, HW, C] (layout 1, BLC; also channels_last memory), 1 <= C <= 512, HW >= 1,
+ *   B HW < 2^30; w [C]; keep: NULL, or one byte (0 / 1) per feature element in the features' layout, with keep_scale = 1 / (1 - p)
+ *   (m_c s below; 1 without a mask).  Per pixel, over the channels, in fp64 and rounded once:
+ *     n0 = sqrt(sum f0_c^2), n1 = sqrt(sum f1_c^2), r0 = 1 / (n0 + 1e-10), r1 = 1 / (n1 + 1e-10), u_c = f0_c r0 - f1_c r1,
+ *     out[b] = (1 / HW) sum_p sum_c w_c (m_c s) u_c^2;
+ *     t_c = -2 w_c (m_c s) u_c, dot = sum_c t_c f1_c, grad_f1_j = (g_out[b] / HW) (r1 t_j - f1_j dot r1^2 / n1);
+ *   at n1 = 0 the second term is 0 (its limit; torch's autograd gives NaN there).  The head is symmetric: the gradient for f0 is the
+ *   same call with f0 and f1 swapped.  16-byte aligned pointers (keep: 4-byte) take 16-byte accesses; 4-byte alignment is required.
+ * The forward is two launches (per-tile fp64 partial sums, one finishing block per image), the backward one; no float atomics, every
+ * sum's order depends on the shape alone: bit-identical from run to run.  Neither reads the host or synchronises.
+ * workspace (forward): lpips_head_workspace_bytes(B, C, HW) bytes (-1: a size outside the limits above), 16-byte aligned, contents
+ * don't-care on entry, nothing kept between calls; NULL, misaligned or short -> GQHIP_ERR_WORKSPACE.  B = 0: GQHIP_OK. */
+int64_t lpips_head_workspace_bytes(int64_t B, int64_t C, int64_t HW);
+int lpips_head_f32(const float *f0, const float *f1, const float *w, const uint8_t *keep_or_null, float keep_scale, float *out,
+                   int64_t B, int64_t C, int64_t HW, int layout, void *workspace, int64_t workspace_bytes, void *stream);
+int lpips_head_backward_f32(const float *f0, const float *f1, const float *w, const uint8_t *keep_or_null, float keep_scale,
+                            const float *g_out, float *grad_f1, int64_t B, int64_t C, int64_t HW, int layout, void *stream);
 
 /* ---- fused GroupNorm (+ SiLU) for the conv stack -----------------------------------
  * y = act( (x - mean_g) * rstd_g * gamma_c + beta_c ), act = SiLU when apply_silu != 0.

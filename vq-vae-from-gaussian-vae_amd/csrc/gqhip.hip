@@ -27,6 +27,7 @@
 #include "vq_train.h"
 #include "lfq_train.h"
 #include "bsq_fsq_train.h"
+#include "lpips_head.h"
 
 using namespace gqhip;
 
@@ -1195,6 +1196,81 @@ int bsq_backward_f32(const float *x, const float *avg, const float *g_q_or_null,
   p.g = g; p.ws = w_s; p.wb = w_b;
   const int64_t blocks = g.mode == 1 ? (g.P + kBsqBchwThreads - 1) / kBsqBchwThreads : g.blocks;
   return launch(bsq_bwd_choice(g), dim3((unsigned)blocks), dim3(g.mode == 1 ? kBsqBchwThreads : 256), 0, static_cast<hipStream_t>(stream), p);
+}
+
+// ---- the LPIPS comparison head (lpips_head.h) ----
+namespace {
+using LpipsKernel = void (*)(const LpipsParams);
+// the kernel of a call and its tile: `wide` = every feature pointer (and w, for "blc") is 16-byte aligned and the keep mask 4-byte
+extern "C++" template <bool BWD>
+LpipsKernel lpips_choice(LpipsGeom *g, bool wide) {
+  if (g->mode == 1) {
+    const bool v4 = wide && g->L % 4 == 0 && g->C <= 256;
+    g->T = v4 ? 64 : 16;
+    return !v4           ? lpips_bchw_kernel<BWD, 1, 32>
+           : g->C <= 64  ? lpips_bchw_kernel<BWD, 4, 4>
+           : g->C <= 128 ? lpips_bchw_kernel<BWD, 4, 8>
+                         : lpips_bchw_kernel<BWD, 4, 16>;
+  }
+  if (wide && g->C % 4 == 0) {
+    const int u = g->C / 4;
+    g->T = u <= 16 ? 64 : 16;
+    return u <= 4    ? lpips_blc_kernel<BWD, 4, 1, 4>
+           : u <= 8  ? lpips_blc_kernel<BWD, 8, 1, 4>
+           : u <= 16 ? lpips_blc_kernel<BWD, 16, 1, 4>
+           : u <= 32 ? lpips_blc_kernel<BWD, 32, 1, 4>
+           : u <= 64 ? lpips_blc_kernel<BWD, 64, 1, 4>
+                     : lpips_blc_kernel<BWD, 64, 2, 4>;
+  }
+  g->T = 16;
+  return g->C <= 64    ? lpips_blc_kernel<BWD, 64, 1, 1>
+         : g->C <= 128 ? lpips_blc_kernel<BWD, 64, 2, 1>
+         : g->C <= 256 ? lpips_blc_kernel<BWD, 64, 4, 1>
+                       : lpips_blc_kernel<BWD, 64, 8, 1>;
+}
+bool lpips_geometry(int64_t B, int64_t C, int64_t HW, int layout, LpipsGeom *g) {
+  if (C < 1 || C > kLpipsMaxC || HW < 1 || !train_geometry(B, HW, layout, 1, g)) return false;
+  g->C = (int)C;
+  return true;
+}
+int64_t lpips_part_bytes(int64_t B, int64_t HW, int64_t T) { return ((B * HW + T - 1) / T) * lpips_slots(B, HW, T) * 8; }
+}  // namespace
+
+// either tile size a call may pick (16, 64): the larger of the two partial-sum tables
+int64_t lpips_head_workspace_bytes(int64_t B, int64_t C, int64_t HW) {
+  LpipsGeom g;
+  if (!lpips_geometry(B, C, HW, GQHIP_LAYOUT_BCHW, &g)) return -1;
+  const int64_t a = lpips_part_bytes(B, HW, 16), b = lpips_part_bytes(B, HW, 64);
+  return align256(a > b ? a : b);
+}
+
+int lpips_head_f32(const float *f0, const float *f1, const float *w, const uint8_t *keep_or_null, float keep_scale, float *out,
+                   int64_t B, int64_t C, int64_t HW, int layout, void *workspace, int64_t workspace_bytes, void *stream) {
+  LpipsParams p{};
+  LpipsGeom &g = p.g_;
+  if (!f0 || !f1 || !w || !out || !lpips_geometry(B, C, HW, layout, &g) || !aligned(3u, f0, f1, w, out)) return GQHIP_ERR_INVALID_ARG;
+  if (g.P == 0) return GQHIP_OK;
+  if (const int rc = workspace_status(workspace, workspace_bytes, lpips_head_workspace_bytes(B, C, HW))) return rc;
+  const LpipsKernel kernel = lpips_choice<false>(&g, aligned(15u, f0, f1) && aligned(g.mode == 2 ? 15u : 3u, w) && aligned(3u, keep_or_null));
+  g.slots = (int)lpips_slots(B, HW, g.T);
+  p.f0 = f0; p.f1 = f1; p.w = w; p.keep = keep_or_null; p.keep_scale = keep_scale;
+  p.part = static_cast<double *>(workspace); p.out = out;
+  return Chain(stream).run(kernel, dim3((unsigned)((g.P + g.T - 1) / g.T)), dim3(256), p)
+      .run(lpips_finish_kernel, dim3((unsigned)B), dim3(256), p).rc;
+}
+
+int lpips_head_backward_f32(const float *f0, const float *f1, const float *w, const uint8_t *keep_or_null, float keep_scale,
+                            const float *g_out, float *grad_f1, int64_t B, int64_t C, int64_t HW, int layout, void *stream) {
+  LpipsParams p{};
+  LpipsGeom &g = p.g_;
+  if (!f0 || !f1 || !w || !g_out || !grad_f1 || !lpips_geometry(B, C, HW, layout, &g) || !aligned(3u, f0, f1, w, g_out, grad_f1))
+    return GQHIP_ERR_INVALID_ARG;
+  if (g.P == 0) return GQHIP_OK;
+  const LpipsKernel kernel =
+      lpips_choice<true>(&g, aligned(15u, f0, f1, grad_f1) && aligned(g.mode == 2 ? 15u : 3u, w) && aligned(3u, keep_or_null));
+  g.slots = (int)lpips_slots(B, HW, g.T);
+  p.f0 = f0; p.f1 = f1; p.w = w; p.keep = keep_or_null; p.keep_scale = keep_scale; p.g = g_out; p.grad = grad_f1;
+  return launch(kernel, dim3((unsigned)((g.P + g.T - 1) / g.T)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,

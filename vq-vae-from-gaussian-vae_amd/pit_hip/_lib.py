@@ -72,6 +72,9 @@ _SIGNATURES = {
                                      _vp, _i64, _vp]),
     "bsq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
                                         ctypes.c_float, _vp, _i64, _vp]),
+    "lpips_head_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "lpips_head_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i64, _i64, _i64, ctypes.c_int, _vp, _i64, _vp]),
+    "lpips_head_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, _vp]),
     "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
                                       ctypes.c_int, _vp]),
     "vq_argmin_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -708,6 +711,59 @@ def bsq_backward(x, avg, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1
         _check(lib().bsq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(g_aux), grad_x.data_ptr(), B, L, C, dim,
                                       GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()), "bsq_backward_f32")
     return grad_x
+
+
+class LpipsHeadWorkspace(_TrainWorkspace):      # of lpips_head
+    _what, _size, _shape = "the LPIPS head's workspace", "lpips_head_workspace_bytes", ("B", "C", "HW")
+
+
+def _lpips_operands(f0, f1, w, keep, layout: str):
+    """The checked operands of the LPIPS head and (B, C, HW): f0, f1 (and keep, uint8) [B, C, ...] ("bchw") or [B, L, C] ("blc")."""
+    f0, f1, w = _dev(f0, torch.float32, "f0"), _dev(f1, torch.float32, "f1"), _dev(w, torch.float32, "w")
+    if layout not in GQHIP_LAYOUT or f0.dim() < 3 or f0.shape != f1.shape:
+        raise GqHipError(f"f0 and f1 must share a shape [B, C, ...] (bchw) or [B, L, C] (blc), got {tuple(f0.shape)}, {tuple(f1.shape)}")
+    if layout == "bchw":
+        B, C, HW = f0.shape[0], f0.shape[1], math.prod(f0.shape[2:])
+    else:
+        B, HW, C = f0.shape[0], math.prod(f0.shape[1:-1]), f0.shape[-1]
+    if w.numel() != C:
+        raise GqHipError(f"w holds {w.numel()} weights for {C} channels")
+    if keep is not None:
+        keep = _dev(keep, torch.uint8, "keep")
+        if keep.shape != f0.shape:
+            raise GqHipError(f"keep must have the shape of the features {tuple(f0.shape)}, got {tuple(keep.shape)}")
+    return f0, f1, w, keep, B, C, HW
+
+
+def lpips_head(f0, f1, w, layout: str, keep=None, keep_scale: float = 1.0, ws: Optional[LpipsHeadWorkspace] = None):
+    """One LPIPS level's comparison head in one call (gqhip.h: lpips_head_f32): features f0, f1 in a library layout, the `lin`
+    weights w [C], an optional uint8 keep mask in the features' layout with its scale -> out float32 [B]."""
+    f0, f1, w, keep, B, C, HW = _lpips_operands(f0, f1, w, keep, layout)
+    ws = ws or LpipsHeadWorkspace()
+    dev = f0.device
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    if B == 0:                                          # an empty tensor has no pointer to hand over
+        return out
+    with torch.cuda.device(dev):
+        wptr, wbytes = ws.get(B, C, HW, dev)
+        _check(lib().lpips_head_f32(f0.data_ptr(), f1.data_ptr(), w.data_ptr(), _ptr(keep), float(keep_scale), out.data_ptr(), B, C, HW,
+                                    GQHIP_LAYOUT[layout], wptr, wbytes, _stream()), "lpips_head_f32")
+    return out
+
+
+def lpips_head_backward(f0, f1, w, g_out, layout: str, keep=None, keep_scale: float = 1.0):
+    """The gradient of ``lpips_head`` for its SECOND feature map in one call (gqhip.h: lpips_head_backward_f32); ``g_out`` [B] is the
+    gradient arriving at out.  The head is symmetric: swap f0 and f1 for the gradient of the first."""
+    f0, f1, w, keep, B, C, HW = _lpips_operands(f0, f1, w, keep, layout)
+    g_out = _grad_of(g_out, (B,), "g_out", "out")
+    grad = torch.empty_like(f1)
+    if B == 0:
+        return grad
+    with torch.cuda.device(f0.device):
+        _check(lib().lpips_head_backward_f32(f0.data_ptr(), f1.data_ptr(), w.data_ptr(), _ptr(keep), float(keep_scale),
+                                             g_out.data_ptr(), grad.data_ptr(), B, C, HW, GQHIP_LAYOUT[layout], _stream()),
+               "lpips_head_backward_f32")
+    return grad
 
 
 def lfq_unpack(idx, nbits: int):
