@@ -9,6 +9,13 @@
  * a gqhip_status (0 = success) instead of throwing.  They are re-entrant and
  * hold no global state except the optional profiling recorder.
  *
+ * The _host suffix is load-bearing: the Python package reads this header when
+ * it loads the library and types a parameter `T *name_host` as a pointer to T
+ * that the library dereferences on the host, every other pointer as an opaque
+ * address (pit_hip/_lib.py:_parse_header), so a new prototype keeps to the
+ * forms used below: `[const] type [*]name` with int, int64_t, float or double
+ * scalars.
+ *
  * Reference interface each entry point replaces (paths under /root/reference):
  *
  *   gq_scores_f32    gq_cuda_extension/gq_cuda/csrc/cuda/gq_cuda.cu:77-118
@@ -106,12 +113,12 @@ int gqhip_last_hip_error(void);
 int gqhip_set_filter(int kind);
 int gqhip_get_filter(void);
 
-/* Diagnostics: launch plan and workspace layout of the fused arg-max for a shape.  out8 = { byte offset of the
+/* Diagnostics: launch plan and workspace layout of the fused arg-max for a shape.  out8_host = { byte offset of the
  * candidate records, code splits, tiles per candidate group, tiles per split, filter kernel the plan selects (0 fp32 MFMA, 1 split-bf16, 2 fp16 + fp8, 3 fp16 main product: the default at dims 8 / 16 / 32), coefficient of the
  * filter error bound (E_f = coeff * 2^-24 * T), row tiles per wave, waves per filter block }.
  * The records are 16 bytes per (row, record set): { fp32 m1; fp16 gaps m1 - m2..m4, rounded towards zero; three 16-bit
  * half-group ids relative to the set's split } (csrc/gq_common.h:Rec); "code splits" counts record sets. */
-int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8);
+int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host);
 
 
 /* ---- workspace ------------------------------------------------------------

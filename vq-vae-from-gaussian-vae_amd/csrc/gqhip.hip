@@ -718,14 +718,14 @@ int gqhip_set_filter(int kind) {
 
 int gqhip_get_filter(void) { return g_filter_kind.load(std::memory_order_relaxed); }
 
-int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8) {
-  if (!out8 || rows < 1 || n < 1 || dim < 1 || dim > kMaxDim) return GQHIP_ERR_INVALID_ARG;
+int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host) {
+  if (!out8_host || rows < 1 || n < 1 || dim < 1 || dim > kMaxDim) return GQHIP_ERR_INVALID_ARG;
   const Plan pl = make_plan(rows, n, dim);
-  out8[0] = ws_layout(pl, rows, dim).rec; out8[1] = pl.stored_rec_sets();
-  out8[2] = pl.gt; out8[3] = pl.tiles_per_split;
-  out8[4] = pl.f16 ? 3 : (pl.mixed ? 2 : (pl.bf16 ? 1 : 0));   // 0 fp32 MFMA filter, 1 split-bf16, 2 fp16 + fp8 (Gaussian score), 3 fp16 main product
-  out8[5] = (int64_t)rerank_bound(pl, kModeGQ, dim).ef_coeff;
-  out8[6] = pl.rt; out8[7] = pl.waves;
+  out8_host[0] = ws_layout(pl, rows, dim).rec; out8_host[1] = pl.stored_rec_sets();
+  out8_host[2] = pl.gt; out8_host[3] = pl.tiles_per_split;
+  out8_host[4] = pl.f16 ? 3 : (pl.mixed ? 2 : (pl.bf16 ? 1 : 0));   // 0 fp32 MFMA filter, 1 split-bf16, 2 fp16 + fp8 (Gaussian score), 3 fp16 main product
+  out8_host[5] = (int64_t)rerank_bound(pl, kModeGQ, dim).ef_coeff;
+  out8_host[6] = pl.rt; out8_host[7] = pl.waves;
   return GQHIP_OK;
 }
 

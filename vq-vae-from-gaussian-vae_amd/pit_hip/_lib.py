@@ -1,4 +1,5 @@
-"""ctypes binding of libgqhip.so (the C ABI declared in include/gqhip.h).
+"""ctypes binding of libgqhip.so (the C ABI declared in include/gqhip.h, which is read at import: the signatures come from its
+prototypes).  A new entry point is a prototype there, a definition in csrc/ and a wrapper here that goes through ``_call``.
 
 torch is used only for device memory and the current HIP stream: every call
 hands raw ``data_ptr()`` values and ``torch.cuda.current_stream().cuda_stream``
@@ -11,6 +12,7 @@ import ctypes
 import threading
 import math
 import os
+import re
 import subprocess
 from typing import NamedTuple, Optional, Tuple
 
@@ -27,142 +29,100 @@ GQHIP_GROUP_CONTIGUOUS = 1
 
 _lib: Optional[ctypes.CDLL] = None
 
-_vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
-_SIGNATURES = {
-    # name: (restype, argtypes)
-    "gqhip_abi_version": (ctypes.c_int, []),
-    "gqhip_status_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "gqhip_last_hip_error": (ctypes.c_int, []),
-    "gqhip_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "gqhip_cb_cache_bytes": (_i64, [_i64, _i64]),
-    "gqhip_grid_search_applies": (ctypes.c_int, [_i64, _i64]),
-    "gqhip_cb_cache_degenerate": (ctypes.c_int, [_vp, _i64, _i64]),
-    "gqhip_debug_grid": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64)]),
-    "gqhip_set_filter": (ctypes.c_int, [ctypes.c_int]),
-    "gqhip_get_filter": (ctypes.c_int, []),
-    "gqhip_debug_plan": (ctypes.c_int, [_i64, _i64, _i64, ctypes.POINTER(_i64)]),
-    "gq_scores_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, _vp]),
-    "gq_argmax_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, _vp, _i64, _vp, _i64, _vp]),
-    "gq_quantize_z_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                         ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                         ctypes.c_double, _vp, _i64, _vp, _i64, _vp]),
-    "gq_quantize_z_gauss_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                               ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                               ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                               ctypes.c_double, ctypes.c_int, _vp, _i64, _vp, _i64, _vp]),
-    "gq_gauss_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp]),
-    "gq_gauss_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                             _vp]),
-    "vq_quantize_z_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
-                                         ctypes.c_int, _vp, _i64, _vp, _i64, _vp]),
-    "vq_backward_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "vq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_double,
-                                       ctypes.c_int, _vp, _i64, _vp]),
-    "lfq_train_workspace_bytes": (_i64, [_i64, _i64]),
-    "lfq_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
-                                     ctypes.c_float, _vp, _i64, _vp]),
-    "lfq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
-                                        ctypes.c_float, _vp, _i64, _vp]),
-    "bsq_train_workspace_bytes": (_i64, [_i64, _i64]),
-    "bsq_train_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float, ctypes.c_float,
-                                     _vp, _i64, _vp]),
-    "bsq_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float,
-                                        ctypes.c_float, _vp, _i64, _vp]),
-    "lpips_head_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "lpips_head_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _i64, _i64, _i64, ctypes.c_int, _vp, _i64, _vp]),
-    "lpips_head_backward_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, _vp]),
-    "gq_dequant_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
-                                      ctypes.c_int, _vp]),
-    "vq_argmin_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
-    "lfq_pack_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
-    "lfq_unpack_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp]),
-    "fsq_quantize_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _vp, _i64, _vp]),
-    "fsq_dequant_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _i64, _vp]),
-    "fsq_train_f32": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _vp, _i64, _i64, ctypes.c_int, _vp]),
-    "fsq_backward_f32": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_int32), _i64, _vp, _i64, _i64, ctypes.c_int, _vp]),
-    "gn_silu_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int,
-                                   ctypes.c_int, _vp, _vp]),
-    "add_bias_stats_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "gn_apply_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp]),
-    "wino_in_nhwc_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "wino4_in_nhwc_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "wino4_out_nhwc_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
-    "wino_out_res_nhwc_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_int,
-                                              ctypes.c_float, _vp]),
-    "wino_in_nhwc_f16x3": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float, _vp]),
-    "wino_in_nhwc_f16x2": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_float, _vp]),
-    "wino_gemm_f16x2": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "upconv2x_f16x3": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64,
-                                      _vp]),
-    "attn_split_qkv_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, _vp]),
-    "attn_softmax_split_f16x3": (ctypes.c_int, [_vp, _vp, _i64, _i64, ctypes.c_float, _vp]),
-    "wino_in_gn_nhwc_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_double,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp]),
-    "wino_in_gn_nhwc_f16x2": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_double,
-                                              ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp]),
-    "conv3x3_gn_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_float, _vp,
-                                         _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
-    "conv1x1_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                      _vp]),
-    "conv1x1_gn_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp,
-                                         _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
-    "conv1x1_qkv_split_f16x3": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, ctypes.c_float, ctypes.c_float,
-                                                _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _i64, _i64, _i64, _vp]),
-    "conv3x3s2_f16x3": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
-                                        _i64, _vp]),
-    "conv3x3_gn_small_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _i64, _i64,
-                                             _i64, _i64, _i64, _vp]),
-    "conv3x3_cin_small_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp]),
-    "conv3x3_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _i64, _i64, _i64,
-                                   _i64, _i64, _vp]),
-    "gqhip_checksum_tensors": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
-    "gn_stats_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "wino_in_gn_nhwc_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_double,
-                                            ctypes.c_int, _vp]),
-    "wino4_in_gn_nhwc_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, ctypes.c_double,
-                                             ctypes.c_int, _vp]),
-    "wino_out_nhwc_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
-    "f16_scales_from_gn_stats": (ctypes.c_int, [_vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp]),
-    "upsample2x_nhwc_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "add_bias_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, _vp]),
-    "gqhip_stats_prezeroed": (ctypes.c_int, [ctypes.c_int]),
-    "gq_index_histogram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
-    "gq_indices_to_u16": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
-    "gq_indices_from_u16": (ctypes.c_int, [_vp, _vp, _i64, _vp]),
-    "gq_step_record_workspace_bytes": (_i64, [_i64, _i64]),
-    "gq_step_record_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),
-    "gq_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "gq_ssim_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _i64, _vp]),
-    "gq_step_record_ssim_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "gq_step_record_ssim_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
-    "gq_indices_pack_bits": (ctypes.c_int, [_vp, _vp, _i64, ctypes.c_int, _i64, _vp, _vp]),
-    "gq_indices_unpack_bits": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _vp]),
-    "gq_index_histogram_packed": (ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _vp]),
-    "gq_step_record_bits_workspace_bytes": (_i64, [_i64, _i64]),
-    "gq_step_record_bits_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, _i64, _vp, _i64, _vp]),
-    "gq_step_record_ssim_bits_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "gq_step_record_ssim_bits_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, _i64,
-                                                     _vp, _i64, _vp]),
-    "gq_mha_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "gq_mha_fwd_f32": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "gq_mha_fwd_lse_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "gq_mha_bwd_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "gq_mha_bwd_f32": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "gqhip_profile_enable": (ctypes.c_int, [ctypes.c_int]),
-    "gqhip_profile_reserve": (ctypes.c_int, [ctypes.c_int]),
-    "gqhip_profile_collect": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]),
-    "gqhip_debug_enable": (ctypes.c_int, [ctypes.c_int]),
-    "gqhip_debug_counters": (ctypes.c_int, [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
-}
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
 class GqHipError(RuntimeError):
     pass
+
+
+# ---- the C ABI, read from include/gqhip.h ------------------------------------------------------------------------------------
+# The header is the one statement of the ABI: scalars map by type, a pointer whose name ends in _host is one the library
+# dereferences on the host (typed), every other pointer is a device address or the stream (opaque).
+_SCALAR_CTYPES = {"int": ctypes.c_int, "int64_t": _i64, "float": ctypes.c_float, "double": ctypes.c_double}
+_HOST_ELEMENT_CTYPES = dict(_SCALAR_CTYPES, int32_t=ctypes.c_int32)
+_RETURN_CTYPES = {"int": ctypes.c_int, "int64_t": _i64, "const char *": ctypes.c_char_p}
+_PROTOTYPE = re.compile(r"^[ \t]*(int64_t\b|int\b|const\s+char\s*\*)\s*(\w+)\s*\(([^()]*)\)\s*;", re.M)
+_PARAMETER = re.compile(r"(?:const\s+)?(\w+)(?:\s+|\s*(\*)\s*)(\w+)")      # [const] type [*] name
+
+
+def _parse_header(text: str):
+    """({name: (restype, [argtypes])}, {name: (parameter names)}) of every prototype ``int | int64_t | const char * name(args);``
+    in the text of a C header.  A parameter the mapping above does not cover raises: a guessed width is a garbage argument."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    signatures, params = {}, {}
+    for ret, name, arglist in _PROTOTYPE.findall(text):
+        argtypes, names = [], []
+        for p in ([] if arglist.strip() == "void" else arglist.split(",")):
+            m = _PARAMETER.fullmatch(p.strip())
+            ctype, star, pname = m.groups() if m else (None, None, "")
+            if not star:
+                arg = _SCALAR_CTYPES.get(ctype)
+            elif not pname.endswith("_host"):
+                arg = ctypes.c_void_p
+            else:
+                arg = ctypes.POINTER(_HOST_ELEMENT_CTYPES[ctype]) if ctype in _HOST_ELEMENT_CTYPES else None
+            if arg is None:
+                raise GqHipError(f"gqhip.h: no ctypes mapping for the parameter {p.strip()!r} of {name}({' '.join(arglist.split())})")
+            argtypes.append(arg)
+            names.append(pname)
+        signatures[name] = (_RETURN_CTYPES[" ".join(ret.replace("*", " *").split())], argtypes)
+        params[name] = tuple(names)
+    return signatures, params
+
+
+def _read_header():
+    path = os.path.normpath(os.path.join(_CSRC, "..", "..", "include", "gqhip.h"))    # the Makefile's -I../../include
+    if not os.path.exists(path):
+        raise GqHipError(f"{path} is missing: the binding reads the C ABI from it. There is no second copy.")
+    with open(path) as f:
+        return _parse_header(f.read())
+
+
+_SIGNATURES, _PARAMS = _read_header()      # name -> (restype, [argtypes]); name -> parameter names
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+
+def _pointer(a):
+    return a if a is None or isinstance(a, int) else a.data_ptr()
+
+
+def _same(a):
+    return a
+
+
+def _converters(name: str):
+    """(one converter per argument the caller passes, whether a trailing ``stream`` follows them) of an entry."""
+    argtypes, names = _SIGNATURES[name][1], _PARAMS[name]
+    has_stream = bool(names) and names[-1] == "stream"
+    kinds = {ctypes.c_void_p: _pointer, ctypes.c_int: int, _i64: int, ctypes.c_float: float, ctypes.c_double: float}
+    return tuple(kinds.get(t, _same) for t in (argtypes[:-1] if has_stream else argtypes)), has_stream
+
+
+_CONVERTERS = {name: _converters(name) for name in _SIGNATURES}
+
+
+def _call_args(name: str, args) -> list:
+    """The caller's arguments of entry ``name`` as ctypes takes them, by the entry's declared types: a tensor for a ``void *``
+    becomes its data_ptr() (None and an int address pass), ``int`` / ``int64_t`` take int() (a bool is 0 / 1), ``float`` /
+    ``double`` take float(), typed host pointers pass.  The stream is not among them: _call supplies it."""
+    converters = _CONVERTERS[name][0]
+    if len(args) != len(converters):
+        raise GqHipError(f"{name}: takes {len(converters)} arguments" + (" and the stream" if _CONVERTERS[name][1] else "")
+                         + f", got {len(args)}")
+    return [c(a) for c, a in zip(converters, args)]
+
+
+def _call(name: str, device, *args) -> None:
+    """THE way into a launching entry point: on ``device``, with _call_args' conversions and the current stream, raising a
+    GqHipError that names the entry when the status is not 0."""
+    with torch.cuda.device(device):
+        converted = _call_args(name, args)
+        if _CONVERTERS[name][1]:
+            converted.append(_stream())
+        rc = getattr(lib(), name)(*converted)
+        if rc != 0:
+            _check(rc, name)
 
 
 def build(force: bool = False) -> str:
@@ -210,7 +170,9 @@ def _dev(t: torch.Tensor, dtype: torch.dtype, name: str) -> torch.Tensor:
 
 
 def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+    """The current stream of the current device as a hipStream_t: torch.cuda.current_stream().cuda_stream without the Stream
+    object in between (about 2 us of an 11 us call: profiles/r30/host_call_overhead.txt; torch's compiled code asks the same way)."""
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -312,9 +274,7 @@ def gq_scores(mu, sd, cb, out, beta: float = 1.0) -> None:
     n = cb.shape[0]
     if sd.shape != mu.shape or cb.shape[1] != dim or tuple(out.shape) != (rows, n):
         raise GqHipError("shape mismatch in gq_scores")
-    with torch.cuda.device(mu.device):
-        _check(lib().gq_scores_f32(mu.data_ptr(), sd.data_ptr(), cb.data_ptr(), out.data_ptr(), dim, rows, n,
-                                   float(beta), _stream()), "gq_scores_f32")
+    _call("gq_scores_f32", mu.device, mu, sd, cb, out, dim, rows, n, beta)
 
 
 def gq_argmax(mu, sd, cb, beta: float = 1.0, logsd=None, ws: Optional[Workspace] = None, want_zhat: bool = True):
@@ -331,8 +291,7 @@ def gq_argmax(mu, sd, cb, beta: float = 1.0, logsd=None, ws: Optional[Workspace]
     with torch.cuda.device(mu.device):
         wptr, wbytes = ws.get(rows, n, dim, mu.device)
         cptr, cbytes = ws.cache(n, dim, mu.device)
-        _check(lib().gq_argmax_f32(mu.data_ptr(), sd.data_ptr(), _ptr(logsd), cb.data_ptr(), idx.data_ptr(),
-                                   _ptr(zhat), dim, rows, n, float(beta), wptr, wbytes, cptr, cbytes, _stream()), "gq_argmax_f32")
+    _call("gq_argmax_f32", mu.device, mu, sd, logsd, cb, idx, zhat, dim, rows, n, beta, wptr, wbytes, cptr, cbytes)
     return idx, zhat
 
 
@@ -360,10 +319,8 @@ def gq_quantize_z(z, cb, dim: int, layout: str, grouping: int, lv_range=(-30.0, 
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, dev)
         cptr, cbytes = ws.cache(n, dim, dev)
-        _check(lib().gq_quantize_z_f32(z.data_ptr(), _ptr(noise), cb.data_ptr(), idx.data_ptr(), zhat.data_ptr(),
-                                       _ptr(noquant), _ptr(mu_o), _ptr(sd_o), B, L, c, dim, n, GQHIP_LAYOUT[layout],
-                                       grouping, float(lv_range[0]), float(lv_range[1]), float(beta),
-                                       wptr, wbytes, cptr, cbytes, _stream()), "gq_quantize_z_f32")
+    _call("gq_quantize_z_f32", dev, z, noise, cb, idx, zhat, noquant, mu_o, sd_o, B, L, c, dim, n, GQHIP_LAYOUT[layout], grouping,
+          lv_range[0], lv_range[1], beta, wptr, wbytes, cptr, cbytes)
     out = (idx, zhat)
     if return_operands:
         out = out + (mu_o, sd_o)
@@ -376,7 +333,8 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
                         lam_factor: float, lam_range, lam_max_decreases: bool, use_ste: bool = True, lv_range=(-30.0, 20.0),
                         beta: float = 1.0, ws: Optional[Workspace] = None, want_std: bool = True):
     """GaussianQuantRegularizer2's eval forward in one call (gqhip.h: gq_quantize_z_gauss_f32).  ``lam_state``: float64 [3] device
-    tensor {lam, lam_min, lam_max}, advanced in place.  Returns (idx, zhat, zhat_noquant, std or None, scalars) with ``scalars`` a
+    tensor {lam, lam_min, lam_max}, advanced in place.  Returns (idx, zhat, zhat_quant, zhat_noquant, std or None, scalars):
+    ``zhat_quant`` holds the codewords themselves (info["zhat_quant"]; zhat itself when ``use_ste`` is off), ``scalars`` is a
     fresh 64-byte device buffer: float32 view [0:4] = kl_loss, bits-mean, bits-min, bits-max; float64 view of bytes 32..56 = the
     lambdas after the update."""
     z, cb, noise = _dev(z, torch.float32, "z"), _dev(cb, torch.float32, "codebook"), _dev(noise, torch.float32, "noise")
@@ -396,12 +354,9 @@ def gq_quantize_z_gauss(z, cb, dim: int, layout: str, grouping: int, noise, lam_
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, dev)
         cptr, cbytes = ws.cache(n, dim, dev)
-        _check(lib().gq_quantize_z_gauss_f32(z.data_ptr(), noise.data_ptr(), cb.data_ptr(), idx.data_ptr(), zhat.data_ptr(),
-                                             _ptr(pure), noquant.data_ptr(), _ptr(std), scalars.data_ptr(), lam_state.data_ptr(), B, L, c, dim,
-                                             n, GQHIP_LAYOUT[layout], grouping, float(lv_range[0]), float(lv_range[1]),
-                                             float(beta), 1 if use_ste else 0, float(log2n), float(tolerance), float(lam_factor),
-                                             float(lam_range[0]), float(lam_range[1]), 1 if lam_max_decreases else 0,
-                                             wptr, wbytes, cptr, cbytes, _stream()), "gq_quantize_z_gauss_f32")
+    _call("gq_quantize_z_gauss_f32", dev, z, noise, cb, idx, zhat, pure, noquant, std, scalars, lam_state, B, L, c, dim, n,
+          GQHIP_LAYOUT[layout], grouping, lv_range[0], lv_range[1], beta, bool(use_ste), log2n, tolerance, lam_factor,
+          lam_range[0], lam_range[1], bool(lam_max_decreases), wptr, wbytes, cptr, cbytes)
     return idx, zhat, (pure if use_ste else zhat), noquant, std, scalars
 
 
@@ -473,12 +428,8 @@ def gq_gauss_train(z, dim: int, layout: str, grouping: int, noise, lam_state, lo
     std = torch.empty_like(zhat) if want_std else None
     kl2row = torch.empty(rows, dtype=torch.float32, device=dev)
     scalars = torch.empty(64, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _check(lib().gq_gauss_train_f32(z.data_ptr(), noise.data_ptr(), zhat.data_ptr(), _ptr(std), kl2row.data_ptr(),
-                                        scalars.data_ptr(), lam_state.data_ptr(), B, L, c, dim, GQHIP_LAYOUT[layout], grouping,
-                                        float(lv_range[0]), float(lv_range[1]), float(log2n), float(tolerance), float(lam_factor),
-                                        float(lam_range[0]), float(lam_range[1]), 1 if lam_max_decreases else 0,
-                                        float(loss_divisor), _stream()), "gq_gauss_train_f32")
+    _call("gq_gauss_train_f32", dev, z, noise, zhat, std, kl2row, scalars, lam_state, B, L, c, dim, GQHIP_LAYOUT[layout], grouping,
+          lv_range[0], lv_range[1], log2n, tolerance, lam_factor, lam_range[0], lam_range[1], bool(lam_max_decreases), loss_divisor)
     return zhat, std, kl2row, scalars
 
 
@@ -498,11 +449,8 @@ def gq_gauss_backward(z, dim: int, layout: str, grouping: int, noise, lam_before
         g_zhat = g_zhat_noquant
     g_kl = _grad_scalar(g_kl, "g_kl")
     grad_z = torch.empty_like(z)
-    with torch.cuda.device(z.device):
-        _check(lib().gq_gauss_backward_f32(z.data_ptr(), noise.data_ptr(), _ptr(g_zhat), _ptr(g_std), _ptr(g_kl),
-                                           lam_before.data_ptr(), grad_z.data_ptr(), B, L, c, dim, GQHIP_LAYOUT[layout], grouping,
-                                           float(lv_range[0]), float(lv_range[1]), float(log2n), float(tolerance),
-                                           float(loss_divisor), _stream()), "gq_gauss_backward_f32")
+    _call("gq_gauss_backward_f32", z.device, z, noise, g_zhat, g_std, g_kl, lam_before, grad_z, B, L, c, dim, GQHIP_LAYOUT[layout],
+          grouping, lv_range[0], lv_range[1], log2n, tolerance, loss_divisor)
     return grad_z
 
 
@@ -523,9 +471,8 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, dev)
         cptr, cbytes = ws.cache(n, dim, dev) if use_cache else (None, 0)
-        _check(lib().vq_quantize_z_f32(z.data_ptr(), emb.data_ptr(), idx.data_ptr(), zq.data_ptr(), loss.data_ptr(), B, L, c, dim,
-                                       n, GQHIP_LAYOUT[layout], float(beta), 1 if legacy else 0, wptr, wbytes, cptr, cbytes,
-                                       _stream()), "vq_quantize_z_f32")
+    _call("vq_quantize_z_f32", dev, z, emb, idx, zq, loss, B, L, c, dim, n, GQHIP_LAYOUT[layout], beta, bool(legacy), wptr, wbytes,
+          cptr, cbytes)
     return idx, zq, loss
 
 
@@ -570,9 +517,8 @@ def vq_backward(z, emb, idx, dim: int, layout: str, beta: float, legacy: bool, g
     grad_emb = torch.empty_like(emb) if want_grad_emb else None
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(items, n, dim, dev)
-        _check(lib().vq_backward_f32(z.data_ptr(), emb.data_ptr(), idx.data_ptr(), _ptr(g_zq), _ptr(g_loss), _ptr(grad_z),
-                                     _ptr(grad_emb), B, L, c, dim, n, GQHIP_LAYOUT[layout], float(beta), 1 if legacy else 0,
-                                     wptr, wbytes, _stream()), "vq_backward_f32")
+    _call("vq_backward_f32", dev, z, emb, idx, g_zq, g_loss, grad_z, grad_emb, B, L, c, dim, n, GQHIP_LAYOUT[layout], beta,
+          bool(legacy), wptr, wbytes)
     return grad_z, grad_emb
 
 
@@ -580,9 +526,7 @@ def gq_dequant(idx, cb, dim: int, layout: str, grouping: int):
     idx, cb = _dev(idx, torch.int64, "indices"), _dev(cb, torch.float32, "codebook")
     B, L, _, K, _, shape, _ = _z_geometry(idx, dim, layout, holds="idx")
     zhat = torch.empty(shape, dtype=torch.float32, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _check(lib().gq_dequant_f32(idx.data_ptr(), cb.data_ptr(), zhat.data_ptr(), B, L, K, dim, cb.shape[0],
-                                    GQHIP_LAYOUT[layout], grouping, _stream()), "gq_dequant_f32")
+    _call("gq_dequant_f32", idx.device, idx, cb, zhat, B, L, K, dim, cb.shape[0], GQHIP_LAYOUT[layout], grouping)
     return zhat
 
 
@@ -598,8 +542,7 @@ def vq_argmin(z, emb, ws: Optional[Workspace] = None, use_cache: bool = True):
     with torch.cuda.device(z.device):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, z.device)
         cptr, cbytes = ws.cache(n, dim, z.device) if use_cache else (None, 0)
-        _check(lib().vq_argmin_f32(z.data_ptr(), emb.data_ptr(), idx.data_ptr(), zq.data_ptr(), dim, rows, n,
-                                   wptr, wbytes, cptr, cbytes, _stream()), "vq_argmin_f32")
+    _call("vq_argmin_f32", z.device, z, emb, idx, zq, dim, rows, n, wptr, wbytes, cptr, cbytes)
     return idx, zq
 
 
@@ -608,8 +551,7 @@ def lfq_pack(x):
     rows, nbits = x.shape
     idx = torch.empty(rows, dtype=torch.int64, device=x.device)
     q = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _check(lib().lfq_pack_f32(x.data_ptr(), idx.data_ptr(), q.data_ptr(), rows, nbits, _stream()), "lfq_pack_f32")
+    _call("lfq_pack_f32", x.device, x, idx, q, rows, nbits)
     return idx, q
 
 
@@ -633,9 +575,8 @@ def lfq_train(x, num_codebooks: int, dim: int, layout: str, w_s: float = 1.0, w_
     scalars = torch.empty(4, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
-        _check(lib().lfq_train_f32(x.data_ptr(), quantized.data_ptr(), idx.data_ptr(), avg.data_ptr(), scalars.data_ptr(), B, L, C,
-                                   num_codebooks, dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()),
-               "lfq_train_f32")
+    _call("lfq_train_f32", dev, x, quantized, idx, avg, scalars, B, L, C, num_codebooks, dim, GQHIP_LAYOUT[layout], w_s, w_b,
+          wptr, wbytes)
     return quantized, idx, avg, scalars
 
 
@@ -654,9 +595,8 @@ def lfq_backward(x, avg, num_codebooks: int, dim: int, layout: str, w_s: float =
     grad_x = torch.empty_like(x)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L * num_codebooks, dim, dev)
-        _check(lib().lfq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(g_aux), _ptr(g_commit), grad_x.data_ptr(), B, L,
-                                      C, num_codebooks, dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()),
-               "lfq_backward_f32")
+    _call("lfq_backward_f32", dev, x, avg, g_q, g_aux, g_commit, grad_x, B, L, C, num_codebooks, dim, GQHIP_LAYOUT[layout], w_s, w_b,
+          wptr, wbytes)
     return grad_x
 
 
@@ -687,8 +627,7 @@ def bsq_train(x, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1.0, ws: 
     scalars = torch.empty(3, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L, dim, dev)
-        _check(lib().bsq_train_f32(x.data_ptr(), quantized.data_ptr(), idx.data_ptr(), avg.data_ptr(), scalars.data_ptr(), B, L, C,
-                                   dim, GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()), "bsq_train_f32")
+    _call("bsq_train_f32", dev, x, quantized, idx, avg, scalars, B, L, C, dim, GQHIP_LAYOUT[layout], w_s, w_b, wptr, wbytes)
     return quantized, idx, avg, scalars
 
 
@@ -708,8 +647,7 @@ def bsq_backward(x, avg, dim: int, layout: str, w_s: float = 1.0, w_b: float = 1
     grad_x = torch.empty_like(x)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B * L, dim, dev)
-        _check(lib().bsq_backward_f32(x.data_ptr(), avg.data_ptr(), _ptr(g_q), _ptr(g_aux), grad_x.data_ptr(), B, L, C, dim,
-                                      GQHIP_LAYOUT[layout], float(w_s), float(w_b), wptr, wbytes, _stream()), "bsq_backward_f32")
+    _call("bsq_backward_f32", dev, x, avg, g_q, g_aux, grad_x, B, L, C, dim, GQHIP_LAYOUT[layout], w_s, w_b, wptr, wbytes)
     return grad_x
 
 
@@ -746,8 +684,7 @@ def lpips_head(f0, f1, w, layout: str, keep=None, keep_scale: float = 1.0, ws: O
         return out
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(B, C, HW, dev)
-        _check(lib().lpips_head_f32(f0.data_ptr(), f1.data_ptr(), w.data_ptr(), _ptr(keep), float(keep_scale), out.data_ptr(), B, C, HW,
-                                    GQHIP_LAYOUT[layout], wptr, wbytes, _stream()), "lpips_head_f32")
+    _call("lpips_head_f32", dev, f0, f1, w, keep, keep_scale, out, B, C, HW, GQHIP_LAYOUT[layout], wptr, wbytes)
     return out
 
 
@@ -759,10 +696,7 @@ def lpips_head_backward(f0, f1, w, g_out, layout: str, keep=None, keep_scale: fl
     grad = torch.empty_like(f1)
     if B == 0:
         return grad
-    with torch.cuda.device(f0.device):
-        _check(lib().lpips_head_backward_f32(f0.data_ptr(), f1.data_ptr(), w.data_ptr(), _ptr(keep), float(keep_scale),
-                                             g_out.data_ptr(), grad.data_ptr(), B, C, HW, GQHIP_LAYOUT[layout], _stream()),
-               "lpips_head_backward_f32")
+    _call("lpips_head_backward_f32", f0.device, f0, f1, w, keep, keep_scale, g_out, grad, B, C, HW, GQHIP_LAYOUT[layout])
     return grad
 
 
@@ -770,8 +704,7 @@ def lfq_unpack(idx, nbits: int):
     idx = _dev(idx, torch.int64, "indices")
     rows = idx.numel()
     q = torch.empty(rows, nbits, dtype=torch.float32, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _check(lib().lfq_unpack_f32(idx.data_ptr(), q.data_ptr(), rows, nbits, _stream()), "lfq_unpack_f32")
+    _call("lfq_unpack_f32", idx.device, idx, q, rows, nbits)
     return q
 
 
@@ -788,9 +721,7 @@ def fsq_quantize(z, levels):
     assert n == nlev
     zhat = torch.empty_like(z)
     idx = torch.empty(rows, dtype=torch.int32, device=z.device)
-    with torch.cuda.device(z.device):
-        _check(lib().fsq_quantize_f32(z.data_ptr(), arr, n, zhat.data_ptr(), idx.data_ptr(), rows, _stream()),
-               "fsq_quantize_f32")
+    _call("fsq_quantize_f32", z.device, z, arr, n, zhat, idx, rows)
     return zhat, idx
 
 
@@ -802,9 +733,7 @@ def fsq_train(z, levels, layout: str):
     arr, n = _levels(levels)
     zhat = torch.empty_like(z)
     idx = torch.empty(shape(1), dtype=torch.int32, device=z.device)
-    with torch.cuda.device(z.device):
-        _check(lib().fsq_train_f32(z.data_ptr(), arr, n, zhat.data_ptr(), idx.data_ptr(), B, L, GQHIP_LAYOUT[layout], _stream()),
-               "fsq_train_f32")
+    _call("fsq_train_f32", z.device, z, arr, n, zhat, idx, B, L, GQHIP_LAYOUT[layout])
     return zhat, idx
 
 
@@ -818,9 +747,7 @@ def fsq_backward(z, g_zhat, levels, layout: str):
         raise GqHipError("g_zhat is required")
     arr, n = _levels(levels)
     grad_z = torch.empty_like(z)
-    with torch.cuda.device(z.device):
-        _check(lib().fsq_backward_f32(z.data_ptr(), g_zhat.data_ptr(), arr, n, grad_z.data_ptr(), B, L, GQHIP_LAYOUT[layout],
-                                      _stream()), "fsq_backward_f32")
+    _call("fsq_backward_f32", z.device, z, g_zhat, arr, n, grad_z, B, L, GQHIP_LAYOUT[layout])
     return grad_z
 
 
@@ -829,8 +756,7 @@ def fsq_dequant(idx, levels):
     arr, n = _levels(levels)
     rows = idx.numel()
     zhat = torch.empty(rows, n, dtype=torch.float32, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _check(lib().fsq_dequant_f32(idx.data_ptr(), arr, n, zhat.data_ptr(), rows, _stream()), "fsq_dequant_f32")
+    _call("fsq_dequant_f32", idx.device, idx, arr, n, zhat, rows)
     return zhat
 
 
@@ -954,10 +880,10 @@ def _pow2_scale(bound, amp: float = 1.0) -> float:
 
 
 def _operand_scales(scale, u_scale: float, post_scale: float = 1.0):
-    """(device scales pointer or None, v_scale, mscale) of a direct fp16 x 3 convolution: ``scale`` is a float bound of the
+    """(device scales or None, v_scale, mscale) of a direct fp16 x 3 convolution: ``scale`` is a float bound of the
     activation, or the device float[2] of f16_scales -- the kernel then reads both factors there, and 0.0 goes in their place."""
     if torch.is_tensor(scale):
-        return scale.data_ptr(), 0.0, 0.0
+        return scale, 0.0, 0.0
     v_scale = _pow2_scale(scale)
     return None, v_scale, float(post_scale) / (v_scale * u_scale)
 
@@ -1010,9 +936,7 @@ def gn_silu(x, gamma, beta, groups: int, eps: float, silu: bool = True, pre_bias
     # modules/unet.py:_with_stats_arena) or a fresh stream-ordered tensor from the caching allocator
     ws = _stats_records(GNSTAT_WORDS * B * groups, x.device)
     y = torch.empty_like(x)  # preserves the memory format
-    with torch.cuda.device(x.device):
-        _check(lib().gn_silu_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(pre_bias), y.data_ptr(), B, C, HW,
-                                 groups, float(eps), 1 if silu else 0, layout, ws.data_ptr(), _stream()), "gn_silu_f32")
+    _call("gn_silu_f32", x.device, x, gamma, beta, pre_bias, y, B, C, HW, groups, eps, bool(silu), layout, ws)
     return y
 
 
@@ -1024,9 +948,7 @@ def add_bias(a, b, bias=None):
     B, C = a.shape[0], a.shape[1]
     HW = a.shape[2] * a.shape[3]
     y = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _check(lib().add_bias_f32(a.data_ptr(), b.data_ptr(), _ptr(bias), y.data_ptr(), B, C, HW, layout, _stream()),
-               "add_bias_f32")
+    _call("add_bias_f32", a.device, a, b, bias, y, B, C, HW, layout)
     return y
 
 
@@ -1039,9 +961,7 @@ def add_bias_stats(a, b, bias, groups: int):
     HW = a.shape[2] * a.shape[3]
     y = torch.empty_like(a)
     stats = _stats_records(GNSTAT_WORDS * B * groups, a.device)
-    with torch.cuda.device(a.device):
-        _check(lib().add_bias_stats_f32(a.data_ptr(), b.data_ptr(), _ptr(bias), y.data_ptr(), B, C, HW, groups,
-                                        stats.data_ptr(), _stream()), "add_bias_stats_f32")
+    _call("add_bias_stats_f32", a.device, a, b, bias, y, B, C, HW, groups, stats)
     return y, stats
 
 
@@ -1051,9 +971,7 @@ def gn_apply(x, gamma, beta, groups: int, eps: float, silu: bool, stats):
     B, C = x.shape[0], x.shape[1]
     HW = x.shape[2] * x.shape[3]
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _check(lib().gn_apply_f32(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), B, C, HW, groups,
-                                  float(eps), 1 if silu else 0, stats.data_ptr(), _stream()), "gn_apply_f32")
+    _call("gn_apply_f32", x.device, x, gamma, beta, y, B, C, HW, groups, eps, bool(silu), stats)
     return y
 
 
@@ -1076,9 +994,7 @@ def gn_stats(x, groups: int, pre_bias=None):
         raise GqHipError("gn_stats needs a GroupNorm-compatible C")
     B, C = x.shape[0], x.shape[1]
     stats = _stats_records(GNSTAT_WORDS * B * groups, x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gn_stats_f32(x.data_ptr(), _ptr(pre_bias), B, C, x.shape[2] * x.shape[3], groups, stats.data_ptr(),
-                                  _stream()), "gn_stats_f32")
+    _call("gn_stats_f32", x.device, x, pre_bias, B, C, x.shape[2] * x.shape[3], groups, stats)
     return stats
 
 
@@ -1112,50 +1028,46 @@ def wino_conv3x3(x, U, gn=None, residual=None, bias=None, stats_groups: int = 0,
         v_scale = _pow2_scale(f16.bound, 100.0 if f4 else 4.0)
         use_own = f16.wf2 is not None and tiles % 256 == 0 and own_gemm_fits(T, tiles, cout, C)
         planes, mscale = 2 if use_own else 3, 1.0 / (v_scale * f16.u_scale)
-    L = lib()
-    with torch.cuda.device(x.device):
-        # 1. input transform (with the GroupNorm + SiLU of gn applied on the way)
-        V = torch.empty((T, tiles, (planes or 1) * C), dtype=torch.float16 if planes else x.dtype, device=x.device)
-        _wino_in(L, x, V, gn, t, planes, v_scale)
-        # 2. the 16 / 36 GEMMs [tiles, Cin] x [Cin, Cout], fp32 accumulation
-        if planes == 2:
-            M = torch.empty((T, tiles, cout), dtype=torch.float32, device=x.device)
-            _check(L.wino_gemm_f16x2(V.data_ptr(), f16.wf2.data_ptr(), M.data_ptr(), T, tiles, C, cout, _stream()), "wino_gemm_f16x2")
-            del V                                             # (this route has always freed its operand before y is taken)
-        elif planes == 3:
-            M = torch.bmm(V, f16.U3, out_dtype=torch.float32)     # ONE fp16 GEMM per tile position
-        else:
-            M = torch.bmm(V, U)                               # hipBLASLt
-        # 3. output transform (with bias, residual and the statistics of the result when asked for)
-        if stats_groups:
-            _need_residual("wino_conv3x3", residual, (B, cout, H, W))
-            if not gn_nhwc_ok(cout, stats_groups):
-                raise GqHipError("wino_conv3x3: the fused tail needs a GroupNorm-compatible Cout")
-            y, stats = _out_and_stats(x, cout, H, W, stats_groups)
-            _check(L.wino_out_res_nhwc_f32(M.data_ptr(), _ptr(residual), _ptr(bias), y.data_ptr(), stats.data_ptr(),
-                                           B, H, W, cout, stats_groups, t, float(mscale), _stream()), "wino_out_res_nhwc_f32")
-            return y, stats
-        y = _out_nhwc(x, cout, H, W)
-        _check((L.wino4_out_nhwc_f32 if f4 else L.wino_out_nhwc_f32)(M.data_ptr(), y.data_ptr(), B, H, W, cout,
-                                                                     float(mscale), _stream()), "wino_out_nhwc_f32")
+    dev = x.device
+    # 1. input transform (with the GroupNorm + SiLU of gn applied on the way)
+    V = torch.empty((T, tiles, (planes or 1) * C), dtype=torch.float16 if planes else x.dtype, device=dev)
+    _wino_in(lib(), x, V, gn, t, planes, v_scale)
+    # 2. the 16 / 36 GEMMs [tiles, Cin] x [Cin, Cout], fp32 accumulation
+    if planes == 2:
+        M = torch.empty((T, tiles, cout), dtype=torch.float32, device=dev)
+        _call("wino_gemm_f16x2", dev, V, f16.wf2, M, T, tiles, C, cout)
+        del V                                                 # (this route has always freed its operand before y is taken)
+    elif planes == 3:
+        M = torch.bmm(V, f16.U3, out_dtype=torch.float32)         # ONE fp16 GEMM per tile position
+    else:
+        M = torch.bmm(V, U)                                   # hipBLASLt
+    # 3. output transform (with bias, residual and the statistics of the result when asked for)
+    if stats_groups:
+        _need_residual("wino_conv3x3", residual, (B, cout, H, W))
+        if not gn_nhwc_ok(cout, stats_groups):
+            raise GqHipError("wino_conv3x3: the fused tail needs a GroupNorm-compatible Cout")
+        y, stats = _out_and_stats(x, cout, H, W, stats_groups)
+        _call("wino_out_res_nhwc_f32", dev, M, residual, bias, y, stats, B, H, W, cout, stats_groups, t, mscale)
+        return y, stats
+    y = _out_nhwc(x, cout, H, W)
+    _call("wino4_out_nhwc_f32" if f4 else "wino_out_nhwc_f32", dev, M, y, B, H, W, cout, mscale)
     return y
 
 
 def _wino_in(L, x, V, gn, t: int, planes: int, v_scale: float) -> None:
     """wino_conv3x3's input transform of F(t x t, 3x3) into V, by one of six entry points: fp32 (``planes`` 0), or the fp16
-    operand of 2 | 3 planes scaled by v_scale; ``gn``: with the GroupNorm in front."""
+    operand of 2 | 3 planes scaled by v_scale; ``gn``: with the GroupNorm in front.  ``L``: the loaded library, as tests and
+    tools that drive the transform alone have always passed it; the call goes through _call like every other."""
     B, C, H, W = x.shape
-    f16_args = (t, float(v_scale)) if planes else ()
+    f16_args = (t, v_scale) if planes else ()
     if gn is None:
         name = {0: "wino4_in_nhwc_f32" if t == 4 else "wino_in_nhwc_f32", 2: "wino_in_nhwc_f16x2", 3: "wino_in_nhwc_f16x3"}[planes]
-        rc = getattr(L, name)(x.data_ptr(), V.data_ptr(), B, H, W, C, *f16_args, _stream())
+        _call(name, x.device, x, V, B, H, W, C, *f16_args)
     else:
         name = {0: "wino4_in_gn_nhwc_f32" if t == 4 else "wino_in_gn_nhwc_f32", 2: "wino_in_gn_nhwc_f16x2",
                 3: "wino_in_gn_nhwc_f16x3"}[planes]
         gn = GnFold(*gn)
-        rc = getattr(L, name)(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
-                              V.data_ptr(), B, H, W, C, gn.groups, float(gn.eps), 1 if gn.silu else 0, *f16_args, _stream())
-    _check(rc, name)
+        _call(name, x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, V, B, H, W, C, gn.groups, gn.eps, bool(gn.silu), *f16_args)
 
 
 _BMM_OUT_DTYPE = None
@@ -1198,13 +1110,10 @@ def attention_from_operands(Q3, K3, V3, sq: float, sv: float):
     C = C3 // 3
     if Ltok not in ATTN_L_OK:
         raise GqHipError("attention_f16x3: token count %d not in %s" % (Ltok, ATTN_L_OK))
-    L_ = lib()
-    with torch.cuda.device(Q3.device):
-        S = torch.bmm(Q3, K3.transpose(1, 2), out_dtype=torch.float32)
-        P3 = torch.empty((B, Ltok, 3 * Ltok), dtype=torch.float16, device=Q3.device)
-        _check(L_.attn_softmax_split_f16x3(S.data_ptr(), P3.data_ptr(), B * Ltok, Ltok, float(C) ** -0.5 / (sq * sq), _stream()),
-               "attn_softmax_split_f16x3")
-        O = torch.bmm(P3, V3, out_dtype=torch.float32)
+    S = torch.bmm(Q3, K3.transpose(1, 2), out_dtype=torch.float32)
+    P3 = torch.empty((B, Ltok, 3 * Ltok), dtype=torch.float16, device=Q3.device)
+    _call("attn_softmax_split_f16x3", Q3.device, S, P3, B * Ltok, Ltok, float(C) ** -0.5 / (sq * sq))
+    O = torch.bmm(P3, V3, out_dtype=torch.float32)
     return O, 1.0 / (16384.0 * sv)
 
 
@@ -1221,10 +1130,8 @@ def attention_f16x3(qkv, q_bound: float, v_bound: float):
     if Ltok not in ATTN_L_OK:
         raise GqHipError("attention_f16x3: token count %d not in %s" % (Ltok, ATTN_L_OK))
     sq, sv = attention_scales(q_bound, v_bound)
-    with torch.cuda.device(qkv.device):
-        Q3, K3, V3 = attention_operands(B, Ltok, C, qkv.device)
-        _check(lib().attn_split_qkv_f16x3(qkv.data_ptr(), Q3.data_ptr(), K3.data_ptr(), V3.data_ptr(), B, Ltok, C, sq, sv,
-                                          _stream()), "attn_split_qkv_f16x3")
+    Q3, K3, V3 = attention_operands(B, Ltok, C, qkv.device)
+    _call("attn_split_qkv_f16x3", qkv.device, qkv, Q3, K3, V3, B, Ltok, C, sq, sv)
     return attention_from_operands(Q3, K3, V3, sq, sv)
 
 
@@ -1279,17 +1186,14 @@ def conv3x3_direct(x, wf, u_scale: float, x_bound: float, gn, residual=None, bia
     v_scale = _pow2_scale(x_bound)
     mscale = 1.0 / (v_scale * u_scale)
     gn = GnFold(*gn)
-    with torch.cuda.device(x.device):
-        y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
-        _check(lib().conv3x3_gn_f16x3(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
-                                      gn.groups, float(gn.eps), 1 if gn.silu else 0, float(v_scale), wf.data_ptr(), _ptr(bias),
-                                      _ptr(residual), y.data_ptr(), _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1),
-                                      mscale, _stream()), "conv3x3_gn_f16x3")
+    y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
+    _call("conv3x3_gn_f16x3", x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, gn.groups, gn.eps, bool(gn.silu), v_scale, wf,
+          bias, residual, y, ostats, B, H, W, C, cout, max(stats_groups, 1), mscale)
     return _y_or_both(y, ostats)
 
 
 def _conv1_args(x, wf, u_scale: float, scale, gn, post_scale: float, what: str, pre_bias=None):
-    """Shared checks of the 1x1 routes (``gn``: a GnFold or None); returns _operand_scales' (device scales pointer or None,
+    """Shared checks of the 1x1 routes (``gn``: a GnFold or None); returns _operand_scales' (device scales or None,
     v_scale, mscale).
     post_scale: x is post_scale^-1 times the tensor meant (a power of two its producer left pending)."""
     _need_nhwc(what, x, c=32, hw=128)
@@ -1318,17 +1222,13 @@ def conv1x1_direct(x, wf, u_scale: float, scale, residual=None, bias=None, stats
     B, C, H, W = x.shape
     cout = wf.shape[2] * 32
     _need_residual("conv1x1_direct", residual, (B, cout, H, W))
-    with torch.cuda.device(x.device):
-        y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
-        if gn is not None:
-            _check(lib().conv1x1_gn_f16x3(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias),
-                                          gn.stats.data_ptr(), gn.groups, float(gn.eps), wf.data_ptr(), float(v_scale),
-                                          float(mscale), _ptr(bias), _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout,
-                                          max(stats_groups, 1), _stream()), "conv1x1_gn_f16x3")
-        else:
-            _check(lib().conv1x1_f16x3(x.data_ptr(), _ptr(pre_bias), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias),
-                                       _ptr(residual), y.data_ptr(), _ptr(ostats), B, H * W, C, cout, max(stats_groups, 1),
-                                       _stream()), "conv1x1_f16x3")
+    y, ostats = _out_and_stats(x, cout, H, W, stats_groups)
+    if gn is not None:
+        _call("conv1x1_gn_f16x3", x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, gn.groups, gn.eps, wf, v_scale, mscale,
+              bias, residual, y, ostats, B, H * W, C, cout, max(stats_groups, 1))
+    else:
+        _call("conv1x1_f16x3", x.device, x, pre_bias, wf, sdev, v_scale, mscale, bias, residual, y, ostats, B, H * W, C, cout,
+              max(stats_groups, 1))
     return _y_or_both(y, ostats)
 
 
@@ -1343,15 +1243,12 @@ def qkv_split_direct(x, wf, u_scale: float, scale: float, sq: float, sv: float, 
     if wf.shape[2] * 32 != 3 * C or C % 128:
         raise GqHipError("qkv_split_direct: needs the [3C, C, 1, 1] projection, C % 128 == 0")
     gn = gn if gn is not None else _NO_GN._replace(pre_bias=pre_bias)
-    with torch.cuda.device(x.device):
-        Q3, K3, V3 = attention_operands(B, H * W, C, x.device) if out is None else out
-        for t, shape in zip((Q3, K3, V3), ((B, H * W, 3 * C), (B, H * W, 3 * C), (B, 3 * H * W, C))):
-            if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise GqHipError("qkv_split_direct: out must be dense fp16 [B, L, 3C], [B, L, 3C], [B, 3L, C]")
-        _check(lib().conv1x1_qkv_split_f16x3(x.data_ptr(), _ptr(gn.gamma), _ptr(gn.beta), _ptr(gn.pre_bias), _ptr(gn.stats),
-                                             gn.groups, float(gn.eps), wf.data_ptr(), float(v_scale), mscale, _ptr(bias), Q3.data_ptr(),
-                                             K3.data_ptr(), V3.data_ptr(), float(sq), float(sv), B, H * W, C, _stream()),
-               "conv1x1_qkv_split_f16x3")
+    Q3, K3, V3 = attention_operands(B, H * W, C, x.device) if out is None else out
+    for t, shape in zip((Q3, K3, V3), ((B, H * W, 3 * C), (B, H * W, 3 * C), (B, 3 * H * W, C))):
+        if not (t.is_cuda and t.dtype == torch.float16 and tuple(t.shape) == shape and t.is_contiguous()):
+            raise GqHipError("qkv_split_direct: out must be dense fp16 [B, L, 3C], [B, L, 3C], [B, 3L, C]")
+    _call("conv1x1_qkv_split_f16x3", x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, gn.groups, gn.eps, wf, v_scale, mscale,
+          bias, Q3, K3, V3, sq, sv, B, H * W, C)
     return Q3, K3, V3
 
 
@@ -1384,10 +1281,8 @@ def conv3x3s2_direct(x, wf, u_scale: float, scale, bias=None, stats_groups: int 
     if wf.shape[0] != 9 * (C // 16):
         raise GqHipError("conv3x3s2_direct: weights do not match the input channels")
     sdev, v_scale, mscale = _operand_scales(scale, u_scale)
-    with torch.cuda.device(x.device):
-        y, ostats = _out_and_stats(x, cout, H // 2, W // 2, stats_groups)
-        _check(lib().conv3x3s2_f16x3(x.data_ptr(), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias), y.data_ptr(),
-                                     _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1), _stream()), "conv3x3s2_f16x3")
+    y, ostats = _out_and_stats(x, cout, H // 2, W // 2, stats_groups)
+    _call("conv3x3s2_f16x3", x.device, x, wf, sdev, v_scale, mscale, bias, y, ostats, B, H, W, C, cout, max(stats_groups, 1))
     return _y_or_both(y, ostats)
 
 
@@ -1413,10 +1308,8 @@ def upconv2x_direct(x, wf, u_scale: float, scale, bias=None, stats_groups: int =
     if wf.shape[0] != 4 or wf.shape[1] != 4 * (C // 16):
         raise GqHipError("upconv2x_direct: weights do not match the input channels")
     sdev, v_scale, mscale = _operand_scales(scale, u_scale)
-    with torch.cuda.device(x.device):
-        y, ostats = _out_and_stats(x, cout, 2 * H, 2 * W, stats_groups)
-        _check(lib().upconv2x_f16x3(x.data_ptr(), wf.data_ptr(), sdev, float(v_scale), float(mscale), _ptr(bias), y.data_ptr(),
-                                    _ptr(ostats), B, H, W, C, cout, max(stats_groups, 1), _stream()), "upconv2x_f16x3")
+    y, ostats = _out_and_stats(x, cout, 2 * H, 2 * W, stats_groups)
+    _call("upconv2x_f16x3", x.device, x, wf, sdev, v_scale, mscale, bias, y, ostats, B, H, W, C, cout, max(stats_groups, 1))
     return _y_or_both(y, ostats)
 
 
@@ -1430,10 +1323,8 @@ def conv3x3_gn_small(x, w_ohwi, bias, gn):
         raise GqHipError("conv3x3_gn_small: weights must be fp32 [Cout, 3, 3, Cin] contiguous")
     gn = GnFold(*gn)
     y = _out_nhwc(x, cout, H, W)
-    with torch.cuda.device(x.device):
-        _check(lib().conv3x3_gn_small_f32(x.data_ptr(), gn.gamma.data_ptr(), gn.beta.data_ptr(), _ptr(gn.pre_bias), gn.stats.data_ptr(),
-                                          gn.groups, float(gn.eps), 1 if gn.silu else 0, w_ohwi.data_ptr(), _ptr(bias), y.data_ptr(),
-                                          B, H, W, C, cout, _stream()), "conv3x3_gn_small_f32")
+    _call("conv3x3_gn_small_f32", x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, gn.groups, gn.eps, bool(gn.silu), w_ohwi,
+          bias, y, B, H, W, C, cout)
     return y
 
 
@@ -1450,8 +1341,7 @@ def checksum_table(tensors):
 
 def checksum_tensors(table, out):
     """out[t] (int64, device) = content hash of tensor t of ``table`` (gqhip.h:gqhip_checksum_tensors); asynchronous."""
-    with torch.cuda.device(table.device):
-        _check(lib().gqhip_checksum_tensors(table.data_ptr(), table.numel() // 2, out.data_ptr(), _stream()), "gqhip_checksum_tensors")
+    _call("gqhip_checksum_tensors", table.device, table, table.numel() // 2, out)
     return out
 
 
@@ -1483,10 +1373,8 @@ def conv3x3_f32(x, wk, cout: int, bias=None, gn=None):
         raise GqHipError(f"conv3x3_f32: shape {tuple(x.shape)} -> {cout} channels is not tiled by the kernel")
     y = _out_nhwc(x, cout, H, W)
     gn = _NO_GN if gn is None else GnFold(*gn)
-    with torch.cuda.device(x.device):
-        _check(lib().conv3x3_f32(x.data_ptr(), _ptr(gn.gamma), _ptr(gn.beta), _ptr(gn.pre_bias), _ptr(gn.stats), gn.groups, float(gn.eps),
-                                 1 if gn.silu else 0, wk.data_ptr(), _ptr(bias), y.data_ptr(), B, H, W, C, cout, _stream()),
-               "conv3x3_f32")
+    _call("conv3x3_f32", x.device, x, gn.gamma, gn.beta, gn.pre_bias, gn.stats, gn.groups, gn.eps, bool(gn.silu), wk, bias, y,
+          B, H, W, C, cout)
     return y
 
 
@@ -1508,10 +1396,8 @@ def conv3x3_cin_small(x, wk, bias=None, stats_groups: int = 0):
     B, C, H, W = x.shape
     if not conv_cin_small_ok(C, wk.shape[1], H, W) or wk.shape[0] != 9 * C or stats_groups not in (0, 32):
         raise GqHipError(f"conv3x3_cin_small: shape {tuple(x.shape)} is not tiled by the kernel")
-    with torch.cuda.device(x.device):
-        y, ostats = _out_and_stats(x, 128, H, W, 32 if stats_groups else 0)
-        _check(lib().conv3x3_cin_small_f32(x.data_ptr(), wk.data_ptr(), _ptr(bias), y.data_ptr(), _ptr(ostats), B, H, W, C, 128,
-                                           32, _stream()), "conv3x3_cin_small_f32")
+    y, ostats = _out_and_stats(x, 128, H, W, 32 if stats_groups else 0)
+    _call("conv3x3_cin_small_f32", x.device, x, wk, bias, y, ostats, B, H, W, C, 128, 32)
     return _y_or_both(y, ostats)
 
 
@@ -1522,9 +1408,7 @@ def f16_scales(stats, amp: float, u_scale: float):
     if not (stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() % GNSTAT_WORDS == 0):
         raise GqHipError("f16_scales needs the statistics tensor of add_bias_stats / wino_conv3x3")
     out = torch.empty(2, dtype=torch.float32, device=stats.device)
-    with torch.cuda.device(stats.device):
-        _check(lib().f16_scales_from_gn_stats(stats.data_ptr(), stats.numel() // GNSTAT_WORDS, float(amp), float(u_scale),
-                                              out.data_ptr(), _stream()), "f16_scales_from_gn_stats")
+    _call("f16_scales_from_gn_stats", stats.device, stats, stats.numel() // GNSTAT_WORDS, amp, u_scale, out)
     return out
 
 
@@ -1533,25 +1417,21 @@ def upsample2x_nhwc(x):
     _need_nhwc("upsample2x_nhwc", x, c=4)
     B, C, H, W = x.shape
     y = _out_nhwc(x, C, 2 * H, 2 * W)
-    with torch.cuda.device(x.device):
-        _check(lib().upsample2x_nhwc_f32(x.data_ptr(), y.data_ptr(), B, H, W, C, _stream()), "upsample2x_nhwc_f32")
+    _call("upsample2x_nhwc_f32", x.device, x, y, B, H, W, C)
     return y
 
 
 def index_histogram(idx, n: int):
     idx = _dev(idx, torch.int64, "indices")
     hist = torch.empty(n, dtype=torch.int32, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _check(lib().gq_index_histogram(idx.data_ptr(), idx.numel(), n, hist.data_ptr(), _stream()),
-               "gq_index_histogram")
+    _call("gq_index_histogram", idx.device, idx, idx.numel(), n, hist)
     return hist
 
 
 def indices_to_u16(idx):
     idx = _dev(idx, torch.int64, "indices")
     out = torch.empty(idx.shape, dtype=torch.uint16, device=idx.device)
-    with torch.cuda.device(idx.device):
-        _check(lib().gq_indices_to_u16(idx.data_ptr(), out.data_ptr(), idx.numel(), _stream()), "gq_indices_to_u16")
+    _call("gq_indices_to_u16", idx.device, idx, out, idx.numel())
     return out
 
 
@@ -1560,9 +1440,7 @@ def indices_from_u16(u16):
         raise GqHipError("expected a uint16 HIP tensor")
     u16 = u16.contiguous()
     out = torch.empty(u16.shape, dtype=torch.int64, device=u16.device)
-    with torch.cuda.device(u16.device):
-        _check(lib().gq_indices_from_u16(u16.data_ptr(), out.data_ptr(), u16.numel(), _stream()),
-               "gq_indices_from_u16")
+    _call("gq_indices_from_u16", u16.device, u16, out, u16.numel())
     return out
 
 
@@ -1603,25 +1481,21 @@ def step_record(x, x_rec, idx, rec, ws_cache: dict, n_metrics: int = 1, index_bi
     those of n_metrics 1 bit for bit.  ``index_bits`` None: idx as uint16 pairs; else the bit-packed stream of that width and the
     violations word (indices outside [0, n_codes)) behind it.  ``ws_cache``: the caller's dict that keeps the (zeroed, self-
     resetting) workspace between calls."""
-    L = lib()
     B, C, H, W = x.shape
     bits = index_bits is not None
     if n_metrics == 1:
-        size, call = (L.gq_step_record_bits_workspace_bytes, L.gq_step_record_bits_f32) if bits else \
-            (L.gq_step_record_workspace_bytes, L.gq_step_record_f32)
-        shape = image = (B, C * H * W)
+        kind, shape = "gq_step_record", (B, C * H * W)
+        image = shape
     elif n_metrics == 3:
-        size, call = (L.gq_step_record_ssim_bits_workspace_bytes, L.gq_step_record_ssim_bits_f32) if bits else \
-            (L.gq_step_record_ssim_workspace_bytes, L.gq_step_record_ssim_f32)
-        shape, image = (B, C, H, W), (B, C, H, W, image_layout(x))
+        kind, shape, image = "gq_step_record_ssim", (B, C, H, W), (B, C, H, W, image_layout(x))
     else:
         raise GqHipError(f"step_record: n_metrics is 1 or 3, not {n_metrics}")
+    kind += "_bits" if bits else ""
     wire = (index_bits, n_codes) if bits else ()
     idx = idx.contiguous()      # (any memory order of the SAME logical [B, K, h, w] order is fine for the caller; contiguous = logical order)
-    ws = _zeroed_ws(ws_cache, ("bits" if bits else "u16", n_metrics, x.device, B, C, H, W), size(*shape), x.device)
-    with torch.cuda.device(x.device):
-        _check(call(x.data_ptr(), x_rec.data_ptr(), idx.data_ptr(), rec.data_ptr(), *image, idx.numel(), *wire, ws.data_ptr(),
-                    ws.numel(), _stream()), call.__name__)
+    need = getattr(lib(), kind + "_workspace_bytes")(*shape)
+    ws = _zeroed_ws(ws_cache, ("bits" if bits else "u16", n_metrics, x.device, B, C, H, W), need, x.device)
+    _call(kind + "_f32", x.device, x, x_rec, idx, rec, *image, idx.numel(), *wire, ws, ws.numel())
     return rec
 
 
@@ -1633,9 +1507,7 @@ def image_quality(x, x_rec, zero_mean: bool, msssim: bool, ws_cache: dict):
     ssim = torch.empty(B, dtype=torch.float32, device=x.device)
     ms = torch.empty(B, dtype=torch.float32, device=x.device) if msssim else None
     ws = _zeroed_ws(ws_cache, ("ssim", x.device, B, C, H, W), lib().gq_ssim_workspace_bytes(B, C, H, W), x.device)
-    with torch.cuda.device(x.device):
-        _check(lib().gq_ssim_f32(x.data_ptr(), x_rec.data_ptr(), B, C, H, W, layout, 1 if zero_mean else 0, ssim.data_ptr(),
-                                 ms.data_ptr() if ms is not None else None, ws.data_ptr(), ws.numel(), _stream()), "gq_ssim_f32")
+    _call("gq_ssim_f32", x.device, x, x_rec, B, C, H, W, layout, bool(zero_mean), ssim, ms, ws, ws.numel())
     return ssim, ms
 
 
@@ -1655,9 +1527,7 @@ def indices_pack_bits(idx, index_bits: int, n_codes: int, out=None, violations=N
     out = torch.empty(n_words, dtype=torch.int32, device=idx.device) if out is None else _words_out(out, n_words, "out")
     if violations is not None:
         _words_out(violations, 1, "violations")
-    with torch.cuda.device(idx.device):
-        _check(lib().gq_indices_pack_bits(idx.data_ptr(), out.data_ptr(), idx.numel(), index_bits, n_codes, _ptr(violations),
-                                          _stream()), "gq_indices_pack_bits")
+    _call("gq_indices_pack_bits", idx.device, idx, out, idx.numel(), index_bits, n_codes, violations)
     return out
 
 
@@ -1672,9 +1542,7 @@ def indices_unpack_bits(records, offset_words: int, count: int, index_bits: int)
     int32 [n_records, words] tensor ``records`` (gqhip.h: gq_indices_unpack_bits)."""
     records = _packed_records(records, "indices_unpack_bits")
     out = torch.empty((records.shape[0], count), dtype=torch.int64, device=records.device)
-    with torch.cuda.device(records.device):
-        _check(lib().gq_indices_unpack_bits(records.data_ptr(), out.data_ptr(), records.shape[0], records.shape[1], offset_words,
-                                            count, index_bits, _stream()), "gq_indices_unpack_bits")
+    _call("gq_indices_unpack_bits", records.device, records, out, records.shape[0], records.shape[1], offset_words, count, index_bits)
     return out
 
 
@@ -1684,9 +1552,8 @@ def index_histogram_packed(records, offset_words: int, count: int, index_bits: i
     records = _packed_records(records, "index_histogram_packed")
     if not (hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.dim() == 1 and hist.device == records.device):
         raise GqHipError("index_histogram_packed: hist must be a contiguous int64 [n] tensor on the records' device")
-    with torch.cuda.device(records.device):
-        _check(lib().gq_index_histogram_packed(records.data_ptr(), records.shape[0], records.shape[1], offset_words, count,
-                                               index_bits, hist.numel(), hist.data_ptr(), _stream()), "gq_index_histogram_packed")
+    _call("gq_index_histogram_packed", records.device, records, records.shape[0], records.shape[1], offset_words, count, index_bits,
+          hist.numel(), hist)
     return hist
 
 
@@ -1714,8 +1581,7 @@ def mha_fwd(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
     need = lib().gq_mha_workspace_bytes(B, L, E, heads)         # 0 today: no scratch; otherwise per call, as in mha_bwd
     ws = torch.empty(need, dtype=torch.uint8, device=qkv.device) if need > 0 else None
-    with torch.cuda.device(qkv.device):
-        _check(lib().gq_mha_fwd_f32(qkv.data_ptr(), out.data_ptr(), B, L, E, heads, _ptr(ws), _stream()), "gq_mha_fwd_f32")
+    _call("gq_mha_fwd_f32", qkv.device, qkv, out, B, L, E, heads, ws)
     return out
 
 
@@ -1726,9 +1592,7 @@ def mha_fwd_lse(qkv: torch.Tensor, heads: int):
     qkv, B, L, E = _mha_qkv(qkv, heads, "mha_fwd_lse")
     out = torch.empty(B, L, E, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(B, heads, L, dtype=torch.float32, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _check(lib().gq_mha_fwd_lse_f32(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, E, heads, None, _stream()),
-               "gq_mha_fwd_lse_f32")
+    _call("gq_mha_fwd_lse_f32", qkv.device, qkv, out, lse, B, L, E, heads, None)
     return out, lse
 
 
@@ -1749,9 +1613,7 @@ def mha_bwd(qkv: torch.Tensor, out: torch.Tensor, lse: torch.Tensor, dout: torch
     dqkv = torch.empty(B, L, 3 * E, dtype=torch.float32, device=qkv.device)
     # delta lives for this call only: from the caching allocator, so that calls on different streams never share it
     ws = torch.empty(max(lib().gq_mha_bwd_workspace_bytes(B, L, E, heads), 8), dtype=torch.uint8, device=qkv.device)
-    with torch.cuda.device(qkv.device):
-        _check(lib().gq_mha_bwd_f32(qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), B, L, E,
-                                    heads, ws.data_ptr(), _stream()), "gq_mha_bwd_f32")
+    _call("gq_mha_bwd_f32", qkv.device, qkv, out, lse, dout, dqkv, B, L, E, heads, ws)
     return dqkv
 
 
