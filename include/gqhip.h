@@ -45,6 +45,7 @@
  *   gn_silu_f32      pit/modules/unet.py:49-57 (Normalize + nonlinearity pairs).
  *   gq_index_histogram eval.py:127,137-141,152-154 (stubbed-out histogram).
  *   gq_ssim_f32      pit/evaluations/ssim.py:5-63 (get_ssim / get_ssim_and_msssim via pytorch_msssim), eval.py:170-178.
+ *   gq_moments_update_f32  eval.py:186-203, 241-257 (the Inception feature blocks kept on the host, np.mean / np.cov over them).
  */
 #ifndef GQHIP_H_
 #define GQHIP_H_
@@ -75,7 +76,8 @@ extern "C" {
                                *    gq_step_record_bits_f32, gq_step_record_ssim_bits_f32 and their two _workspace_bytes functions), the train steps of
                                *    BSQQuantizer (bsq_train_f32, bsq_backward_f32, bsq_train_workspace_bytes) and FSQQuantizer (fsq_train_f32,
                                *    fsq_backward_f32), the LPIPS comparison head (lpips_head_f32, lpips_head_backward_f32,
-                               *    lpips_head_workspace_bytes) */
+                               *    lpips_head_workspace_bytes), the fp64 feature moments of the Frechet statistics (gq_moments_update_f32,
+                               *    gq_moments_state_bytes) */
 
 /* GroupNorm statistics of one (image, group): GQHIP_GNSTAT_WORDS int64 words = {sum: 3 limbs, sum of squares: 3 limbs, poison,
  * unused}; value = q0 2^-56 + q1 2^-16 + q2 2^24.  Every kernel that leaves statistics behind adds its threads' fp32 partial
@@ -429,6 +431,26 @@ int lpips_head_f32(const float *f0, const float *f1, const float *w, const uint8
                    int64_t B, int64_t C, int64_t HW, int layout, void *workspace, int64_t workspace_bytes, void *stream);
 int lpips_head_backward_f32(const float *f0, const float *f1, const float *w, const uint8_t *keep_or_null, float keep_scale,
                             const float *g_out, float *grad_f1, int64_t B, int64_t C, int64_t HW, int layout, void *stream);
+
+/* ---- raw first and second moments of a feature block, accumulated in fp64 (csrc/gq_moments.h): what the Frechet statistics of
+ * eval.py:186-203, 241-257 need, without a feature row leaving the device.
+ *   state: (D D + D + 1) fp64 words = [ outer: D D, row-major | sum: D | count: 1 ]; gq_moments_state_bytes(D) bytes (-1 for a D
+ *   outside 1 .. 8192).  The caller zeroes it once; each call adds to it.
+ *   x: [rows, D] fp32, row r at x + r row_stride, row_stride >= D.  For r = 0 .. rows - 1, IN ASCENDING r:
+ *     outer[i][j] <- fma((double)x[r][i], (double)x[r][j], outer[i][j])   for j >= i
+ *     sum[i]      <- sum[i] + (double)x[r][i]
+ *   and count <- count + rows (a double: exact to 2^53).  Only the upper triangle (j >= i) of outer is defined; what it holds
+ *   below the diagonal is unspecified.
+ *   The product of two fp32 values has at most 48 significant bits and its exponent lies far inside fp64's range even for two fp32
+ *   subnormals, so it is exact in fp64 and every step is one rounding of outer + product.  Hence: a plain sequential fp64 loop on
+ *   the host reproduces every bit; splitting the rows over several calls changes no bit; a * b + c and fma(a, b, c) agree.
+ *   Limits: 1 <= D <= 8192, rows >= 0, rows row_stride < 2^31; x 4-byte and state 8-byte aligned, neither NULL; anything else is
+ *   GQHIP_ERR_INVALID_ARG.  rows == 0: GQHIP_OK, nothing is launched.  x 16-byte aligned with row_stride % 4 == 0 takes 16-byte
+ *   loads, a 16-byte aligned state with an even D 16-byte accesses; the bits are the same either way.
+ * One launch over the tile pairs of the upper triangle; every output element has one owning thread, no atomics of any kind, no
+ * workspace, no host read: asynchronous and graph-capturable. */
+int64_t gq_moments_state_bytes(int64_t D);
+int gq_moments_update_f32(const float *x, int64_t rows, int64_t D, int64_t row_stride, double *state, void *stream);
 
 /* ---- fused GroupNorm (+ SiLU) for the conv stack -----------------------------------
  * y = act( (x - mean_g) * rstd_g * gamma_c + beta_c ), act = SiLU when apply_silu != 0.

@@ -28,6 +28,7 @@
 #include "lfq_train.h"
 #include "bsq_fsq_train.h"
 #include "lpips_head.h"
+#include "gq_moments.h"
 
 using namespace gqhip;
 
@@ -1271,6 +1272,22 @@ int lpips_head_backward_f32(const float *f0, const float *f1, const float *w, co
   g.slots = (int)lpips_slots(B, HW, g.T);
   p.f0 = f0; p.f1 = f1; p.w = w; p.keep = keep_or_null; p.keep_scale = keep_scale; p.g = g_out; p.grad = grad_f1;
   return launch(kernel, dim3((unsigned)((g.P + g.T - 1) / g.T)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+}
+
+// ---- raw feature moments in fp64 (gq_moments.h) ----
+int64_t gq_moments_state_bytes(int64_t D) { return D < 1 || D > kMomMaxD ? -1 : (D * D + D + 1) * 8; }
+
+int gq_moments_update_f32(const float *x, int64_t rows, int64_t D, int64_t row_stride, double *state, void *stream) {
+  if (!x || !state || D < 1 || D > kMomMaxD || rows < 0 || row_stride < D || !aligned(3u, x) || !aligned(7u, state))
+    return GQHIP_ERR_INVALID_ARG;
+  if (row_stride > 0x7fffffffL || rows * row_stride > 0x7fffffffL) return GQHIP_ERR_INVALID_ARG;   // each factor < 2^31: no overflow
+  if (rows == 0) return GQHIP_OK;
+  MomentsParams p{};
+  p.x = x; p.state = state; p.rows = (int)rows; p.D = (int)D; p.stride = (int)row_stride;
+  p.T = (int)((D + kMomTile - 1) / kMomTile);
+  p.vec_x = aligned(15u, x) && row_stride % 4 == 0;
+  p.wide_state = aligned(15u, state) && D % 2 == 0;
+  return launch(moments_update_kernel, dim3((unsigned)(p.T * (p.T + 1) / 2)), dim3(256), 0, static_cast<hipStream_t>(stream), p);
 }
 
 int gq_dequant_f32(const int64_t *idx, const float *cb, float *zhat, int64_t B, int64_t L, int64_t K,

@@ -1557,6 +1557,39 @@ def index_histogram_packed(records, offset_words: int, count: int, index_bits: i
     return hist
 
 
+def moments_state_words(D: int) -> int:
+    """fp64 words of the moments state of D features, [outer: D D | sum: D | count: 1] (gqhip.h: gq_moments_state_bytes)."""
+    need = lib().gq_moments_state_bytes(D)
+    if need < 0:
+        raise GqHipError(f"unsupported shape D={D}")
+    return need // 8
+
+
+def moments_update(x, state):
+    """state += the raw moments of the rows of ``x`` (gqhip.h: gq_moments_update_f32), in ascending row order, bit for bit what a
+    sequential fp64 loop gives.  ``x``: fp32 [rows, D] on a HIP device with unit inner stride (a column slice of a wider tensor
+    passes: its row stride goes to the library); there is no silent ``.float()``, the exactness argument needs fp32 inputs.
+    ``state``: contiguous fp64 with D D + D + 1 elements on the same device, zeroed once by its owner.  Returns ``state``."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError(f"moments_update: x must be a float32 [rows, D] tensor with unit inner stride, got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))} strides {getattr(x, 'stride', tuple)()}")
+    rows, D = x.shape
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or not state.is_contiguous() \
+            or state.numel() != D * D + D + 1:
+        raise ValueError(f"moments_update: state must be a contiguous float64 tensor of D D + D + 1 = {D * D + D + 1} elements, got "
+                         f"{getattr(state, 'dtype', type(state))} {tuple(getattr(state, 'shape', ()))}")
+    if not (x.is_cuda and state.is_cuda and x.device == state.device):
+        raise GqHipError(f"moments_update: x and state must be on one HIP device (got {x.device}, {state.device}); "
+                         "the HIP path has no CPU fallback")
+    if rows == 0:                                       # an empty tensor has no pointer to hand over
+        return state
+    row_stride = x.stride(0) if rows > 1 else max(x.stride(0), D)      # the stride of a one-row view is arbitrary
+    if row_stride < D:
+        raise ValueError(f"moments_update: x must not overlap its own rows (row stride {row_stride} < D = {D})")
+    _call("gq_moments_update_f32", x.device, x, rows, D, row_stride, state)
+    return state
+
+
 MHA_HEAD_DIMS = (64,)    # head dims gq_mha_fwd_f32 is built for
 
 

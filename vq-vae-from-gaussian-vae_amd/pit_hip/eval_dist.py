@@ -19,6 +19,10 @@ metric -> all_gather, :207-257 rank-0 re-interleave).  What changes:
   4 MiB codebook and the weights are replicated (regenerated from the seed).
 * SSIM and MS-SSIM (eval.py:170-178, pit/evaluations/ssim.py) ride in the same
   record (``metrics=("psnr", "ssim", "ms_ssim")``): still one gather per step.
+* FID (eval.py:186-203, 241-259; ``fid_features=...``): instead of two more
+  gathers and two host copies per step and 2 N 2048 features kept on the host,
+  each rank folds its feature blocks into fp64 raw moments on its own device
+  (pit_hip/evaluations/fid/fid_score.py) and the ranks meet ONCE, after the loop.
 
 Sharding semantics are exactly ``DistributedSampler(shuffle=False)`` (pads the
 index list by wrapping so every rank gets ceil(N/W) items) followed by a
@@ -444,12 +448,52 @@ def codebook_usage(indices: torch.Tensor, n_codes: int):
     return hist, usage, ent
 
 
+class FidAccumulator:
+    """One rank's Frechet statistics of the inputs and of the reconstructions (eval.py:186-203 without its two gathers and two
+    host copies per step).  ``features``: a callable images -> fp32 [B, D] or [B, D, h, w] (pooled as eval.py:188-190 pools);
+    D is taken from the first call.  The raw moments are additive over images, so the ranks meet ONCE, after the loop."""
+
+    def __init__(self, features) -> None:
+        self.features = features
+        self.stats = None                     # [FrechetStats of the inputs, of the reconstructions], made at the first step
+
+    def update(self, x: torch.Tensor, x_rec: torch.Tensor) -> None:
+        from .evaluations.fid.fid_score import FrechetStats
+
+        blocks = [self.features(x), self.features(x_rec)]
+        if self.stats is None:
+            self.stats = [FrechetStats(f.shape[1], f.device) for f in blocks]
+        for stats, feats in zip(self.stats, blocks):
+            stats.update(feats)
+
+    def reduce(self, world: int) -> None:
+        """Every rank's two states summed in rank order, on every rank: ONE all_gather_into_tensor of the stacked
+        [2, D D + D + 1] fp64 states (not all_reduce, whose order is not fixed).  Every rank must call it; ranks without a step
+        (then no rank has one: the sampler gives every rank the same number of batches) have nothing to gather."""
+        if world == 1 or self.stats is None:
+            return
+        both = gather_step(torch.stack([s.state for s in self.stats]), world).reshape(world, 2, -1)
+        for k, stats in enumerate(self.stats):
+            stats.state.zero_()
+            stats.merge_(both[r, k] for r in range(world))
+
+    def result(self) -> Dict[str, object]:
+        """{"fid", "fid_count"}: the reference's mean / covariance / calculate_frechet_distance (eval.py:241-259) of everything
+        folded in; the count includes the items the sampler wrapped around (eval.py:205, total_num)."""
+        from .evaluations.fid.fid_score import calculate_frechet_distance
+
+        (n, mu_x, cov_x), (_, mu_r, cov_r) = (s.moments() for s in self.stats)
+        return {"fid": calculate_frechet_distance(mu_r, cov_r, mu_x, cov_x), "fid_count": n}
+
+
 @torch.no_grad()
 def sharded_eval_steps(model, images_for, batches, layout: StepRecord, world: int, device,
-                       hist: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+                       hist: Optional[torch.Tensor] = None, fid: Optional["FidAccumulator"] = None) -> List[torch.Tensor]:
     """The per-step loop of evaluate_sharded: encode / decode / pack / ONE gather per batch of ``batches``; returns the gathered
     [world, words] records, one per step.  ``hist`` (int64 [n_codes], bit-packed records only): each gathered record's indices are
-    added to it as they arrive.  With a bit-packed ``layout`` nothing in the loop reads the device from the host."""
+    added to it as they arrive.  ``fid`` (a FidAccumulator): the features of every batch and of its reconstruction are folded into
+    this rank's two FrechetStats -- no collective, no host read.  With a bit-packed ``layout`` nothing in the loop reads the device
+    from the host."""
     gathered = []
     for ids in batches:
         x = images_for(ids).to(device, non_blocking=True)
@@ -462,13 +506,15 @@ def sharded_eval_steps(model, images_for, batches, layout: StepRecord, world: in
         gathered.append(gather_step(rec, world))
         if hist is not None:
             layout.add_to_histogram(gathered[-1], hist)
+        if fid is not None:
+            fid.update(x, rec_img)
     return gathered
 
 
 @torch.no_grad()
 def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world: int, device,
                      tokens_per_image: int, metrics: Sequence[str] = ("psnr",),
-                     n_codes: Optional[int] = None) -> Optional[Dict[str, torch.Tensor]]:
+                     n_codes: Optional[int] = None, fid_features=None) -> Optional[Dict[str, torch.Tensor]]:
     """The reference eval loop for this path: each rank encodes/decodes its shard, one gather per
     step, rank 0 returns indices + PSNR in dataset order.  ``images_for(ids) -> [len(ids),3,H,W]``.
     ``metrics``: ("psnr",) or ("psnr", "ssim", "ms_ssim") (eval.py:165-178; any order): the three-metric record, still ONE
@@ -479,7 +525,13 @@ def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world
     ValueError naming the first (rank, step) whose indices left [0, n_codes).  Rank 0 also accumulates the whole evaluated
     set's usage histogram from the gathered records (eval.py:127,152-154's all_hist; the items the sampler wraps around to pad
     the last batch count, as they do in "indices") and the result gains "hist" (int64 [n_codes]), "usage" and "entropy"
-    (cal_ent: eval.py:137-141)."""
+    (cal_ent: eval.py:137-141).
+    ``fid_features``: None, or a callable images -> fp32 [B, D] or [B, D, h, w] (eval.py:186-203's inception_v3(img)[0]).  Each
+    step calls it on the batch and on its reconstruction and folds the features into two per-rank FrechetStats on the device
+    (pit_hip/evaluations/fid/fid_score.py): the step keeps its ONE gather, with no new collective and no host read.  After the loop
+    every rank takes part in ONE all-gather of the stacked states, summed in rank order, and rank 0's result gains "fid" (a
+    float: calculate_frechet_distance of the reconstructions' statistics against the inputs', eval.py:241-259) and "fid_count"
+    (the rows behind it; the wrapped items count, as in eval.py:205)."""
     names = set(metrics)
     if names == {"psnr"}:
         n_metrics = 1
@@ -495,7 +547,10 @@ def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world
         layout = StepRecord(bs, tokens_per_image, n_metrics=n_metrics, n_codes=n_codes)
         if rank == 0:
             hist = torch.zeros(n_codes, dtype=torch.int64, device=device)
-    gathered = sharded_eval_steps(model, images_for, batches, layout, world, device, hist)
+    fid = None if fid_features is None else FidAccumulator(fid_features)
+    gathered = sharded_eval_steps(model, images_for, batches, layout, world, device, hist, fid)
+    if fid is not None:
+        fid.reduce(world)      # a collective: before any rank returns
     if not gathered or (rank != 0 and n_codes is None):
         return None
     if n_codes is not None:
@@ -519,4 +574,6 @@ def evaluate_sharded(model, images_for, n_images: int, bs: int, rank: int, world
     if n_codes is not None:
         out["hist"] = hist
         out["usage"], out["entropy"] = cal_ent(hist)
+    if fid is not None:
+        out.update(fid.result())
     return out
