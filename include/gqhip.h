@@ -115,6 +115,23 @@ int gqhip_last_hip_error(void);
 int gqhip_set_filter(int kind);
 int gqhip_get_filter(void);
 
+/* Route of the codebook dims between the filter dims -- 5..7, 9..15, 17..31 -- in gq_argmax_f32 / gq_quantize_z_f32 /
+ * gq_quantize_z_gauss_f32 / vq_argmin_f32 / vq_quantize_z_f32.  EXHAUSTIVE (default): one block per row scores every code with the
+ * reference's arithmetic.  PADDED: the rows and the codebook are zero-padded in the workspace to the next filter dim (8, 16, 32:
+ * mu 0, sd 1, log sd 0, code 0 in the pad columns), the selected filter runs there unchanged, and the exact re-rank -- which alone
+ * decides an index -- scores with the TRUE dim, so the indices, zhat and every other output are the same bits either way
+ * (DESIGN.md section 3.1).  Such a call keeps nothing in the codebook cache (gqhip_cb_cache_bytes stays 0 at these dims): the padded
+ * operand image is rebuilt in the workspace on every call.  Dims 1..3 and 33..64 stay on the exhaustive kernel under either value.
+ * Process-wide; initial value from the environment (GQHIP_ODD_DIMS=padded).  The workspace size depends on it: query
+ * gqhip_workspace_bytes after changing it.  An unknown kind: GQHIP_ERR_INVALID_ARG, the selection stays.  (No reference counterpart.) */
+#define GQHIP_ODD_DIMS_EXHAUSTIVE 0
+#define GQHIP_ODD_DIMS_PADDED 1
+int gqhip_set_odd_dims(int kind);
+int gqhip_get_odd_dims(void);
+/* Diagnostic: the dim the filter of the fused arg-max runs at for (n, dim) under the current selections -- `dim` itself at 4, 8,
+ * 16, 32; 8, 16 or 32 for a dim the PADDED route serves; 0 where the exhaustive kernel runs; -1: n < 1 or dim outside 1..64. */
+int64_t gqhip_filter_dim(int64_t n, int64_t dim);
+
 /* Diagnostics: launch plan and workspace layout of the fused arg-max for a shape.  out8_host = { byte offset of the
  * candidate records, code splits, tiles per candidate group, tiles per split, filter kernel the plan selects (0 fp32 MFMA, 1 split-bf16, 2 fp16 + fp8, 3 fp16 main product: the default at dims 8 / 16 / 32), coefficient of the
  * filter error bound (E_f = coeff * 2^-24 * T), row tiles per wave, waves per filter block }.
@@ -180,7 +197,9 @@ int gq_scores_f32(const float *mu, const float *sd, const float *cb, float *out,
  * zhat[r] = cb[idx[r]]  (optional, may be NULL).
  * logsd_or_null: log(sd) as the caller computed it; NULL -> the kernel uses
  *           float(log(double(sd))) (correctly rounded).
- * dim: any 1..64 (4, 8, 16, 32 run on the MFMA filter; others exhaustive).
+ * dim: any 1..64 (4, 8, 16, 32 run on the MFMA filter; 5..7, 9..15, 17..31 too, zero-padded to the next of them, once
+ *           gqhip_set_odd_dims(GQHIP_ODD_DIMS_PADDED) selects that -- prep of the padded operands, filter, re-rank, the same
+ *           indices; every other case exhaustive).
  * Dim 4 with a codebook cache: prep -> index check -> pruned exact search -> finish of the rows it left undecided
  * (csrc/gq_grid.h; four launches, the second and fourth exit at once in the common case).
  * Three launches on `stream` for the other MFMA dims: prep (operand images, bound sums,

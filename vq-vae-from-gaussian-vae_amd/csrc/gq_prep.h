@@ -642,4 +642,41 @@ __global__ __launch_bounds__(256) void prep_plain_kernel(const PrepPlainParams p
   }
 }
 
+// The padded route of the dims between the filter dims (gqhip.h: gqhip_set_odd_dims): true-dim rows and codebook -> copies of
+// width dp (the next filter dim) whose pad columns hold mu 0, sd 1, log sd 0 and code 0.  gq_prep_kernel<.., dp, from rows> then
+// derives everything the dp filter and re-rank read from them: a pad column's filter products A 0^2 + B 0 are exactly 0 in fp16 and
+// fp32, its terms of the bound sums (1/sd^2 = 1, the rest 0) only loosen the bound, and it adds nothing to max|cb| or a code norm.
+// One thread per padded element, rows first, then codes; memory-bound and small beside the filter.
+struct PadParams {
+  const float *mu, *sd, *lsd;   // [rows, dim]; sd NULL: VQ (mu only); lsd NULL: float(log(double(sd))), as the exhaustive kernel forms it
+  const float *cb;              // [n, dim]
+  float *pmu, *psd, *plsd;      // [rows, dp]
+  float *pcb;                   // [n, dp]
+  long rows, n;
+  int dim, dp;
+};
+constexpr int kPadMaxBlocks = 1 << 16;
+
+__global__ __launch_bounds__(256) void gq_pad_kernel(const PadParams p) {
+  const long row_elems = p.rows * p.dp, total = row_elems + p.n * p.dp;
+  for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+    const bool is_row = t < row_elems;
+    const long e = is_row ? t : t - row_elems;
+    const long r = e / p.dp;
+    const int g = (int)(e % p.dp);
+    const bool in = g < p.dim;
+    const long src = r * p.dim + g;       // read only when `in`: r < rows | n and g < dim
+    if (!is_row) {
+      p.pcb[e] = in ? p.cb[src] : 0.0f;
+      continue;
+    }
+    p.pmu[e] = in ? p.mu[src] : 0.0f;
+    if (p.sd) {
+      const float s = in ? p.sd[src] : 1.0f;
+      p.psd[e] = s;
+      p.plsd[e] = in ? (p.lsd ? p.lsd[src] : (float)log((double)s)) : 0.0f;
+    }
+  }
+}
+
 }  // namespace gqhip

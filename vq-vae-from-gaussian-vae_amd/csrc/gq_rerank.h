@@ -162,11 +162,12 @@ __device__ __forceinline__ bool better_d(double sa, int ia, double sb, int ib) {
   return sa > sb || (sa == sb && ia < ib);
 }
 
-__device__ __forceinline__ void write_result(const RerankParams &p, long row, int best, int lane) {
+// `stride`: floats per code row of p.cb (p.dim, or the filter dim of a padded call's codebook copy)
+__device__ __forceinline__ void write_result(const RerankParams &p, long row, int best, int lane, int stride) {
   if (lane == 0) p.idx[out_idx_offset(p.omap, row)] = (int64_t)best;
   if (p.zhat && lane < p.dim) {
     const long o = out_zhat_offset(p.omap, row, lane, p.dim);
-    p.zhat[o] = ste_mix(p.hdr, o, p.cb[(long)best * p.dim + lane]);
+    p.zhat[o] = ste_mix(p.hdr, o, p.cb[(long)best * stride + lane]);
   }
 }
 
@@ -257,6 +258,56 @@ __device__ __forceinline__ float ref_score_lds(const float (&n)[DIM], const floa
   return s;
 }
 
+// The two scorers of a PADDED call (gqhip.h: gqhip_set_odd_dims): code row and row operands are held at the filter dim DIM, zero-padded,
+// and the score is the one of the first `dim` (the true dim) of them -- operation for operation ref_score_ops(n, ro, dim, beta) and
+// vq_neg_dist(e, z, dim), which is what the exhaustive kernel evaluates at that dim.  (Scoring all DIM columns would not be: the pad
+// terms are not zero, and even exact zeros change where the strided accumulators round.)
+template <int DIM>
+__device__ __forceinline__ float ref_score_lds_true(const float (&n)[DIM], const float *ops, float beta, int dim) {
+#pragma clang fp contract(off)
+  static_assert(DIM >= 8, "padded dims are 8, 16, 32");
+  float acc[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc[k] = k < dim ? ref_term(n[k], ops[k], ops[DIM + k], ops[2 * DIM + k], beta) : 0.0f;
+#pragma unroll
+  for (int i0 = 8; i0 < DIM; i0 += 8)
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      if (i0 + k < dim) acc[k] = acc[k] + ref_term(n[i0 + k], ops[i0 + k], ops[DIM + i0 + k], ops[2 * DIM + i0 + k], beta);
+  float s = acc[0];
+#pragma unroll
+  for (int k = 1; k < 8; ++k)
+    if (k < dim) s = s + acc[k];
+  return s;
+}
+template <int DIM>
+__device__ __forceinline__ double vq_neg_dist_true(const float (&e)[DIM], const float *z, int dim) {
+  double zz = 0.0, ee = 0.0, ze = 0.0;
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    if (i < dim) {
+      const double a = z[i], b = e[i];
+      zz += a * a;
+      ee += b * b;
+      ze += a * b;
+    }
+  }
+  double r = -(zz + ee - 2.0 * ze);
+  asm volatile("" : "+v"(r));     // (as in vq_neg_dist)
+  return r;
+}
+// PAD: `p.dim` is the true dim, below DIM; rows, coefficients and `p.cb` are the padded copies of width DIM
+template <int MODE, int DIM, bool PAD>
+__device__ __forceinline__ double exact_of(const RerankParams &p, const float (&n)[DIM], const float *ops) {
+  if constexpr (MODE == kModeGQ) {
+    if constexpr (PAD) return (double)ref_score_lds_true<DIM>(n, ops, p.beta, p.dim);
+    else return (double)ref_score_lds<DIM>(n, ops, p.beta);
+  } else {
+    if constexpr (PAD) return vq_neg_dist_true<DIM>(n, ops, p.dim);
+    else return vq_neg_dist(n, ops, DIM);
+  }
+}
+
 // The exact re-rank.  16 lanes per row (4 rows per wave, 16 per block); a candidate = one "half-group" of the filter
 // = the 16 codes of one lane half in each of `gt` consecutive tiles, so every lane owns `gt` codes per candidate.
 // The kernel is a chain of dependent memory round trips (records -> code rows -> result), so everything a row needs
@@ -279,7 +330,7 @@ constexpr int kRerankLanes = 16;               // lanes per row
 // The in-block finish of ONE undecided row (block-wide; see the head of this file).  `mask`: record sets to scan; codes with
 // f^ >= thr (or all of them: keep_all) get the reference's own arithmetic; the winner leaves in torch.argmax order.
 // (Inlined at the block's very end: by then the hot path's registers are dead, and a call would cost the kernel a stack.)
-template <int MODE, int DIM>
+template <int MODE, int DIM, bool PAD = false>
 __device__ __forceinline__ void finish_row_by_scan(const RerankParams &p, long row, unsigned long long mask, float thr,
                                                              bool keep_all, const float *ops, double *sh_s, int *sh_i) {
   const int tid = threadIdx.x;
@@ -331,9 +382,7 @@ __device__ __forceinline__ void finish_row_by_scan(const RerankParams &p, long r
 #pragma unroll
         for (int i = 0; i < DIM; ++i) f = __builtin_fmaf(__builtin_fmaf(cA[i], n[u][i], cB[i]), n[u][i], f);
         if (ok[u] && (keep_all || !(f < thr))) {          // a NaN value passes
-          double sc;
-          if constexpr (MODE == kModeGQ) sc = (double)ref_score_lds<DIM>(n[u], ops, p.beta);
-          else sc = vq_neg_dist(n[u], ops, DIM);
+          const double sc = exact_of<MODE, DIM, PAD>(p, n[u], ops);
           if (!have || better_d(sc, code[u], best_s, best_i)) { best_s = sc; best_i = code[u]; have = true; }
         }
       }
@@ -353,11 +402,11 @@ __device__ __forceinline__ void finish_row_by_scan(const RerankParams &p, long r
     __syncthreads();
   }
   const int best = sh_i[0];     // (always a code: the scanned sets contain the filter's own maximum, whose f^ passes thr)
-  if (best != 0x7fffffff) write_result(p, row, best, tid);
+  if (best != 0x7fffffff) write_result(p, row, best, tid, PAD ? DIM : p.dim);
   __syncthreads();
 }
 
-template <int MODE, int DIM, int GT, int NSI>
+template <int MODE, int DIM, int GT, int NSI, bool PAD = false>
 __device__ __forceinline__ void rerank_block(const RerankParams &p, const int vblock, const int nrows) {
   constexpr int GROUP = kRerankLanes;
   constexpr int RPW = 64 / GROUP;            // rows per wave
@@ -564,9 +613,7 @@ __device__ __forceinline__ void rerank_block(const RerankParams &p, const int vb
   int best_i = 0x7fffffff;
   bool have = false;
   auto exact = [&](const float (&n)[DIM], int code) {
-    double s;
-    if constexpr (MODE == kModeGQ) s = (double)ref_score_lds<DIM>(n, ops, p.beta);
-    else s = vq_neg_dist(n, ops, DIM);
+    const double s = exact_of<MODE, DIM, PAD>(p, n, ops);
     if (!have || better_d(s, code, best_s, best_i)) {
       best_s = s;
       best_i = code;
@@ -643,8 +690,8 @@ __device__ __forceinline__ void rerank_block(const RerankParams &p, const int vb
     for (int j = threadIdx.x; j < RPB * DIM; j += 256) {
       int lr, g;
       if (p.omap.mode == 1) { lr = j % RPB; g = j / RPB; } else { lr = j / DIM; g = j % DIM; }
-      if (s_best[lr] >= 0) {
-        const long o = out_zhat_offset(p.omap, row0 + lr, g, DIM);
+      if (s_best[lr] >= 0 && (!PAD || g < p.dim)) {     // (PAD: the true dim's columns, in the true dim's layout)
+        const long o = out_zhat_offset(p.omap, row0 + lr, g, PAD ? p.dim : DIM);
         p.zhat[o] = ste_mix(p.hdr, o, s_zhat[lr][g]);
       }
     }
@@ -660,7 +707,7 @@ __device__ __forceinline__ void rerank_block(const RerankParams &p, const int vb
   // ---- the rows the candidates could not decide: finished here, by the whole block, one after the other ----
   for (int sl = 0; sl < RPB; ++sl) {
     const unsigned long long m = s_scan_mask[sl];     // block-uniform (written before the barrier above)
-    if (m != 0ull) finish_row_by_scan<MODE, DIM>(p, row0 + sl, m, s_scan_thr[sl], s_scan_keep[sl] != 0, s_ops[sl], sh_s, sh_i);
+    if (m != 0ull) finish_row_by_scan<MODE, DIM, PAD>(p, row0 + sl, m, s_scan_thr[sl], s_scan_keep[sl] != 0, s_ops[sl], sh_s, sh_i);
   }
 }
 
@@ -682,6 +729,15 @@ __global__ __launch_bounds__(256, DIM >= 32 ? 2 : 4) void gq_rerank_kernel(const
     }
   }
   rerank_block<MODE, DIM, GT, NSI>(p, vblock, p.rows);
+}
+
+// The re-rank of a padded call (dims 5-7, 9-15, 17-31 at the next filter dim DIM; gqhip.hip:run_padded): records, pre-filter, bounds
+// and gathers at DIM on the zero-padded copies; the exact scorer, the finish scan's scorer and the zhat / idx output at p.dim, the true
+// dim.  Kernels of their own, so the instantiations of the filter dims themselves stay what they were.  (GQ2's statistics never ride in
+// this launch.)
+template <int MODE, int DIM, int GT, int NSI>
+__global__ __launch_bounds__(256, DIM >= 32 ? 2 : 4) void gq_rerank_pad_kernel(const RerankParams p) {
+  rerank_block<MODE, DIM, GT, NSI, true>(p, (int)blockIdx.x, p.rows);
 }
 
 // Exhaustive exact arg-max of rows list[first], list[first + stride], ... (list == NULL: the rows themselves): one
@@ -725,7 +781,7 @@ __device__ __forceinline__ void exhaustive_rows(const RerankParams &p, const int
     }
     const int best = sh_i[0];
     __syncthreads();
-    write_result(p, row, best, tid);
+    write_result(p, row, best, tid, p.dim);
   }
 }
 

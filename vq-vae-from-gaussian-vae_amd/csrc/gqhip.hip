@@ -64,11 +64,14 @@ int filter_kind_from(const char *e) {
   if (e && (e[0] == 'm' || e[0] == 'M')) return GQHIP_FILTER_MIXED;   // fp16 + fp8
   return GQHIP_FILTER_AUTO;
 }
+// GQHIP_ODD_DIMS=padded, by its first letter in either case -> GQHIP_ODD_DIMS_PADDED; anything else: the exhaustive kernel
+int odd_dims_kind_from(const char *e) { return e && (e[0] == 'p' || e[0] == 'P') ? GQHIP_ODD_DIMS_PADDED : GQHIP_ODD_DIMS_EXHAUSTIVE; }
 
 // Every GQHIP_* variable this translation unit reads: diagnostics and A/B timing, never needed in production.  Read once per
 // process, when the library is loaded (g_filter_kind's initialiser is the first user).
 struct Env {
   int filter = filter_kind_from(env_str("GQHIP_FILTER"));   // initial filter selection (gqhip_set_filter() changes it at run time)
+  int odd_dims = odd_dims_kind_from(env_str("GQHIP_ODD_DIMS"));   // initial route of dims 5-7, 9-15, 17-31 (gqhip_set_odd_dims() changes it at run time)
   int rt = env_int("GQHIP_RT", 0);                           // 1 | 2: row tiles per wave of the filter (default: 2 from 8192 rows)
   int target_blocks = env_int("GQHIP_TARGET_BLOCKS", 0);     // > 0: filter blocks the code splits aim at (default: 256 / 512, make_plan)
   int nsplit = env_int("GQHIP_NSPLIT", 0);                   // > 0: code splits of the filter, before make_plan's caps
@@ -98,6 +101,19 @@ const Env &env() {
 std::atomic<int> g_filter_kind{env().filter};
 int filter_kind() { return g_filter_kind.load(std::memory_order_relaxed); }
 
+// Route of the dims between the filter dims (gqhip.h: gqhip_set_odd_dims).  The filter only nominates candidates and the re-rank
+// scores with the true dim, so the choice never changes an index either.
+std::atomic<int> g_odd_dims{env().odd_dims};
+// the filter dim an odd dim is zero-padded to under PADDED (5-7 -> 8, 9-15 -> 16, 17-31 -> 32); 0: no such route for this dim
+// (dims 1-3: 65 536 codes are dense in so few dimensions, the rows would live in the finish scan; 33-64: no K = 64 filter)
+int64_t padded_dim(int64_t dim) {
+  if (g_odd_dims.load(std::memory_order_relaxed) != GQHIP_ODD_DIMS_PADDED) return 0;
+  if (dim > 4 && dim < 8) return 8;
+  if (dim > 8 && dim < 16) return 16;
+  if (dim > 16 && dim < 32) return 32;
+  return 0;
+}
+
 // ---- launch plan: identical on the sizing and the launching side -----------
 struct Plan {
   bool mfma;            // filter kernel applies (dim in {4,8,16,32}, n >= 32)
@@ -113,6 +129,8 @@ struct Plan {
   int waves;            // waves per block: 8 (one block per CU) for the split-bf16 filter, else 4
   bool mixed;           // dim 16, Gaussian score: fp16 main product + fp8 corrections instead of three bf16 products
   bool f16;             // fp16 main product only + the data-dependent bound of the re-rank (round 3: the default filter)
+  int fdim;             // the dim the filter and the re-rank's templates run at: dim itself, the next filter dim on the padded route, 0 without a filter
+  bool padded;          // fdim > dim: rows and codebook are zero-padded in the workspace first (run_padded)
 
   // The fp16 + fp8 filter scores Gaussians only: under that selection a VQ call runs the split-bf16 kernels.  The sizing side does
   // not know the mode and sizes for the Gaussian score (mode defaulted), which needs no less.
@@ -162,7 +180,7 @@ bool grid_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes
   return need > 0 && cache && cache_bytes >= need && filter_kind() == GQHIP_FILTER_AUTO;
 }
 
-Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
+Plan plan_at(int64_t rows, int64_t n, int64_t dim) {
   const Env &e = env();
   Plan pl{};
   pl.mfma = (dim == 4 || dim == 8 || dim == 16 || dim == 32) && n >= 1 && rows >= 1;
@@ -218,7 +236,21 @@ Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
       pl.nsplit = (pl.tiles_total + pl.tiles_per_split - 1) / pl.tiles_per_split;
     }
   }
+  pl.fdim = pl.mfma ? (int)dim : 0;
   return pl;
+}
+
+// The one place that decides the route: the plan of `dim`, or -- under GQHIP_ODD_DIMS_PADDED, for a dim between two filter dims --
+// the plan of the filter dim it is padded to, marked `padded`.
+Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
+  if (const int64_t dp = padded_dim(dim)) {
+    Plan pl = plan_at(rows, n, dp);
+    if (pl.mfma) {      // (a codebook beyond the split cap runs the exhaustive kernel, at its true dim)
+      pl.padded = true;
+      return pl;
+    }
+  }
+  return plan_at(rows, n, dim);
 }
 
 inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
@@ -233,19 +265,22 @@ int64_t image_cache_bytes(const Plan &pl, int64_t dim) {
 }
 
 struct WsLayout {
-  int64_t hdr, rec, fb, dbg, mu, sd, lsd, rowsum, coef, cbimg, rowimg, rowscale, rowaux, kl2, total;
+  int64_t hdr, rec, fb, dbg, mu, sd, lsd, rowsum, coef, cbimg, rowimg, rowscale, rowaux, kl2, pmu, psd, plsd, pcb, total;
 };
 
-WsLayout ws_layout(const Plan &pl, int64_t rows, int64_t dim) {
+// `dim`: the caller's; on the padded route everything the filter and the re-rank read is sized at pl.fdim, and the padded rows and the
+// zero-padded fp32 codebook they gather from follow the regions of every other route
+WsLayout ws_layout(const Plan &pl, int64_t rows, int64_t dim_true) {
   WsLayout w{};
+  const int64_t dim = pl.padded ? pl.fdim : dim_true;
   int64_t off = 0;
   w.hdr = off; off += (int64_t)sizeof(WsHeader);
   w.rec = off; off += align256((int64_t)sizeof(Rec) * rows * pl.stored_rec_sets());
   w.fb = off;  off += align256(4 * rows);
   w.dbg = off; off += 128 * 1024;     // diagnostic builds only (GQHIP_CLOCK_STAMPS: per-block timeline records of the filter | of the re-rank)
-  w.mu = off;  off += align256(4 * rows * dim);
-  w.sd = off;  off += align256(4 * rows * dim);
-  w.lsd = off; off += align256(4 * rows * dim);
+  w.mu = off;  off += align256(4 * rows * dim_true);
+  w.sd = off;  off += align256(4 * rows * dim_true);
+  w.lsd = off; off += align256(4 * rows * dim_true);
   w.rowsum = off; off += pl.mfma ? align256(8 * 4 * rows) : 0;
   w.coef = off; off += pl.mfma ? align256(4 * 2 * rows * dim) : 0;
   // split-bf16 operand images: 2*NV vectors of 16 B per (code, half) / (row, half), NV = dim / 8
@@ -255,6 +290,12 @@ WsLayout ws_layout(const Plan &pl, int64_t rows, int64_t dim) {
   w.rowscale = off; off += (pl.mixed || pl.f16) ? align256(4 * rows) : 0;
   w.rowaux = off; off += pl.f16 ? align256(32 * rows) : 0;
   w.kl2 = off; off += align256(4 * rows);       // per-row KL bits of gq_quantize_z_gauss_f32
+  if (pl.padded) {
+    w.pmu = off;  off += align256(4 * rows * dim);
+    w.psd = off;  off += align256(4 * rows * dim);
+    w.plsd = off; off += align256(4 * rows * dim);
+    w.pcb = off;  off += align256(4 * (int64_t)pl.tiles_total * kTileCodes * dim);
+  }
   w.total = off;
   return w;
 }
@@ -374,6 +415,22 @@ template <int MODE, int DIM, int GT>
 RerankKernel rerank_kernel_nsi(int rec_sets) {
   return rec_sets <= 16 ? gq_rerank_kernel<MODE, DIM, GT, 1> : gq_rerank_kernel<MODE, DIM, GT, 4>;
 }
+// ... and of a padded call: the same block with the scorer, the output and nothing else at the true dim (gq_rerank.h)
+template <int MODE, int DIM, int GT>
+RerankKernel rerank_pad_kernel_nsi(int rec_sets) {
+  return rec_sets <= 16 ? gq_rerank_pad_kernel<MODE, DIM, GT, 1> : gq_rerank_pad_kernel<MODE, DIM, GT, 4>;
+}
+template <int MODE>
+RerankKernel rerank_pad_kernel(int64_t dim, int gt, int rec_sets) {
+  switch (dim * 100 + gt) {
+    case 804: return rerank_pad_kernel_nsi<MODE, 8, 4>(rec_sets);
+    case 1602: return rerank_pad_kernel_nsi<MODE, 16, 2>(rec_sets);
+    case 1604: return rerank_pad_kernel_nsi<MODE, 16, 4>(rec_sets);
+    case 3202: return rerank_pad_kernel_nsi<MODE, 32, 2>(rec_sets);
+    case 3204: return rerank_pad_kernel_nsi<MODE, 32, 4>(rec_sets);
+    default: return nullptr;
+  }
+}
 template <int MODE>
 RerankKernel rerank_kernel(int64_t dim, int gt, int rec_sets) {
   switch (dim * 100 + gt) {
@@ -433,6 +490,7 @@ struct Call {
   WsHeader *hdr;
   float *ws_lsd;
   const float *r_mu, *r_sd, *r_lsd;             // the rows every later kernel reads
+  int64_t dim_true = 0;                         // > 0: `dim` is the filter dim of a padded call, rows and `cb` its padded copies (run_padded)
   bool from_z() const { return in.z != nullptr; }
   template <class T>
   T *at(int64_t off) const { return reinterpret_cast<T *>(ws + off); }
@@ -448,7 +506,7 @@ RerankParams rerank_params(const Call &c) {
   rp.rec = c.at<const Rec>(c.w.rec);
   rp.idx = c.idx; rp.zhat = c.zhat; rp.hdr = c.hdr;
   rp.fb_list = c.at<int>(c.w.fb);
-  rp.rows = (int)c.rows; rp.n = (int)c.n; rp.dim = (int)c.dim;
+  rp.rows = (int)c.rows; rp.n = (int)c.n; rp.dim = (int)(c.dim_true ? c.dim_true : c.dim);
   const RerankBound b = rerank_bound(pl, MODE, c.dim);
   rp.ef_coeff = env().ef_coeff > 0.0 ? (float)env().ef_coeff : b.ef_coeff;
   rp.n1_limit = b.n1_limit; rp.n1_min = b.n1_min;
@@ -502,8 +560,10 @@ PrepParams prep_params(const Call &c, bool grid, bool stats_in_rerank) {
 }
 
 // dims outside {4, 8, 16, 32}: prep -> exact score of every code (gq_exhaustive_kernel)
+// the rows of a call without a gq_prep_kernel at its dim: header zeroed, then (module entry points) z -> rows at the true dim with
+// zhat_noquant, sd_out, the per-row KL bits and the straight-through words
 template <int MODE>
-int run_exhaustive(const Call &c) {
+int run_prep_plain(const Call &c) {
   const PrepInput &in = c.in;
   if (hipMemsetAsync(c.hdr, 0, sizeof(WsHeader), c.st) != hipSuccess) return check_launch();
   if (c.from_z()) {
@@ -514,9 +574,15 @@ int run_exhaustive(const Call &c) {
     pq.hdr = c.hdr; pq.ste_kind = in.ste_kind; pq.ste = in.ste; pq.pure = in.pure;
     pq.mu = const_cast<float *>(c.r_mu); pq.sd = const_cast<float *>(c.r_sd); pq.lsd = c.ws_lsd;
     pq.rows = c.rows; pq.dim = (int)c.dim; pq.lv_min = in.lv_min; pq.lv_max = in.lv_max; pq.omap = c.omap;
-    const int rc = launch(prep_plain_kernel, dim3((unsigned)((c.rows * c.dim + 255) / 256)), dim3(256), 0, c.st, pq);
-    if (rc != GQHIP_OK) return rc;
+    return launch(prep_plain_kernel, dim3((unsigned)((c.rows * c.dim + 255) / 256)), dim3(256), 0, c.st, pq);
   }
+  return GQHIP_OK;
+}
+
+template <int MODE>
+int run_exhaustive(const Call &c) {
+  const int rc = run_prep_plain<MODE>(c);
+  if (rc != GQHIP_OK) return rc;
   const int ex_blocks = (int)(c.rows < 4096 ? c.rows : 4096);
   return launch(gq_exhaustive_kernel<MODE>, dim3((unsigned)ex_blocks), dim3(256), 0, c.st, rerank_params<MODE>(c));
 }
@@ -596,7 +662,35 @@ int run_dense(const Call &c, bool stats_in_rerank) {
   // ---- launch 3: exact re-rank of the candidates; rows they cannot decide are finished by their own block ----
   const RerankParams rp = rerank_params<MODE>(c);
   const dim3 rgrid((unsigned)((c.rows + 15) / 16 + (stats_in_rerank ? 1 : 0)));
-  return launch(rerank_kernel<MODE>(c.dim, rp.gt, rp.nsplit), rgrid, dim3(256), 0, c.st, rp);
+  const RerankKernel rk = c.dim_true ? rerank_pad_kernel<MODE>(c.dim, rp.gt, rp.nsplit) : rerank_kernel<MODE>(c.dim, rp.gt, rp.nsplit);
+  return launch(rk, rgrid, dim3(256), 0, c.st, rp);
+}
+
+// Dims 5-7, 9-15, 17-31 under GQHIP_ODD_DIMS_PADDED: rows at the true dim as on the exhaustive path (so zhat_noquant, sd_out, the KL
+// bits and the VQ loss's rows are what they are there), gq_pad_kernel -> rows and codebook zero-padded to the plan's filter dim, then
+// the dense path on the padded copies: its from-rows prep, the selected filter and the re-rank, which scores and stores at the true dim.
+// No codebook cache: the padded operand image is rebuilt in the workspace on every call.
+template <int MODE>
+int run_padded(const Call &c) {
+  int rc = run_prep_plain<MODE>(c);
+  if (rc != GQHIP_OK) return rc;
+  const int64_t dp = c.pl.fdim;
+  PadParams pd{};
+  pd.mu = c.r_mu; pd.sd = MODE == kModeGQ ? c.r_sd : nullptr;
+  pd.lsd = MODE == kModeGQ ? (c.from_z() ? c.ws_lsd : c.lsd) : nullptr;
+  pd.cb = c.cb;
+  pd.pmu = c.at<float>(c.w.pmu); pd.psd = c.at<float>(c.w.psd); pd.plsd = c.at<float>(c.w.plsd); pd.pcb = c.at<float>(c.w.pcb);
+  pd.rows = (long)c.rows; pd.n = (long)c.n; pd.dim = (int)c.dim; pd.dp = (int)dp;
+  const int64_t pblocks = ((c.rows + c.n) * dp + 255) / 256;
+  rc = launch(gq_pad_kernel, dim3((unsigned)(pblocks < kPadMaxBlocks ? pblocks : kPadMaxBlocks)), dim3(256), 0, c.st, pd);
+  if (rc != GQHIP_OK) return rc;
+  PrepInput pin;
+  pin.ste_kind = c.in.ste_kind; pin.ste = c.in.ste; pin.pure = c.in.pure;
+  Call cp{pin, MODE == kModeGQ ? pd.plsd : nullptr, pd.pcb, c.idx, c.zhat, dp, c.rows, c.n, c.beta, nullptr, 0, c.omap, c.st, c.pl, c.w, c.ws};
+  cp.hdr = c.hdr; cp.ws_lsd = pd.plsd;
+  cp.r_mu = pd.pmu; cp.r_sd = pd.psd; cp.r_lsd = MODE == kModeGQ ? pd.plsd : nullptr;
+  cp.dim_true = c.dim;
+  return run_dense<MODE>(cp, false);
 }
 
 // The fused arg-max, shared by GQ and VQ: checks, plan and workspace layout (once per call), the rows every kernel reads, then one
@@ -621,6 +715,10 @@ int run_argmax(const PrepInput &in, const float *mu, const float *sd, const floa
   c.r_sd = from_z ? (in.sd_out ? in.sd_out : c.at<float>(w.sd)) : sd;
   c.r_lsd = from_z ? c.ws_lsd : (MODE == kModeGQ ? (lsd ? lsd : (pl.mfma ? c.ws_lsd : nullptr)) : nullptr);
   if (!pl.mfma) return run_exhaustive<MODE>(c);
+  if (pl.padded) {
+    if (in.stats_done) *in.stats_done = false;     // GQ2's statistics: the launch of their own the exhaustive path has
+    return run_padded<MODE>(c);
+  }
   const bool grid = grid_applies(n, dim, cb_cache, cb_cache_bytes);
   const bool stats_in_rerank = MODE == kModeGQ && in.want_kl2 && !grid;
   if (in.stats_done) *in.stats_done = stats_in_rerank;
@@ -719,13 +817,26 @@ int gqhip_set_filter(int kind) {
 
 int gqhip_get_filter(void) { return g_filter_kind.load(std::memory_order_relaxed); }
 
+int gqhip_set_odd_dims(int kind) {
+  if (kind != GQHIP_ODD_DIMS_EXHAUSTIVE && kind != GQHIP_ODD_DIMS_PADDED) return GQHIP_ERR_INVALID_ARG;
+  g_odd_dims.store(kind, std::memory_order_relaxed);
+  return GQHIP_OK;
+}
+
+int gqhip_get_odd_dims(void) { return g_odd_dims.load(std::memory_order_relaxed); }
+
+int64_t gqhip_filter_dim(int64_t n, int64_t dim) {
+  if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
+  return make_plan(65536, n, dim).fdim;
+}
+
 int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host) {
   if (!out8_host || rows < 1 || n < 1 || dim < 1 || dim > kMaxDim) return GQHIP_ERR_INVALID_ARG;
   const Plan pl = make_plan(rows, n, dim);
   out8_host[0] = ws_layout(pl, rows, dim).rec; out8_host[1] = pl.stored_rec_sets();
   out8_host[2] = pl.gt; out8_host[3] = pl.tiles_per_split;
   out8_host[4] = pl.f16 ? 3 : (pl.mixed ? 2 : (pl.bf16 ? 1 : 0));   // 0 fp32 MFMA filter, 1 split-bf16, 2 fp16 + fp8 (Gaussian score), 3 fp16 main product
-  out8_host[5] = (int64_t)rerank_bound(pl, kModeGQ, dim).ef_coeff;
+  out8_host[5] = (int64_t)rerank_bound(pl, kModeGQ, pl.padded ? pl.fdim : dim).ef_coeff;
   out8_host[6] = pl.rt; out8_host[7] = pl.waves;
   return GQHIP_OK;
 }

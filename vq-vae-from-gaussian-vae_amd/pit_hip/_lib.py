@@ -214,7 +214,8 @@ class Workspace(_Scratch):
     """Caller-owned scratch, grown on demand and reused across calls, plus the persistent CODEBOOK CACHE of the shapes that keep
     one (gqhip.h: gqhip_cb_cache_bytes -- dims 4 / 8: the spatial index of the pruned search; the library validates it against a
     content hash of the codebook on every call and rebuilds it in-stream when it is stale, so nothing here has to track the
-    codebook).  One workspace serves one stream at a time (its header carries the per-call counters).  Graph captures: the rule
+    codebook).  The sizes come from the library under its current selections (``set_filter``, ``set_odd_dims``): nothing to redo here
+    after changing one.  One workspace serves one stream at a time (its header carries the per-call counters).  Graph captures: the rule
     of ``_Scratch``, one pin for both buffers; size them with a warm-up call first (``reserve``)."""
 
     _what = "workspace"
@@ -1685,6 +1686,28 @@ def set_filter(kind: str) -> None:
 def get_filter() -> str:
     k = lib().gqhip_get_filter()
     return next(name for name, v in FILTER_KINDS.items() if v == k)
+
+
+ODD_DIMS_KINDS = {"exhaustive": 0, "padded": 1}
+
+
+def set_odd_dims(kind: str) -> None:
+    """Route of the codebook dims 5-7, 9-15, 17-31: "exhaustive" (default): every code scored per row; "padded": zero-padded to the
+    next filter dim (8, 16, 32) and run through filter + re-rank, which scores with the true dim.  Process-wide; every output is the
+    same bits either way.  The workspace size depends on it (a ``Workspace`` asks the library on every call and grows by itself)."""
+    if kind not in ODD_DIMS_KINDS:
+        raise GqHipError(f"unknown odd-dims route {kind!r} (expected one of {sorted(ODD_DIMS_KINDS)})")
+    _check(lib().gqhip_set_odd_dims(ODD_DIMS_KINDS[kind]), "gqhip_set_odd_dims")
+
+
+def get_odd_dims() -> str:
+    k = lib().gqhip_get_odd_dims()
+    return next(name for name, v in ODD_DIMS_KINDS.items() if v == k)
+
+
+def filter_dim(n: int, dim: int) -> int:
+    """The dim the filter runs at for (n, dim) under the current selections; 0: the exhaustive kernel."""
+    return int(lib().gqhip_filter_dim(n, dim))
 
 
 def debug_plan(rows: int, n: int, dim: int) -> dict:
