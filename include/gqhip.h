@@ -121,7 +121,8 @@ int gqhip_get_filter(void);
  * mu 0, sd 1, log sd 0, code 0 in the pad columns), the selected filter runs there unchanged, and the exact re-rank -- which alone
  * decides an index -- scores with the TRUE dim, so the indices, zhat and every other output are the same bits either way
  * (DESIGN.md section 3.1).  Such a call keeps nothing in the codebook cache (gqhip_cb_cache_bytes stays 0 at these dims): the padded
- * operand image is rebuilt in the workspace on every call.  Dims 1..3 and 33..64 stay on the exhaustive kernel under either value.
+ * operand image is rebuilt in the workspace on every call.  Dims 1..3 and 33..64 stay on the exhaustive kernel under either value
+ * (dims 1..3 have a switch of their own: gqhip_set_low_dims below).
  * Process-wide; initial value from the environment (GQHIP_ODD_DIMS=padded).  The workspace size depends on it: query
  * gqhip_workspace_bytes after changing it.  An unknown kind: GQHIP_ERR_INVALID_ARG, the selection stays.  (No reference counterpart.) */
 #define GQHIP_ODD_DIMS_EXHAUSTIVE 0
@@ -131,6 +132,26 @@ int gqhip_get_odd_dims(void);
 /* Diagnostic: the dim the filter of the fused arg-max runs at for (n, dim) under the current selections -- `dim` itself at 4, 8,
  * 16, 32; 8, 16 or 32 for a dim the PADDED route serves; 0 where the exhaustive kernel runs; -1: n < 1 or dim outside 1..64. */
 int64_t gqhip_filter_dim(int64_t n, int64_t dim);
+
+/* Route of the codebook dims 1..3 in gq_argmax_f32 / gq_quantize_z_f32 / gq_quantize_z_gauss_f32 (the Gaussian score only).
+ * EXHAUSTIVE (default): one block per row scores every code with the reference's arithmetic.  SEARCH: a call with 4096 <= n <= 2^20
+ * codes and a codebook cache of gqhip_cb_cache_bytes runs a pruned exact search (csrc/gq_lowdim.h): rows as on the exhaustive
+ * route -> codebook hash -> index builder (exits unless the cache is stale) -> search -> finish of the rows it listed.  The index
+ * buckets the codes into 4096 cells with tight bounding boxes (4096 / 64 x 64 / 16 x 16 x 16 quantile cells) under 256 coarse
+ * nodes; a row gives the reference's arithmetic to the codes of the cells whose closed-form bound is within the rounding margin of
+ * its best code, and the (score, lowest index) order decides: the indices, zhat and every other output are the same bits either way
+ * (DESIGN.md section 3.2b).  Rows with a non-finite operand, bound or codebook, with sd <= 0, or that reach an overfull cell get
+ * the exhaustive kernel itself in the finish launch.  There is no filter: gqhip_filter_dim stays 0, and gqhip_set_filter /
+ * gqhip_set_odd_dims do not matter here.  What keeps today's route under either value: the VQ entry points, gq_scores_f32, the train
+ * steps, n outside the range, a NULL or short cache, every other dim.  Process-wide; initial value from the environment
+ * (GQHIP_LOW_DIMS=search).  gqhip_cb_cache_bytes depends on it, and gqhip_workspace_bytes may: query them after changing it.  An
+ * unknown kind: GQHIP_ERR_INVALID_ARG, the selection stays.  (No reference counterpart.) */
+#define GQHIP_LOW_DIMS_EXHAUSTIVE 0   /* default */
+#define GQHIP_LOW_DIMS_SEARCH 1
+int gqhip_set_low_dims(int kind);
+int gqhip_get_low_dims(void);
+/* 1: a GQ call of this codebook shape with a cache runs the search (SEARCH selected, dim 1..3, 4096 <= n <= 2^20); 0 otherwise. */
+int gqhip_low_dim_search_applies(int64_t n, int64_t dim);
 
 /* Diagnostics: launch plan and workspace layout of the fused arg-max for a shape.  out8_host = { byte offset of the
  * candidate records, code splits, tiles per candidate group, tiles per split, filter kernel the plan selects (0 fp32 MFMA, 1 split-bf16, 2 fp16 + fp8, 3 fp16 main product: the default at dims 8 / 16 / 32), coefficient of the
@@ -155,7 +176,9 @@ int64_t gqhip_workspace_bytes(int64_t rows, int64_t n, int64_t dim);
  * of width `dim` across calls; 0 when this shape keeps nothing (then pass NULL / 0).  Today: dim 4 with 2^14 <= n <= 2^20
  * -- the codes sorted into 4096 sub-leaves under a tree of bounding boxes (16 -> 256 -> 1024 -> 4096), which lets dim 4 run a pruned
  * exact search (~8 sub-leaves of ~16 codes per row instead of all n codes; csrc/gq_grid.h) in place of filter + re-rank --; dims
- * 8 / 16 / 32: the fp16 operand image of the codebook that the MFMA filter reads (each 1/256 slice stamped with its content hash).
+ * 8 / 16 / 32: the fp16 operand image of the codebook that the MFMA filter reads (each 1/256 slice stamped with its content hash);
+ * dims 1 / 2 / 3 with 4096 <= n <= 2^20, only under gqhip_set_low_dims(GQHIP_LOW_DIMS_SEARCH): the cell index of csrc/gq_lowdim.h
+ * (same header, hashes and rebuild protocol; every offset and index read from its body is bounded by the codebook size as well).
  * Contract: the caller owns the buffer, hands the SAME buffer to every call that uses the same codebook, and never writes it;
  * its initial contents are don't-care.  The library validates it on EVERY call -- the first launch hashes the codebook it is
  * given (it reads it anyway) and compares with the hashes the cache was stamped with -- and rebuilds it in-stream (one extra
@@ -176,7 +199,9 @@ int gqhip_grid_search_applies(int64_t n, int64_t dim);
  * codebooks), so every row that lists it is handed to gq_grid_finish_kernel, a block per row: a multi-millisecond call where the dense
  * filter + re-rank takes ~100 us; a host that sees 1 should stop passing the cache for this codebook (NULL / 0: the dense path).
  * 0: fine.  -1: no current index in `cb_cache` (never built, stale, another shape) or a shape without a search.  pit_hip's Workspace
- * asks once, at the call after the one that built the index.  (No reference counterpart.) */
+ * asks once, at the call after the one that built the index.  Dims 1..3 under GQHIP_LOW_DIMS_SEARCH: the same answers for the cell
+ * index of csrc/gq_lowdim.h -- 1: some cell holds more than max(256, n / 256) codes, and every row that reaches it is finished by the
+ * exhaustive kernel.  (No reference counterpart.) */
 int gqhip_cb_cache_degenerate(const void *cb_cache, int64_t n, int64_t dim);
 
 /* ---- compat op: the reference's native boundary ---------------------------
@@ -199,7 +224,9 @@ int gq_scores_f32(const float *mu, const float *sd, const float *cb, float *out,
  *           float(log(double(sd))) (correctly rounded).
  * dim: any 1..64 (4, 8, 16, 32 run on the MFMA filter; 5..7, 9..15, 17..31 too, zero-padded to the next of them, once
  *           gqhip_set_odd_dims(GQHIP_ODD_DIMS_PADDED) selects that -- prep of the padded operands, filter, re-rank, the same
- *           indices; every other case exhaustive).
+ *           indices; 1..3 with a codebook cache run the pruned search of csrc/gq_lowdim.h once
+ *           gqhip_set_low_dims(GQHIP_LOW_DIMS_SEARCH) selects that -- five launches, the builder and the finish exit at once in
+ *           the common case, the same indices; every other case exhaustive).
  * Dim 4 with a codebook cache: prep -> index check -> pruned exact search -> finish of the rows it left undecided
  * (csrc/gq_grid.h; four launches, the second and fourth exit at once in the common case).
  * Three launches on `stream` for the other MFMA dims: prep (operand images, bound sums,
@@ -823,7 +850,8 @@ int gqhip_profile_collect(int *launches_host, double *total_ms_host);
 
 /* Diagnostics of the last fused call on `workspace` (device-side counters,
  * copied out synchronously): rows sent to the exhaustive fallback and total
- * half-tiles re-ranked.  For tests / DESIGN.md statistics only. */
+ * half-tiles re-ranked.  For tests / DESIGN.md statistics only.  After a dims 1..3 search call (gqhip_set_low_dims) the first
+ * word is the number of rows its finish launch took, the second (with gqhip_debug_enable(1)) the codes scored exactly. */
 /* on != 0: the re-rank kernel also counts re-ranked half-tiles (adds one
  * contended atomic per row -- keep off when timing). */
 int gqhip_debug_enable(int on);

@@ -19,6 +19,7 @@
 #include "gq_filter_bf16.h"
 #include "gq_gauss_train.h"
 #include "gq_grid.h"
+#include "gq_lowdim.h"
 #include "gq_prep.h"
 #include "gq_rerank.h"
 #include "gq_scores.h"
@@ -67,11 +68,15 @@ int filter_kind_from(const char *e) {
 // GQHIP_ODD_DIMS=padded, by its first letter in either case -> GQHIP_ODD_DIMS_PADDED; anything else: the exhaustive kernel
 int odd_dims_kind_from(const char *e) { return e && (e[0] == 'p' || e[0] == 'P') ? GQHIP_ODD_DIMS_PADDED : GQHIP_ODD_DIMS_EXHAUSTIVE; }
 
+// GQHIP_LOW_DIMS=search, by its first letter in either case -> GQHIP_LOW_DIMS_SEARCH; anything else: the exhaustive kernel
+int low_dims_kind_from(const char *e) { return e && (e[0] == 's' || e[0] == 'S') ? GQHIP_LOW_DIMS_SEARCH : GQHIP_LOW_DIMS_EXHAUSTIVE; }
+
 // Every GQHIP_* variable this translation unit reads: diagnostics and A/B timing, never needed in production.  Read once per
 // process, when the library is loaded (g_filter_kind's initialiser is the first user).
 struct Env {
   int filter = filter_kind_from(env_str("GQHIP_FILTER"));   // initial filter selection (gqhip_set_filter() changes it at run time)
   int odd_dims = odd_dims_kind_from(env_str("GQHIP_ODD_DIMS"));   // initial route of dims 5-7, 9-15, 17-31 (gqhip_set_odd_dims() changes it at run time)
+  int low_dims = low_dims_kind_from(env_str("GQHIP_LOW_DIMS"));   // initial route of dims 1-3 (gqhip_set_low_dims() changes it at run time)
   int rt = env_int("GQHIP_RT", 0);                           // 1 | 2: row tiles per wave of the filter (default: 2 from 8192 rows)
   int target_blocks = env_int("GQHIP_TARGET_BLOCKS", 0);     // > 0: filter blocks the code splits aim at (default: 256 / 512, make_plan)
   int nsplit = env_int("GQHIP_NSPLIT", 0);                   // > 0: code splits of the filter, before make_plan's caps
@@ -112,6 +117,18 @@ int64_t padded_dim(int64_t dim) {
   if (dim > 8 && dim < 16) return 16;
   if (dim > 16 && dim < 32) return 32;
   return 0;
+}
+
+// Route of the Gaussian arg-max at dims 1-3 (gqhip.h: gqhip_set_low_dims): under SEARCH a call with a codebook cache runs the pruned
+// exact search of gq_lowdim.h, whose winner is decided by the reference's arithmetic as on the exhaustive route: never another index.
+std::atomic<int> g_low_dims{env().low_dims};
+int64_t low_cache_bytes(int64_t n, int64_t dim) {
+  if (g_low_dims.load(std::memory_order_relaxed) != GQHIP_LOW_DIMS_SEARCH || dim < 1 || dim > 3 || n < 4096 || n > (1 << 20)) return 0;
+  return low_layout(n, dim).total;
+}
+bool low_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes) {
+  const int64_t need = low_cache_bytes(n, dim);
+  return need > 0 && cache && cache_bytes >= need;
 }
 
 // ---- launch plan: identical on the sizing and the launching side -----------
@@ -587,6 +604,35 @@ int run_exhaustive(const Call &c) {
   return launch(gq_exhaustive_kernel<MODE>, dim3((unsigned)ex_blocks), dim3(256), 0, c.st, rerank_params<MODE>(c));
 }
 
+// Dims 1-3 under GQHIP_LOW_DIMS_SEARCH with a codebook cache (GQ): rows as on the exhaustive path -> codebook hash and max|cb| ->
+// index builder (exits unless the hash or the stamp says the cache is stale) -> pruned exact search (gq_lowdim.h) -> the rows it
+// listed, through gq_exhaustive_kernel itself (exits at once when there are none).
+int run_low(const Call &c) {
+  int rc = run_prep_plain<kModeGQ>(c);
+  if (rc != GQHIP_OK) return rc;
+  LowHashParams hp{};
+  hp.cb = c.cb; hp.hdr = c.hdr; hp.cache = static_cast<GridHdr *>(c.cb_cache); hp.count = (long)(c.n * c.dim);
+  rc = launch(gq_low_hash_kernel, dim3(kLowHashBlocks), dim3(256), 0, c.st, hp);
+  if (rc != GQHIP_OK) return rc;
+  LowBuildParams bp{};
+  bp.cb = c.cb; bp.cache = static_cast<char *>(c.cb_cache); bp.hdr = c.hdr; bp.n = (int)c.n;
+  const auto build = c.dim == 1 ? gq_low_build_kernel<1> : (c.dim == 2 ? gq_low_build_kernel<2> : gq_low_build_kernel<3>);
+  rc = launch(build, dim3(1), dim3(kLowBuildThreads), 0, c.st, bp);
+  if (rc != GQHIP_OK) return rc;
+  RerankParams rp = rerank_params<kModeGQ>(c);
+  rp.all_rows = 0;                                  // the finish launch: the listed rows only
+  LowParams lp{};
+  lp.mu = c.r_mu; lp.sd = c.r_sd; lp.lsd = c.r_lsd; lp.cb = c.cb; lp.cache = static_cast<const char *>(c.cb_cache);
+  lp.idx = c.idx; lp.zhat = c.zhat; lp.hdr = c.hdr; lp.fb_list = rp.fb_list;
+  lp.rows = (int)c.rows; lp.n = (int)c.n; lp.beta = (float)c.beta; lp.stats = g_debug_stats; lp.omap = c.omap;
+  const auto search = c.dim == 1 ? gq_low_search_kernel<1> : (c.dim == 2 ? gq_low_search_kernel<2> : gq_low_search_kernel<3>);
+  const int64_t nsets = (c.rows + 15) / 16;
+  rc = launch(ProfScope(), search, dim3((unsigned)(nsets < 4096 ? nsets : 4096)), dim3(kLowThreads), 0, c.st, lp);
+  if (rc != GQHIP_OK) return rc;
+  const int fin_blocks = (int)(c.rows < 1024 ? c.rows : 1024);
+  return launch(gq_exhaustive_kernel<kModeGQ>, dim3((unsigned)fin_blocks), dim3(256), 0, c.st, rp);
+}
+
 // dims 4 / 8 with a codebook cache: prep (rows, bound sums, max|cb|, codebook hash) -> index builder (exits unless the hash says the
 // cache is stale) -> pruned exact search (gq_grid.h) -> the rows it left undecided.  Four launches, no filter, no re-rank.
 template <int MODE>
@@ -714,7 +760,11 @@ int run_argmax(const PrepInput &in, const float *mu, const float *sd, const floa
   c.r_mu = from_z ? (in.mu_out ? in.mu_out : c.at<float>(w.mu)) : mu;
   c.r_sd = from_z ? (in.sd_out ? in.sd_out : c.at<float>(w.sd)) : sd;
   c.r_lsd = from_z ? c.ws_lsd : (MODE == kModeGQ ? (lsd ? lsd : (pl.mfma ? c.ws_lsd : nullptr)) : nullptr);
-  if (!pl.mfma) return run_exhaustive<MODE>(c);
+  if (!pl.mfma) {     // the one place that chooses between the exhaustive kernel and the low-dim search
+    if constexpr (MODE == kModeGQ)
+      if (low_applies(n, dim, cb_cache, cb_cache_bytes)) return run_low(c);
+    return run_exhaustive<MODE>(c);
+  }
   if (pl.padded) {
     if (in.stats_done) *in.stats_done = false;     // GQ2's statistics: the launch of their own the exhaustive path has
     return run_padded<MODE>(c);
@@ -825,6 +875,16 @@ int gqhip_set_odd_dims(int kind) {
 
 int gqhip_get_odd_dims(void) { return g_odd_dims.load(std::memory_order_relaxed); }
 
+int gqhip_set_low_dims(int kind) {
+  if (kind != GQHIP_LOW_DIMS_EXHAUSTIVE && kind != GQHIP_LOW_DIMS_SEARCH) return GQHIP_ERR_INVALID_ARG;
+  g_low_dims.store(kind, std::memory_order_relaxed);
+  return GQHIP_OK;
+}
+
+int gqhip_get_low_dims(void) { return g_low_dims.load(std::memory_order_relaxed); }
+
+int gqhip_low_dim_search_applies(int64_t n, int64_t dim) { return low_cache_bytes(n, dim) > 0; }
+
 int64_t gqhip_filter_dim(int64_t n, int64_t dim) {
   if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
   return make_plan(65536, n, dim).fdim;
@@ -844,17 +904,18 @@ int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host) {
 int gqhip_grid_search_applies(int64_t n, int64_t dim) { return grid_cache_bytes(n, dim) > 0 && filter_kind() == GQHIP_FILTER_AUTO; }
 
 int gqhip_cb_cache_degenerate(const void *cb_cache, int64_t n, int64_t dim) {
-  if (!cb_cache || grid_cache_bytes(n, dim) <= 0) return -1;
+  const bool low = low_cache_bytes(n, dim) > 0;
+  if (!cb_cache || (!low && grid_cache_bytes(n, dim) <= 0)) return -1;
   GridHdr g;
   if (hipMemcpy(&g, cb_cache, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) { (void)check_launch(); return -1; }
-  if (g.magic != kGridMagic || g.n != (int)n || g.dim != (int)dim || g.stale != 0) return -1;
-  return g.max_sub > 255 ? 1 : 0;
+  if (g.magic != (low ? kLowMagic : kGridMagic) || g.n != (int)n || g.dim != (int)dim || g.stale != 0) return -1;
+  return g.max_sub > (low ? low_cell_cap(n) : 255) ? 1 : 0;
 }
 
 int64_t gqhip_cb_cache_bytes(int64_t n, int64_t dim) {
   if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
-  const int64_t g = grid_cache_bytes(n, dim);
-  return g > 0 ? g : image_cache_bytes(make_plan(65536, n, dim), dim);
+  const int64_t g = grid_cache_bytes(n, dim), low = low_cache_bytes(n, dim);
+  return g > 0 ? g : (low > 0 ? low : image_cache_bytes(make_plan(65536, n, dim), dim));
 }
 
 int64_t gqhip_workspace_bytes(int64_t rows, int64_t n, int64_t dim) {

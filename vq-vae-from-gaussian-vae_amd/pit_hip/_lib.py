@@ -251,7 +251,8 @@ class Workspace(_Scratch):
         # the block-per-row finish kernel -- milliseconds per call where filter + re-rank takes ~100 us.  Such a book goes
         # back to the dense path for good (always exact; a codebook that changes every step should not pass a cache at all: vq.py).
         self._cache_calls += 1
-        if self._cache_calls == 2 and lib().gqhip_grid_search_applies(n, dim) and not torch.cuda.is_current_stream_capturing():
+        searches = lib().gqhip_grid_search_applies(n, dim) or lib().gqhip_low_dim_search_applies(n, dim)   # (dims 1-3: the exhaustive route then)
+        if self._cache_calls == 2 and searches and not torch.cuda.is_current_stream_capturing():
             if lib().gqhip_cb_cache_degenerate(out[0], n, dim) == 1:
                 self.no_search = True
                 return None, 0
@@ -471,7 +472,7 @@ def vq_quantize_z(z, emb, dim: int, layout: str, beta: float, legacy: bool, ws: 
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, dev)
-        cptr, cbytes = ws.cache(n, dim, dev) if use_cache else (None, 0)
+        cptr, cbytes = ws.cache(n, dim, dev) if use_cache and not low_dim_search_applies(n, dim) else (None, 0)   # (dims 1-3: that cache serves the Gaussian score only)
     _call("vq_quantize_z_f32", dev, z, emb, idx, zq, loss, B, L, c, dim, n, GQHIP_LAYOUT[layout], beta, bool(legacy), wptr, wbytes,
           cptr, cbytes)
     return idx, zq, loss
@@ -542,7 +543,7 @@ def vq_argmin(z, emb, ws: Optional[Workspace] = None, use_cache: bool = True):
     zq = torch.empty(rows, dim, dtype=torch.float32, device=z.device)
     with torch.cuda.device(z.device):
         wptr, wbytes = ws.get(max(rows, 1), n, dim, z.device)
-        cptr, cbytes = ws.cache(n, dim, z.device) if use_cache else (None, 0)
+        cptr, cbytes = ws.cache(n, dim, z.device) if use_cache and not low_dim_search_applies(n, dim) else (None, 0)
     _call("vq_argmin_f32", z.device, z, emb, idx, zq, dim, rows, n, wptr, wbytes, cptr, cbytes)
     return idx, zq
 
@@ -1703,6 +1704,28 @@ def set_odd_dims(kind: str) -> None:
 def get_odd_dims() -> str:
     k = lib().gqhip_get_odd_dims()
     return next(name for name, v in ODD_DIMS_KINDS.items() if v == k)
+
+
+LOW_DIMS_KINDS = {"exhaustive": 0, "search": 1}
+
+
+def set_low_dims(kind: str) -> None:
+    """Route of the Gaussian arg-max at codebook dims 1-3: "exhaustive" (default): every code scored per row; "search": with 4096
+    to 2^20 codes, a pruned exact search over a cell index kept in the codebook cache (csrc/gq_lowdim.h).  Process-wide; every output
+    is the same bits either way.  The cache size depends on it (a ``Workspace`` asks the library on every call)."""
+    if kind not in LOW_DIMS_KINDS:
+        raise GqHipError(f"unknown low-dims route {kind!r} (expected one of {sorted(LOW_DIMS_KINDS)})")
+    _check(lib().gqhip_set_low_dims(LOW_DIMS_KINDS[kind]), "gqhip_set_low_dims")
+
+
+def get_low_dims() -> str:
+    k = lib().gqhip_get_low_dims()
+    return next(name for name, v in LOW_DIMS_KINDS.items() if v == k)
+
+
+def low_dim_search_applies(n: int, dim: int) -> bool:
+    """Whether a GQ call with ``n`` codes of width ``dim`` and a codebook cache runs the dims 1-3 search under the current selection."""
+    return bool(lib().gqhip_low_dim_search_applies(n, dim))
 
 
 def filter_dim(n: int, dim: int) -> int:
