@@ -2,7 +2,7 @@
 """Are two builds' gfx950 code objects the same device code?  For a host-only change the answer must be yes.
 
     hipcc <the Makefile's FLAGS> -I include --cuda-device-only --no-gpu-bundle-output -c -o A.co gqhip.hip    (in each tree)
-    python tools/devcode_compare.py A.co B.co [A2.co B2.co ...]
+    python tools/devcode_compare.py [--all] A.co B.co [A2.co B2.co ...]      # --all: every differing name, not the first five
 
 Compares, per pair: the set of function symbols (llvm-readelf -sW), every function's disassembly (llvm-objdump -d without
 addresses; a pc-relative reference -- s_getpc_b64 + s_add_u32 -- is compared as the symbol + offset it resolves to, so emission
@@ -93,7 +93,7 @@ def metadata(path):
     return recs
 
 
-def compare(a, b):
+def compare(a, b, shown=5):
     fa, fb = functions(a), functions(b)
     da, db = disassembly(a), disassembly(b)
     oa, ob = objects(a), objects(b)
@@ -104,10 +104,10 @@ def compare(a, b):
     unresolved = sum(t.count("<unresolved") for d in (da, db) for body in d.values() for t in body)
     print(f"{a}\n  vs {b}")
     print(f"  function symbols: {len(fa)} vs {len(fb)}; only in first {sorted(fa - fb)}; only in second {sorted(fb - fa)}")
-    print(f"  instructions compared: {sum(len(da.get(s, [])) for s in fa & fb)}; functions whose disassembly differs: {len(diff_code)} {diff_code[:5]};"
+    print(f"  instructions compared: {sum(len(da.get(s, [])) for s in fa & fb)}; functions whose disassembly differs: {len(diff_code)} {diff_code[:shown]};"
           f" pc-relative references left unresolved: {unresolved}")
-    print(f"  data objects (kernel descriptors, constant tables): {len(oa)} vs {len(ob)}; differing: {len(diff_obj)} {diff_obj[:5]}")
-    print(f"  kernel metadata records: {len(ma)} vs {len(mb)}; differing: {len(diff_meta)} {diff_meta[:5]}")
+    print(f"  data objects (kernel descriptors, constant tables): {len(oa)} vs {len(ob)}; differing: {len(diff_obj)} {diff_obj[:shown]}")
+    print(f"  kernel metadata records: {len(ma)} vs {len(mb)}; differing: {len(diff_meta)} {diff_meta[:shown]}")
     same = (fa == fb and not diff_code and not diff_obj and not diff_meta and not unresolved and len(ma) == len(mb) == len(fa) > 0
             and all(da.get(s) for s in fa))
     print("  IDENTICAL device code" if same else "  DIFFERENT")
@@ -115,7 +115,8 @@ def compare(a, b):
 
 
 if __name__ == "__main__":
-    args = sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    shown = None if "--all" in sys.argv[1:] else 5
     assert args and len(args) % 2 == 0, __doc__
-    results = [compare(args[i], args[i + 1]) for i in range(0, len(args), 2)]   # (every pair is reported)
+    results = [compare(args[i], args[i + 1], shown) for i in range(0, len(args), 2)]   # (every pair is reported)
     sys.exit(0 if all(results) else 1)

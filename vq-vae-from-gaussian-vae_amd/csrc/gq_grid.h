@@ -29,14 +29,13 @@
 //     the largest expansion, pass 2 the reference's arithmetic within the margin --; rows with a non-finite operand or bound, or
 //     behind a non-finite codebook, over ALL codes, everything exact (the re-rank's exhaustive semantics).
 //
-// The index lives in a caller-owned, persistent buffer (the "codebook cache": gqhip_cb_cache_bytes), is validated on EVERY call
-// against a content hash of the codebook the caller passes (the first launch hashes it anyway while it reduces max|cb|), and is
-// rebuilt in-stream by a one-block kernel when the hash -- or the buffer's own stamp -- does not match: a codebook edited in place
-// by any route is seen by the very next call, a fresh or clobbered buffer costs one rebuild.
+// The index lives in the caller's codebook cache, validated on every call and rebuilt in-stream by a one-block kernel when it is not
+// current: the protocol and the builder's steps are gq_index.h's; the layout, the thresholds and grid_sub_of are defined here.
 #pragma once
 #include <type_traits>
 
 #include "gq_common.h"
+#include "gq_index.h"
 #include "gq_rerank.h"
 
 namespace gqhip {
@@ -50,23 +49,9 @@ constexpr int kGridBuildThreads = 1024;
 constexpr int kGridLeafCap = 128;                  // leaf-list capacity of the search (16-bit ids; 48 / 64 / 96 were measured: grid_search_variants.txt)
 constexpr int kGridSubCap = 96;                    // sub-leaf list capacity (a longer list: its best part is visited, then ONE rebuild)
 
-struct GridHdr {                                   // first 4 KiB of the codebook cache
-  unsigned magic;
-  int n, dim;
-  int stale;                                       // set by the first launch when the codebook's hash differs; cleared by the builder
-  int max_sub;                                     // the builder's census: codes in the fullest sub-leaf (> 255: the search hands every row that lists
-                                                   // it to gq_grid_finish_kernel -- a degenerate book; hosts read it through gqhip_cb_cache_degenerate)
-  int pad0[11];
-  float thr[8][8];                                 // per axis: the (cells - 1) ascending thresholds of its coordinate, rest +inf
-  unsigned long long blk_sum[kAbsmaxParts];        // hash of the codebook slice of prep's code block k when the index was built
-  int pad1[432];
-};
-static_assert(sizeof(GridHdr) == 4096, "cache header is 4 KiB");
-
 struct GridLayout {
   int64_t hdr, box1, box2, box3, start, sstart, sbox, scb, sidx, total;   // box1 | box2 | box3 | start are contiguous: one linear copy into LDS
 };
-__host__ __device__ inline int64_t grid_align(int64_t v) { return (v + 255) / 256 * 256; }
 __host__ __device__ inline GridLayout grid_layout(int64_t n, int64_t dim) {
   GridLayout g{};
   int64_t off = 0;
@@ -117,18 +102,11 @@ __device__ __forceinline__ int grid_sub_of(const float (&x)[DIM], const float (*
   return (((l1 * 16 + l2) * 4 + l3) * 4) + l4;
 }
 
-// ---------------------------------------------------------------------------------------------------- builder (one block)
-struct GridBuildParams {
-  const float *cb;
-  char *cache;            // the codebook cache (grid_layout)
-  const WsHeader *hdr;    // this call's workspace header: cbsum[] = the hashes the first launch just computed
-  int n;
-};
-
+// ---------------------------------------------------------------------------------------------------- builder (one block; gq_index.h)
 template <int DIM>
-__global__ __launch_bounds__(kGridBuildThreads) void gq_grid_build_kernel(const GridBuildParams p) {
+__global__ __launch_bounds__(kGridBuildThreads) void gq_grid_build_kernel(const IndexBuildParams p) {
   GridHdr *gh = reinterpret_cast<GridHdr *>(p.cache);
-  if (gh->magic == kGridMagic && gh->n == p.n && gh->dim == DIM && gh->stale == 0) return;   // (block-uniform) the index is current
+  if (index_current(gh, kGridMagic, p.n, DIM)) return;   // (block-uniform)
   const GridLayout L = grid_layout(p.n, DIM);
   float *box1 = reinterpret_cast<float *>(p.cache + L.box1), *box2 = reinterpret_cast<float *>(p.cache + L.box2);
   float *box3 = reinterpret_cast<float *>(p.cache + L.box3);
@@ -138,41 +116,21 @@ __global__ __launch_bounds__(kGridBuildThreads) void gq_grid_build_kernel(const 
   float *scb = reinterpret_cast<float *>(p.cache + L.scb);
   int *sidx = reinterpret_cast<int *>(p.cache + L.sidx);
   constexpr int NT = kGridBuildThreads;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   __shared__ double s_red[NT / 64][2 * DIM];
   __shared__ float s_thr[8][8];
   __shared__ int s_cnt[kGridSubs];
   __shared__ int s_wsum[NT / 64];
 
-  // ---- 1. per-axis mean / deviation -> thresholds at the normal quantiles (any thresholds are valid; these balance a Gaussian book)
-  double acc[2 * DIM];
-#pragma unroll
-  for (int i = 0; i < 2 * DIM; ++i) acc[i] = 0.0;
-  for (int j = tid; j < p.n; j += NT) {
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) {
-      const double v = (double)p.cb[(long)j * DIM + i];
-      acc[i] += v;
-      acc[DIM + i] += v * v;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * DIM; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) s_red[wave][i] = v;
-  }
+  // thresholds at the normal quantiles of each axis' own mean and deviation (these balance a Gaussian book)
+  index_moments<DIM, NT>(p.cb, p.n, tid, s_red);
   __syncthreads();
   if (tid < 64) {
     const int i = tid >> 3, t = tid & 7;
     float th = __builtin_inff();
     if (i < DIM) {
-      double s = 0.0, q = 0.0;
-      for (int w = 0; w < NT / 64; ++w) { s += s_red[w][i]; q += s_red[w][DIM + i]; }
-      const double mean = s / p.n;
-      const double var = q / p.n - mean * mean;
-      const double sd = sqrt(var > 0.0 ? var : 0.0);
+      double mean, sd;
+      index_mean_sd<DIM, NT>(s_red, i, p.n, mean, sd);
       const int cells = grid_cells_of_axis<DIM>(i);
       // N(0,1) quantiles k / cells
       const double q8[7] = {-1.1503493803760079, -0.6744897501960817, -0.3186393639643752, 0.0, 0.3186393639643752,
@@ -183,123 +141,18 @@ __global__ __launch_bounds__(kGridBuildThreads) void gq_grid_build_kernel(const 
     s_thr[i][t] = th;
     gh->thr[i][t] = th;
   }
-  for (int c = tid; c < kGridSubs; c += NT) s_cnt[c] = 0;
-  __syncthreads();
-
-  // ---- 2. sub-leaf histogram
-  auto sub_of_code = [&](int j) {
-    float x[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) x[i] = p.cb[(long)j * DIM + i];
-    return grid_sub_of<DIM>(x, s_thr);
-  };
-  for (int j = tid; j < p.n; j += NT) atomicAdd(&s_cnt[sub_of_code(j)], 1);
-  __syncthreads();
-  {   // census: the fullest sub-leaf (one wave-reduced atomicMax per wave into LDS)
-    __shared__ int s_maxsub;
-    if (tid == 0) s_maxsub = 0;
-    __syncthreads();
-    int mx = 0;
-    for (int c = tid; c < kGridSubs; c += NT) mx = max(mx, s_cnt[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
-    if (lane == 0) atomicMax(&s_maxsub, mx);
-    __syncthreads();
-    if (tid == 0) gh->max_sub = s_maxsub;
-  }
-
-  // ---- 3. exclusive scan of the sub-leaf counters (one leaf = four of them per thread) -> sstart[], start[], cursors in s_cnt
-  {
-    constexpr int PER = kGridSubs / NT;
-    static_assert(kGridSubs % NT == 0 && PER == kGridSubPerLeaf && NT == kGridLeaves, "a thread scans the sub-leaves of one leaf");
-    int loc[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { loc[k] = s_cnt[tid * PER + k]; sum += loc[k]; }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o);
-      if (lane >= o) inc += v;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wsum[w];
-    int run = base + inc - sum;
-    start[tid] = run;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      sstart[tid * PER + k] = run;
-      s_cnt[tid * PER + k] = run;
-      run += loc[k];
-    }
-    if (tid == NT - 1) { start[kGridLeaves] = run; sstart[kGridSubs] = run; }
-  }
-  __syncthreads();
-
-  // ---- 4. scatter the codes into leaf order (order inside a leaf: arbitrary -- the search's result does not depend on it)
-  for (int j = tid; j < p.n; j += NT) {
-    float x[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) x[i] = p.cb[(long)j * DIM + i];
-    const int pos = atomicAdd(&s_cnt[grid_sub_of<DIM>(x, s_thr)], 1);
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) scb[(long)pos * DIM + i] = x[i];
-    sidx[pos] = j;
-  }
-  __threadfence();
-  __syncthreads();
-
-  // ---- 5. tight bounding boxes, bottom-up ([lo | hi]; an empty node: lo = +inf, hi = -inf)
-  const float INF = __builtin_inff();
-  for (int c = tid; c < kGridSubs; c += NT) {
-    float lo[DIM], hi[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { lo[i] = INF; hi[i] = -INF; }
-    const int s = sstart[c], e = sstart[c + 1];
-    for (int j = s; j < e; ++j) {
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        const float v = scb[(long)j * DIM + i];
-        lo[i] = __builtin_fminf(lo[i], v);
-        hi[i] = __builtin_fmaxf(hi[i], v);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { sbox[(long)c * 2 * DIM + i] = lo[i]; sbox[(long)c * 2 * DIM + DIM + i] = hi[i]; }
-  }
-  __threadfence();
-  __syncthreads();
-  auto merge = [&](const float *child, float *parent, int node, int fan) {
-    float lo[DIM], hi[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { lo[i] = INF; hi[i] = -INF; }
-    for (int k = 0; k < fan; ++k) {
-      const float *b = child + (long)(node * fan + k) * 2 * DIM;
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) { lo[i] = __builtin_fminf(lo[i], b[i]); hi[i] = __builtin_fmaxf(hi[i], b[DIM + i]); }
-    }
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { parent[(long)node * 2 * DIM + i] = lo[i]; parent[(long)node * 2 * DIM + DIM + i] = hi[i]; }
-  };
-  if (tid < kGridLeaves) merge(sbox, box3, tid, kGridSubPerLeaf);
-  __threadfence();
-  __syncthreads();
-  if (tid < kGridL2) merge(box3, box2, tid, kGridLeaves / kGridL2);
-  __threadfence();
-  __syncthreads();
-  if (tid < kGridL1) merge(box2, box1, tid, kGridL2 / kGridL1);
-  if (tid < 15) { start[kGridLeaves + 1 + tid] = p.n; sstart[kGridSubs + 1 + tid] = p.n; }   // padding (start: copied to LDS in 16-byte pieces)
-  // ---- 6. stamp: the hashes this call's first launch computed of the very codebook that was just indexed
-  if (tid < kAbsmaxParts) gh->blk_sum[tid] = p.hdr->cbsum[tid];
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    gh->n = p.n;
-    gh->dim = DIM;
-    gh->stale = 0;
-    gh->magic = kGridMagic;
-  }
+  const auto sub_of = [&](const float (&x)[DIM]) { return grid_sub_of<DIM>(x, s_thr); };
+  index_histogram_census<DIM, NT>(p.cb, p.n, tid, s_cnt, sub_of, &gh->max_sub);
+  static_assert(kGridSubs == kIndexBuckets && kGridSubs / NT == kGridSubPerLeaf && NT == kGridLeaves, "a thread scans the sub-leaves of one leaf");
+  index_scan4096<NT, true>(tid, s_cnt, s_wsum, sstart, start);
+  index_scatter<DIM, NT>(p.cb, p.n, tid, s_cnt, sub_of, scb, sidx);
+  index_tight_boxes<DIM, NT>(sstart, scb, sbox, tid);
+  index_merge_boxes<DIM>(sbox, box3, kGridLeaves, kGridSubPerLeaf, tid);
+  index_publish();
+  index_merge_boxes<DIM>(box3, box2, kGridL2, kGridLeaves / kGridL2, tid);
+  index_publish();
+  index_merge_boxes<DIM>(box2, box1, kGridL1, kGridL2 / kGridL1, tid);
+  index_stamp(gh, p.hdr, p.n, DIM, kGridMagic, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- the search
@@ -365,24 +218,6 @@ __device__ __forceinline__ float grid_box_ub(const float (&A)[DIM], const float 
   return grid_box_ub_v<DIM>(A, B, M, lo, hi, concave);
 }
 
-// Reductions over the 16 lanes of a DPP row (= one search group) without an LDS round trip: quad_perm [1,0,3,2], [2,3,0,1],
-// row_half_mirror, row_mirror -- afterwards every lane of the row holds the result.
-// (Written out: from the builtins the compiler makes v_mov_b32_dpp + a canonicalising v_max + the v_max itself per step, twelve
-//  VALU instructions per reduction of a kernel that is VALU-issue bound; the fused form is four.  s_nop 1: the two wait states a
-//  DPP read needs after a VALU write of its source.  Every lane of a row is active or none is, and no source lane is invalid for
-//  these four patterns.)
-__device__ __forceinline__ float row16_max(float v) {
-  asm("s_nop 1\n\t"
-      "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
-      "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf"
-      : "+v"(v));
-  return v;
-}
 // max of two values that are never NaN here (rows with non-finite operands or bounds do not get this far): one v_med3_f32 instead
 // of the canonicalise-then-max pair that fmaxf becomes under IEEE mode
 __device__ __forceinline__ float fmax_nn(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, __builtin_inff()); }

@@ -6,7 +6,7 @@
 // margin of a row's best are a few hundred at dim 1 and a handful at dims 2 and 3, so the reference's arithmetic
 // is needed for those, not for 65 536.
 //
-// Index (the caller's codebook cache, validated and rebuilt as gq_grid.h's): the codes bucketed into 4096 CELLS by per-axis
+// Index (the caller's codebook cache; its protocol and the builder's steps: gq_index.h): the codes bucketed into 4096 CELLS by per-axis
 // thresholds at the normal quantiles of the book's own mean and deviation -- 4096 at dim 1, 64 x 64 at dim 2, 16 x 16 x 16 at dim 3 --
 // each cell with the TIGHT bounding box of its members (at dim 1: the interval [min, max] of a run of the value-ordered book) and
 // their original indices; 256 COARSE nodes of 16 neighbouring cells each (16 consecutive cells, 4 x 4, 2 x 2 x 4), whose boxes
@@ -40,6 +40,7 @@
 #pragma once
 #include "gq_common.h"
 #include "gq_grid.h"
+#include "gq_index.h"
 #include "gq_rerank.h"
 
 namespace gqhip {
@@ -72,9 +73,8 @@ __host__ __device__ inline LowLayout low_layout(int64_t n, int64_t dim) {
 }
 
 // ---------------------------------------------------------------------------------------------------- codebook hash (256 blocks)
-// What gq_prep_kernel's code blocks do on the dim-4 route, for a call whose rows are prepared by prep_plain_kernel: max |cb| (NaN
-// reads as +inf) and the content hash of this block's slice into the workspace header, and the cache's `stale` word set when the
-// slice's hash differs from the one the index was built from.
+// What gq_prep_kernel's code blocks do on the dim-4 route, for a call whose rows are prepared by prep_plain_kernel (gq_index.h:
+// cb_hash_block).
 struct LowHashParams {
   const float *cb;
   WsHeader *hdr;
@@ -82,33 +82,10 @@ struct LowHashParams {
   long count;             // n * dim
 };
 __global__ __launch_bounds__(256) void gq_low_hash_kernel(const LowHashParams p) {
-  const int tid = threadIdx.x, cbk = blockIdx.x;
-  float amax = 0.0f;
-  unsigned long long hsum = 0ull;
-  for (long i = (long)cbk * 256 + tid; i < p.count; i += (long)kLowHashBlocks * 256) {
-    const float x = p.cb[i];
-    const float a = fabsf(x);
-    amax = (a != a) ? __builtin_inff() : __builtin_fmaxf(amax, a);
-    hsum += cb_hash_term(x, i);
-  }
-  __shared__ float s_amax[4];
-  __shared__ unsigned long long s_hsum[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    amax = __builtin_fmaxf(amax, __shfl_xor(amax, o));
-    hsum += __shfl_xor(hsum, o);
-  }
-  if ((tid & 63) == 0) { s_amax[tid >> 6] = amax; s_hsum[tid >> 6] = hsum; }
-  __syncthreads();
-  if (tid == 0) {
-    p.hdr->absmax_part[cbk] = __builtin_fmaxf(__builtin_fmaxf(s_amax[0], s_amax[1]), __builtin_fmaxf(s_amax[2], s_amax[3]));
-    const unsigned long long h = s_hsum[0] + s_hsum[1] + s_hsum[2] + s_hsum[3];
-    p.hdr->cbsum[cbk] = h;
-    if (p.cache->blk_sum[cbk] != h) p.cache->stale = 1;
-  }
+  cb_hash_block(p.cb, p.count, blockIdx.x, kLowHashBlocks, threadIdx.x, p.hdr, p.cache->blk_sum, &p.cache->stale);
 }
 
-// ---------------------------------------------------------------------------------------------------- builder (one block)
+// ---------------------------------------------------------------------------------------------------- builder (one block; gq_index.h)
 // N(0, 1) quantile (P. J. Acklam's rational approximation, relative error 1e-9): any ascending thresholds are valid, these balance a
 // Gaussian book.
 __device__ inline double low_norm_quantile(double pr) {
@@ -152,170 +129,40 @@ __device__ __forceinline__ int low_cell_of(const float (&x)[DIM], const float *t
   else return ((((c[0] >> 1) * 8 + (c[1] >> 1)) * 4 + (c[2] >> 2)) * 16) + (c[0] & 1) * 8 + (c[1] & 1) * 4 + (c[2] & 3);
 }
 
-struct LowBuildParams {
-  const float *cb;
-  char *cache;            // the codebook cache (low_layout)
-  const WsHeader *hdr;    // this call's workspace header: cbsum[] = the hashes gq_low_hash_kernel just computed
-  int n;
-};
-
 template <int DIM>
-__global__ __launch_bounds__(kLowBuildThreads) void gq_low_build_kernel(const LowBuildParams p) {
+__global__ __launch_bounds__(kLowBuildThreads) void gq_low_build_kernel(const IndexBuildParams p) {
   GridHdr *gh = reinterpret_cast<GridHdr *>(p.cache);
-  if (gh->magic == kLowMagic && gh->n == p.n && gh->dim == DIM && gh->stale == 0) return;   // (block-uniform) the index is current
+  if (index_current(gh, kLowMagic, p.n, DIM)) return;   // (block-uniform)
   const LowLayout L = low_layout(p.n, DIM);
   float *cbox = reinterpret_cast<float *>(p.cache + L.cbox), *box = reinterpret_cast<float *>(p.cache + L.box);
   int *start = reinterpret_cast<int *>(p.cache + L.start);
   float *scb = reinterpret_cast<float *>(p.cache + L.scb);
   int *sidx = reinterpret_cast<int *>(p.cache + L.sidx);
   constexpr int NT = kLowBuildThreads, C = low_axis_cells(DIM);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   __shared__ double s_red[NT / 64][2 * DIM];
   __shared__ double s_ms[2 * DIM];
   __shared__ float s_thr[DIM * C];
   __shared__ int s_cnt[kLowCells];
   __shared__ int s_wsum[NT / 64];
-  __shared__ int s_max;
 
-  // ---- 1. per-axis mean / deviation -> thresholds at the normal quantiles k / C
-  double acc[2 * DIM];
-#pragma unroll
-  for (int i = 0; i < 2 * DIM; ++i) acc[i] = 0.0;
-  for (int j = tid; j < p.n; j += NT) {
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) {
-      const double v = (double)p.cb[(long)j * DIM + i];
-      acc[i] += v;
-      acc[DIM + i] += v * v;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * DIM; ++i) {
-    double v = acc[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) s_red[wave][i] = v;
-  }
-  if (tid == 0) s_max = 0;
+  // thresholds at the normal quantiles k / C of each axis' own mean and deviation
+  index_moments<DIM, NT>(p.cb, p.n, tid, s_red);
   __syncthreads();
-  if (tid < DIM) {
-    double s = 0.0, q = 0.0;
-    for (int w = 0; w < NT / 64; ++w) { s += s_red[w][tid]; q += s_red[w][DIM + tid]; }
-    const double mean = s / p.n;
-    const double var = q / p.n - mean * mean;
-    s_ms[tid] = mean;
-    s_ms[DIM + tid] = sqrt(var > 0.0 ? var : 0.0);
-  }
+  if (tid < DIM) index_mean_sd<DIM, NT>(s_red, tid, p.n, s_ms[tid], s_ms[DIM + tid]);
   __syncthreads();
   for (int k = tid; k < DIM * C; k += NT) {
     const int i = k / C, t = k % C;
     s_thr[k] = t < C - 1 ? (float)(s_ms[i] + s_ms[DIM + i] * low_norm_quantile((double)(t + 1) / C)) : __builtin_inff();
   }
-  for (int c = tid; c < kLowCells; c += NT) s_cnt[c] = 0;
-  __syncthreads();
-
-  // ---- 2. cell histogram, and the census of the fullest cell
-  auto cell_of_code = [&](int j, float (&x)[DIM]) {
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) x[i] = p.cb[(long)j * DIM + i];
-    return low_cell_of<DIM>(x, s_thr);
-  };
-  for (int j = tid; j < p.n; j += NT) {
-    float x[DIM];
-    atomicAdd(&s_cnt[cell_of_code(j, x)], 1);
-  }
-  __syncthreads();
-  {
-    int mx = 0;
-    for (int c = tid; c < kLowCells; c += NT) mx = max(mx, s_cnt[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
-    if (lane == 0) atomicMax(&s_max, mx);
-    __syncthreads();
-    if (tid == 0) gh->max_sub = s_max;
-  }
-
-  // ---- 3. exclusive scan of the cell counters (four per thread) -> start[], cursors in s_cnt
-  {
-    constexpr int PER = kLowCells / NT;
-    int loc[PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) { loc[k] = s_cnt[tid * PER + k]; sum += loc[k]; }
-    int inc = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(inc, o);
-      if (lane >= o) inc += v;
-    }
-    if (lane == 63) s_wsum[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wsum[w];
-    int run = base + inc - sum;
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-      start[tid * PER + k] = run;
-      s_cnt[tid * PER + k] = run;
-      run += loc[k];
-    }
-    if (tid == NT - 1)
-      for (int k = 0; k < 16; ++k) start[kLowCells + k] = run;     // (= n; the padding is never a cell)
-  }
-  __syncthreads();
-
-  // ---- 4. scatter the codes into cell order (order inside a cell: arbitrary -- ties are broken by the original index)
-  for (int j = tid; j < p.n; j += NT) {
-    float x[DIM];
-    const int pos = atomicAdd(&s_cnt[cell_of_code(j, x)], 1);
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) scb[(long)pos * DIM + i] = x[i];
-    sidx[pos] = j;
-  }
-  __threadfence();
-  __syncthreads();
-
-  // ---- 5. tight bounding boxes ([lo | hi]; an empty cell: lo = +inf, hi = -inf), then the coarse nodes'
-  const float INF = __builtin_inff();
-  for (int c = tid; c < kLowCells; c += NT) {
-    float lo[DIM], hi[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { lo[i] = INF; hi[i] = -INF; }
-    const int s = start[c], e = start[c + 1];
-    for (int j = s; j < e; ++j) {
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        const float v = scb[(long)j * DIM + i];
-        lo[i] = __builtin_fminf(lo[i], v);
-        hi[i] = __builtin_fmaxf(hi[i], v);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { box[(long)c * 2 * DIM + i] = lo[i]; box[(long)c * 2 * DIM + DIM + i] = hi[i]; }
-  }
-  __threadfence();
-  __syncthreads();
-  if (tid < kLowCoarse) {
-    float lo[DIM], hi[DIM];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { lo[i] = INF; hi[i] = -INF; }
-    for (int k = 0; k < kLowFan; ++k) {
-      const float *b = box + (long)(tid * kLowFan + k) * 2 * DIM;
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) { lo[i] = __builtin_fminf(lo[i], b[i]); hi[i] = __builtin_fmaxf(hi[i], b[DIM + i]); }
-    }
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) { cbox[(long)tid * 2 * DIM + i] = lo[i]; cbox[(long)tid * 2 * DIM + DIM + i] = hi[i]; }
-  }
-  // ---- 6. stamp: the hashes this call computed of the very codebook that was just indexed
-  if (tid < kAbsmaxParts) gh->blk_sum[tid] = p.hdr->cbsum[tid];
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    gh->n = p.n;
-    gh->dim = DIM;
-    gh->stale = 0;
-    gh->magic = kLowMagic;
-  }
+  const auto cell_of = [&](const float (&x)[DIM]) { return low_cell_of<DIM>(x, s_thr); };
+  index_histogram_census<DIM, NT>(p.cb, p.n, tid, s_cnt, cell_of, &gh->max_sub);
+  static_assert(kLowCells == kIndexBuckets, "the builder's bucket count");
+  index_scan4096<NT, false>(tid, s_cnt, s_wsum, start, nullptr);
+  index_scatter<DIM, NT>(p.cb, p.n, tid, s_cnt, cell_of, scb, sidx);
+  index_tight_boxes<DIM, NT>(start, scb, box, tid);
+  index_merge_boxes<DIM>(box, cbox, kLowCoarse, kLowFan, tid);
+  index_stamp(gh, p.hdr, p.n, DIM, kLowMagic, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------- the search
@@ -332,20 +179,6 @@ struct LowParams {
   int stats;
   OutMap omap;
 };
-
-// max over the 16 lanes of a DPP row (gq_grid.h:row16_max; volatile: it stays where the row's lanes have converged)
-__device__ __forceinline__ float low_row16_max(float v) {
-  asm volatile("s_nop 1\n\t"
-               "v_max_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\t"
-               "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\t"
-               "v_max_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-               "s_nop 1\n\t"
-               "v_max_f32_dpp %0, %0, %0 row_mirror row_mask:0xf bank_mask:0xf"
-               : "+v"(v));
-  return v;
-}
 
 template <int DIM>
 __global__ __launch_bounds__(kLowThreads) void gq_low_search_kernel(const LowParams p) {
@@ -444,7 +277,7 @@ __global__ __launch_bounds__(kLowThreads) void gq_low_search_kernel(const LowPar
           ++exact_n;
         }
       }
-      F = fmax_nn(F, low_row16_max(fl));
+      F = fmax_nn(F, row16_max<true>(fl));
       thr = thr_of(F);
     };
     auto visit_cell = [&](int cell, bool exact) {
@@ -478,7 +311,7 @@ __global__ __launch_bounds__(kLowThreads) void gq_low_search_kernel(const LowPar
         return grid_box_ub_v<DIM>(cA, cB, cM, lo, hi, concave);
       };
       {
-        const float ubg = low_row16_max(ubl);
+        const float ubg = row16_max<true>(ubl);
         const unsigned who = group_bits(ubl == ubg && ubg > NEG_INF);
         if (who == 0u) {
           hand = true;                                  // no node with a bound (cannot happen behind a finite book): all codes
@@ -486,7 +319,7 @@ __global__ __launch_bounds__(kLowThreads) void gq_low_search_kernel(const LowPar
           const int l = __builtin_ctz(who);
           const int node = __shfl(kb, gshift + l) * GROUP + l;
           const float cu = cell_ub(node * kLowFan + sub);
-          const float cg = low_row16_max(cu);
+          const float cg = row16_max<true>(cu);
           const unsigned cw = group_bits(cu == cg && cg > NEG_INF);
           if (cw == 0u) hand = true;
           else visit_cell(node * kLowFan + __builtin_ctz(cw), false);

@@ -18,6 +18,7 @@
 #pragma once
 #include "gq_common.h"
 #include "gq_filter_bf16.h"
+#include "gq_index.h"
 #include "gq_rerank.h"
 
 namespace gqhip {
@@ -273,33 +274,17 @@ __global__ __launch_bounds__(256) void gq_prep_kernel(const PrepParams p) {
         }
       }
       }   // pass
+      // the image's norm bound beside the words every code block leaves (gq_index.h: cb_hash_store, whose barrier orders s_r2)
+      __shared__ float s_r2[4];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) r2max = __builtin_fmaxf(r2max, __shfl_xor(r2max, o));
+      if ((tid & 63) == 0) s_r2[tid >> 6] = r2max;
+      cb_hash_store(amax, hsum, cbk, tid, p.hdr, p.cache_sums, p.cache_stale);
+      if (tid == 0) p.hdr->r2_part[cbk] = __builtin_fmaxf(__builtin_fmaxf(s_r2[0], s_r2[1]), __builtin_fmaxf(s_r2[2], s_r2[3]));
     } else {
       // no operand image in this call (fp32 filter; grid search, gq_grid.h): max |cb| and the content hash of this block's slice
-      const long count = (long)p.n * DIM;
-      for (long i = (long)cbk * 256 + tid; i < count; i += (long)kPrepCodeBlocks * 256) {
-        const float x = p.cb[i];
-        const float a = fabsf(x);
-        amax = (a != a) ? __builtin_inff() : __builtin_fmaxf(amax, a);
-        hsum += cb_hash_term(x, i);
-      }
-    }
-    __shared__ float s_amax[4], s_r2[4];
-    __shared__ unsigned long long s_hsum[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      amax = __builtin_fmaxf(amax, __shfl_xor(amax, o));
-      r2max = __builtin_fmaxf(r2max, __shfl_xor(r2max, o));
-      hsum += __shfl_xor(hsum, o);
-    }
-    if ((tid & 63) == 0) { s_amax[tid >> 6] = amax; s_r2[tid >> 6] = r2max; s_hsum[tid >> 6] = hsum; }
-    __syncthreads();
-    if (tid == 0) {
-      p.hdr->absmax_part[cbk] = __builtin_fmaxf(__builtin_fmaxf(s_amax[0], s_amax[1]), __builtin_fmaxf(s_amax[2], s_amax[3]));
-      p.hdr->r2_part[cbk] = __builtin_fmaxf(__builtin_fmaxf(s_r2[0], s_r2[1]), __builtin_fmaxf(s_r2[2], s_r2[3]));
-      const unsigned long long h = s_hsum[0] + s_hsum[1] + s_hsum[2] + s_hsum[3];
-      p.hdr->cbsum[cbk] = h;
-      // grid index (gq_grid.h): built from other bytes -> rebuilt, by the one-block kernel that follows, before its use
-      if (p.cache_sums && p.cache_stale && p.cache_sums[cbk] != h) *p.cache_stale = 1;
+      if (tid == 0) p.hdr->r2_part[cbk] = 0.0f;
+      cb_hash_block(p.cb, (long)p.n * DIM, cbk, kPrepCodeBlocks, tid, p.hdr, p.cache_sums, p.cache_stale);
     }
     return;
   }

@@ -122,14 +122,6 @@ int64_t padded_dim(int64_t dim) {
 // Route of the Gaussian arg-max at dims 1-3 (gqhip.h: gqhip_set_low_dims): under SEARCH a call with a codebook cache runs the pruned
 // exact search of gq_lowdim.h, whose winner is decided by the reference's arithmetic as on the exhaustive route: never another index.
 std::atomic<int> g_low_dims{env().low_dims};
-int64_t low_cache_bytes(int64_t n, int64_t dim) {
-  if (g_low_dims.load(std::memory_order_relaxed) != GQHIP_LOW_DIMS_SEARCH || dim < 1 || dim > 3 || n < 4096 || n > (1 << 20)) return 0;
-  return low_layout(n, dim).total;
-}
-bool low_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes) {
-  const int64_t need = low_cache_bytes(n, dim);
-  return need > 0 && cache && cache_bytes >= need;
-}
 
 // ---- launch plan: identical on the sizing and the launching side -----------
 struct Plan {
@@ -187,14 +179,6 @@ RerankBound rerank_bound(const Plan &pl, int mode, int64_t dim) {
 bool grid_dim_enabled(int64_t dim) {
   const int g = env().grid;
   return g == 48 ? (dim == 4 || dim == 8) : (g != 0 && dim == g);
-}
-int64_t grid_cache_bytes(int64_t n, int64_t dim) {
-  if (!grid_dim_enabled(dim) || n < 16384 || n > (1 << 20)) return 0;
-  return grid_layout(n, dim).total;
-}
-bool grid_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes) {
-  const int64_t need = grid_cache_bytes(n, dim);
-  return need > 0 && cache && cache_bytes >= need && filter_kind() == GQHIP_FILTER_AUTO;
 }
 
 Plan plan_at(int64_t rows, int64_t n, int64_t dim) {
@@ -279,6 +263,34 @@ inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 int64_t image_cache_bytes(const Plan &pl, int64_t dim) {
   if (env().img_cache == 0 || (dim != 8 && dim != 16 && dim != 32) || filter_kind() != GQHIP_FILTER_AUTO || !pl.f16) return 0;
   return (int64_t)sizeof(GridHdr) + align256((int64_t)(pl.tiles_total + pl.ct) * (dim / 8) * 64 * 16);
+}
+
+// The one answer to "which codebook cache does (n, dim) keep, and how many bytes": the index of the dim-4 / 8 search first, then the
+// index of the dims 1-3 search, then the fp16 image.  An index also names its stamp and the bucket size beyond which it is degenerate.
+// (Whether a search RUNS is the caller's to add: run_argmax wants the caller's buffer, the dim-4 / 8 search the AUTO filter besides.)
+struct CacheUse {
+  enum Kind { kNone, kImage, kGrid, kLow } kind;
+  int64_t bytes;
+  unsigned magic;
+  int degenerate_above;
+  bool fits(const void *cache, int64_t cache_bytes) const { return kind != kNone && cache && cache_bytes >= bytes; }
+};
+// `pl`: a plan of (n, dim) the caller already has (any serves: what the image depends on does not depend on rows)
+CacheUse cache_use(int64_t n, int64_t dim, const Plan *pl = nullptr) {
+  if (grid_dim_enabled(dim) && n >= 16384 && n <= (1 << 20)) return {CacheUse::kGrid, grid_layout(n, dim).total, kGridMagic, 255};
+  if (g_low_dims.load(std::memory_order_relaxed) == GQHIP_LOW_DIMS_SEARCH && dim >= 1 && dim <= 3 && n >= 4096 && n <= (1 << 20))
+    return {CacheUse::kLow, low_layout(n, dim).total, kLowMagic, low_cell_cap(n)};
+  if (n < 1 || dim < 1 || dim > kMaxDim) return {CacheUse::kNone, 0, 0u, 0};
+  const int64_t img = image_cache_bytes(pl ? *pl : make_plan(65536, n, dim), dim);
+  return {img > 0 ? CacheUse::kImage : CacheUse::kNone, img, 0u, 0};
+}
+bool grid_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes, const Plan &pl) {
+  const CacheUse u = cache_use(n, dim, &pl);
+  return u.kind == CacheUse::kGrid && u.fits(cache, cache_bytes) && filter_kind() == GQHIP_FILTER_AUTO;
+}
+bool low_applies(int64_t n, int64_t dim, const void *cache, int64_t cache_bytes, const Plan &pl) {
+  const CacheUse u = cache_use(n, dim, &pl);
+  return u.kind == CacheUse::kLow && u.fits(cache, cache_bytes);
 }
 
 struct WsLayout {
@@ -462,7 +474,7 @@ RerankKernel rerank_kernel(int64_t dim, int gt, int rec_sets) {
 }
 
 struct GridKernels {
-  void (*build)(GridBuildParams);
+  void (*build)(IndexBuildParams);
   void (*search)(GridParams);
   void (*finish)(GridParams);
 };
@@ -607,6 +619,13 @@ int run_exhaustive(const Call &c) {
 // Dims 1-3 under GQHIP_LOW_DIMS_SEARCH with a codebook cache (GQ): rows as on the exhaustive path -> codebook hash and max|cb| ->
 // index builder (exits unless the hash or the stamp says the cache is stale) -> pruned exact search (gq_lowdim.h) -> the rows it
 // listed, through gq_exhaustive_kernel itself (exits at once when there are none).
+// the second launch of both searches: one block that exits unless the hash or the stamp says the index is not current
+int launch_index_builder(const Call &c, void (*build)(IndexBuildParams), int threads) {
+  IndexBuildParams bp{};
+  bp.cb = c.cb; bp.cache = static_cast<char *>(c.cb_cache); bp.hdr = c.hdr; bp.n = (int)c.n;
+  return launch(build, dim3(1), dim3((unsigned)threads), 0, c.st, bp);
+}
+
 int run_low(const Call &c) {
   int rc = run_prep_plain<kModeGQ>(c);
   if (rc != GQHIP_OK) return rc;
@@ -614,10 +633,8 @@ int run_low(const Call &c) {
   hp.cb = c.cb; hp.hdr = c.hdr; hp.cache = static_cast<GridHdr *>(c.cb_cache); hp.count = (long)(c.n * c.dim);
   rc = launch(gq_low_hash_kernel, dim3(kLowHashBlocks), dim3(256), 0, c.st, hp);
   if (rc != GQHIP_OK) return rc;
-  LowBuildParams bp{};
-  bp.cb = c.cb; bp.cache = static_cast<char *>(c.cb_cache); bp.hdr = c.hdr; bp.n = (int)c.n;
   const auto build = c.dim == 1 ? gq_low_build_kernel<1> : (c.dim == 2 ? gq_low_build_kernel<2> : gq_low_build_kernel<3>);
-  rc = launch(build, dim3(1), dim3(kLowBuildThreads), 0, c.st, bp);
+  rc = launch_index_builder(c, build, kLowBuildThreads);
   if (rc != GQHIP_OK) return rc;
   RerankParams rp = rerank_params<kModeGQ>(c);
   rp.all_rows = 0;                                  // the finish launch: the listed rows only
@@ -643,9 +660,7 @@ int run_grid(const Call &c) {
   const dim3 pgrid((unsigned)(pp.row_blocks + kPrepCodeBlocks));
   int rc = launch(prep_kernel<MODE>(c.from_z(), c.dim, false, false), pgrid, dim3(256), 0, c.st, pp);
   if (rc != GQHIP_OK) return rc;
-  GridBuildParams bp{};
-  bp.cb = c.cb; bp.cache = static_cast<char *>(c.cb_cache); bp.hdr = c.hdr; bp.n = (int)c.n;
-  rc = launch(k.build, dim3(1), dim3(kGridBuildThreads), 0, c.st, bp);
+  rc = launch_index_builder(c, k.build, kGridBuildThreads);
   if (rc != GQHIP_OK) return rc;
   GridParams gp{};
   gp.mu = c.r_mu; gp.sd = c.r_sd; gp.lsd = c.r_lsd; gp.rowsum = pp.rowsum; gp.coef = pp.coef; gp.cb = c.cb;
@@ -762,14 +777,14 @@ int run_argmax(const PrepInput &in, const float *mu, const float *sd, const floa
   c.r_lsd = from_z ? c.ws_lsd : (MODE == kModeGQ ? (lsd ? lsd : (pl.mfma ? c.ws_lsd : nullptr)) : nullptr);
   if (!pl.mfma) {     // the one place that chooses between the exhaustive kernel and the low-dim search
     if constexpr (MODE == kModeGQ)
-      if (low_applies(n, dim, cb_cache, cb_cache_bytes)) return run_low(c);
+      if (low_applies(n, dim, cb_cache, cb_cache_bytes, pl)) return run_low(c);
     return run_exhaustive<MODE>(c);
   }
   if (pl.padded) {
     if (in.stats_done) *in.stats_done = false;     // GQ2's statistics: the launch of their own the exhaustive path has
     return run_padded<MODE>(c);
   }
-  const bool grid = grid_applies(n, dim, cb_cache, cb_cache_bytes);
+  const bool grid = grid_applies(n, dim, cb_cache, cb_cache_bytes, pl);
   const bool stats_in_rerank = MODE == kModeGQ && in.want_kl2 && !grid;
   if (in.stats_done) *in.stats_done = stats_in_rerank;
   return grid ? run_grid<MODE>(c) : run_dense<MODE>(c, stats_in_rerank);
@@ -883,7 +898,7 @@ int gqhip_set_low_dims(int kind) {
 
 int gqhip_get_low_dims(void) { return g_low_dims.load(std::memory_order_relaxed); }
 
-int gqhip_low_dim_search_applies(int64_t n, int64_t dim) { return low_cache_bytes(n, dim) > 0; }
+int gqhip_low_dim_search_applies(int64_t n, int64_t dim) { return cache_use(n, dim).kind == CacheUse::kLow; }
 
 int64_t gqhip_filter_dim(int64_t n, int64_t dim) {
   if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
@@ -901,21 +916,22 @@ int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host) {
   return GQHIP_OK;
 }
 
-int gqhip_grid_search_applies(int64_t n, int64_t dim) { return grid_cache_bytes(n, dim) > 0 && filter_kind() == GQHIP_FILTER_AUTO; }
+int gqhip_grid_search_applies(int64_t n, int64_t dim) {
+  return cache_use(n, dim).kind == CacheUse::kGrid && filter_kind() == GQHIP_FILTER_AUTO;
+}
 
 int gqhip_cb_cache_degenerate(const void *cb_cache, int64_t n, int64_t dim) {
-  const bool low = low_cache_bytes(n, dim) > 0;
-  if (!cb_cache || (!low && grid_cache_bytes(n, dim) <= 0)) return -1;
+  const CacheUse use = cache_use(n, dim);
+  if (!cb_cache || (use.kind != CacheUse::kGrid && use.kind != CacheUse::kLow)) return -1;
   GridHdr g;
   if (hipMemcpy(&g, cb_cache, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) { (void)check_launch(); return -1; }
-  if (g.magic != (low ? kLowMagic : kGridMagic) || g.n != (int)n || g.dim != (int)dim || g.stale != 0) return -1;
-  return g.max_sub > (low ? low_cell_cap(n) : 255) ? 1 : 0;
+  if (!index_current(&g, use.magic, (int)n, (int)dim)) return -1;
+  return g.max_sub > use.degenerate_above ? 1 : 0;
 }
 
 int64_t gqhip_cb_cache_bytes(int64_t n, int64_t dim) {
   if (n < 1 || dim < 1 || dim > kMaxDim) return -1;
-  const int64_t g = grid_cache_bytes(n, dim), low = low_cache_bytes(n, dim);
-  return g > 0 ? g : (low > 0 ? low : image_cache_bytes(make_plan(65536, n, dim), dim));
+  return cache_use(n, dim).bytes;
 }
 
 int64_t gqhip_workspace_bytes(int64_t rows, int64_t n, int64_t dim) {
@@ -1926,7 +1942,7 @@ int gqhip_debug_grid(const void *workspace, const void *cb_cache, int64_t *out4_
   if (cb_cache) {
     GridHdr g;
     if (hipMemcpy(&g, cb_cache, sizeof(g), hipMemcpyDeviceToHost) != hipSuccess) return check_launch();
-    out4_host[3] = (g.magic == kGridMagic && g.stale == 0) ? 1 : 0;
+    out4_host[3] = index_current(&g, kGridMagic, g.n, g.dim) ? 1 : 0;   // (this query knows neither n nor dim: the stamp and `stale` decide)
   }
   return GQHIP_OK;
 }
