@@ -122,7 +122,7 @@ int gqhip_get_filter(void);
  * decides an index -- scores with the TRUE dim, so the indices, zhat and every other output are the same bits either way
  * (DESIGN.md section 3.1).  Such a call keeps nothing in the codebook cache (gqhip_cb_cache_bytes stays 0 at these dims): the padded
  * operand image is rebuilt in the workspace on every call.  Dims 1..3 and 33..64 stay on the exhaustive kernel under either value
- * (dims 1..3 have a switch of their own: gqhip_set_low_dims below).
+ * (they have switches of their own: gqhip_set_low_dims and gqhip_set_wide_dims below).
  * Process-wide; initial value from the environment (GQHIP_ODD_DIMS=padded).  The workspace size depends on it: query
  * gqhip_workspace_bytes after changing it.  An unknown kind: GQHIP_ERR_INVALID_ARG, the selection stays.  (No reference counterpart.) */
 #define GQHIP_ODD_DIMS_EXHAUSTIVE 0
@@ -130,8 +130,26 @@ int gqhip_get_filter(void);
 int gqhip_set_odd_dims(int kind);
 int gqhip_get_odd_dims(void);
 /* Diagnostic: the dim the filter of the fused arg-max runs at for (n, dim) under the current selections -- `dim` itself at 4, 8,
- * 16, 32; 8, 16 or 32 for a dim the PADDED route serves; 0 where the exhaustive kernel runs; -1: n < 1 or dim outside 1..64. */
+ * 16, 32; 8, 16 or 32 for a dim the PADDED route serves; 64 for dims 33..64 where the wide route (gqhip_set_wide_dims below) runs;
+ * 0 where the exhaustive kernel runs; -1: n < 1 or dim outside 1..64. */
 int64_t gqhip_filter_dim(int64_t n, int64_t dim);
+
+/* Route of the codebook dims 33..64 in gq_argmax_f32 / gq_quantize_z_f32 / gq_quantize_z_gauss_f32 / vq_argmin_f32 /
+ * vq_quantize_z_f32 (and the train forwards that call the last two).  EXHAUSTIVE (default): one block per row scores every code with
+ * the reference's arithmetic.  FILTER: with the filter selection AUTO (the fp16 main product) the filter and the exact re-rank run at
+ * dim 64 -- 128 fp16 products per value, eight v_mfma_f32_32x32x16_f16 per tile.  Dim 64 itself: prep -> filter -> re-rank, as at
+ * dims 8 / 16 / 32.  Dims 33..63: rows and codebook are zero-padded to 64 in the workspace first (mu 0, sd 1, log sd 0, code 0 in the
+ * pad columns), exactly as gqhip_set_odd_dims(PADDED) does below 32, and the re-rank -- which alone decides an index -- scores, scans
+ * and stores with the TRUE dim: the indices, zhat and every other output are the same bits either way.
+ * What keeps the exhaustive kernel under either value: the filter selections FP32 / BF16 / MIXED (no dim-64 kernel of theirs:
+ * gqhip_filter_dim says 0), a codebook beyond the split cap, gq_scores_f32's own route.  Nothing is kept in the codebook cache at these
+ * dims (gqhip_cb_cache_bytes and gqhip_grid_search_applies stay 0): the operand image is rebuilt in the workspace on every call.
+ * Process-wide; initial value from the environment (GQHIP_WIDE_DIMS=filter).  The workspace size depends on it: query
+ * gqhip_workspace_bytes after changing it.  An unknown kind: GQHIP_ERR_INVALID_ARG, the selection stays.  (No reference counterpart.) */
+#define GQHIP_WIDE_DIMS_EXHAUSTIVE 0   /* default */
+#define GQHIP_WIDE_DIMS_FILTER 1
+int gqhip_set_wide_dims(int kind);
+int gqhip_get_wide_dims(void);
 
 /* Route of the codebook dims 1..3 in gq_argmax_f32 / gq_quantize_z_f32 / gq_quantize_z_gauss_f32 (the Gaussian score only).
  * EXHAUSTIVE (default): one block per row scores every code with the reference's arithmetic.  SEARCH: a call with 4096 <= n <= 2^20
@@ -155,7 +173,8 @@ int gqhip_low_dim_search_applies(int64_t n, int64_t dim);
 
 /* Diagnostics: launch plan and workspace layout of the fused arg-max for a shape.  out8_host = { byte offset of the
  * candidate records, code splits, tiles per candidate group, tiles per split, filter kernel the plan selects (0 fp32 MFMA, 1 split-bf16, 2 fp16 + fp8, 3 fp16 main product: the default at dims 8 / 16 / 32), coefficient of the
- * filter error bound (E_f = coeff * 2^-24 * T), row tiles per wave, waves per filter block }.
+ * filter error bound (E_f = coeff * 2^-24 * T; fp16 main product: 16700 at filter dims 8 / 16 / 32 -- up to 64 products per value --,
+ * 17000 at the wide route's filter dim 64 -- 128 products), row tiles per wave, waves per filter block }.
  * The records are 16 bytes per (row, record set): { fp32 m1; fp16 gaps m1 - m2..m4, rounded towards zero; three 16-bit
  * half-group ids relative to the set's split } (csrc/gq_common.h:Rec); "code splits" counts record sets. */
 int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host);
@@ -226,7 +245,8 @@ int gq_scores_f32(const float *mu, const float *sd, const float *cb, float *out,
  *           gqhip_set_odd_dims(GQHIP_ODD_DIMS_PADDED) selects that -- prep of the padded operands, filter, re-rank, the same
  *           indices; 1..3 with a codebook cache run the pruned search of csrc/gq_lowdim.h once
  *           gqhip_set_low_dims(GQHIP_LOW_DIMS_SEARCH) selects that -- five launches, the builder and the finish exit at once in
- *           the common case, the same indices; every other case exhaustive).
+ *           the common case, the same indices; 33..64 run the dim-64 filter + re-rank once
+ *           gqhip_set_wide_dims(GQHIP_WIDE_DIMS_FILTER) selects that, the same indices; every other case exhaustive).
  * Dim 4 with a codebook cache: prep -> index check -> pruned exact search -> finish of the rows it left undecided
  * (csrc/gq_grid.h; four launches, the second and fourth exit at once in the common case).
  * Three launches on `stream` for the other MFMA dims: prep (operand images, bound sums,

@@ -99,8 +99,9 @@ __device__ __forceinline__ float kl_bits_term(float m, float lv) {
 // 2 = F16: the fp16 images of the main-product-only filter (gq_filter_bf16.h), every MFMA dim, GQ and VQ.
 template <int MODE, int DIM, bool FROM_Z, int FK = 0>
 __global__ __launch_bounds__(256) void gq_prep_kernel(const PrepParams p) {
-  static_assert(DIM == 4 || DIM == 8 || DIM == 16 || DIM == 32, "MFMA filter dims");
+  static_assert(DIM == 4 || DIM == 8 || DIM == 16 || DIM == 32 || DIM == 64, "MFMA filter dims");
   constexpr bool MIXED = FK == 1, F16 = FK == 2;
+  static_assert(DIM != 64 || F16, "dim 64 (the wide route, gqhip.h: gqhip_set_wide_dims): fp16 main-product images only");
   static_assert(!MIXED || (DIM == 16 && MODE == kModeGQ), "fp16 + fp8 images: dim 16, Gaussian score");
   constexpr bool PACKED = DIM == 4;
   constexpr int NV = PACKED ? 1 : DIM / 8;     // 8-slot groups per operand half
@@ -185,7 +186,18 @@ __global__ __launch_bounds__(256) void gq_prep_kernel(const PrepParams p) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
               const int g = PACKED ? k : 16 * m + 8 * h + k;
-              const float x = nv[g < DIM ? g : g - DIM];
+              float x;
+              if constexpr (DIM == 64) {
+                // the same element, named by constants (h picks one of two VALUES; the empty asm keeps the compiler from folding the
+                // choice back into a run-time subscript, with which the 64-float code row lives in scratch)
+                constexpr int kHalfSlots = DIM / 16;                       // MFMAs that carry the squares (as many carry the values)
+                const int e0 = 16 * (m % kHalfSlots) + k;                  // (compile-time after unrolling)
+                float x0 = nv[e0], x1 = nv[e0 + 8];
+                asm volatile("" : "+v"(x0), "+v"(x1));
+                x = h ? x1 : x0;
+              } else {
+                x = nv[g < DIM ? g : g - DIM];
+              }
               float t = g < DIM ? x * x : x;
               asm volatile("" : "+v"(t));          // the fp32 square is the feature (no fused multiply-convert)
               v[k] = (PACKED && h == 1) ? (_Float16)0.0f : (_Float16)t;
@@ -627,8 +639,8 @@ __global__ __launch_bounds__(256) void prep_plain_kernel(const PrepPlainParams p
   }
 }
 
-// The padded route of the dims between the filter dims (gqhip.h: gqhip_set_odd_dims): true-dim rows and codebook -> copies of
-// width dp (the next filter dim) whose pad columns hold mu 0, sd 1, log sd 0 and code 0.  gq_prep_kernel<.., dp, from rows> then
+// The padded route of the dims between the filter dims (gqhip.h: gqhip_set_odd_dims) and of dims 33-63 (gqhip_set_wide_dims, dp = 64):
+// true-dim rows and codebook -> copies of width dp (the next filter dim) whose pad columns hold mu 0, sd 1, log sd 0 and code 0.  gq_prep_kernel<.., dp, from rows> then
 // derives everything the dp filter and re-rank read from them: a pad column's filter products A 0^2 + B 0 are exactly 0 in fp16 and
 // fp32, its terms of the bound sums (1/sd^2 = 1, the rest 0) only loosen the bound, and it adds nothing to max|cb| or a code norm.
 // One thread per padded element, rows first, then codes; memory-bound and small beside the filter.

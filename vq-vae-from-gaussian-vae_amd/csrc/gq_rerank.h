@@ -265,7 +265,7 @@ __device__ __forceinline__ float ref_score_lds(const float (&n)[DIM], const floa
 template <int DIM>
 __device__ __forceinline__ float ref_score_lds_true(const float (&n)[DIM], const float *ops, float beta, int dim) {
 #pragma clang fp contract(off)
-  static_assert(DIM >= 8, "padded dims are 8, 16, 32");
+  static_assert(DIM >= 8, "padded dims are 8, 16, 32, 64");
   float acc[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) acc[k] = k < dim ? ref_term(n[k], ops[k], ops[DIM + k], ops[2 * DIM + k], beta) : 0.0f;
@@ -357,7 +357,7 @@ __device__ __forceinline__ void finish_row_by_scan(const RerankParams &p, long r
     // U codes per thread and pass, their rows loaded BEFORE the first expansion: the scan is a chain of L2 latencies (one 4 DIM-byte
     // row per thread in flight and ~0.7 us each: 270 us per 65 536 codes at dim 16 with the plain loop), so the loads in flight are
     // what sets its speed
-    constexpr int U = DIM <= 8 ? 8 : (DIM == 16 ? 3 : 4);
+    constexpr int U = DIM <= 8 ? 8 : (DIM == 16 ? 3 : (DIM == 32 ? 4 : 2));     // (dim 64: 2 x 64 registers of code rows beside 128 of coefficients)
     for (int it0 = tid; it0 < items; it0 += 256 * U) {
       float n[U][DIM];
       int code[U];
@@ -712,9 +712,11 @@ __device__ __forceinline__ void rerank_block(const RerankParams &p, const int vb
 }
 
 // (256, 4): at most 128 VGPRs, four blocks per CU -- the kernel lives on memory-level parallelism across waves
-// (dim 32 needs 2 x 32 coefficient registers alone: two blocks per CU there)
+// (dim 32 needs 2 x 32 coefficient registers alone: two blocks per CU there; dim 64 -- 2 x 64 coefficients, 64 of the lane's best code
+// row, 64 of the row in flight -- gets one block per CU and with it the whole register file of its four waves)
+constexpr int rerank_blocks_per_cu(int dim) { return dim >= 64 ? 1 : (dim >= 32 ? 2 : 4); }
 template <int MODE, int DIM, int GT, int NSI>
-__global__ __launch_bounds__(256, DIM >= 32 ? 2 : 4) void gq_rerank_kernel(const RerankParams p) {
+__global__ __launch_bounds__(256, rerank_blocks_per_cu(DIM)) void gq_rerank_kernel(const RerankParams p) {
   // gq_quantize_z_gauss_f32 launches ONE block more than the rows need: block 0 then runs GQ2's statistics (gq_gauss.h) beside the
   // re-rank's blocks -- its input, the per-row KL bits, was left by the call's first launch -- so that call has no fourth launch
   int vblock = (int)blockIdx.x;
@@ -736,7 +738,7 @@ __global__ __launch_bounds__(256, DIM >= 32 ? 2 : 4) void gq_rerank_kernel(const
 // dim.  Kernels of their own, so the instantiations of the filter dims themselves stay what they were.  (GQ2's statistics never ride in
 // this launch.)
 template <int MODE, int DIM, int GT, int NSI>
-__global__ __launch_bounds__(256, DIM >= 32 ? 2 : 4) void gq_rerank_pad_kernel(const RerankParams p) {
+__global__ __launch_bounds__(256, rerank_blocks_per_cu(DIM)) void gq_rerank_pad_kernel(const RerankParams p) {
   rerank_block<MODE, DIM, GT, NSI, true>(p, (int)blockIdx.x, p.rows);
 }
 

@@ -71,12 +71,16 @@ int odd_dims_kind_from(const char *e) { return e && (e[0] == 'p' || e[0] == 'P')
 // GQHIP_LOW_DIMS=search, by its first letter in either case -> GQHIP_LOW_DIMS_SEARCH; anything else: the exhaustive kernel
 int low_dims_kind_from(const char *e) { return e && (e[0] == 's' || e[0] == 'S') ? GQHIP_LOW_DIMS_SEARCH : GQHIP_LOW_DIMS_EXHAUSTIVE; }
 
+// GQHIP_WIDE_DIMS=filter, by its first letter in either case -> GQHIP_WIDE_DIMS_FILTER; anything else: the exhaustive kernel
+int wide_dims_kind_from(const char *e) { return e && (e[0] == 'f' || e[0] == 'F') ? GQHIP_WIDE_DIMS_FILTER : GQHIP_WIDE_DIMS_EXHAUSTIVE; }
+
 // Every GQHIP_* variable this translation unit reads: diagnostics and A/B timing, never needed in production.  Read once per
 // process, when the library is loaded (g_filter_kind's initialiser is the first user).
 struct Env {
   int filter = filter_kind_from(env_str("GQHIP_FILTER"));   // initial filter selection (gqhip_set_filter() changes it at run time)
   int odd_dims = odd_dims_kind_from(env_str("GQHIP_ODD_DIMS"));   // initial route of dims 5-7, 9-15, 17-31 (gqhip_set_odd_dims() changes it at run time)
   int low_dims = low_dims_kind_from(env_str("GQHIP_LOW_DIMS"));   // initial route of dims 1-3 (gqhip_set_low_dims() changes it at run time)
+  int wide_dims = wide_dims_kind_from(env_str("GQHIP_WIDE_DIMS"));   // initial route of dims 33-64 (gqhip_set_wide_dims() changes it at run time)
   int rt = env_int("GQHIP_RT", 0);                           // 1 | 2: row tiles per wave of the filter (default: 2 from 8192 rows)
   int target_blocks = env_int("GQHIP_TARGET_BLOCKS", 0);     // > 0: filter blocks the code splits aim at (default: 256 / 512, make_plan)
   int nsplit = env_int("GQHIP_NSPLIT", 0);                   // > 0: code splits of the filter, before make_plan's caps
@@ -110,7 +114,7 @@ int filter_kind() { return g_filter_kind.load(std::memory_order_relaxed); }
 // scores with the true dim, so the choice never changes an index either.
 std::atomic<int> g_odd_dims{env().odd_dims};
 // the filter dim an odd dim is zero-padded to under PADDED (5-7 -> 8, 9-15 -> 16, 17-31 -> 32); 0: no such route for this dim
-// (dims 1-3: 65 536 codes are dense in so few dimensions, the rows would live in the finish scan; 33-64: no K = 64 filter)
+// (dims 1-3: 65 536 codes are dense in so few dimensions, the rows would live in the finish scan; 33-64: wide_dim below)
 int64_t padded_dim(int64_t dim) {
   if (g_odd_dims.load(std::memory_order_relaxed) != GQHIP_ODD_DIMS_PADDED) return 0;
   if (dim > 4 && dim < 8) return 8;
@@ -119,13 +123,23 @@ int64_t padded_dim(int64_t dim) {
   return 0;
 }
 
+// Route of dims 33-64 (gqhip.h: gqhip_set_wide_dims).  Under FILTER, with the fp16 main-product filter selected (AUTO), they run the
+// filter and the re-rank at dim 64 -- 33-63 zero-padded as the odd dims are, 64 as it is.  The re-rank decides with the true dim, so the
+// choice never changes an index.  Returns the filter dim, 0: no such route for this dim under the current selections.
+std::atomic<int> g_wide_dims{env().wide_dims};
+constexpr int64_t kWideDim = 64;
+int64_t wide_dim(int64_t dim) {
+  if (g_wide_dims.load(std::memory_order_relaxed) != GQHIP_WIDE_DIMS_FILTER || filter_kind() != GQHIP_FILTER_AUTO) return 0;
+  return dim > 32 && dim <= kWideDim ? kWideDim : 0;
+}
+
 // Route of the Gaussian arg-max at dims 1-3 (gqhip.h: gqhip_set_low_dims): under SEARCH a call with a codebook cache runs the pruned
 // exact search of gq_lowdim.h, whose winner is decided by the reference's arithmetic as on the exhaustive route: never another index.
 std::atomic<int> g_low_dims{env().low_dims};
 
 // ---- launch plan: identical on the sizing and the launching side -----------
 struct Plan {
-  bool mfma;            // filter kernel applies (dim in {4,8,16,32}, n >= 32)
+  bool mfma;            // filter kernel applies (dim in {4,8,16,32}, or 64 on the wide route; n >= 1)
   int rt;               // row tiles per wave
   int rows_per_block;   // 128 * rt
   int row_blocks;
@@ -140,6 +154,7 @@ struct Plan {
   bool f16;             // fp16 main product only + the data-dependent bound of the re-rank (round 3: the default filter)
   int fdim;             // the dim the filter and the re-rank's templates run at: dim itself, the next filter dim on the padded route, 0 without a filter
   bool padded;          // fdim > dim: rows and codebook are zero-padded in the workspace first (run_padded)
+  bool wide;            // the dim-64 filter of gqhip_set_wide_dims(FILTER): dims 33-63 padded to it, dim 64 itself
 
   // The fp16 + fp8 filter scores Gaussians only: under that selection a VQ call runs the split-bf16 kernels.  The sizing side does
   // not know the mode and sizes for the Gaussian score (mode defaulted), which needs no less.
@@ -158,9 +173,14 @@ constexpr float kMixedEfCoeff = 2450.0f;
 constexpr float kMixedN1Limit = 16.0f;   // ... and max|cb| >= 1 (gq_rerank.h)
 // fp16 main-product filter (gq_filter_bf16.h, F16): per product the two fp16 roundings, (1 + 2^-11)^2 - 1 = 16384 u + 4 u, the fp32
 // roundings of A / B, of n^2 and of the row normalisation's inputs (3 u), 4 u per accumulation step of up to 2 x 64 slots
-// ... charged for the widest layout (dim 32: 64 products): 16384 + 4 + 3 + 4 * 64 = 16647, rounded up.  Operands in fp16's
-// subnormal range are charged separately, as an absolute term (gq_rerank.h:f16_bound).
+// ... charged for the widest layout of the default routes (dim 32: 64 products): 16384 + 4 + 3 + 4 * 64 = 16647, rounded up.  Operands
+// in fp16's subnormal range are charged separately, as an absolute term (gq_rerank.h:f16_bound).
 constexpr float kF16EfCoeff = 16700.0f;
+// The dim-64 filter (wide route): 128 products per value, accumulated by eight chained v_mfma_f32_32x32x16_f16 (each adds its 16
+// products to the fp32 accumulator the previous one left).  Whatever order the matrix core adds its 16 products in, a product takes
+// part in at most 16 additions inside its MFMA and the accumulator in one more per later MFMA: at most 128 roundings on any path,
+// each charged 4 u of the running magnitude (<= T) as above: 16384 + 4 + 3 + 4 * 128 = 16903, rounded up.
+constexpr float kF16EfCoeffWide = 17000.0f;
 constexpr float kF16N1Limit = 255.0f;    // n^2 must stay a finite fp16
 
 // The re-rank's bound on the filter's error: its coefficient, and the range of max|cb| (n1) inside which it holds.
@@ -169,7 +189,7 @@ struct RerankBound {
   float ef_coeff, n1_limit, n1_min;
 };
 RerankBound rerank_bound(const Plan &pl, int mode, int64_t dim) {
-  if (pl.f16) return {kF16EfCoeff, kF16N1Limit, 0.0f};
+  if (pl.f16) return {dim > 32 ? kF16EfCoeffWide : kF16EfCoeff, kF16N1Limit, 0.0f};   // `dim`: the filter dim
   if (pl.mixed_in(mode)) return {kMixedEfCoeff, kMixedN1Limit, 1.0f};
   return {pl.bf16 ? (float)(dim == 4 ? 332 : 220 + 24 * dim) : (float)(2 * dim + 4), 0.0f, 0.0f};
 }
@@ -181,10 +201,12 @@ bool grid_dim_enabled(int64_t dim) {
   return g == 48 ? (dim == 4 || dim == 8) : (g != 0 && dim == g);
 }
 
-Plan plan_at(int64_t rows, int64_t n, int64_t dim) {
+// `wide`: dim is kWideDim and the caller is the wide route (without it dim 64 has no filter, as every dim outside the four has none)
+Plan plan_at(int64_t rows, int64_t n, int64_t dim, bool wide = false) {
   const Env &e = env();
   Plan pl{};
-  pl.mfma = (dim == 4 || dim == 8 || dim == 16 || dim == 32) && n >= 1 && rows >= 1;
+  pl.wide = wide && dim == kWideDim;
+  pl.mfma = (dim == 4 || dim == 8 || dim == 16 || dim == 32 || pl.wide) && n >= 1 && rows >= 1;
   pl.tiles_total = (int)((n + kTileCodes - 1) / kTileCodes);
   pl.rt = rows >= 8192 ? 2 : 1;
   if (e.rt == 1 || e.rt == 2) pl.rt = e.rt;
@@ -219,6 +241,7 @@ Plan plan_at(int64_t rows, int64_t n, int64_t dim) {
   pl.nsplit = (pl.tiles_total + pl.tiles_per_split - 1) / pl.tiles_per_split;
   pl.mixed = pl.bf16 && filter_kind() == GQHIP_FILTER_MIXED && dim == 16 && pl.waves == 8 && pl.ct == 16 && pl.gt == 4;
   if (pl.f16) pl.ct = dim == 32 ? 8 : 16;   // one 16-byte vector per MFMA, lane and tile: 16-tile chunks are 16 / 32 KiB
+  if (pl.wide) pl.ct = 4;                   // dim 64: 8 KiB per tile, 4-tile chunks of 32 KiB as at dim 32
   const int split_cap = kMaxSplit / pl.rec_halves();   // the re-rank takes at most kMaxSplit record sets
   if (pl.nsplit > split_cap) {
     pl.tiles_per_split = ((pl.tiles_total + split_cap - 1) / split_cap + pl.gt - 1) / pl.gt * pl.gt;
@@ -242,8 +265,16 @@ Plan plan_at(int64_t rows, int64_t n, int64_t dim) {
 }
 
 // The one place that decides the route: the plan of `dim`, or -- under GQHIP_ODD_DIMS_PADDED, for a dim between two filter dims --
-// the plan of the filter dim it is padded to, marked `padded`.
+// the plan of the filter dim it is padded to, marked `padded`; or -- under GQHIP_WIDE_DIMS_FILTER, for dims 33-64 -- the plan of the
+// dim-64 filter, `padded` below 64.
 Plan make_plan(int64_t rows, int64_t n, int64_t dim) {
+  if (const int64_t dw = wide_dim(dim)) {
+    Plan pl = plan_at(rows, n, dw, true);
+    if (pl.mfma && pl.f16) {      // (only the fp16 main-product filter has a dim-64 kernel; beyond the split cap: exhaustive, as below)
+      pl.padded = dim < dw;
+      return pl;
+    }
+  }
   if (const int64_t dp = padded_dim(dim)) {
     Plan pl = plan_at(rows, n, dp);
     if (pl.mfma) {      // (a codebook beyond the split cap runs the exhaustive kernel, at its true dim)
@@ -301,7 +332,7 @@ struct WsLayout {
 // zero-padded fp32 codebook they gather from follow the regions of every other route
 WsLayout ws_layout(const Plan &pl, int64_t rows, int64_t dim_true) {
   WsLayout w{};
-  const int64_t dim = pl.padded ? pl.fdim : dim_true;
+  const int64_t dim = pl.padded ? pl.fdim : dim_true;     // (the wide route at dim 64 itself: fdim == dim_true, no padded copies)
   int64_t off = 0;
   w.hdr = off; off += (int64_t)sizeof(WsHeader);
   w.rec = off; off += align256((int64_t)sizeof(Rec) * rows * pl.stored_rec_sets());
@@ -397,6 +428,8 @@ FilterBfKernel filter_bf16_kernel(const Plan &pl, int64_t dim, bool mixed) {
       case 162: return gq_filter_bf16_kernel<2, 2, 16, 4, 8, 2>;
       case 321: return gq_filter_bf16_kernel<4, 1, 8, 4, 8, 2>;
       case 322: return gq_filter_bf16_kernel<4, 2, 8, 4, 8, 2>;
+      case 641: return gq_filter_bf16_kernel<8, 1, 4, 4, 8, 2>;     // the wide route: eight MFMAs per tile and row tile
+      case 642: return gq_filter_bf16_kernel<8, 2, 4, 4, 8, 2>;
       default: return nullptr;
     }
   }
@@ -431,6 +464,7 @@ PrepKernel prep_kernel_z(int64_t dim, bool mixed, bool f16) {
     case 82: return gq_prep_kernel<MODE, 8, FROM_Z, 2>;
     case 162: return gq_prep_kernel<MODE, 16, FROM_Z, 2>;
     case 322: return gq_prep_kernel<MODE, 32, FROM_Z, 2>;
+    case 642: return gq_prep_kernel<MODE, 64, FROM_Z, 2>;     // the wide route
     default: return nullptr;
   }
 }
@@ -457,6 +491,7 @@ RerankKernel rerank_pad_kernel(int64_t dim, int gt, int rec_sets) {
     case 1604: return rerank_pad_kernel_nsi<MODE, 16, 4>(rec_sets);
     case 3202: return rerank_pad_kernel_nsi<MODE, 32, 2>(rec_sets);
     case 3204: return rerank_pad_kernel_nsi<MODE, 32, 4>(rec_sets);
+    case 6404: return rerank_pad_kernel_nsi<MODE, 64, 4>(rec_sets);     // dims 33-63 on the wide route
     default: return nullptr;
   }
 }
@@ -469,6 +504,7 @@ RerankKernel rerank_kernel(int64_t dim, int gt, int rec_sets) {
     case 1604: return rerank_kernel_nsi<MODE, 16, 4>(rec_sets);
     case 3202: return rerank_kernel_nsi<MODE, 32, 2>(rec_sets);
     case 3204: return rerank_kernel_nsi<MODE, 32, 4>(rec_sets);
+    case 6404: return rerank_kernel_nsi<MODE, 64, 4>(rec_sets);         // dim 64 on the wide route
     default: return nullptr;
   }
 }
@@ -727,7 +763,7 @@ int run_dense(const Call &c, bool stats_in_rerank) {
   return launch(rk, rgrid, dim3(256), 0, c.st, rp);
 }
 
-// Dims 5-7, 9-15, 17-31 under GQHIP_ODD_DIMS_PADDED: rows at the true dim as on the exhaustive path (so zhat_noquant, sd_out, the KL
+// Dims 5-7, 9-15, 17-31 under GQHIP_ODD_DIMS_PADDED, dims 33-63 under GQHIP_WIDE_DIMS_FILTER: rows at the true dim as on the exhaustive path (so zhat_noquant, sd_out, the KL
 // bits and the VQ loss's rows are what they are there), gq_pad_kernel -> rows and codebook zero-padded to the plan's filter dim, then
 // the dense path on the padded copies: its from-rows prep, the selected filter and the re-rank, which scores and stores at the true dim.
 // No codebook cache: the padded operand image is rebuilt in the workspace on every call.
@@ -898,6 +934,14 @@ int gqhip_set_low_dims(int kind) {
 
 int gqhip_get_low_dims(void) { return g_low_dims.load(std::memory_order_relaxed); }
 
+int gqhip_set_wide_dims(int kind) {
+  if (kind != GQHIP_WIDE_DIMS_EXHAUSTIVE && kind != GQHIP_WIDE_DIMS_FILTER) return GQHIP_ERR_INVALID_ARG;
+  g_wide_dims.store(kind, std::memory_order_relaxed);
+  return GQHIP_OK;
+}
+
+int gqhip_get_wide_dims(void) { return g_wide_dims.load(std::memory_order_relaxed); }
+
 int gqhip_low_dim_search_applies(int64_t n, int64_t dim) { return cache_use(n, dim).kind == CacheUse::kLow; }
 
 int64_t gqhip_filter_dim(int64_t n, int64_t dim) {
@@ -911,7 +955,7 @@ int gqhip_debug_plan(int64_t rows, int64_t n, int64_t dim, int64_t *out8_host) {
   out8_host[0] = ws_layout(pl, rows, dim).rec; out8_host[1] = pl.stored_rec_sets();
   out8_host[2] = pl.gt; out8_host[3] = pl.tiles_per_split;
   out8_host[4] = pl.f16 ? 3 : (pl.mixed ? 2 : (pl.bf16 ? 1 : 0));   // 0 fp32 MFMA filter, 1 split-bf16, 2 fp16 + fp8 (Gaussian score), 3 fp16 main product
-  out8_host[5] = (int64_t)rerank_bound(pl, kModeGQ, pl.padded ? pl.fdim : dim).ef_coeff;
+  out8_host[5] = (int64_t)rerank_bound(pl, kModeGQ, pl.mfma ? pl.fdim : dim).ef_coeff;
   out8_host[6] = pl.rt; out8_host[7] = pl.waves;
   return GQHIP_OK;
 }

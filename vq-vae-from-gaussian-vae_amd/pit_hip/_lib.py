@@ -214,7 +214,7 @@ class Workspace(_Scratch):
     """Caller-owned scratch, grown on demand and reused across calls, plus the persistent CODEBOOK CACHE of the shapes that keep
     one (gqhip.h: gqhip_cb_cache_bytes -- dims 4 / 8: the spatial index of the pruned search; the library validates it against a
     content hash of the codebook on every call and rebuilds it in-stream when it is stale, so nothing here has to track the
-    codebook).  The sizes come from the library under its current selections (``set_filter``, ``set_odd_dims``): nothing to redo here
+    codebook).  The sizes come from the library under its current selections (``set_filter``, ``set_odd_dims``, ``set_wide_dims``): nothing to redo here
     after changing one.  One workspace serves one stream at a time (its header carries the per-call counters).  Graph captures: the rule
     of ``_Scratch``, one pin for both buffers; size them with a warm-up call first (``reserve``)."""
 
@@ -1721,6 +1721,24 @@ def set_low_dims(kind: str) -> None:
 def get_low_dims() -> str:
     k = lib().gqhip_get_low_dims()
     return next(name for name, v in LOW_DIMS_KINDS.items() if v == k)
+
+
+WIDE_DIMS_KINDS = {"exhaustive": 0, "filter": 1}
+
+
+def set_wide_dims(kind: str) -> None:
+    """Route of the codebook dims 33-64: "exhaustive" (default): every code scored per row; "filter": with the filter selection
+    "auto", filter + re-rank at dim 64 (dims 33-63 zero-padded to it; the re-rank scores with the true dim).  Process-wide; every
+    output is the same bits either way.  The workspace size depends on it (a ``Workspace`` asks the library on every call and grows
+    by itself)."""
+    if kind not in WIDE_DIMS_KINDS:
+        raise GqHipError(f"unknown wide-dims route {kind!r} (expected one of {sorted(WIDE_DIMS_KINDS)})")
+    _check(lib().gqhip_set_wide_dims(WIDE_DIMS_KINDS[kind]), "gqhip_set_wide_dims")
+
+
+def get_wide_dims() -> str:
+    k = lib().gqhip_get_wide_dims()
+    return next(name for name, v in WIDE_DIMS_KINDS.items() if v == k)
 
 
 def low_dim_search_applies(n: int, dim: int) -> bool:
